@@ -7,20 +7,26 @@ prediction volume that is already resident in HBM when the timed region starts. 
 JSON line ("Measurement").
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--flags SET]
+                  [--dump-outputs DIR] [--full]
 
-Default workload: ``synth512_p9`` = BASELINE.json configs[2] (512^3 volume, 9^3 patch, dense
-foreground, float16 prediction resident: 196 GB), the configuration the north star's target is
-stated on, with the reference's SHIPPED flylight flag set (``--flags shipped``: mutex watershed
-and thinning on; exact entries in the JSON's config.flags) and the uint32 instance ids of the
-reference's blockwise entry.  A step of that volume takes the better part of a minute; so that a
-default run always ends inside the driver's window, the first warm-up step is timed and, if
-(W + K) steps would exceed PPP_BENCH_BUDGET_S (default 1500 s), the timed loop falls back to
-``flylight140_p7`` (configs[1]) and the one 512^3 step is reported as ``config2_end_to_end``.
+Timed workload without --workload: ``flylight140_p7`` = BASELINE.json configs[1] (140^3 volume,
+7^3 patch, float16 prediction resident), with the reference's SHIPPED flylight flag set (``--flags
+shipped``: mutex watershed and thinning on; exact entries in the JSON's config.flags).  A step of
+``synth512_p9`` = configs[2] (512^3 volume, 9^3 patch, dense foreground, 196 GB of float16
+prediction resident, the uint32 instance ids of the reference's blockwise entry), the configuration
+the north star's target is stated on, takes the better part of a minute: ``--workload synth512_p9``
+times it, and ``--full`` without --workload adds one end-to-end step of it as
+``config2_end_to_end``.
 
-At N = 1 the same line also carries
-  * ``roofline`` for the scoring kernel S1 on the timed workload (HIP events of this run; for
-    flylight140_p7 additionally ``roofline_north_star``: the kernel over the 512^3 / 9^3 volume),
+A plain run sets up, warms up, times the K steps and prints the line: ``roofline``,
+``roofline_valu``, ``roofline_other_kernels`` and ``kernel_ms`` come from the HIP events of the
+timed steps.  ``--dump-outputs DIR`` writes the instance map of the last timed step as
+``DIR/instances.npy`` (float64; a fixed, seeded sample of the voxels when the map is larger than
+6 Mi voxels).  ``--full`` adds what takes runs of its own:
+  * ``stage_wall_ms``: one extra step after the timed loop with a device sync around every stage,
+  * ``roofline_north_star`` (flylight140_p7 only): the S1 kernel over the 512^3 / 9^3 volume,
   * ``variants`` (flylight140_p7 only): ms per step of the other flag sets,
+  * ``counter_calibration_bytes`` (with PPP_BENCH_CALIBRATE=1),
   * ``cpu_baseline``: the CPU oracle (C, -O3) on host cores -- one thread and all threads.
 
 N > 1 is launched by torch.distributed.run, one rank per GPU: ONE volume, split into z-slabs
@@ -93,8 +99,11 @@ DECODER = dict(activation="relu", num_fmaps=[64, 128], downsample_factors=[[2, 2
 DECODER_2D = dict(activation="relu", num_fmaps=[32, 64, 128], downsample_factors=[[2, 2], [2, 2], [2, 2]],
                   upsampling="resize_conv", kernel_size=3, num_repetitions=2, padding="same",
                   code_fmaps=16, code_units=256, input_shape_squeezed=(25, 25))
-DEFAULT_WORKLOAD = "synth512_p9"      # BASELINE.json configs[2]
-FALLBACK_WORKLOAD = "flylight140_p7"  # BASELINE.json configs[1]
+# BASELINE.json configs[1]: what a run without --workload times
+DEFAULT_WORKLOAD = "flylight140_p7"
+# BASELINE.json configs[2], the north star's volume (a step takes about 42 s): --dry-run-plan's and
+# --cpu-baseline-only's default, and the one end-to-end step --full adds without --workload
+NORTH_STAR_WORKLOAD = "synth512_p9"
 NORTH_STAR = ((512, 512, 512), (9, 9, 9), (24, 24, 24))   # BASELINE.json configs[2]
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s
 
@@ -472,6 +481,46 @@ class Workload:
         torch.cuda.empty_cache()
 
 
+DUMP_WHOLE_VOXELS = 6 << 20     # --dump-outputs: maps up to this size are written whole (float64: 48 MiB)
+DUMP_SAMPLE = 4 << 20           # draws of the seeded voxel sample of a larger map (at most 32 MiB)
+
+
+def dump_index(gshape):
+    """Flat indices of the voxels --dump-outputs writes: None (all of them) up to
+    DUMP_WHOLE_VOXELS, else a fixed seeded sample, sorted and without repeats -- the same for every
+    run of the same workload, so that two builds can be compared voxel for voxel."""
+    n = int(np.prod(gshape))
+    if n <= DUMP_WHOLE_VOXELS:
+        return None
+    rng = np.random.default_rng(0x5EED)
+    return np.unique(rng.integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+
+
+def dump_outputs(out_dir, inst, gshape, own_range, dist, rank, world):
+    """--dump-outputs: the instance map the last timed step returned, as float64 (ids are exact),
+    to out_dir/instances.npy -- the (Z, Y, X) map, or its values at dump_index(gshape).  With the
+    result kept per rank (own z-range) every rank contributes the voxels of its own slices."""
+    arr = np.ascontiguousarray(inst)
+    idx = dump_index(gshape)
+    if arr.shape[0] == gshape[0]:
+        vals = arr if idx is None else arr.reshape(-1)[idx]
+    else:
+        z0, z1 = own_range
+        assert arr.shape[0] == z1 - z0, (arr.shape, own_range)
+        plane = int(gshape[1]) * int(gshape[2])
+        flat = np.arange(int(np.prod(gshape)), dtype=np.int64) if idx is None else idx
+        a, b = (int(v) for v in np.searchsorted(flat, [z0 * plane, z1 * plane]))
+        parts = [None] * world
+        dist.all_gather_object(parts, (a, arr.reshape(-1)[flat[a:b] - z0 * plane]))
+        vals = np.concatenate([p for _, p in sorted(parts, key=lambda t: t[0])])
+        assert vals.size == flat.size, (vals.size, flat.size)
+        if idx is None:
+            vals = vals.reshape(tuple(gshape))
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "instances.npy"), vals.astype(np.float64))
+
+
 def rooflines(ev, notes, wl, ps, args, rank, world):
     """The three roofline blocks of the JSON line from the HIP-event times of the timed steps (`ev`) and the
     workload statistics (`notes`): S1 -- the contract's `roofline` (HBM-read fraction, counter traffic from the
@@ -550,8 +599,8 @@ def main():
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
-                    help="default: %s (BASELINE configs[2]) with a fall-back to %s when the run would "
-                         "not fit the time budget" % (DEFAULT_WORKLOAD, FALLBACK_WORKLOAD))
+                    help="default: %s (BASELINE configs[1]); --full then adds one end-to-end step of "
+                         "%s (BASELINE configs[2])" % (DEFAULT_WORKLOAD, NORTH_STAR_WORKLOAD))
     ap.add_argument("--flags", default="shipped", choices=["shipped", "cc", "nothin_cc"],
                     help="flag set (patchperpix_amd/flags.py): shipped = default.toml "
                          "[vote_instances] (mws + thinning), cc = mws off, nothin_cc = "
@@ -559,6 +608,12 @@ def main():
     ap.add_argument("--scaling", default="strong", choices=["weak", "strong"],
                     help="N > 1: strong = the 1-GPU volume is split over the ranks, weak = the volume "
                          "grows with N (N x taller)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the instance map of the last timed step to DIR/instances.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures that take runs of their own: the staged step "
+                         "(stage_wall_ms), the other flag sets, the north-star S1 pass, the counter "
+                         "calibration and the CPU baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-only", action="store_true", help="time the CPU oracle and exit")
     ap.add_argument("--no-north-star", action="store_true",
@@ -574,7 +629,7 @@ def main():
     args = ap.parse_args()
     if args.dry_run_plan:
         from patchperpix_amd import tiling
-        name = args.workload or DEFAULT_WORKLOAD
+        name = args.workload or NORTH_STAR_WORKLOAD
         shape, ps, _cell = WORKLOADS[name]
         plan = tiling.dry_run_plan(shape, ps, args.gpus, provider=name in PROVIDER_WORKLOADS,
                                    halo_mode=os.environ.get("PPP_BENCH_HALO", "exchange"),
@@ -583,6 +638,8 @@ def main():
         return
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started plainly (`python bench.py --gpus N`): start the N ranks ourselves, as a CHILD
         # launcher, before anything in this process touches torch or the GPU
@@ -595,7 +652,7 @@ def main():
 
     kw = dict(flagsets.FLAG_SETS[args.flags])
     if args.cpu_baseline_only:
-        shape, ps, cell = WORKLOADS[args.workload or DEFAULT_WORKLOAD]
+        shape, ps, cell = WORKLOADS[args.workload or NORTH_STAR_WORKLOAD]
         print(json.dumps(cpu_baseline(ps, cell, kw)))
         return
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -657,60 +714,22 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    budget_s = float(os.environ.get("PPP_BENCH_BUDGET_S", "1500"))
+    # Without --workload the timed loop runs DEFAULT_WORKLOAD (BASELINE configs[1]); --full then adds
+    # one end-to-end step of NORTH_STAR_WORKLOAD (configs[2], 512^3) as `config2_end_to_end`.
     auto = args.workload is None
     wl = Workload(torch, args.workload or DEFAULT_WORKLOAD, kw, args, world, rank, comm)
     barrier()
-    warm_done = 0
     config2 = None
-    if auto:
-        # the first step of the default workload is timed (it also serves as the first warm-up
-        # step): would W + K steps fit the budget?
-        backend.NOTES.clear()
-        backend.HOST_TIMES = {}
-        t0 = time.perf_counter()
-        inst = wl.step()
-        barrier()
-        t_first = agree_max(time.perf_counter() - t0)
-        stages = {k: float(np.sum(v) * 1e3) for k, v in backend.HOST_TIMES.items()}
-        backend.HOST_TIMES = None
-        warm_done = 1
-        planned = t_first * (args.steps + args.warmup)
-        if planned > budget_s and planned < 1.3 * budget_s and args.warmup >= 2:
-            # borderline: the first step also pays first-touch costs (the pooled buffers, library
-            # handles); time a second warm-up step before giving the headline workload up
-            t1 = time.perf_counter()
-            inst = wl.step()
-            barrier()
-            t_second = agree_max(time.perf_counter() - t1)
-            warm_done = 2
-            planned = t_first + t_second * (args.steps + args.warmup - 1)
-            t_first = min(t_first, t_second)
-        if planned > budget_s:
-            config2 = {
-                "workload": wl.name, "volume": list(wl.gshape), "patchshape": list(wl.ps),
-                "flag_set": args.flags, "ids": wl.ids, "steps": 1, "warmup": 0,
-                "ms_per_step": t_first * 1e3, "value": float(np.prod(wl.gshape)) / t_first / 1e6,
-                "unit": "Mvoxels/s", "instances_found": count_instances(torch, inst),
-                "instances_crc32": int(zlib.crc32(np.ascontiguousarray(inst).tobytes())),
-                "stage_wall_ms": stages, "workload_stats": dict(backend.NOTES),
-                "why_not_timed": "%d steps of %.1f s = %.0f s exceed the budget of %.0f s "
-                                 "(PPP_BENCH_BUDGET_S)" % (args.steps + args.warmup, t_first, planned, budget_s)}
-            del inst
-            wl.free(torch)
-            wl = Workload(torch, FALLBACK_WORKLOAD, kw, args, world, rank, comm)
-            warm_done = 0
-            barrier()
     shape, ps, cell, gshape = wl.shape, wl.ps, wl.cell, wl.gshape
     step = wl.step
 
-    for _ in range(max(0, args.warmup - warm_done)):
+    for _ in range(args.warmup):
         inst = step()
 
     backend.EVENTS = {}
     backend.NOTES.clear()
     barrier()
-    # The timed loop runs WITHOUT per-stage device syncs (round 6): the stage breakdown
+    # The timed loop runs WITHOUT per-stage device syncs (round 6): with --full the stage breakdown
     # (`stage_wall_ms`) comes from ONE extra step after it, with a sync around every stage.
     # PPP_BENCH_STAGES=inline: the syncs inside the timed loop, as up to round 5; =0: no breakdown.
     stages_mode = os.environ.get("PPP_BENCH_STAGES", "1")
@@ -730,9 +749,11 @@ def main():
     notes = dict(backend.NOTES)
     backend.EVENTS = None
     backend.HOST_TIMES = None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, inst, gshape, getattr(wl, "own_range", None), dist, rank, world)
     stage_steps = args.steps
     staged_step_ms = None
-    if stages_mode not in ("0", "inline"):
+    if args.full and stages_mode not in ("0", "inline"):
         backend.HOST_TIMES = host_times = {}
         keep_notes = dict(backend.NOTES)
         barrier()
@@ -796,7 +817,7 @@ def main():
     if rank == 0:
         per_step = ("s1_base_voxels", "s2_base_voxels", "s5_rows_dispatched", "s1_output_bytes")
         out = {
-            "metric": "Mvoxels/sec assembled (vote_instances)", "value": value,
+            "metric": "Mvoxels/sec assembled (vote_instances)", "value": value, "workload": wl.name,
             "unit": "Mvoxels/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
             # (one volume whatever N: with the default --scaling strong the N = 1 run is the
@@ -847,10 +868,35 @@ def main():
                                 if staged_step_ms is not None else None),
             "workload_stats": {k: (v // args.steps if k in per_step else v) for k, v in notes.items()},
         }
-        if config2 is not None:
-            out["config2_end_to_end"] = config2
-    if world == 1:
-        small = wl.name == FALLBACK_WORKLOAD
+
+    def end_to_end():
+        """--full without --workload: one step of NORTH_STAR_WORKLOAD (BASELINE configs[2]) end to end,
+        with a device sync around every stage (`stage_wall_ms`)"""
+        big = Workload(torch, NORTH_STAR_WORKLOAD, kw, args, world, rank, comm)
+        barrier()
+        backend.NOTES.clear()
+        backend.HOST_TIMES = {}
+        t0 = time.perf_counter()
+        binst = big.step()
+        barrier()
+        t_one = agree_max(time.perf_counter() - t0)
+        stages = {k: float(np.sum(v) * 1e3) for k, v in backend.HOST_TIMES.items()}
+        backend.HOST_TIMES = None
+        res = {
+            "workload": big.name, "volume": list(big.gshape), "patchshape": list(big.ps),
+            "flag_set": args.flags, "ids": big.ids, "steps": 1, "warmup": 0,
+            "ms_per_step": t_one * 1e3, "value": float(np.prod(big.gshape)) / t_one / 1e6,
+            "unit": "Mvoxels/s", "instances_found": count_instances(torch, binst),
+            "instances_crc32": int(zlib.crc32(np.ascontiguousarray(binst).tobytes())),
+            "stage_wall_ms": stages, "workload_stats": dict(backend.NOTES),
+            "why_not_timed": "one end-to-end step: without --workload the timed loop runs %s; "
+                             "--workload %s times this volume" % (DEFAULT_WORKLOAD, NORTH_STAR_WORKLOAD)}
+        del binst
+        big.free(torch)
+        return res
+
+    if world == 1 and args.full:
+        small = wl.name == DEFAULT_WORKLOAD
         # ---- the other flag sets on the same volume (a few steps each; small volume only)
         if not args.no_variants and small:
             variants = {}
@@ -883,13 +929,20 @@ def main():
             out["counter_calibration_bytes"] = {"read": rb, "write": wb, "read_f32": rb32}
             del scratch
         wl.free(torch)
+        if auto:
+            config2 = end_to_end()
         # ---- the north-star shape of the scoring kernel, in this run (when the timed workload is
         # not that shape itself)
         if not args.no_north_star and small and config2 is None:
             out["roofline_north_star"] = north_star_s1(torch, backend, kw)
         if not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(ps, cell, kw)
+    elif args.full and auto:
+        wl.free(torch)
+        config2 = end_to_end()
     if rank == 0:
+        if config2 is not None:
+            out["config2_end_to_end"] = config2
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()
@@ -912,7 +965,7 @@ def pmc_sq(kernel, workload):
         except ValueError:
             continue
         f = meta_f.replace(".meta.json", "_pmc_sq.txt")
-        if meta.get("workload", FALLBACK_WORKLOAD) == workload and meta.get("src_sha16") == sha and os.path.exists(f):
+        if meta.get("workload", DEFAULT_WORKLOAD) == workload and meta.get("src_sha16") == sha and os.path.exists(f):
             found = f
     if found is None:
         return {}
@@ -993,7 +1046,7 @@ def pmc_traffic(kernel, workload, read_width="pred"):
         except ValueError:
             continue
         f = meta_f.replace(".meta.json", "_pmc_fetch_write.txt")
-        if meta.get("workload", FALLBACK_WORKLOAD) != workload or not os.path.exists(f):
+        if meta.get("workload", DEFAULT_WORKLOAD) != workload or not os.path.exists(f):
             continue
         if meta.get("src_sha16") == sha:
             match.append((f, meta))

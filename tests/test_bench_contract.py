@@ -6,6 +6,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -61,12 +62,12 @@ def test_calibration_kernels_correct_the_counters(fake_profiles):
 def test_workloads_name_the_baseline_configurations():
     base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
     assert len(base["configs"]) == 5
-    # configs [0]..[4] -> worm2d_p25, flylight140_p7, synth512_p9 (default), synth1024_p9, dec256_p7
+    # configs [0]..[4] -> worm2d_p25, flylight140_p7 (default), synth512_p9, synth1024_p9, dec256_p7
     for name, shape, ps in (("worm2d_p25", (1, 520, 696), (1, 25, 25)), ("flylight140_p7", (140,) * 3, (7,) * 3),
                             ("synth512_p9", (512,) * 3, (9,) * 3), ("synth1024_p9", (1024,) * 3, (9,) * 3),
                             ("dec256_p7", (256,) * 3, (7,) * 3)):
         assert bench.WORKLOADS[name][0] == shape and bench.WORKLOADS[name][1] == ps
-    assert bench.DEFAULT_WORKLOAD == "synth512_p9" and bench.FALLBACK_WORKLOAD == "flylight140_p7"
+    assert bench.DEFAULT_WORKLOAD == "flylight140_p7" and bench.NORTH_STAR_WORKLOAD == "synth512_p9"
     assert "synth1024_p9" in bench.PROVIDER_WORKLOADS and "dec256_p7" in bench.DECODE_WORKLOADS
 
 
@@ -116,3 +117,84 @@ def test_self_launched_ranks_reproduce_the_one_rank_checksum():
     assert a["config"]["instances_slice_crc32"] is not None
     assert a["config"]["instances_slice_crc32"] == b["config"]["instances_slice_crc32"]
     assert a["config"]["instances_found"] == b["config"]["instances_found"]
+
+
+def test_dump_index_is_fixed_and_bounded():
+    """--dump-outputs: small maps whole, larger ones at the same seeded sample in every run, within
+    64 MB as float64."""
+    assert bench.dump_index((64, 64, 64)) is None
+    a = bench.dump_index((512, 512, 512))
+    assert a is not None and a.ndim == 1 and a.size * 8 <= 64e6
+    assert np.array_equal(a, bench.dump_index((512, 512, 512)))
+    assert np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < 512 ** 3
+
+
+class _FakeDist:
+    """all_gather_object over ranks that are simulated one after the other"""
+
+    def __init__(self, parts):
+        self.parts = parts
+
+    def all_gather_object(self, out, obj):
+        for i, p in enumerate(self.parts):
+            out[i] = p if p is not None else obj
+
+
+def test_dump_outputs_whole_and_split_over_ranks(tmp_path, monkeypatch):
+    rng = np.random.default_rng(3)
+    gshape = (40, 30, 20)
+    inst = rng.integers(0, 70000, size=gshape).astype(np.uint32)
+    bench.dump_outputs(str(tmp_path / "one"), inst, gshape, None, None, 0, 1)
+    got = np.load(tmp_path / "one" / "instances.npy")
+    assert got.dtype == np.float64 and got.shape == gshape and np.array_equal(got, inst)
+    # own z-ranges per rank: rank 1's part arrives through the collective, rank 0 writes the file
+    monkeypatch.setattr(bench, "DUMP_WHOLE_VOXELS", 1000)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 5000)
+    idx = bench.dump_index(gshape)
+    plane = gshape[1] * gshape[2]
+    cut = 17
+    a1 = int(np.searchsorted(idx, cut * plane))
+    other = (a1, inst.reshape(-1)[idx[a1:]])
+    bench.dump_outputs(str(tmp_path / "two"), inst[:cut], gshape, (0, cut), _FakeDist([None, other]), 0, 2)
+    got = np.load(tmp_path / "two" / "instances.npy")
+    assert np.array_equal(got, inst.reshape(-1)[idx].astype(np.float64))
+
+
+def test_dump_outputs_whole_map_split_over_ranks(tmp_path):
+    """A map small enough to be written whole, held as own z-ranges by two ranks: rank 0 puts the
+    (Z, Y, X) map back together from its slices and rank 1's."""
+    rng = np.random.default_rng(4)
+    gshape = (40, 30, 20)
+    inst = rng.integers(0, 70000, size=gshape).astype(np.uint32)
+    assert bench.dump_index(gshape) is None
+    cut = 23
+    other = (cut * gshape[1] * gshape[2], inst[cut:].reshape(-1))
+    bench.dump_outputs(str(tmp_path), inst[:cut], gshape, (0, cut), _FakeDist([None, other]), 0, 2)
+    got = np.load(tmp_path / "instances.npy")
+    assert got.dtype == np.float64 and got.shape == gshape and np.array_equal(got, inst)
+
+
+def test_help_names_full_and_dump_outputs():
+    r = _run_bench(["--help"], timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run: the line holds the headline fields and none of what --full adds; the dumped map
+    is the one the line's checksum describes."""
+    import zlib
+    r = _run_bench(["--workload", "synth64_p5", "--steps", "3", "--warmup", "1",
+                    "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d
+    assert d["steps"] == 3 and len(d["step_ms"]) == 3 and d["ms_per_step"] > 0
+    for k in ("cpu_baseline", "variants", "roofline_north_star"):
+        assert k not in d
+    assert d["stage_wall_ms"] == {} and d["stage_wall_from"] is None
+    got = np.load(tmp_path / "instances.npy")
+    assert got.dtype == np.float64 and got.shape == (64, 64, 64)
+    ids = got.astype(np.uint16)
+    assert np.array_equal(ids, got) and zlib.crc32(ids.tobytes()) == d["config"]["instances_crc32"]

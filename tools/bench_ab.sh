@@ -6,7 +6,7 @@ tag=$1; shift
 out=gpurun_out/${tag}.txt
 : > $out
 for setting in "$@"; do
-  env $setting PPP_BENCH_STAGES=0 python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
+  env $setting PPP_BENCH_STAGES=0 python3 bench.py --workload synth512_p9 --steps 1 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 k = d['kernel_ms']

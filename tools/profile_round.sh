@@ -12,8 +12,8 @@ tag=$1; shift
 out=gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-python3 bench.py "$@" > $out/bench.json 2> $out/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py "$@" --no-cpu-baseline --no-north-star --no-variants > $out/bench_under_rocprof.json 2>> $out/bench.err
+python3 bench.py --full "$@" > $out/bench.json 2> $out/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --full "$@" --no-cpu-baseline --no-north-star --no-variants > $out/bench_under_rocprof.json 2>> $out/bench.err
 python3 tools/summarize_prof.py $out/stats $out/kernel_stats.txt > /dev/null
 # (the PMC passes also run the library's counter-calibration kernels: a known byte count, read and
 # written with the access widths of the hot kernels -- MI355X_MICROARCH.md, "calibrate on a known
@@ -21,12 +21,12 @@ python3 tools/summarize_prof.py $out/stats $out/kernel_stats.txt > /dev/null
 export PPP_BENCH_CALIBRATE=1
 export PPP_BENCH_STAGES=0        # (no extra staged step in the counter passes)
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --output-format csv -d $out/pmc_$c -- python3 bench.py "$@" --steps 1 --warmup 0 --no-cpu-baseline --no-north-star --no-variants > $out/bench_pmc_$c.json 2>> $out/bench.err
+  rocprofv3 --pmc $c --output-format csv -d $out/pmc_$c -- python3 bench.py --full "$@" --steps 1 --warmup 0 --no-cpu-baseline --no-north-star --no-variants > $out/bench_pmc_$c.json 2>> $out/bench.err
 done
 unset PPP_BENCH_CALIBRATE
 # SQ counters of the same command (two more passes: instruction counts / issue, waits + LDS)
-rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_BUSY_CYCLES SQ_WAVE_CYCLES --output-format csv -d $out/pmc_sq1 -- python3 bench.py "$@" --steps 1 --warmup 0 --no-cpu-baseline --no-north-star --no-variants > /dev/null 2>> $out/bench.err
-rocprofv3 --pmc SQ_THREAD_CYCLES_VALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_RD SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVES --output-format csv -d $out/pmc_sq2 -- python3 bench.py "$@" --steps 1 --warmup 0 --no-cpu-baseline --no-north-star --no-variants > /dev/null 2>> $out/bench.err
+rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_BUSY_CYCLES SQ_WAVE_CYCLES --output-format csv -d $out/pmc_sq1 -- python3 bench.py --full "$@" --steps 1 --warmup 0 --no-cpu-baseline --no-north-star --no-variants > /dev/null 2>> $out/bench.err
+rocprofv3 --pmc SQ_THREAD_CYCLES_VALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_RD SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVES --output-format csv -d $out/pmc_sq2 -- python3 bench.py --full "$@" --steps 1 --warmup 0 --no-cpu-baseline --no-north-star --no-variants > /dev/null 2>> $out/bench.err
 python3 - <<PY
 import glob, os, shutil, sys
 sys.path.insert(0, "tools")

@@ -3,9 +3,10 @@
 # usage: tools/run_workloads.sh <tag> <steps> <workload> [workload ...]
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 tag=$1; steps=$2; shift 2
+out=${PPP_OUT_DIR:-out}; mkdir -p $out
 for w in "$@"; do
-  timeout 1500 python3 bench.py --workload $w --steps $steps --warmup 1 --no-cpu-baseline --no-north-star --no-variants 2>gpurun_out/${tag}_$w.err | tail -1 > gpurun_out/${tag}_bench_$w.json
-  python3 - $w gpurun_out/${tag}_bench_$w.json <<'PY'
+  timeout 1500 python3 bench.py --workload $w --steps $steps --warmup 1 --full --no-cpu-baseline --no-north-star --no-variants 2>$out/${tag}_$w.err | tail -1 > $out/${tag}_bench_$w.json
+  python3 - $w $out/${tag}_bench_$w.json <<'PY'
 import json, sys
 w, f = sys.argv[1:3]
 try:
