@@ -509,6 +509,45 @@ int ppp_patch_pairs_fill_subset(const int32_t *d_sorted_zyx, int64_t n, int32_t 
                                 const int64_t *d_global_offsets, int64_t n_local_rows,
                                 int64_t n_rows_total, int32_t include_single, uint32_t *d_rows,
                                 int64_t *d_row_ids, const ppp_params *p, void *stream);
+/* --- a stack of independent 2-d images (pz = 1) ----------------------------------------------
+ * The z axis is a batch of N images that one call per image would vote separately; these entry
+ * points give, slice by slice, exactly what such a call computes.  Additive: ppp_params is the
+ * same, and every other entry point keeps its meaning.
+ *   ppp_patch_pairs_count_slices / _fill_slices  as ppp_patch_pairs_count / _fill, on the selected
+ *       list sorted by (z, x) (stably): partners only in the same slice, scanned up to the end of
+ *       it -- the rows of slice k are those of slice k's own list, in its canonical order.
+ *   ppp_patch_graph_slices / ppp_patch_graph_lcg_slices / ppp_patch_graph_by_patch_lcg_slices
+ *       as the entry points without the suffix, with the per-pair LCG seed of every image's own
+ *       coordinates (z = 0: the seed is 0, computePatchGraph.cu:24-27).
+ *   ppp_thin_cover_slices  as ppp_thin_cover with the loop's stop rule per slice:
+ *       h_slice_interior int64[Z] (HOST) = set interior voxels of every slice of d_mask.
+ *   ppp_label_slice_renumber  d_labels int32[n] (in/out): ranks over the stack ascending by
+ *       (slice, order key) in, ids numbered from 1 in every slice out (0 stays 0);
+ *       d_slice_min / d_slice_max int32[Z] out: smallest rank / largest id of every slice.     */
+int ppp_patch_pairs_count_slices(const int32_t *d_sorted_zyx, int64_t n, int32_t max_ps_dist,
+                                 int64_t *d_counts, const ppp_params *p, void *stream);
+int ppp_patch_pairs_fill_slices(const int32_t *d_sorted_zyx, int64_t n, int32_t max_ps_dist,
+                                const int64_t *d_offsets, int64_t n_pair_rows, int32_t include_single,
+                                uint32_t *d_rows, const ppp_params *p, void *stream);
+int ppp_patch_graph_slices(const void *d_pred, int pred_dtype, const float *d_cons,
+                           const uint32_t *d_pairs, const uint32_t *d_order, uint64_t n_pairs,
+                           float *d_aff, const ppp_params *p, void *stream);
+int ppp_patch_graph_lcg_slices(const void *d_pred, int pred_dtype, const uint32_t *d_pairs,
+                               const uint32_t *d_order, const int64_t *d_lcg_pos, int64_t n_lcg,
+                               const int64_t *d_drop_off, uint64_t *d_drops, const ppp_params *p,
+                               void *stream);
+int ppp_patch_graph_by_patch_lcg_slices(const void *d_pred, int pred_dtype, const float *d_cons_vm,
+                                        const uint32_t *d_pairs, const uint32_t *d_order,
+                                        const int64_t *d_group_start, const int64_t *d_chunk_offsets,
+                                        int32_t n_groups, int64_t n_blocks, int32_t chunk, float *d_aff,
+                                        const int64_t *d_drop_off, const uint64_t *d_drops,
+                                        const ppp_params *p, void *stream);
+int ppp_thin_cover_slices(const uint8_t *d_mask, const uint32_t *d_bits, const int64_t *d_lin, int64_t n,
+                          uint8_t *d_keep, void *d_work, const int64_t *h_slice_interior,
+                          const ppp_params *p, void *stream, int32_t *rounds);
+int ppp_label_slice_renumber(const uint32_t *d_nodes, uint64_t n_nodes, int32_t *d_labels,
+                             int32_t *d_slice_min, int32_t *d_slice_max, const ppp_params *p, void *stream);
+
 /* sort keys (int64) that group pair rows by patch offset B - A, then by position of A: an
  * argsort of them is a good d_order for ppp_patch_graph                                    */
 int ppp_pair_sort_keys(const uint32_t *d_rows, uint64_t n_rows, int64_t *d_keys,

@@ -268,6 +268,35 @@ _SIGNATURES = {
     "ppp_host_patch_pairs": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                               ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
                                               ctypes.c_void_p]),
+    # a stack of independent 2-d images (the *_slices entry points, vote_instances/batch2d.py)
+    "ppp_patch_pairs_count_slices": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                                    ctypes.c_void_p, ctypes.POINTER(Params),
+                                                    ctypes.c_void_p]),
+    "ppp_patch_pairs_fill_slices": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                                   ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                                   ctypes.c_void_p, ctypes.POINTER(Params),
+                                                   ctypes.c_void_p]),
+    "ppp_patch_graph_slices": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                              ctypes.c_void_p, ctypes.POINTER(Params),
+                                              ctypes.c_void_p]),
+    "ppp_patch_graph_lcg_slices": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                  ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.POINTER(Params), ctypes.c_void_p]),
+    "ppp_patch_graph_by_patch_lcg_slices": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                           ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
+                                                           ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                           ctypes.c_void_p, ctypes.POINTER(Params),
+                                                           ctypes.c_void_p]),
+    "ppp_thin_cover_slices": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.POINTER(Params), ctypes.c_void_p,
+                                             ctypes.POINTER(ctypes.c_int32)]),
+    "ppp_label_slice_renumber": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(Params),
+                                                ctypes.c_void_p]),
 }
 
 
@@ -737,24 +766,26 @@ def patch_graph_prepare(pred, pairs, Pv, ahead=False):
     return job
 
 
-def _pa_masks(job, pred, pairs, Pv, b):
+def _pa_masks(job, pred, pairs, Pv, b, slices=False):
     """the thinning masks of batch b into the buffer (filled and read batch after batch)"""
     n_b = len(job.cuts) - 1
     if job.plan is None or b >= n_b or b in job.masks_done:
         return
     lo, hi = job.plan["pos_cuts"][b], job.plan["pos_cuts"][b + 1]
     if hi > lo:
+        fn = lib().ppp_patch_graph_lcg_slices if slices else lib().ppp_patch_graph_lcg
         with _timed("patch_graph_lcg"):
-            check(lib().ppp_patch_graph_lcg(
+            check(fn(
                 _dev_ptr(pred), pred_dtype_code(pred), _dev_ptr(pairs), _dev_ptr(job.order32),
                 _dev_ptr(job.plan["pos"][lo:hi]), hi - lo, _dev_ptr(job.plan["drop_off"]),
                 _dev_ptr(job.bufs[b % 2]), ctypes.byref(Pv), _stream()))
     job.masks_done.add(b)
 
 
-def patch_graph_by_patch(pred, cons_vm, pairs, Pv, job=None):
+def patch_graph_by_patch(pred, cons_vm, pairs, Pv, job=None, slices=False):
     """S5 with one workgroup per patch A (ppp_patch_graph_by_patch).  job: what patch_graph_prepare
-    made for these rows (None: made here)."""
+    made for these rows (None: made here).  slices: the z axis is a stack of independent 2-d images
+    (every image's own LCG seeds, ppp_patch_graph_by_patch_lcg_slices)."""
     if job is None:
         job = patch_graph_prepare(pred, pairs, Pv)
     aff = job.aff
@@ -765,11 +796,12 @@ def patch_graph_by_patch(pred, cons_vm, pairs, Pv, job=None):
     for b in range(n_b):
         g0, g1 = cuts[b], cuts[b + 1]
         if plan is not None:
-            _pa_masks(job, pred, pairs, Pv, b)
+            _pa_masks(job, pred, pairs, Pv, b, slices)
         co = job.chunk_offsets[g0:g1 + 1]
         n_blocks = int(job.co_host[g1] - job.co_host[g0])
+        fn = lib().ppp_patch_graph_by_patch_lcg_slices if slices else lib().ppp_patch_graph_by_patch_lcg
         with _timed("patch_graph"):
-            check(lib().ppp_patch_graph_by_patch_lcg(
+            check(fn(
                 _dev_ptr(pred), pred_dtype_code(pred), _dev_ptr(cons_vm), _dev_ptr(pairs),
                 _dev_ptr(job.order32), _dev_ptr(job.group_start[g0:g1 + 1].contiguous()),
                 _dev_ptr((co - co[0]).contiguous()), g1 - g0, n_blocks, job.chunk, _dev_ptr(aff),
@@ -869,7 +901,7 @@ def _lcg_plan(dkey, group_start, Pv):
                 drop_off=drop_off.contiguous(), buffer_words=max(buffer_words, 1))
 
 
-def patch_graph_auto(pred, cons_compact, pairs, P, job=None):
+def patch_graph_auto(pred, cons_compact, pairs, P, job=None, slices=False):
     """S5 from a COMPACT consensus: re-layout to voxel-major, then the workgroup-per-patch
     kernel (consensus rows staged once per patch in LDS; 0.3 TB instead of 5.4 TB of HBM reads
     on the 140^3 benchmark).  PPP_PATCH_GRAPH=pairs selects the pair-per-lane gather kernel
@@ -885,19 +917,23 @@ def patch_graph_auto(pred, cons_compact, pairs, P, job=None):
     if os.environ.get("PPP_PATCH_GRAPH", "patch") != "pairs" and \
             int(lib().ppp_patch_graph_by_patch_chunk(ctypes.byref(Pv))) > 0 and \
             max(P.pz, P.py) <= P.px:
-        return patch_graph_by_patch(pred, vm, pairs, Pv, job=job)
-    return patch_graph(pred, vm, pairs, Pv, order=pair_order(pairs, Pv))
+        return patch_graph_by_patch(pred, vm, pairs, Pv, job=job, slices=slices)
+    return patch_graph(pred, vm, pairs, Pv, order=pair_order(pairs, Pv), slices=slices)
 
 
-def device_patch_pairs(sorted_zyx, P, max_ps_dist=2, include_single=True):
+def device_patch_pairs(sorted_zyx, P, max_ps_dist=2, include_single=True, slices=False):
     """Pair rows on the device from the x-sorted selected list (device int32 [n, 3]).
-    Returns device int32 [rows, 6] (uint32 bit patterns) or None when there are no rows."""
+    Returns device int32 [rows, 6] (uint32 bit patterns) or None when there are no rows.
+    slices: the z axis is a stack of independent 2-d images, the list is sorted by (z, x) and
+    partners are searched in the same slice only (ppp_patch_pairs_*_slices)."""
     torch = _torch()
     n = int(sorted_zyx.shape[0])
     counts = torch.zeros((max(n, 1),), dtype=torch.int64, device=sorted_zyx.device)
+    count_fn = lib().ppp_patch_pairs_count_slices if slices else lib().ppp_patch_pairs_count
+    fill_fn = lib().ppp_patch_pairs_fill_slices if slices else lib().ppp_patch_pairs_fill
     with _timed("patch_pairs"):
-        check(lib().ppp_patch_pairs_count(_dev_ptr(sorted_zyx), n, int(max_ps_dist),
-                                          _dev_ptr(counts), ctypes.byref(P), _stream()))
+        check(count_fn(_dev_ptr(sorted_zyx), n, int(max_ps_dist),
+                       _dev_ptr(counts), ctypes.byref(P), _stream()))
         ends = torch.cumsum(counts, 0)
         n_rows = int(ends[n - 1].item()) if n else 0
         total = n_rows + (n if include_single else 0)
@@ -905,9 +941,9 @@ def device_patch_pairs(sorted_zyx, P, max_ps_dist=2, include_single=True):
             return None
         offsets = (ends - counts).contiguous()
         rows = torch.empty((total, 6), dtype=torch.int32, device=sorted_zyx.device)
-        check(lib().ppp_patch_pairs_fill(_dev_ptr(sorted_zyx), n, int(max_ps_dist),
-                                         _dev_ptr(offsets), n_rows, 1 if include_single else 0,
-                                         _dev_ptr(rows), ctypes.byref(P), _stream()))
+        check(fill_fn(_dev_ptr(sorted_zyx), n, int(max_ps_dist),
+                      _dev_ptr(offsets), n_rows, 1 if include_single else 0,
+                      _dev_ptr(rows), ctypes.byref(P), _stream()))
     return rows
 
 
@@ -1010,16 +1046,17 @@ class LabelState:
         return keys
 
 
-def patch_graph(pred, cons, pairs, P, order=None):
+def patch_graph(pred, cons, pairs, P, order=None, slices=False):
     """S5.  pairs: device uint32-as-int32 [N, 6]; order: optional device int32 permutation
-    (see pair_order); returns float32 [N]."""
+    (see pair_order); returns float32 [N].  slices: every image of a stack of 2-d images seeds
+    its pairs' LCG with its own coordinates (ppp_patch_graph_slices)."""
     torch = _torch()
     n = int(pairs.shape[0])
     aff = torch.zeros((n,), dtype=torch.float32, device=pred.device)
+    fn = lib().ppp_patch_graph_slices if slices else lib().ppp_patch_graph
     with _timed("patch_graph"):
-        check(lib().ppp_patch_graph(_dev_ptr(pred), pred_dtype_code(pred), _dev_ptr(cons),
-                                    _dev_ptr(pairs), _dev_ptr(order), n, _dev_ptr(aff),
-                                    ctypes.byref(P), _stream()))
+        check(fn(_dev_ptr(pred), pred_dtype_code(pred), _dev_ptr(cons), _dev_ptr(pairs), _dev_ptr(order), n,
+                 _dev_ptr(aff), ctypes.byref(P), _stream()))
     return aff
 
 
@@ -1037,6 +1074,20 @@ def label_components(pairs, aff, nodes, P):
                                          _dev_ptr(keys), _dev_ptr(work), ctypes.byref(P),
                                          _stream()))
     return keys.to(torch.int64) & 0xFFFFFFFF
+
+
+def label_slice_renumber(nodes, labels, P):
+    """Ids per slice of a stack of independent 2-d images (ppp_label_slice_renumber).  nodes int32
+    [K, 3] device, labels int32 [K] device: ranks over the stack ascending by (slice, order key),
+    renumbered in place from 1 in every slice.  Returns the largest id of every slice (int32 [Z])."""
+    torch = _torch()
+    slice_min = torch.empty((int(P.Z),), dtype=torch.int32, device=nodes.device)
+    slice_max = torch.empty((int(P.Z),), dtype=torch.int32, device=nodes.device)
+    with _timed("label_slice_renumber"):
+        check(lib().ppp_label_slice_renumber(_dev_ptr(nodes.contiguous()), int(nodes.shape[0]),
+                                             _dev_ptr(labels), _dev_ptr(slice_min), _dev_ptr(slice_max),
+                                             ctypes.byref(P), _stream()))
+    return slice_max
 
 
 def paint_instances(pred, nodes, labels, instances, P):
@@ -1242,10 +1293,12 @@ def cover_pass_device(mask, bits, lin, state, pix_th, P, bits_first_voxel=None):
     return cleared, int(rounds.value)
 
 
-def thin_cover_device(mask, bits, lin, P):
+def thin_cover_device(mask, bits, lin, P, slice_interior=None):
     """Set-cover thinning on the device (ppp_thin_cover; foreground_cover.py:183-256).
     mask uint8 (Z,Y,X) device tensor = mask_to_cover (not modified), bits int32 [n, words] /
-    lin int64 [n]: the selected patches in list order.  Returns keep, bool [n] device tensor."""
+    lin int64 [n]: the selected patches in list order.  Returns keep, bool [n] device tensor.
+    slice_interior (int64 [Z] host array): the z axis is a stack of independent 2-d images whose
+    interiors hold that many set voxels -- the loop's stop rule per slice (ppp_thin_cover_slices)."""
     torch = _torch()
     n = int(lin.numel())
     keep = torch.zeros(max(n, 1), dtype=torch.uint8, device=mask.device)
@@ -1256,9 +1309,16 @@ def thin_cover_device(mask, bits, lin, P):
     work = torch.empty(nbytes, dtype=torch.uint8, device=mask.device)
     rounds = ctypes.c_int32(0)
     with _timed("thin_cover"):
-        check(lib().ppp_thin_cover(_dev_ptr(mask), _dev_ptr(bits.contiguous()), _dev_ptr(lin.contiguous()),
-                                   n, _dev_ptr(keep), _dev_ptr(work), ctypes.byref(P), _stream(),
-                                   ctypes.byref(rounds)))
+        if slice_interior is None:
+            check(lib().ppp_thin_cover(_dev_ptr(mask), _dev_ptr(bits.contiguous()), _dev_ptr(lin.contiguous()),
+                                       n, _dev_ptr(keep), _dev_ptr(work), ctypes.byref(P), _stream(),
+                                       ctypes.byref(rounds)))
+        else:
+            si = np.ascontiguousarray(slice_interior, dtype=np.int64)
+            assert si.shape == (int(P.Z),)
+            check(lib().ppp_thin_cover_slices(_dev_ptr(mask), _dev_ptr(bits.contiguous()),
+                                              _dev_ptr(lin.contiguous()), n, _dev_ptr(keep), _dev_ptr(work),
+                                              _np_ptr(si), ctypes.byref(P), _stream(), ctypes.byref(rounds)))
     note("thin_rounds", rounds.value)
     return keep[:n].bool()
 
@@ -1459,6 +1519,20 @@ def mws_labels_device(rows, aff, nodes, P):
     labels = np.zeros((k,), dtype=np.int32)
     if n == 0 or k == 0:
         return torch.from_numpy(labels).to(nodes.device), 0
+    eu_h, ev_h = mws_edges_device(rows, aff, nodes, P)
+    ne = len(eu_h)
+    with host_timer("s6b_mws_loop"):
+        issued = int(lib().ppp_host_mws_sorted(_np_ptr(eu_h), _np_ptr(ev_h), ne, k, _np_ptr(labels)))
+    note("mws_edges", ne)
+    return torch.from_numpy(labels).to(nodes.device), issued
+
+
+def mws_edges_device(rows, aff, nodes, P):
+    """The edge list of the mutex watershed made on the device (ppp_mws_edges) and copied to the
+    host: (eu, ev) int32 [n_edges] node numbers in the order the loop visits them, bit 31 of ev =
+    attractive.  rows / aff / nodes: device tensors as for mws_labels_device (n, k > 0)."""
+    torch = _torch()
+    n, k = int(rows.shape[0]), int(nodes.shape[0])
     nbytes = int(lib().ppp_mws_edges_workspace_bytes(n, k, ctypes.byref(P)))
     check(min(nbytes, 0))
     work = torch.empty(nbytes, dtype=torch.uint8, device=rows.device)
@@ -1473,11 +1547,7 @@ def mws_labels_device(rows, aff, nodes, P):
         ne = int(n_edges.value)
         eu_h = eu[:ne].cpu().numpy()
         ev_h = ev[:ne].cpu().numpy()
-    del work, eu, ev
-    with host_timer("s6b_mws_loop"):
-        issued = int(lib().ppp_host_mws_sorted(_np_ptr(eu_h), _np_ptr(ev_h), ne, k, _np_ptr(labels)))
-    note("mws_edges", ne)
-    return torch.from_numpy(labels).to(nodes.device), issued
+    return eu_h, ev_h
 
 
 def host_rank_order(score, foreground, patchshape):

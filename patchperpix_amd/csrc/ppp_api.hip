@@ -291,11 +291,21 @@ int ppp_rank_patches_vm(const void *d_pred, int pred_dtype, const float *d_cons_
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_rank_patches_vm");
 }
 
-int ppp_patch_graph(const void *d_pred, int pred_dtype, const float *d_cons,
-                    const uint32_t *d_pairs, const uint32_t *d_order, uint64_t n_pairs,
-                    float *d_aff, const ppp_params *p, void *stream) {
+// the *_slices entry points: the z axis is a stack of independent 2-d images (pz = 1)
+static int slices_geo(const ppp_params *p, int slices, ppp::Geo *G) {
+    PPP_TRY(make_geo(p, G));
+    if (slices) {
+        if (G->pz != 1) return fail(PPP_ERR_INVALID_ARG, "independent slices need 2-d patches (pz = 1, not %d)", G->pz);
+        G->slice_seeds = 1;
+    }
+    return PPP_OK;
+}
+
+static int patch_graph_impl(const void *d_pred, int pred_dtype, const float *d_cons,
+                            const uint32_t *d_pairs, const uint32_t *d_order, uint64_t n_pairs,
+                            float *d_aff, const ppp_params *p, void *stream, int slices) {
     ppp::Geo G;
-    PPP_TRY(make_geo(p, &G));
+    PPP_TRY(slices_geo(p, slices, &G));
     PPP_TRY(check_dtype(pred_dtype));
     if (n_pairs == 0) return PPP_OK;
     if (n_pairs >= (1ull << 32)) return fail(PPP_ERR_UNSUPPORTED, "more than 2^32-1 pair rows");
@@ -304,6 +314,18 @@ int ppp_patch_graph(const void *d_pred, int pred_dtype, const float *d_cons,
     PPP_TRY(need_device());
     hipError_t e = ppp::launch_patch_graph(d_pred, pred_dtype, d_cons, d_pairs, d_order, n_pairs, d_aff, G, (hipStream_t)stream);
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_patch_graph");
+}
+
+int ppp_patch_graph(const void *d_pred, int pred_dtype, const float *d_cons,
+                    const uint32_t *d_pairs, const uint32_t *d_order, uint64_t n_pairs,
+                    float *d_aff, const ppp_params *p, void *stream) {
+    return patch_graph_impl(d_pred, pred_dtype, d_cons, d_pairs, d_order, n_pairs, d_aff, p, stream, 0);
+}
+
+int ppp_patch_graph_slices(const void *d_pred, int pred_dtype, const float *d_cons,
+                           const uint32_t *d_pairs, const uint32_t *d_order, uint64_t n_pairs,
+                           float *d_aff, const ppp_params *p, void *stream) {
+    return patch_graph_impl(d_pred, pred_dtype, d_cons, d_pairs, d_order, n_pairs, d_aff, p, stream, 1);
 }
 
 int32_t ppp_patch_graph_by_patch_chunk(const ppp_params *p) {
@@ -324,11 +346,12 @@ int64_t ppp_patch_graph_lcg_words(int32_t dz, int32_t dy, int32_t dx, const ppp_
     return ppp::patch_graph_lcg_words(G, dz, dy, dx);
 }
 
-int ppp_patch_graph_lcg(const void *d_pred, int pred_dtype, const uint32_t *d_pairs,
-                        const uint32_t *d_order, const int64_t *d_lcg_pos, int64_t n_lcg,
-                        const int64_t *d_drop_off, uint64_t *d_drops, const ppp_params *p, void *stream) {
+static int patch_graph_lcg_impl(const void *d_pred, int pred_dtype, const uint32_t *d_pairs,
+                                const uint32_t *d_order, const int64_t *d_lcg_pos, int64_t n_lcg,
+                                const int64_t *d_drop_off, uint64_t *d_drops, const ppp_params *p,
+                                void *stream, int slices) {
     ppp::Geo G;
-    PPP_TRY(make_geo(p, &G));
+    PPP_TRY(slices_geo(p, slices, &G));
     PPP_TRY(check_dtype(pred_dtype));
     if (n_lcg <= 0) return PPP_OK;
     if (!d_pred || !d_pairs || !d_order || !d_lcg_pos || !d_drop_off || !d_drops)
@@ -342,6 +365,21 @@ int ppp_patch_graph_lcg(const void *d_pred, int pred_dtype, const uint32_t *d_pa
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_patch_graph_lcg");
 }
 
+int ppp_patch_graph_lcg(const void *d_pred, int pred_dtype, const uint32_t *d_pairs,
+                        const uint32_t *d_order, const int64_t *d_lcg_pos, int64_t n_lcg,
+                        const int64_t *d_drop_off, uint64_t *d_drops, const ppp_params *p, void *stream) {
+    return patch_graph_lcg_impl(d_pred, pred_dtype, d_pairs, d_order, d_lcg_pos, n_lcg, d_drop_off, d_drops,
+                                p, stream, 0);
+}
+
+int ppp_patch_graph_lcg_slices(const void *d_pred, int pred_dtype, const uint32_t *d_pairs,
+                               const uint32_t *d_order, const int64_t *d_lcg_pos, int64_t n_lcg,
+                               const int64_t *d_drop_off, uint64_t *d_drops, const ppp_params *p,
+                               void *stream) {
+    return patch_graph_lcg_impl(d_pred, pred_dtype, d_pairs, d_order, d_lcg_pos, n_lcg, d_drop_off, d_drops,
+                                p, stream, 1);
+}
+
 int ppp_patch_graph_by_patch_chunked(const void *d_pred, int pred_dtype, const float *d_cons_vm,
                                      const uint32_t *d_pairs, const uint32_t *d_order,
                                      const int64_t *d_group_start, const int64_t *d_chunk_offsets,
@@ -352,14 +390,14 @@ int ppp_patch_graph_by_patch_chunked(const void *d_pred, int pred_dtype, const f
                                         p, stream);
 }
 
-int ppp_patch_graph_by_patch_lcg(const void *d_pred, int pred_dtype, const float *d_cons_vm,
-                                 const uint32_t *d_pairs, const uint32_t *d_order,
-                                 const int64_t *d_group_start, const int64_t *d_chunk_offsets,
-                                 int32_t n_groups, int64_t n_blocks, int32_t chunk, float *d_aff,
-                                 const int64_t *d_drop_off, const uint64_t *d_drops,
-                                 const ppp_params *p, void *stream) {
+static int patch_graph_by_patch_impl(const void *d_pred, int pred_dtype, const float *d_cons_vm,
+                                     const uint32_t *d_pairs, const uint32_t *d_order,
+                                     const int64_t *d_group_start, const int64_t *d_chunk_offsets,
+                                     int32_t n_groups, int64_t n_blocks, int32_t chunk, float *d_aff,
+                                     const int64_t *d_drop_off, const uint64_t *d_drops,
+                                     const ppp_params *p, void *stream, int slices) {
     ppp::Geo G;
-    PPP_TRY(make_geo(p, &G));
+    PPP_TRY(slices_geo(p, slices, &G));
     PPP_TRY(check_dtype(pred_dtype));
     if (n_groups == 0) return PPP_OK;
     if (!d_pred || !d_cons_vm || !d_pairs || !d_order || !d_group_start || !d_chunk_offsets || !d_aff)
@@ -377,6 +415,28 @@ int ppp_patch_graph_by_patch_lcg(const void *d_pred, int pred_dtype, const float
     if (e == hipErrorNotSupported)
         return fail(PPP_ERR_UNSUPPORTED, "no per-patch kernel for this patch shape / chunk size");
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_patch_graph_by_patch");
+}
+
+int ppp_patch_graph_by_patch_lcg(const void *d_pred, int pred_dtype, const float *d_cons_vm,
+                                 const uint32_t *d_pairs, const uint32_t *d_order,
+                                 const int64_t *d_group_start, const int64_t *d_chunk_offsets,
+                                 int32_t n_groups, int64_t n_blocks, int32_t chunk, float *d_aff,
+                                 const int64_t *d_drop_off, const uint64_t *d_drops,
+                                 const ppp_params *p, void *stream) {
+    return patch_graph_by_patch_impl(d_pred, pred_dtype, d_cons_vm, d_pairs, d_order, d_group_start,
+                                     d_chunk_offsets, n_groups, n_blocks, chunk, d_aff, d_drop_off, d_drops,
+                                     p, stream, 0);
+}
+
+int ppp_patch_graph_by_patch_lcg_slices(const void *d_pred, int pred_dtype, const float *d_cons_vm,
+                                        const uint32_t *d_pairs, const uint32_t *d_order,
+                                        const int64_t *d_group_start, const int64_t *d_chunk_offsets,
+                                        int32_t n_groups, int64_t n_blocks, int32_t chunk, float *d_aff,
+                                        const int64_t *d_drop_off, const uint64_t *d_drops,
+                                        const ppp_params *p, void *stream) {
+    return patch_graph_by_patch_impl(d_pred, pred_dtype, d_cons_vm, d_pairs, d_order, d_group_start,
+                                     d_chunk_offsets, n_groups, n_blocks, chunk, d_aff, d_drop_off, d_drops,
+                                     p, stream, 1);
 }
 
 int ppp_patch_graph_by_patch(const void *d_pred, int pred_dtype, const float *d_cons_vm,
@@ -522,6 +582,47 @@ int ppp_patch_pairs_fill(const int32_t *d_sorted_zyx, int64_t n, int32_t max_ps_
     PPP_TRY(need_device());
     hipError_t e = ppp::launch_pairs_fill(d_sorted_zyx, n, box, l1max, d_offsets, n_pair_rows, include_single, d_rows, (hipStream_t)stream);
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_patch_pairs_fill");
+}
+
+int ppp_patch_pairs_count_slices(const int32_t *d_sorted_zyx, int64_t n, int32_t max_ps_dist,
+                                 int64_t *d_counts, const ppp_params *p, void *stream) {
+    ppp::Geo G;
+    PPP_TRY(slices_geo(p, 1, &G));
+    if (n == 0) return PPP_OK;
+    if (!d_sorted_zyx || !d_counts) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    int box[3], l1max;
+    PPP_TRY(pair_box(p, max_ps_dist, box, &l1max));
+    PPP_TRY(need_device());
+    hipError_t e = ppp::launch_pairs_count(d_sorted_zyx, n, box, l1max, d_counts, (hipStream_t)stream,
+                                           nullptr, 0, true);
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_patch_pairs_count_slices");
+}
+
+int ppp_patch_pairs_fill_slices(const int32_t *d_sorted_zyx, int64_t n, int32_t max_ps_dist,
+                                const int64_t *d_offsets, int64_t n_pair_rows, int32_t include_single,
+                                uint32_t *d_rows, const ppp_params *p, void *stream) {
+    ppp::Geo G;
+    PPP_TRY(slices_geo(p, 1, &G));
+    if (n == 0) return PPP_OK;
+    if (!d_sorted_zyx || !d_offsets || !d_rows) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    int box[3], l1max;
+    PPP_TRY(pair_box(p, max_ps_dist, box, &l1max));
+    PPP_TRY(need_device());
+    hipError_t e = ppp::launch_pairs_fill(d_sorted_zyx, n, box, l1max, d_offsets, n_pair_rows, include_single,
+                                          d_rows, (hipStream_t)stream, true);
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_patch_pairs_fill_slices");
+}
+
+int ppp_label_slice_renumber(const uint32_t *d_nodes, uint64_t n_nodes, int32_t *d_labels,
+                             int32_t *d_slice_min, int32_t *d_slice_max, const ppp_params *p, void *stream) {
+    ppp::Geo G;
+    PPP_TRY(slices_geo(p, 1, &G));
+    if ((n_nodes && (!d_nodes || !d_labels)) || !d_slice_min || !d_slice_max)
+        return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    PPP_TRY(need_device());
+    hipError_t e = ppp::launch_label_slice_renumber(d_nodes, n_nodes, d_labels, d_slice_min, d_slice_max, G,
+                                                    (hipStream_t)stream);
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_label_slice_renumber");
 }
 
 int ppp_pair_sort_keys(const uint32_t *d_rows, uint64_t n_rows, int64_t *d_keys,
@@ -842,11 +943,11 @@ int64_t ppp_thin_workspace_bytes(int64_t n, const ppp_params *p) {
     return (int64_t)ppp::thin_workspace_bytes(n < 0 ? 0 : n, G);
 }
 
-int ppp_thin_cover(const uint8_t *d_mask, const uint32_t *d_bits, const int64_t *d_lin, int64_t n,
-                   uint8_t *d_keep, void *d_work, const ppp_params *p, void *stream,
-                   int32_t *rounds) {
+static int thin_cover_impl(const uint8_t *d_mask, const uint32_t *d_bits, const int64_t *d_lin, int64_t n,
+                           uint8_t *d_keep, void *d_work, const ppp_params *p, void *stream,
+                           int32_t *rounds, const int64_t *h_slice_interior) {
     ppp::Geo G;
-    PPP_TRY(make_geo(p, &G));
+    PPP_TRY(slices_geo(p, h_slice_interior != nullptr, &G));
     if (rounds) *rounds = 0;
     if (n <= 0) return PPP_OK;
     if (n > 0x7F000000LL) return fail(PPP_ERR_INVALID_ARG, "too many selected patches for ppp_thin_cover");
@@ -856,9 +957,22 @@ int ppp_thin_cover(const uint8_t *d_mask, const uint32_t *d_bits, const int64_t 
     PPP_TRY(need_device());
     int r = 0;
     hipError_t e = ppp::run_thin_cover(d_mask, d_bits, (const long long *)d_lin, n, d_keep, d_work, G,
-                                       (hipStream_t)stream, &r);
+                                       (hipStream_t)stream, &r, (const long long *)h_slice_interior);
     if (rounds) *rounds = r;
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_thin_cover");
+}
+
+int ppp_thin_cover(const uint8_t *d_mask, const uint32_t *d_bits, const int64_t *d_lin, int64_t n,
+                   uint8_t *d_keep, void *d_work, const ppp_params *p, void *stream,
+                   int32_t *rounds) {
+    return thin_cover_impl(d_mask, d_bits, d_lin, n, d_keep, d_work, p, stream, rounds, nullptr);
+}
+
+int ppp_thin_cover_slices(const uint8_t *d_mask, const uint32_t *d_bits, const int64_t *d_lin, int64_t n,
+                          uint8_t *d_keep, void *d_work, const int64_t *h_slice_interior,
+                          const ppp_params *p, void *stream, int32_t *rounds) {
+    if (!h_slice_interior) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    return thin_cover_impl(d_mask, d_bits, d_lin, n, d_keep, d_work, p, stream, rounds, h_slice_interior);
 }
 
 /* ---- sharded cover: the rounds of ppp_cover_pass one step at a time on a rank's z-range ---- */

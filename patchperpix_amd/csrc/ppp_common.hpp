@@ -41,6 +41,7 @@ struct Geo {
     int ring;           // voxel-major rows in a ring of `ring` z-slices (0: the plain box), ppp_params.ring_z
     int pred_clean;     // 1: every prediction value in [0, 1] and != TH (ppp_params.pred_clean, ppp_pred_check)
     int rank_tile;      // ppp_params.rank_tile: 0 = the launcher's rule, 1 / 2 / 3 = 8x8x16 / 8x16x16 / 16x8x16
+    int slice_seeds;    // 1: the z axis is a stack of independent 2-d images (the *_slices entry points)
 };
 
 // A HIP grid is limited to 2^32 - 1 work-items per dimension (blocks x threads): a larger launch
@@ -86,6 +87,13 @@ __device__ __forceinline__ long long cons_at(const Geo &G, int dz, int dy, int d
 // (z + origin) mod ring when the buffer is a ring
 __device__ __forceinline__ int row_slice(const Geo &G, int z) {
     return G.ring ? (z + G.oz) % G.ring : z - G.bz0;
+}
+// per-pair LCG seed of S5: the product of the six GLOBAL coordinates (computePatchGraph.cu:24-27).
+// With slice_seeds every image of the stack has its own z = 0, so the z factors -- and the seed --
+// are 0, which is what one call per image computes.  (Products mod 2^32: the order is free.)
+__device__ __forceinline__ uint32_t pair_seed(const Geo &G, int az, int ay, int ax, int bz, int by, int bx) {
+    const uint32_t zz = G.slice_seeds ? 0u : (uint32_t)(az + G.oz) * (uint32_t)(bz + G.oz);
+    return zz * (uint32_t)(ay + G.oy) * (uint32_t)(by + G.oy) * (uint32_t)(ax + G.ox) * (uint32_t)(bx + G.ox);
 }
 // value of one vote from the float product x = v1*v2 or v1*(1-v2)
 // (fillConsensusArray.cu:104-110,127-133): normalisation in double, rounded to float.

@@ -755,7 +755,8 @@ __global__ void __launch_bounds__(256)
 
 // keep u8 [n] (device).  Synchronises the stream.
 hipError_t run_thin_cover(const uint8_t *mask, const uint32_t *bits, const long long *lin, long long n,
-                          uint8_t *keep, void *work, const Geo &G, hipStream_t s, int *rounds) {
+                          uint8_t *keep, void *work, const Geo &G, hipStream_t s, int *rounds,
+                          const long long *slice_interior) {
     *rounds = 0;
     if (n <= 0) return hipSuccess;
     if (n >= (1ll << 31) || G.C >= THIN_MAXC) return hipErrorInvalidValue;
@@ -803,13 +804,36 @@ hipError_t run_thin_cover(const uint8_t *mask, const uint32_t *bits, const long 
         if (st[(size_t)i] == 1) order.push_back(((THIN_MAXC - (long long)cnt[(size_t)i]) << 32) | i);
     std::sort(order.begin(), order.end());
     std::vector<uint8_t> k8((size_t)n, 0);
-    long long remaining = (long long)interior;
-    for (size_t j = 0; j < order.size() && remaining > 0; ++j) {
-        const long long i = order[j] & 0xFFFFFFFFll;
-        k8[(size_t)i] = 1;
-        remaining -= clr[(size_t)i];
+    if (!slice_interior) {
+        long long remaining = (long long)interior;
+        for (size_t j = 0; j < order.size() && remaining > 0; ++j) {
+            const long long i = order[j] & 0xFFFFFFFFll;
+            k8[(size_t)i] = 1;
+            remaining -= clr[(size_t)i];
+        }
+        if (remaining > 0) k8[0] = 1;   // every count is 0 with voxels left: np.argmax picks patch 0
+    } else {
+        // a stack of independent 2-d images (pz = 1: no window reaches another slice, so the rounds
+        // above are every image's own): the stop rule per slice, on the slice's subsequence of the
+        // keys (the order its own loop keeps them in) and the slice's interior count; "patch 0" is
+        // the first patch of the slice in list order
+        std::vector<long long> hz((size_t)n);
+        if ((e = hipMemcpyAsync(hz.data(), lin, (size_t)n * 8, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+        if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+        const long long plane = (long long)G.Y * G.X;
+        std::vector<long long> remaining(slice_interior, slice_interior + G.Z);
+        std::vector<long long> first((size_t)G.Z, -1);
+        for (long long i = n - 1; i >= 0; --i) first[(size_t)(hz[(size_t)i] / plane)] = i;
+        for (size_t j = 0; j < order.size(); ++j) {
+            const long long i = order[j] & 0xFFFFFFFFll;
+            const size_t z = (size_t)(hz[(size_t)i] / plane);
+            if (remaining[z] <= 0) continue;
+            k8[(size_t)i] = 1;
+            remaining[z] -= clr[(size_t)i];
+        }
+        for (int z = 0; z < G.Z; ++z)
+            if (remaining[(size_t)z] > 0 && first[(size_t)z] >= 0) k8[(size_t)first[(size_t)z]] = 1;
     }
-    if (remaining > 0) k8[0] = 1;   // every count is 0 with voxels left: np.argmax picks patch 0
     if ((e = hipMemcpyAsync(keep, k8.data(), (size_t)n, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
     return hipStreamSynchronize(s);
 }

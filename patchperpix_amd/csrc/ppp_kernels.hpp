@@ -73,7 +73,7 @@ hipError_t launch_label(const uint32_t *pairs, const float *aff, uint64_t n,
                         const Geo &G, hipStream_t s);
 hipError_t launch_pairs_count(const int32_t *pts, int64_t n, const int *box, int l1max,
                               int64_t *counts, hipStream_t s, const int64_t *subset = nullptr,
-                              int64_t m = 0);
+                              int64_t m = 0, bool slices = false);
 hipError_t launch_pairs_subset(const int32_t *pts, int64_t n, const int *box, int l1max,
                                const int64_t *subset, int64_t m, const int64_t *local_off,
                                const int64_t *gid_off, int64_t n_local_rows, int64_t n_rows_total,
@@ -89,7 +89,7 @@ hipError_t launch_label_finish(const uint32_t *nodes, uint64_t n_nodes, long lon
                                uint32_t *key32, void *work, const Geo &G, hipStream_t s);
 hipError_t launch_pairs_fill(const int32_t *pts, int64_t n, const int *box, int l1max,
                              const int64_t *offsets, int64_t n_pair_rows, int include_single,
-                             uint32_t *rows, hipStream_t s);
+                             uint32_t *rows, hipStream_t s, bool slices = false);
 hipError_t launch_pair_group_keys(const uint32_t *rows, uint64_t n, int64_t *keys, const Geo &G,
                                   hipStream_t s);
 hipError_t launch_pair_keys(const uint32_t *rows, uint64_t n, int64_t *keys, const Geo &G,
@@ -146,7 +146,10 @@ hipError_t run_mws_edges(const uint32_t *rows, const float *aff, long long n_row
 
 size_t thin_workspace_bytes(long long n, const Geo &G);
 hipError_t run_thin_cover(const uint8_t *mask, const uint32_t *bits, const long long *lin, long long n,
-                          uint8_t *keep, void *work, const Geo &G, hipStream_t s, int *rounds);
+                          uint8_t *keep, void *work, const Geo &G, hipStream_t s, int *rounds,
+                          const long long *slice_interior = nullptr);
+hipError_t launch_label_slice_renumber(const uint32_t *nodes, uint64_t n, int32_t *labels, int32_t *slice_min,
+                                       int32_t *slice_max, const Geo &G, hipStream_t s);
 
 hipError_t cover_open(const uint8_t *mask, const long long *lin, const int32_t *rankid, long long n,
                       const int32_t *state, int32_t *cleared, void *work, const Geo &G, hipStream_t s);

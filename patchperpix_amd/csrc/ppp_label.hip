@@ -179,6 +179,41 @@ hipError_t launch_label(const uint32_t *pairs, const float *aff, uint64_t n,
     return launch_label_finish(nodes, n_nodes, nullptr, node_key, work, G, s);
 }
 
+// ---- ids per slice ----------------------------------------------------------------------
+// A stack of independent 2-d images: every image numbers its components from 1.  `labels` come
+// in as ranks over the whole stack ascending by (slice, order key), so the ids of slice z are one
+// contiguous range; they leave as label - (smallest id of the slice) + 1 (0 stays 0), and
+// slice_max[z] receives the largest id of slice z (the caller checks it against the id type).
+__global__ void slice_min_kernel(const uint32_t *__restrict__ nodes, uint64_t n,
+                                 const int32_t *__restrict__ labels, int32_t *__restrict__ slice_min) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n || labels[k] <= 0) return;
+    atomicMin(&slice_min[nodes[k * 3]], labels[k]);
+}
+__global__ void slice_renumber_kernel(const uint32_t *__restrict__ nodes, uint64_t n,
+                                      int32_t *__restrict__ labels, const int32_t *__restrict__ slice_min,
+                                      int32_t *__restrict__ slice_max) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n || labels[k] <= 0) return;
+    const uint32_t z = nodes[k * 3];
+    const int32_t lab = labels[k] - slice_min[z] + 1;
+    labels[k] = lab;
+    atomicMax(&slice_max[z], lab);
+}
+
+hipError_t launch_label_slice_renumber(const uint32_t *nodes, uint64_t n, int32_t *labels, int32_t *slice_min,
+                                       int32_t *slice_max, const Geo &G, hipStream_t s) {
+    hipError_t e;
+    if ((e = hipMemsetD32Async((hipDeviceptr_t)slice_min, 0x7FFFFFFF, (size_t)G.Z, s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(slice_max, 0, (size_t)G.Z * 4, s)) != hipSuccess) return e;
+    if (n == 0) return hipSuccess;
+    PPP_GRID_CHECK((n + 255) / 256, 256);
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    slice_min_kernel<<<grid, block, 0, s>>>(nodes, n, labels, slice_min);
+    slice_renumber_kernel<<<grid, block, 0, s>>>(nodes, n, labels, slice_min, slice_max);
+    return hipGetLastError();
+}
+
 // ---- paint ----------------------------------------------------------------------------
 template <typename T>
 __global__ void __launch_bounds__(256)

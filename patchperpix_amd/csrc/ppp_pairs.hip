@@ -11,11 +11,16 @@
 // hits with ballot/popcount -- hits come out in ascending j, i.e. rows are produced directly
 // in the canonical (i, j) order, with no sort and no atomics.  Two passes: count, then fill at
 // the offsets given by an exclusive scan of the counts.
+//
+// SLICES (a stack of independent 2-d images, ppp_patch_pairs_*_slices): the list is sorted by
+// (z, x), a partner must lie in the same slice, and the scan of patch i stops at the end of its
+// slice -- so the rows of slice k are exactly, and in the order of, what the list of slice k alone
+// gives (its patches in the same relative order: a stable sort by x).
 #include "ppp_kernels.hpp"
 
 namespace ppp {
 
-template <bool FILL>
+template <bool FILL, bool SLICES>
 __global__ void __launch_bounds__(256)
     pairs_kernel(const int32_t *__restrict__ pts, const int64_t n, const int bz, const int by,
                  const int bx, const int l1max, int64_t *__restrict__ counts,
@@ -37,7 +42,7 @@ __global__ void __launch_bounds__(256)
         bool beyond = true;
         if (j < n) {
             jz = pts[j * 3]; jy = pts[j * 3 + 1]; jx = pts[j * 3 + 2];
-            beyond = jx - x > bx;
+            beyond = (SLICES && jz != z) || jx - x > bx;
             const int az = abs(jz - z), ay = abs(jy - y), ax = abs(jx - x);
             hit = !beyond && az <= bz && ay <= by && ax <= bx && az + ay + ax <= l1max;
         }
@@ -49,7 +54,8 @@ __global__ void __launch_bounds__(256)
         }
         out += __popcll(m);
         found += __popcll(m);
-        // sorted by x: once a whole chunk lies beyond x + bx nothing further can match
+        // sorted by x (by (z, x)): once a whole chunk lies beyond x + bx (or the slice) nothing
+        // further can match
         if (__ballot(beyond) == ~0ull) break;
     }
     if (!FILL && lane == 0) counts[i] = found;
@@ -128,22 +134,33 @@ hipError_t launch_pairs_subset(const int32_t *pts, int64_t n, const int *box, in
 }
 
 hipError_t launch_pairs_count(const int32_t *pts, int64_t n, const int *box, int l1max,
-                              int64_t *counts, hipStream_t s, const int64_t *subset, int64_t m) {
+                              int64_t *counts, hipStream_t s, const int64_t *subset, int64_t m,
+                              bool slices) {
     const int64_t waves = subset ? m : n;
     if (n == 0 || waves == 0) return hipSuccess;
     PPP_GRID_CHECK((waves + 3) / 4, 256);
-    pairs_kernel<false><<<dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s>>>(
-        pts, n, box[0], box[1], box[2], l1max, counts, nullptr, nullptr, subset, m);
+    const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
+    if (slices)
+        pairs_kernel<false, true><<<grid, block, 0, s>>>(pts, n, box[0], box[1], box[2], l1max, counts,
+                                                         nullptr, nullptr, subset, m);
+    else
+        pairs_kernel<false, false><<<grid, block, 0, s>>>(pts, n, box[0], box[1], box[2], l1max, counts,
+                                                          nullptr, nullptr, subset, m);
     return hipGetLastError();
 }
 
 hipError_t launch_pairs_fill(const int32_t *pts, int64_t n, const int *box, int l1max,
                              const int64_t *offsets, int64_t n_pair_rows, int include_single,
-                             uint32_t *rows, hipStream_t s) {
+                             uint32_t *rows, hipStream_t s, bool slices) {
     if (n == 0) return hipSuccess;
     PPP_GRID_CHECK((n + 3) / 4, 256);
-    pairs_kernel<true><<<dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s>>>(
-        pts, n, box[0], box[1], box[2], l1max, nullptr, offsets, rows, nullptr, 0);
+    const dim3 grid((unsigned)((n + 3) / 4)), block(256);
+    if (slices)
+        pairs_kernel<true, true><<<grid, block, 0, s>>>(pts, n, box[0], box[1], box[2], l1max, nullptr,
+                                                        offsets, rows, nullptr, 0);
+    else
+        pairs_kernel<true, false><<<grid, block, 0, s>>>(pts, n, box[0], box[1], box[2], l1max, nullptr,
+                                                         offsets, rows, nullptr, 0);
     if (include_single)
         self_pairs_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(
             pts, n, rows + n_pair_rows * 6);

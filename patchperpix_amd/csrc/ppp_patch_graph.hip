@@ -66,9 +66,8 @@ __global__ void __launch_bounds__(64 * PG_WAVES)
         patch_fg_words(pred, G, az, ay, ax, lds_a + lane, words);
         patch_fg_words(pred, G, bz, by, bx, lds_b + lane, words);
     }
-    // the LCG seed is the product of the GLOBAL coordinates (computePatchGraph.cu:24-27)
-    uint32_t rnd = (uint32_t)(az + G.oz) * (uint32_t)(bz + G.oz) * (uint32_t)(ay + G.oy) *
-                   (uint32_t)(by + G.oy) * (uint32_t)(ax + G.ox) * (uint32_t)(bx + G.ox);
+    // the LCG seed: the product of the GLOBAL coordinates (computePatchGraph.cu:24-27, pair_seed)
+    uint32_t rnd = pair_seed(G, az, ay, ax, bz, by, bx);
     // consensus strides of the base voxel (tile or volume) and this lane's base index of cA
     long long sY, sZ, laneA;
     if (G.layout == PPP_CONS_REFERENCE) {
@@ -189,9 +188,8 @@ __global__ void __launch_bounds__(64 * PG_WAVES)
         patch_fg_words(pred, G, az, ay, ax, lds_a + lane, words);
         patch_fg_words(pred, G, bz, by, bx, lds_b + lane, words);
     }
-    // the LCG seed is the product of the GLOBAL coordinates (computePatchGraph.cu:24-27)
-    uint32_t rnd = (uint32_t)(az + G.oz) * (uint32_t)(bz + G.oz) * (uint32_t)(ay + G.oy) *
-                   (uint32_t)(by + G.oy) * (uint32_t)(ax + G.ox) * (uint32_t)(bx + G.ox);
+    // the LCG seed: the product of the GLOBAL coordinates (computePatchGraph.cu:24-27, pair_seed)
+    uint32_t rnd = pair_seed(G, az, ay, ax, bz, by, bx);
     const long long sY = G.bX, sZ = (long long)G.bX * G.bY;
     const long long laneA = ((long long)(az - G.bz0) * G.bY + (ay - G.by0)) * G.bX + (ax - G.bx0);
     const int W = (2 * G.pz - 1) * G.wy * G.wx, Lc = (W - 1) / 2;
@@ -296,9 +294,8 @@ __global__ void __launch_bounds__(64 * PG_WAVES)
         patch_fg_words(pred, G, az, ay, ax, lds_a + lane, words);
         patch_fg_words(pred, G, bz, by, bx, lds_b + lane, words);
     }
-    // the LCG seed is the product of the GLOBAL coordinates (computePatchGraph.cu:24-27)
-    uint32_t rnd = (uint32_t)(az + G.oz) * (uint32_t)(bz + G.oz) * (uint32_t)(ay + G.oy) *
-                   (uint32_t)(by + G.oy) * (uint32_t)(ax + G.ox) * (uint32_t)(bx + G.ox);
+    // the LCG seed: the product of the GLOBAL coordinates (computePatchGraph.cu:24-27, pair_seed)
+    uint32_t rnd = pair_seed(G, az, ay, ax, bz, by, bx);
     const long long sY = G.bX, sZ = (long long)G.bX * G.bY;
     const long long laneA = live ? ((long long)(az - G.bz0) * G.bY + (ay - G.by0)) * G.bX + (ax - G.bx0) : 0;
     const int W = (2 * G.pz - 1) * G.wy * G.wx, Lc = (W - 1) / 2;

@@ -244,8 +244,7 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
         const uint32_t *rw = rows + (size_t)row_id * 6;
         const int bz = (int)rw[3], by = (int)rw[4], bx = (int)rw[5];
         dz = bz - az; dy = by - ay; dx = bx - ax;
-        rnd = (uint32_t)(az + G.oz) * (uint32_t)(bz + G.oz) * (uint32_t)(ay + G.oy) *
-              (uint32_t)(by + G.oy) * (uint32_t)(ax + G.ox) * (uint32_t)(bx + G.ox);
+        rnd = pair_seed(G, az, ay, ax, bz, by, bx);
         const long long lb = vox(G, bz, by, bx);
         int r = 0;
         for (int w = 0; w < words; ++w) {
@@ -695,8 +694,7 @@ __global__ void __launch_bounds__(64)
     const int nz = live ? G.pz - abs(dz) : 0, ny = live ? G.py - abs(dy) : 0, nx = live ? PX - abs(dx) : 0;
     const int z1lo = max(dz, 0), y1lo = max(dy, 0), x1lo = max(dx, 0);
     const int z2lo = max(-dz, 0), y2lo = max(-dy, 0), x2lo = max(-dx, 0);
-    uint32_t rnd = (uint32_t)(az + G.oz) * (uint32_t)(bz + G.oz) * (uint32_t)(ay + G.oy) *
-                   (uint32_t)(by + G.oy) * (uint32_t)(ax + G.ox) * (uint32_t)(bx + G.ox);
+    uint32_t rnd = pair_seed(G, az, ay, ax, bz, by, bx);
     for (int w = 0; w < words; ++w) fa[w * 64 + lane] = 0u;
     for (int w = 0; w < words + 2; ++w) fb[w * 64 + lane] = 0u;
     {
@@ -818,8 +816,7 @@ __global__ void __launch_bounds__(64 * LCGW_WAVES)
     if (nz <= 0 || ny <= 0 || nx <= 0) return;
     const int z1lo = max(dz, 0), y1lo = max(dy, 0), x1lo = max(dx, 0);
     const int z2lo = max(-dz, 0), y2lo = max(-dy, 0), x2lo = max(-dx, 0);
-    const uint32_t seed = (uint32_t)(az + G.oz) * (uint32_t)(bz + G.oz) * (uint32_t)(ay + G.oy) *
-                          (uint32_t)(by + G.oy) * (uint32_t)(ax + G.ox) * (uint32_t)(bx + G.ox);
+    const uint32_t seed = pair_seed(G, az, ay, ax, bz, by, bx);
     for (int w = lane; w < 2 * words + 2; w += 64) fa[w] = 0u;
     __builtin_amdgcn_wave_barrier();
     {

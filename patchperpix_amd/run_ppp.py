@@ -67,10 +67,40 @@ def vote_instances_sample(config, pred_folder, output_folder, sample):
                                aff_key=pred.get("aff_key"), fg_key=pred.get("fg_key"))
 
 
+def label_batched(config, pred_folder, output_folder, samples):
+    """`label` with ``[vote_instances] batch_2d = N``: 2-d samples of equal shape are voted N at a
+    time in one call (vote_instances.do_all_batched); the result files are those of a run
+    without it."""
+    from . import vote_instances as vi
+    cfg = dict(config["vote_instances"], result_folder=output_folder, check_required=False)
+    out_fmt = cfg.get("output_format", "hdf")
+    pred_fmt = config["prediction"]["output_format"]
+    todo = []
+    for sample in samples:
+        output_fn = os.path.join(output_folder, os.path.basename(sample) + "." + out_fmt)
+        if not config.get("general", {}).get("overwrite", False) and os.path.exists(output_fn):
+            logger.info("Skipping vote instances for %s. Already exists!", output_fn)
+            continue
+        todo.append(os.path.join(pred_folder, sample + "." + pred_fmt))
+    if not todo:
+        return
+    pred = config["prediction"]
+    cfg.pop("affinities", None)
+    vi.vote_instances.main(**cfg, **config["model"], aff_files=todo, numinst_key=pred.get("numinst_key"),
+                           aff_key=pred.get("aff_key"), fg_key=pred.get("fg_key"))
+
+
 def label(args, config):
     samples = get_list_samples(args.pred_folder, config["prediction"]["output_format"],
                                args.sample)
     os.makedirs(args.output_folder, exist_ok=True)
+    cfg = config["vote_instances"]
+    if int(cfg.get("batch_2d") or 0) > 1 and not cfg.get("blockwise", False):
+        t0 = time.time()
+        label_batched(config, args.pred_folder, args.output_folder, samples)
+        logger.info("time vote_instances (batch_2d = %d, %d samples): %.2fs", int(cfg["batch_2d"]),
+                    len(samples), time.time() - t0)
+        return
     for idx, sample in enumerate(samples):
         t0 = time.time()
         print("labelling {}/{}: {}".format(idx, len(samples), sample))

@@ -48,6 +48,16 @@ def halo(patchshape):
     return 2 * pz + pz // 2
 
 
+def plan_slice_chunks(n_slices, per_slice_bytes, free_bytes):
+    """Slices per chunk of a stack of independent 2-d images (vote_instances/batch2d.py): as many
+    as fit `free_bytes` at `per_slice_bytes` each, at least one.  The images share nothing, so a
+    chunk is whole slices with no halo, and every chunk is one batch."""
+    if n_slices <= 0:
+        return 1
+    fit = int(max(free_bytes, 0) // max(int(per_slice_bytes), 1))
+    return max(1, min(int(n_slices), fit))
+
+
 def plan_slabs(Z, n_slabs):
     """n_slabs contiguous z-ranges covering [0, Z)."""
     n_slabs = max(1, min(int(n_slabs), int(Z)))

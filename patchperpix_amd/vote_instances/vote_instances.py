@@ -128,8 +128,16 @@ def to_instance_seg(pred_affs, foreground, mask_to_cover, numinst, patchshape, *
     (the three fields may also be device tensors, resident like the prediction)
     Returns (instances uint16 (Z,Y,X), foreground uint8) -- or (pairs uint32 [N,6],
     aff float32 [N]) with ``return_intermediates`` -- with the reference's early-outs.
+
+    ``independent_slices=True`` (2-d patches only): the Z axis is a stack of N independent 2-d
+    images, voted in one batch; slice k of the result is, bit for bit, what a call on slice k
+    alone returns (batch2d.py).  With ``return_intermediates`` a list of N per-slice (pairs, aff).
     """
     import torch
+    if kwargs.pop("independent_slices", False):
+        from . import batch2d
+        return batch2d.to_instance_seg_slices(pred_affs, foreground, mask_to_cover, numinst, patchshape,
+                                              **kwargs)
     # cuda=False selects the reference's NumPy SEMANTICS (int16 votes, integer ranks, all-pairs
     # graph weights: a different function, numpy_semantics.py) -- computed on the device as well;
     # nothing in this package falls back to the CPU
@@ -409,6 +417,61 @@ def do_all(aff_file, patchshape=np.array([1, 25, 25]), **kwargs):
     write_result(out_fn, {res_key + res_ext: instances, 'vote_foreground' + res_ext: foreground})
 
 
+def do_all_batched(aff_files, patchshape=np.array([1, 25, 25]), batch_2d=16, **kwargs):
+    """do_all for many prediction files: 2-d samples (Z = 1) of equal shape and dtype are voted
+    up to `batch_2d` at a time in one ``independent_slices`` call; each sample's result file is
+    written exactly as do_all writes it.  Everything else goes through do_all one by one.
+    A group is voted and written as soon as it holds `batch_2d` samples (the rest of every group
+    at the end): at most (distinct shapes x batch_2d) predictions are held at a time."""
+    if type(patchshape) is not np.ndarray:
+        patchshape = np.array(patchshape)
+    res_ext = getResKey(**kwargs) if kwargs.get('add_suffix', False) else ''
+    res_key = kwargs.get('res_key', 'vote_instances')
+    batch_2d = max(1, int(batch_2d))
+
+    def vote_and_write(part):
+        pred = np.concatenate([m[1] for m in part], axis=1)
+        fg = np.concatenate([m[3] for m in part])
+        ni = np.concatenate([m[2] for m in part])
+        inst, fg_out = to_instance_seg(pred, fg, np.copy(fg), ni, patchshape, independent_slices=True, **kwargs)
+        for k, (aff_file, _, _, _) in enumerate(part):
+            instances, foreground = inst[k:k + 1], fg_out[k:k + 1].astype(np.uint8)
+            if kwargs.get('crop_to_foreground', True):
+                instances[..., foreground == 0] = 0
+            fn = os.path.splitext(os.path.basename(aff_file))[0]
+            write_result(os.path.join(kwargs['result_folder'], fn + ".hdf"),
+                         {res_key + res_ext: instances, 'vote_foreground' + res_ext: foreground})
+
+    groups = {}
+    for aff_file in aff_files:
+        if int(patchshape[0]) != 1:
+            do_all(aff_file, patchshape=patchshape, **kwargs)
+            continue
+        loaded = loadAffinities(aff_file, res_ext, patchshape=patchshape, **kwargs)
+        if loaded is None:
+            continue
+        affinities, numinst, foreground = loaded
+        if foreground.ndim == 4:
+            foreground = foreground[0]
+        if foreground.shape[0] != 1:
+            del loaded, affinities, numinst, foreground
+            do_all(aff_file, patchshape=patchshape, **kwargs)
+            continue
+        if numinst is None:
+            numinst = np.copy(foreground)
+        key = (tuple(np.shape(affinities)), str(np.asarray(affinities).dtype), str(numinst.dtype))
+        members = groups.setdefault(key, [])
+        members.append((aff_file, affinities, numinst, foreground))
+        del loaded, affinities, numinst, foreground
+        if len(members) == batch_2d:
+            vote_and_write(members)
+            members.clear()
+    for members in groups.values():
+        if members:
+            vote_and_write(members)
+            members.clear()
+
+
 def write_result(out_fn, datasets):
     """HDF5 (the reference's format, vote_instances.py:542-554) through h5py or the HDF5 C library;
     without either a zarr store ``<stem>.zarr`` with the same dataset names, dtypes and attributes
@@ -440,6 +503,17 @@ def main(**kwargs):
     os.makedirs(args['result_folder'], exist_ok=True)
 
     source = args['affinities']
+    if args.get('aff_files') is not None:
+        # a list of prediction files (run_ppp's `label` with [vote_instances] batch_2d)
+        files = [f for f in args.pop('aff_files')]
+        args.pop('affinities', None)
+        if int(args.get('batch_2d') or 0) > 1:
+            do_all_batched(files, **args)
+        else:
+            for aff_file in files:
+                do_all(aff_file, **args)
+        delete_cuda(args.get('context'))
+        return
     if source is not None and (source.endswith(".zarr") or os.path.isfile(source)):
         do_all(source, **args)          # (the reference returns here without delete_cuda, :584-586)
         return
