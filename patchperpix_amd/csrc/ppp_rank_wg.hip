@@ -59,6 +59,23 @@
 //     v_fma_f32; a conflict-free ds_read_b32 costs the CU 2.6 cycles; with 1 / 2 / 3 / 4 resident
 //     workgroups per CU the 112 x 176 x 176 launch takes 579 / 348 / 279 / 248 ms (a fifth would
 //     give ~6 %); without masks, table and row reads at all it takes 180 ms.
+//
+// Round 7, the default benchmark's launch (140^3 centres, 7^3; profiles/r07_b_*):
+//   * kept: the items of a row dealt to the lanes by bank (rank_deal_table_kernel; 7^3 only) and the lightest
+//     tiles of a launch's part-filled last round split into halves (rw_choose_splits): the S2 call
+//     66.7 -> 55.6 ms (59.9 with the dealing alone), the kernel 64.0 -> 52.4 ms; SQ_LDS_BANK_CONFLICT /
+//     SQ_LDS_IDX_ACTIVE 8.22e9 / 20.23e9 = 0.41 -> 3.06e9 / 15.56e9 = 0.20 (tools/s2_bank_sim.py: 0.44 ->
+//     0.20), SQ_WAIT_ANY / SQ_WAVE_CYCLES 0.60 -> 0.63, FETCH_SIZE 65 -> 86 GB (the lanes of a chunk no
+//     longer hold whole x-runs of centres: their mask loads touch more lines).  The dealing also takes the
+//     kernel from 100 to 95 VGPRs -- FIVE workgroups per CU instead of four (the divisions by nx, ny of the
+//     enumeration are gone) -- and five are faster than four here: 59.9 against 64.0 ms with the fifth kept
+//     out by unused LDS.
+//   * dropped: splitting the HEAVIEST tiles (64.3 ms: their halves are dealt in the middle of the launch and
+//     the whole light tiles still run last and alone); splitting fewer tiles than the last round holds (12 of
+//     23 per XCD: 59.9 ms, no gain) or many more (46: 57.5, 80: 57.9, every tile: 62.5 ms); 8 x 8 x 16 or
+//     16 x 8 x 16 tiles for the whole launch (66.4 / 66.1 against 66.5 ms on the parent).
+//   * not done: the XCDs of the launch still end between 36 and 56 ms (the y-edge slabs of the y-major
+//     numbering are light): ranges of equal WEIGHT instead of equal tile count would need slots to spare.
 #include <stdlib.h>
 #include <string.h>
 
@@ -83,12 +100,24 @@ namespace ppp {
 // half-wave straddles the step from the last az of one ay to the first of the next.
 // (-DPPP_RW_ZRUNS=0: the old enumeration and image.)
 // Measured (tools/time_s2.py, profiles/r04_j_s2_zruns.txt): 9^3 190 -> 166 ms at 128^3, 102 -> 84 ms
-// at 96^3; 7^3 (plane stride 169 = 9 mod 32 already, conflicts mild before) 62.2 -> 64.7 ms at
-// 140^3 -- so only 9^3 takes it.  With all nine az present (rows in the z-interior of a tile at
+// at 96^3; 7^3 62.2 -> 64.7 ms at 140^3 -- so only 9^3 takes it.  At 7^3 the conflicts were as bad as at
+// 9^3 -- SQ_LDS_BANK_CONFLICT 8.46e9 of SQ_LDS_IDX_ACTIVE 20.75e9, 41 % of the LDS cycles, at 140^3
+// (profiles/r07_a_bench_flylight140_p7_pmc_sq.txt) -- and the z-runs do not remove them there: a tile is 8
+// thick, so most rows have fewer than seven az (or ax) and the lattice of runs breaks; counted per row
+// class on the CPU (tools/s2_bank_sim.py) the share of conflict passes is 0.44 for x-runs on strides
+// 13 / 169, 0.38 at best for z-runs, 0.33 at best for any of the six enumerations on any pair of strides
+// (x-runs, line stride 39, plane stride 529), 0.30 with the enumeration chosen per row, and 0.10 with x-runs
+// padded to 8 lanes on a line stride of 40 -- which walks 1.4 x the chunks.  7^3 therefore deals its items
+// BY BANK (PPP_RW_BANKDEAL, round 7): 0.20 predicted on the unchanged image with the dense number of chunks.  With all nine az present (rows in the z-interior of a tile at
 // least 9 thick) the step to the next ay continues the lattice (81 = 17 mod 32 = the y stride):
 // the 16 x 8 x 16 tile has half of its items in such rows.
 #ifndef PPP_RW_ZRUNS
 #define PPP_RW_ZRUNS(PX) ((PX) == 9)
+#endif
+// Round 7, 7^3: the items of a row are dealt to the lanes BY BANK (see rank_deal_table_kernel below).
+// (-DPPP_RW_BANKDEAL(PX)=0: the enumeration above for every patch size.)
+#ifndef PPP_RW_BANKDEAL
+#define PPP_RW_BANKDEAL(PX) ((PX) == 7)
 #endif
 static constexpr int RW_PAD = 8;
 #ifndef PPP_RW_WAVES
@@ -352,21 +381,99 @@ __global__ void __launch_bounds__(256)
     }
 }
 // one workgroup per XCD range: its tiles in descending order of weight (position = the number of tiles
-// of the range that come before: heavier, or as heavy with a smaller index)
+// of the range that come before: heavier, or as heavy with a smaller index).
+// Round 7, split tiles: the `splits` lightest tiles of the range -- those that the dispatcher hands out last,
+// into the launch's part-filled last round -- become two RECORDS each, the tile's lower and upper half in y
+// (the kernel takes ragged tiles, a half is a tile of TY / 2 lines), weighed at half the tile; the records
+// are dealt heaviest first.  record = tile | RW_HALF_LO / RW_HALF_HI; an XCD's range
+// of the order array has per_xcd + splits slots.
+static constexpr int32_t RW_HALF_LO = 1 << 28, RW_HALF_HI = 2 << 28, RW_TILE_MASK = (1 << 28) - 1;
 __global__ void __launch_bounds__(256)
-    rank_tile_order_kernel(const int32_t *__restrict__ weight, const int n_tiles, const int per_xcd,
+    rank_tile_order_kernel(const int32_t *__restrict__ weight, const int n_tiles, const int per_xcd, const int splits,
                            int32_t *__restrict__ order) {
     __shared__ int32_t w[RW_ORDER_MAX / 8 + 8];
+    __shared__ int32_t key[RW_ORDER_MAX / 8 + 8];      // weight of the tile's records; bit 30: the tile is split
     const int lo = blockIdx.x * per_xcd, hi = min(lo + per_xcd, n_tiles), n = max(hi - lo, 0);
+    const int slot0 = blockIdx.x * (per_xcd + splits);
     for (int i = threadIdx.x; i < n; i += blockDim.x) w[i] = weight[lo + i];
+    for (int t = threadIdx.x; t < per_xcd + splits; t += blockDim.x) order[slot0 + t] = -1;
     __syncthreads();
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
         const int wi = w[i];
-        int before = 0;
-        for (int j = 0; j < n; ++j) before += (w[j] > wi || (w[j] == wi && j < i)) ? 1 : 0;
-        order[lo + before] = lo + i;
+        int before = 0, with_work = 0;
+        for (int j = 0; j < n; ++j) {
+            before += (w[j] > wi || (w[j] == wi && j < i)) ? 1 : 0;
+            with_work += w[j] > 0 ? 1 : 0;
+        }
+        // (the tiles without work rank last and leave at once: the lightest WITH work are split)
+        key[i] = (wi > 0 && before >= with_work - splits) ? (((wi + 1) >> 1) | (1 << 30)) : wi;
     }
-    for (int t = lo + n + threadIdx.x; t < lo + per_xcd; t += blockDim.x) order[t] = -1;
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int ki = key[i] & ~(1 << 30);
+        int before = 0;
+        for (int j = 0; j < n; ++j) {
+            const int kj = key[j] & ~(1 << 30), cj = (key[j] >> 30) + 1;
+            before += (kj > ki || (kj == ki && j < i)) ? cj : 0;
+        }
+        if (key[i] >> 30) {
+            order[slot0 + before] = (lo + i) | RW_HALF_LO;
+            order[slot0 + before + 1] = (lo + i) | RW_HALF_HI;
+        } else {
+            order[slot0 + before] = lo + i;
+        }
+    }
+    // (fewer records than slots where the range is short or has fewer tiles with work than `splits`: the
+    // slots are cleared first, the records written after the barrier)
+
+}
+
+// ---- items dealt by bank (round 7) -----------------------------------------------------------
+// A lane reads the row image at base - (az SZ + ay SY + ax) + immediate: the banks of one read are those of
+// the lanes' (ax + SY ay + SZ az) mod 32, whatever the partner.  A row of a tile is a box of nx x ny x nz
+// items, n = 1 .. P per axis (P only where the voxel lies at least the radius inside the tile): P^3 classes
+// of rows.  For every class this kernel writes which item the lane of slot i0 + lane takes: lane l of a
+// half-wave takes items of bank class l -- half-wave k the k-th such item in (az, ay) order -- so a
+// half-wave is conflict-free by construction.  The row keeps its dense number of chunks, ceil(n / 64): where
+// a bank class holds more items than the row has half-waves, the surplus goes, in order, to the lanes left
+// empty (each costs its half-wave one further pass -- far less than a chunk more for the whole wave).
+// tools/s2_bank_sim.py restates this dealing and counts the passes.
+// entry: bit 15 = the slot holds an item, az << 8 | ay << 4 | ax relative to the row's first item.
+static constexpr int rw_deal_slots(int P) { return (P * P * P + 63) / 64 * 64; }
+static size_t rw_deal_bytes(int P) { return PPP_RW_BANKDEAL(P) ? (size_t)P * P * P * rw_deal_slots(P) * 2 : 0; }
+template <int P>
+__global__ void __launch_bounds__(32) rank_deal_table_kernel(uint16_t *__restrict__ T, const int SY, const int SZ) {
+    constexpr int SLOTS = rw_deal_slots(P), MAXOVER = 16;
+    __shared__ uint16_t slot[SLOTS];
+    __shared__ uint16_t over[32][MAXOVER];
+    __shared__ int n_over[32];
+    const int cls = blockIdx.x, r = threadIdx.x;
+    const int nx = cls % P + 1, ny = (cls / P) % P + 1, nz = cls / (P * P) + 1;
+    const int H = (nx * ny * nz + 63) / 64 * 2;
+    for (int i = r; i < SLOTS; i += 32) slot[i] = 0;
+    __syncthreads();
+    int k = 0;
+    for (int az = 0; az < nz; ++az)
+        for (int ay = 0; ay < ny; ++ay) {
+            const int ax = (r - SY * ay - SZ * az) & 31;
+            if (ax >= nx) continue;
+            const uint16_t e = (uint16_t)(0x8000 | (az << 8) | (ay << 4) | ax);
+            if (k < H) slot[32 * k + r] = e;
+            else if (k - H < MAXOVER) over[r][k - H] = e;     // (a class holds at most ceil(P^3 / 32) + 1 items)
+            ++k;
+        }
+    n_over[r] = k > H ? min(k - H, MAXOVER) : 0;
+    __syncthreads();
+    if (r == 0) {
+        int f = 0;
+        for (int rr = 0; rr < 32; ++rr)
+            for (int o = 0; o < n_over[rr]; ++o) {
+                while (f < 32 * H && slot[f] != 0) ++f;
+                if (f < 32 * H) slot[f] = over[rr][o];
+            }
+    }
+    __syncthreads();
+    for (int i = r; i < SLOTS; i += 32) T[(size_t)cls * SLOTS + i] = slot[i];
 }
 
 // ---- main kernel ---------------------------------------------------------------------------
@@ -376,7 +483,7 @@ __global__ void __launch_bounds__(64 * RW_WAVES, PPP_RW_MINWAVES(PX))
                    const uint32_t *__restrict__ info, const uint8_t *__restrict__ valid,
                    float *__restrict__ score, const ppp_box sb, const Geo G, const int tiles_y,
                    const int tiles_x, const int n_tiles, const int *__restrict__ any_e,
-                   const int32_t *__restrict__ order, const int y_major
+                   const int32_t *__restrict__ order, const int y_major, const uint16_t *__restrict__ dealT
 #ifdef PPP_RW_STAMPS
                    , uint32_t *__restrict__ stamps
 #endif
@@ -386,7 +493,8 @@ __global__ void __launch_bounds__(64 * RW_WAVES, PPP_RW_MINWAVES(PX))
 #ifdef PPP_RW_STAMPS
     // (diagnostic build -DPPP_RW_STAMPS, tools/s2_wg_times.py: when does every workgroup start and
     // end, and on which CU -- the tile weights' array of the workspace is free once the order is made)
-    const unsigned long long t_start = __builtin_readcyclecounter();
+    // (wall_clock64: the 100 MHz counter the whole device shares -- the cycle counter is a clock per CU)
+    const unsigned long long t_start = wall_clock64();
 #endif
     constexpr int C = PZ * PY * PX, W16 = (C + 15) / 16, RZ = PZ / 2, RY = PY / 2, RX = PX / 2;
     constexpr int W16P = P1 ? rw_p1_words(C) : rw_mask_words(C);   // mask words per centre in M
@@ -417,12 +525,15 @@ __global__ void __launch_bounds__(64 * RW_WAVES, PPP_RW_MINWAVES(PX))
     const int per_xcd = (n_blocks + 7) / 8;
     const int slot = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
     // (heavy tiles first within the XCD's range when the launcher made an order)
-    const int bid = order ? order[slot] : slot;
-    if (bid < 0 || bid >= n_tiles) return;
+    const int rec = order ? order[slot] : slot;
+    if (rec < 0) return;
+    // (a record of the order is a tile or, round 7, the lower / upper half in y of a split tile)
+    const int bid = rec & RW_TILE_MASK, half_hi = (rec & RW_HALF_HI) ? 1 : 0, halved = (rec & (RW_HALF_LO | RW_HALF_HI)) ? 1 : 0;
+    if (bid >= n_tiles) return;
     int tx_i, ty_i, tz_i;
     rw_tile_decode(bid, n_tiles, tiles_y, tiles_x, y_major, tz_i, ty_i, tx_i);
-    const int c0z = sb.z0 + tz_i * TZ, c0y = sb.y0 + ty_i * TY, c0x = sb.x0 + tx_i * TX;
-    const int tz = min(TZ, sb.z1 - c0z), ty = min(TY, sb.y1 - c0y), tx = min(TX, sb.x1 - c0x);
+    const int c0z = sb.z0 + tz_i * TZ, c0y = sb.y0 + ty_i * TY + half_hi * (TY / 2), c0x = sb.x0 + tx_i * TX;
+    const int tz = min(TZ, sb.z1 - c0z), ty = min(halved ? TY / 2 : TY, sb.y1 - c0y), tx = min(TX, sb.x1 - c0x);
     if (tz <= 0 || ty <= 0 || tx <= 0) return;
 
     auto sb_index = [&](int lz, int ly, int lx) -> long long {
@@ -491,7 +602,7 @@ __global__ void __launch_bounds__(64 * RW_WAVES, PPP_RW_MINWAVES(PX))
     // geometry of a row (which pixels a of voxel u have their centre in the tile) and of the item a
     // lane takes in chunk i0 of it -- functions of the row index, so that the masks of the NEXT
     // chunk (of this row or of the next) can be requested ahead
-    struct RowG { int uz, uy, ux, az0, ay0, ax0, nz, ny, nx, n_box; };
+    struct RowG { int uz, uy, ux, az0, ay0, ax0, nz, ny, nx, n_box, cls; };
     struct ItemG { bool in; int cl, a, az, ay, ax; long long t, q0; };
     auto row_geom = [&](int k) -> RowG {
         RowG r;
@@ -503,16 +614,25 @@ __global__ void __launch_bounds__(64 * RW_WAVES, PPP_RW_MINWAVES(PX))
         r.ny = min(PY - 1, r.uy + RY - c0y) - r.ay0 + 1;
         r.nx = min(PX - 1, r.ux + RX - c0x) - r.ax0 + 1;
         r.n_box = (r.nz <= 0 || r.ny <= 0 || r.nx <= 0) ? 0 : r.nz * r.ny * r.nx;
+        r.cls = r.n_box ? ((r.nz - 1) * PY + (r.ny - 1)) * PX + (r.nx - 1) : 0;      // (its class in the dealing table)
         return r;
     };
     auto item_geom = [&](const RowG &r, int i0) -> ItemG {
         ItemG g;
         const int i = i0 + lane;
+        if constexpr (PPP_RW_BANKDEAL(PX)) {
+            // (dealt by bank: i0 + lane < 64 ceil(n_box / 64) <= the slots of a class; an empty slot reads
+            // the row's first item, like a lane beyond the row in the enumeration below)
+            const uint32_t e = dealT[r.cls * rw_deal_slots(PX) + i];
+            g.in = (e >> 15) != 0;
+            g.ax = r.ax0 + (int)(e & 15u); g.ay = r.ay0 + (int)((e >> 4) & 15u); g.az = r.az0 + (int)((e >> 8) & 15u);
+        } else {
         g.in = i < r.n_box;
         const int ii = g.in ? i : 0;
         g.ax = r.ax0 + ii % r.nx;
         g.ay = PPP_RW_ZRUNS(PX) ? r.ay0 + ii / (r.nx * r.nz) : r.ay0 + (ii / r.nx) % r.ny;
         g.az = PPP_RW_ZRUNS(PX) ? r.az0 + (ii / r.nx) % r.nz : r.az0 + ii / (r.nx * r.ny);
+        }
         const int lz = r.uz + RZ - g.az - c0z, ly = r.uy + RY - g.ay - c0y, lx = r.ux + RX - g.ax - c0x;
         g.cl = (lz * TY + ly) * TX + lx;
         g.a = (g.az * PY + g.ay) * PX + g.ax;
@@ -747,15 +867,15 @@ __global__ void __launch_bounds__(64 * RW_WAVES, PPP_RW_MINWAVES(PX))
     }
 #ifdef PPP_RW_STAMPS
     if (tid == 0 && stamps && blockIdx.x < RW_ORDER_MAX / 4) {
-        const unsigned long long t_end = __builtin_readcyclecounter();
+        const unsigned long long t_end = wall_clock64();
         unsigned hw_id;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_id));
-        unsigned xcc_id;          // (s_memtime is a counter per XCD: the tool needs to know whose clock a stamp is)
+        unsigned xcc_id;          // (the tool reports per XCD)
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc_id));
-        stamps[4 * blockIdx.x + 0] = (uint32_t)(t_start >> 8);     // (256-cycle units: 32 bits hold minutes)
-        stamps[4 * blockIdx.x + 1] = (uint32_t)(t_end >> 8);
+        stamps[4 * blockIdx.x + 0] = (uint32_t)t_start;     // (10 ns units: 32 bits hold 42 s)
+        stamps[4 * blockIdx.x + 1] = (uint32_t)t_end;
         stamps[4 * blockIdx.x + 2] = hw_id;
-        stamps[4 * blockIdx.x + 3] = (uint32_t)bid | ((xcc_id & 0xFu) << 24);
+        stamps[4 * blockIdx.x + 3] = (uint32_t)bid | ((xcc_id & 0xFu) << 24) | ((uint32_t)halved << 23);
     }
 #endif
 }
@@ -773,7 +893,45 @@ bool rank_wg_supported(const Geo &G) {
 size_t rank_wg_workspace_bytes(const ppp_box &sb, const Geo &G) {
     const size_t sbV = (size_t)(sb.x1 - sb.x0) * (sb.y1 - sb.y0) * (sb.z1 - sb.z0);
     return up256w(rw_mask_bytes(sb.z1 - sb.z0, sb.y1 - sb.y0, sb.x1 - sb.x0, G.C)) + up256w(sbV * 4) + up256w((size_t)G.V) + 256 +
-           2 * (size_t)RW_ORDER_MAX * 4;
+           2 * (size_t)RW_ORDER_MAX * 4 + up256w(rw_deal_bytes(G.px));
+}
+
+// ---- how many tiles of a launch to split (round 7) ---------------------------------------------
+// Every XCD deals its range of tiles, heaviest first, to the workgroups its 32 CUs hold at a time, and a launch
+// ends with its last workgroup.  140^3 centres are 183 tiles of 8 x 16 x 16 per XCD: one round, and a second one
+// that is a fraction full (per-workgroup stamps, 7^3 at four workgroups per CU: 41 % of the launch's CU time
+// with fewer than four resident, 16 % with none).  The tiles of the last round are the lightest, and they run
+// alone on their CUs: cut in two they run side by side in half the time.  So the lightest k tiles are split,
+// k = the tiles beyond the launch's last full round -- unless their halves would not fit that round either;
+// a launch of less than one round is left alone.  A half costs 0.57 of a tile (it stages (8 + 2 r) / (16 + 2 r)
+// of the tile's rows for half of its items), which is why nothing else is split.  From the box shape and the
+// kernel's occupancy alone, so that the grid is known when the launch is made.
+static int rw_choose_splits(int tiles_per_xcd, int slots_per_xcd) {
+    if (slots_per_xcd <= 0 || tiles_per_xcd <= slots_per_xcd) return 0;
+    const int rem = tiles_per_xcd % slots_per_xcd;
+    return 2 * rem <= slots_per_xcd ? rem : 0;
+}
+// workgroups of the 8 x 16 x 16 kernel a CU holds (registers and LDS; asked once per patch size)
+template <int P>
+static int rw_resident_per_cu() {
+    static thread_local int memo = 0;
+    if (memo == 0) {
+        int nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rank_wg_kernel<P, P, P, 8, 16, 16, false>, 64 * RW_WAVES, 0) != hipSuccess || nb < 1)
+            nb = PPP_RW_MINWAVES(P);
+        memo = nb;
+    }
+    return memo;
+}
+static int rw_cus_per_xcd() {
+    static thread_local int memo = 0;
+    if (memo == 0) {
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8)
+            cus = 256;
+        memo = cus / 8;
+    }
+    return memo;
 }
 
 template <typename T>
@@ -829,12 +987,26 @@ static hipError_t launch_rwg(const T *pred, const float *S, const uint8_t *ov, f
     const int TZ = tall ? 16 : 8, TY = tall ? 8 : (big ? 16 : 8), TX = 16;
     const int tiles_z = (sZ + TZ - 1) / TZ, tiles_y = (sY + TY - 1) / TY, tiles_x = (sX + TX - 1) / TX;
     const long long n_tiles = (long long)tiles_z * tiles_y * tiles_x;
-    const long long n_blocks = (n_tiles + 7) / 8 * 8;
-    PPP_GRID_CHECK(n_blocks, 64 * RW_WAVES);
+    const int per_xcd = (int)((n_tiles + 7) / 8);
     // heavy tiles first (PPP_RANK_ORDER=0: spatial order)
     static EnvSwitch order_sw("PPP_RANK_ORDER");
     int32_t *weight = (int32_t *)((char *)any_e + 256), *order = weight + RW_ORDER_MAX;
+    uint16_t *dealT = (uint16_t *)(order + RW_ORDER_MAX);
     if (n_tiles > RW_ORDER_MAX || (order_sw.get() && order_sw.get()[0] == '0')) order = nullptr;
+    // 8 x 16 x 16 tiles by the rule above: the lightest tiles of every XCD's range are split in two so that the
+    // launch's last round runs halves side by side instead of a few whole tiles (rw_choose_splits).
+    // PPP_RANK_WG_SPLIT=<tiles per XCD> overrides (0: whole tiles only), also with a forced tile shape.
+    static EnvSwitch split_sw("PPP_RANK_WG_SPLIT");
+    int splits = 0;
+    if (order) {
+        if (split_sw.get() && split_sw.get()[0] >= '0' && split_sw.get()[0] <= '9') splits = atoi(split_sw.get());
+        else if (big && !tall && !tile_sw.get() && !G.rank_tile)
+            splits = rw_choose_splits(per_xcd, rw_cus_per_xcd() * (G.px == 5 ? rw_resident_per_cu<5>() : (G.px == 7 ? rw_resident_per_cu<7>() : rw_resident_per_cu<9>())));
+        splits = splits < per_xcd ? splits : per_xcd;
+        if (8LL * (per_xcd + splits) > RW_ORDER_MAX) splits = RW_ORDER_MAX / 8 - per_xcd;
+    }
+    const long long n_blocks = 8LL * (per_xcd + splits);
+    PPP_GRID_CHECK(n_blocks, 64 * RW_WAVES);
     const bool by_centres = order_sw.get() && order_sw.get()[0] == 'c';
     static EnvSwitch major_sw("PPP_RANK_TILE_MAJOR");
     const int y_major = (major_sw.get() && major_sw.get()[0] == 'z') ? 0 : 1;
@@ -848,7 +1020,7 @@ static hipError_t launch_rwg(const T *pred, const float *S, const uint8_t *ov, f
 #endif
 #define PPP_RW_LAUNCH1(A_, D_, E_, F_, P1_)                                                                 \
     rank_wg_kernel<A_, A_, A_, D_, E_, F_, P1_><<<dim3((unsigned)n_blocks), dim3(64 * RW_WAVES), dyn_lds, s>>>( \
-        S, M, info, valid, score, sb, G, tiles_y, tiles_x, (int)n_tiles, p1 ? any_e : nullptr, order, y_major PPP_RW_STAMP_ARG)
+        S, M, info, valid, score, sb, G, tiles_y, tiles_x, (int)n_tiles, p1 ? any_e : nullptr, order, y_major, dealT PPP_RW_STAMP_ARG)
 #define PPP_RW_LAUNCH(A_, D_, E_, F_)                                                                       \
     do {                                                                                                    \
         if (p1 && pass == 0) PPP_RW_LAUNCH1(A_, D_, E_, F_, true);                                          \
@@ -862,6 +1034,9 @@ static hipError_t launch_rwg(const T *pred, const float *S, const uint8_t *ov, f
         break;
     // pass 0: the one-bit form (when possible); then the two-bit pre-pass and kernel -- both return
     // at once unless the one-bit pre-pass found a partner that equals the threshold
+    // (the dealing table of the row classes; the strides are those of the kernel's row image)
+    if (PPP_RW_BANKDEAL(7) && G.px == 7)
+        rank_deal_table_kernel<7><<<dim3(7 * 7 * 7), dim3(32), 0, s>>>(dealT, 2 * 7 - 1, (2 * 7 - 1) * (2 * 7 - 1));
     for (int pass = p1 ? 0 : 1; pass < 2; ++pass) {
         if (pass == 1)
             rank_masks_il_kernel<T><<<dim3((unsigned)((sbV + 255) / 256)), dim3(256), 0, s>>>(pred, ov, sb, M, info, score,
@@ -869,7 +1044,7 @@ static hipError_t launch_rwg(const T *pred, const float *S, const uint8_t *ov, f
         if (order && pass == (p1 ? 0 : 1)) {      // (`info` is the same from either pre-pass)
             rank_tile_weight_kernel<<<dim3((unsigned)n_tiles), dim3(256), 0, s>>>(info, valid, sb, TZ, TY, TX, tiles_y, tiles_x,
                                                                                   by_centres ? 1 : 0, y_major, weight, G);
-            rank_tile_order_kernel<<<dim3(8), dim3(256), 0, s>>>(weight, (int)n_tiles, (int)(n_blocks / 8), order);
+            rank_tile_order_kernel<<<dim3(8), dim3(256), 0, s>>>(weight, (int)n_tiles, per_xcd, splits, order);
         }
 #ifdef PPP_RW_STAMPS
         (void)hipMemsetAsync(weight, 0, (size_t)RW_ORDER_MAX * 4, s);      // (the weights are spent: room for the stamps)
