@@ -169,6 +169,32 @@ int ppp_consensus_rows(const void *d_pred, int pred_dtype, const uint8_t *d_over
 int ppp_consensus_part(const void *d_pred, int pred_dtype, const uint8_t *d_overlap, float *d_cons,
                        const ppp_params *p, const ppp_box *part, void *stream);
 
+/* S1 on SPARSE foreground (tubes: a few percent of the volume).  The reference's thread returns at
+ * once when its voxel is not foreground (fillConsensusArray.cu:25-32); the packed kernel votes for
+ * every work item (run of 64 base voxels x 2 slices, offset row (dz, dy)) and masks when it writes.
+ * An item is ACTIVE iff some base voxel u of the run is valid foreground AND some w = u + (dz, dy, dx)
+ * inside the volume is; every other item stores only +0.0f.
+ * Bytes of device work space ppp_consensus_sparse needs for these parameters and this part (NULL =
+ * cons_box): validity bits, item flags, the item list.  0 when the packed kernel does not serve the
+ * parameters (ppp_consensus_writes_voxel_major; COMPACT or VOXEL_MAJOR only) -- use the dense
+ * entry points then.  (fillConsensusArray.cu:25-32) */
+int64_t ppp_consensus_sparse_workspace_bytes(const ppp_params *p, const ppp_box *part);
+/* ppp_consensus (part NULL, open_rows 0), ppp_consensus_rows (part NULL, open_rows 1) or
+ * ppp_consensus_part (part given; d_count NULL) with the work taken from item lists: a pre-pass
+ * flags the active items from the centre channel and the overlap mask alone, the packed kernel runs
+ * over the active ones and a light kernel stores the zeros the others owe -- the same entries, bit
+ * for bit, as the dense call writes (the output stays fully overwritten).
+ * mode 0 = auto: one device -> host read of the active count; at or above the measured break-even
+ *          share the dense launch of today is made (same kernel, same grid), below it the lists;
+ * mode 1 = always the lists.  Synchronises `stream` once (the count).
+ * The reference's per-thread foreground return: fillConsensusArray.cu:25-32. */
+int ppp_consensus_sparse(const void *d_pred, int pred_dtype, const uint8_t *d_overlap, float *d_cons,
+                         float *d_count, const ppp_params *p, const ppp_box *part, int open_rows, void *d_work,
+                         int mode, void *stream);
+/* what the last ppp_consensus_sparse call counted and chose: all items, active items, 1 when it
+ * launched over the lists (the per-item form of the return at fillConsensusArray.cu:25-32) */
+void ppp_consensus_last_items(int64_t *total, int64_t *active, int *took_lists);
+
 /* --- S2: patch ranking ---------------------------------------------------------------
  * replaces rank_patches_cuda (ranked_patches.py:33-74) + kernel rankPatches
  * (cuda/rankPatches.cu:1-161).  Scores are written for the voxels of `score_box`

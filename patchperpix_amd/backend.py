@@ -97,6 +97,12 @@ _SIGNATURES = {
     "ppp_consensus_part": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.POINTER(Params), ctypes.POINTER(Box),
                                           ctypes.c_void_p]),
+    "ppp_consensus_sparse_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(Params), ctypes.POINTER(Box)]),
+    "ppp_consensus_sparse": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.POINTER(Params), ctypes.POINTER(Box),
+                                            ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "ppp_consensus_last_items": (None, [ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                        ctypes.POINTER(ctypes.c_int)]),
     "ppp_cons_planes_to_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Box), ctypes.c_void_p,
                                                ctypes.POINTER(Params), ctypes.c_void_p]),
     "ppp_rank_patches": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
@@ -589,6 +595,135 @@ def with_pred_clean(pred, P):
     return Q
 
 
+# S1 on sparse foreground (ppp_consensus_sparse): PPP_S1_SPARSE = 0 (the dense launch), 1 (always the
+# item lists) or auto (the lists below the measured break-even share of active items).  A caller's
+# `_s1_sparse` kwarg (tiling.assemble, vote_instances.to_instance_seg) overrides the environment
+# for the duration of its call.
+S1_SPARSE_DEFAULT = "0"
+_S1_SPARSE = None
+_S1_WORK = {}
+
+
+class s1_sparse_scope:
+    """`with s1_sparse_scope(v)`: v None = the environment decides, "auto", True / False"""
+
+    def __init__(self, value):
+        self.value = value
+
+    def __enter__(self):
+        global _S1_SPARSE
+        self.old = _S1_SPARSE
+        if self.value is not None:
+            _S1_SPARSE = self.value
+
+    def __exit__(self, *exc):
+        global _S1_SPARSE
+        _S1_SPARSE = self.old
+
+
+def s1_sparse_mode():
+    """None (dense entry points), 0 (auto) or 1 (lists): the `mode` of ppp_consensus_sparse"""
+    v = _S1_SPARSE if _S1_SPARSE is not None else os.environ.get("PPP_S1_SPARSE", S1_SPARSE_DEFAULT)
+    if v is True or v == 1 or v == "1":
+        return 1
+    if v == "auto":
+        return 0
+    if v is False or v == 0 or v == "0":
+        return None
+    raise ValueError("PPP_S1_SPARSE / _s1_sparse must be 0, 1 or auto, got %r" % (v,))
+
+
+def consensus_last_items():
+    """(items, active items, took_lists) of the last ppp_consensus_sparse call"""
+    t, a, k = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int(0)
+    lib().ppp_consensus_last_items(ctypes.byref(t), ctypes.byref(a), ctypes.byref(k))
+    return int(t.value), int(a.value), int(k.value)
+
+
+def _consensus_sparse(pred, overlap, cons, cnt, P, part, open_rows):
+    """The sparse entry when the mode asks for it and the packed kernel serves P; False when the
+    caller is to make its dense call."""
+    mode = s1_sparse_mode()
+    if mode is None:
+        return False
+    L = lib()
+    pb = ctypes.byref(part) if part is not None else None
+    need = int(L.ppp_consensus_sparse_workspace_bytes(ctypes.byref(P), pb))
+    if need <= 0:
+        return False        # (v2 / gather / 25-wide kernels, reference layout: the dense path)
+    key = str(pred.device)
+    work = _S1_WORK.get(key)
+    if work is None or work.numel() < need:
+        work = _S1_WORK[key] = _torch().empty((need,), dtype=_torch().uint8, device=pred.device)
+    check(L.ppp_consensus_sparse(_dev_ptr(pred), pred_dtype_code(pred), _dev_ptr(overlap), _dev_ptr(cons),
+                                 _dev_ptr(cnt), ctypes.byref(P), pb, 1 if open_rows else 0, _dev_ptr(work),
+                                 mode, _stream()))
+    total, active, took = consensus_last_items()
+    note_add("s1_items", total)
+    note_add("s1_active_items", active)
+    note_add("s1_list_launches", took)
+    return True
+
+
+def s1_items_host(valid, patchshape, part=None):
+    """NumPy restatement of the item criterion of ppp_consensus_sparse (csrc/ppp_consensus_sparse.hip).
+
+    valid  bool (Z, Y, X): pred[mid] > TH and not overlapped;  part: the compute box (z0, y0, x0, z1,
+    y1, x1), None = the whole volume.  An item is (run, offset row): a run is 64 base voxels of the
+    compute box (one line, or two lines flattened over y * x when the box's x extent is >= 64 and no
+    multiple of 64) times two slices; the rows are (0, dy >= 0), then (dz >= 1, every dy).
+    Returns (active bool [n_runs, n_rows], runs, rows): runs[i] = list of (z, y, x0, n) line segments
+    of base voxels, rows[r] = (dz, dy).  Active = some valid base voxel u of the run has a valid
+    partner u + (dz, dy, dx) inside the volume, |dx| <= px - 1 (dx > 0 only in row (0, 0))."""
+    valid = np.asarray(valid, dtype=bool)
+    Z, Y, X = valid.shape
+    pz, py, px = [int(p) for p in patchshape]
+    cz0, cy0, cx0, cz1, cy1, cx1 = [int(v) for v in (part if part is not None else (0, 0, 0, Z, Y, X))]
+    cZ, cY, cX = cz1 - cz0, cy1 - cy0, cx1 - cx0
+    flat = cX >= 64 and cX % 64 != 0 and py >= 3 and cY > 1
+    rows = [(0, dy) for dy in range(py)] + \
+        [(dz, dy) for dz in range(1, pz) for dy in range(-(py - 1), py)]
+    # partners along x: any valid voxel at x + dx, dx in [-(px-1), px-1] / in [1, px-1]
+    pad = np.zeros((Z, Y, X + 2 * (px - 1)), dtype=bool)
+    pad[:, :, px - 1:px - 1 + X] = valid
+    dil_all = np.zeros_like(valid)
+    dil_pos = np.zeros_like(valid)
+    for dx in range(-(px - 1), px):
+        sh = pad[:, :, px - 1 + dx:px - 1 + dx + X]
+        dil_all |= sh
+        if dx > 0:
+            dil_pos |= sh
+    rpl = (cX * cY + 63) // 64 if flat else (cX + 63) // 64
+    n_runs = rpl * (1 if flat else cY) * ((cZ + 1) // 2)
+    runs = []
+    active = np.zeros((n_runs, len(rows)), dtype=bool)
+    for run in range(n_runs):
+        xr, r2 = run % rpl, run // rpl
+        if flat:
+            f0 = xr * 64
+            uy, uz, ux0 = cy0 + f0 // cX, cz0 + 2 * r2, cx0 + f0 % cX
+            nA = min(64, cX - f0 % cX)
+            segs = [(uy, ux0, nA)]
+            if nA < 64 and uy + 1 < cy1:
+                segs.append((uy + 1, cx0, 64 - nA))
+        else:
+            uy, uz, ux0 = cy0 + r2 % cY, cz0 + 2 * (r2 // cY), cx0 + xr * 64
+            segs = [(uy, ux0, min(64, cx1 - ux0))]
+        lines = [(uz + s, y, x0, n) for s in (0, 1) if uz + s < cz1 for (y, x0, n) in segs]
+        runs.append(lines)
+        for (z, y, x0, n) in lines:
+            U = valid[z, y, x0:x0 + n]
+            if not U.any():
+                continue
+            for r, (dz, dy) in enumerate(rows):
+                zw, yw = z + dz, y + dy
+                if active[run, r] or zw >= Z or yw < 0 or yw >= Y:
+                    continue
+                D = (dil_pos if r == 0 else dil_all)[zw, yw, x0:x0 + n]
+                active[run, r] = bool((U & D).any())
+    return active, runs, rows
+
+
 def consensus(pred, overlap, P, want_count=False, out=None, open_rows=False):
     """S1.  Returns cons (and count) as device float32 tensors shaped
     [planes, bz, by, bx] (compact), [bz, by, bx, W] (voxel-major) or [NSZ, NSY, NSX, Z, Y, X]
@@ -613,7 +748,10 @@ def consensus(pred, overlap, P, want_count=False, out=None, open_rows=False):
     note_add("s1_base_voxels", int(np.prod(P.cons_box.shape())))
     note_add("s1_output_bytes", 4 * n_el)
     with _timed("consensus"):
-        if open_rows and P.cons_layout == CONS_VOXEL_MAJOR and cnt is None:
+        if _consensus_sparse(pred, overlap, cons, cnt, P, None,
+                             open_rows and P.cons_layout == CONS_VOXEL_MAJOR and cnt is None):
+            pass
+        elif open_rows and P.cons_layout == CONS_VOXEL_MAJOR and cnt is None:
             # rows for the library's own consumers: no zeroing of entries they never read
             check(L.ppp_consensus_rows(_dev_ptr(pred), pred_dtype_code(pred), _dev_ptr(overlap),
                                        _dev_ptr(cons), ctypes.byref(P), _stream()))
@@ -1177,8 +1315,9 @@ def consensus_part(pred, overlap, P, part, out):
     note_add("s1_base_voxels", int(np.prod(b.shape())))
     P = with_pred_clean(pred, P)
     with _timed("consensus"):
-        check(lib().ppp_consensus_part(_dev_ptr(pred), pred_dtype_code(pred), _dev_ptr(overlap), _dev_ptr(out),
-                                       ctypes.byref(P), ctypes.byref(b), _stream()))
+        if not _consensus_sparse(pred, overlap, out, None, P, b, True):
+            check(lib().ppp_consensus_part(_dev_ptr(pred), pred_dtype_code(pred), _dev_ptr(overlap), _dev_ptr(out),
+                                           ctypes.byref(P), ctypes.byref(b), _stream()))
     note("s1_kernel", lib().ppp_consensus_kernel_name().decode())
 
 

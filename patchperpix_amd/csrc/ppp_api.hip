@@ -213,6 +213,60 @@ int ppp_consensus_part(const void *d_pred, int pred_dtype, const uint8_t *d_over
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_consensus_part");
 }
 
+// ---- S1 on sparse foreground: the item pre-pass and the launch over item lists ----
+static long long g_s1_items = 0, g_s1_active = 0;
+static int g_s1_took_lists = 0;
+
+// the Geo of a sparse call (NULL part: the whole cons_box); what ppp_consensus_part checks of `part`
+static int sparse_geo(const ppp_params *p, const ppp_box *part, ppp::Geo *G) {
+    PPP_TRY(make_geo(p, G));
+    if (!part) return PPP_OK;
+    const ppp_box &b = p->cons_box;
+    if (part->z0 < b.z0 || part->y0 < b.y0 || part->x0 < b.x0 || part->z1 > b.z1 || part->y1 > b.y1 ||
+        part->x1 > b.x1 || part->z1 <= part->z0 || part->y1 <= part->y0 || part->x1 <= part->x0)
+        return fail(PPP_ERR_INVALID_ARG, "part must be a non-empty sub-box of cons_box");
+    G->cz0 = part->z0; G->cy0 = part->y0; G->cx0 = part->x0;
+    G->cZ = part->z1 - part->z0; G->cY = part->y1 - part->y0; G->cX = part->x1 - part->x0;
+    return PPP_OK;
+}
+
+int64_t ppp_consensus_sparse_workspace_bytes(const ppp_params *p, const ppp_box *part) {
+    ppp::Geo G;
+    if (!p || sparse_geo(p, part, &G) != PPP_OK) return 0;
+    return (int64_t)ppp::consensus_sparse_workspace_bytes(G);
+}
+
+int ppp_consensus_sparse(const void *d_pred, int pred_dtype, const uint8_t *d_overlap, float *d_cons,
+                         float *d_count, const ppp_params *p, const ppp_box *part, int open_rows, void *d_work,
+                         int mode, void *stream) {
+    ppp::Geo G;
+    PPP_TRY(sparse_geo(p, part, &G));
+    PPP_TRY(check_dtype(pred_dtype));
+    if (!d_pred || (!d_cons && !d_count) || (part && !d_cons)) return fail(PPP_ERR_INVALID_ARG, "NULL pred / outputs");
+    if (part && d_count) return fail(PPP_ERR_INVALID_ARG, "a part writes no counts (as ppp_consensus_part)");
+    if (G.use_overlap && !d_overlap) return fail(PPP_ERR_INVALID_ARG, "use_overlap set but d_overlap is NULL");
+    if (mode != 0 && mode != 1) return fail(PPP_ERR_INVALID_ARG, "mode must be 0 (auto) or 1 (lists)");
+    if ((G.layout != PPP_CONS_VOXEL_MAJOR && G.layout != PPP_CONS_COMPACT) || !ppp::consensus_v3_supported(G) ||
+        (G.layout == PPP_CONS_VOXEL_MAJOR && (d_count || !d_cons)))
+        return fail(PPP_ERR_UNSUPPORTED, "ppp_consensus_sparse serves the packed kernel only: COMPACT planes (with counts) "
+                                         "or VOXEL_MAJOR rows (see ppp_consensus_writes_voxel_major)");
+    if (G.ring && !part) return fail(PPP_ERR_UNSUPPORTED, "ring_z: rows of a ring are written part by part");
+    if (ppp::consensus_sparse_workspace_bytes(G) == 0)
+        return fail(PPP_ERR_UNSUPPORTED, "ppp_consensus_sparse: too many work items for 32-bit item numbers");
+    if (!d_work) return fail(PPP_ERR_INVALID_ARG, "d_work is NULL (ppp_consensus_sparse_workspace_bytes)");
+    PPP_TRY(need_device());
+    if (part || open_rows) G.vm_open = 1;
+    hipError_t e = ppp::run_consensus_sparse(d_pred, pred_dtype, d_overlap, d_cons, d_count, G, d_work, mode, &g_s1_items,
+                                             &g_s1_active, &g_s1_took_lists, (hipStream_t)stream);
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_consensus_sparse");
+}
+
+void ppp_consensus_last_items(int64_t *total, int64_t *active, int *took_lists) {
+    if (total) *total = g_s1_items;
+    if (active) *active = g_s1_active;
+    if (took_lists) *took_lists = g_s1_took_lists;
+}
+
 int ppp_consensus_writes_voxel_major(const ppp_params *p) {
     ppp::Geo G;
     if (!p || make_geo(p, &G) != PPP_OK) return 0;

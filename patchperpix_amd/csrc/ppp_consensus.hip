@@ -94,6 +94,7 @@ __global__ void __launch_bounds__(256)
 
 static const char *g_s1_kernel = "none";
 const char *last_consensus_kernel() { return g_s1_kernel; }
+void note_consensus_kernel(const char *name) { g_s1_kernel = name; }
 
 hipError_t launch_consensus(const void *pred, int dtype, const uint8_t *ov, float *cons,
                             float *cnt, const Geo &G, hipStream_t s) {

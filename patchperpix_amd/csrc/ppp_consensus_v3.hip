@@ -322,22 +322,36 @@ __device__ __forceinline__ float ldf_at3(const T *base, unsigned byte_off) {
 // 1 + 255 [v < 0.5]: two packed operations per "about u" pair and three per "about w" pair instead
 // of four and five, no range check of the staged values (four integer maxima per staging iteration)
 // and no exact path in the kernel -- 12 instead of 24 vector instructions per staging iteration.
-template <typename T, int PX, bool FLAT, bool CLEAN>
+//
+// Where a wave takes its work item (x-run, offset row) from:
+//   V3_DENSE  from its index, wid -> (run, row): every item of the compute box (the kernel as it was)
+//   V3_LIST   from a list of item numbers (the ACTIVE items of ppp_consensus_sparse.hip: those with a
+//             valid pair (u, w) in the wave, i.e. a write stage whose `ok` is true somewhere)
+//   V3_ZERO   from the list of the other items, whose every stored value is +0.0f whatever the
+//             prediction holds (the reference's thread returns at once there,
+//             fillConsensusArray.cu:25-32): no validity rows, no tiles, only the write stage -- the
+//             same addresses as the dense kernel, so the output stays "fully overwritten"
+// One kernel template; everything the lists add sits behind `if constexpr (MODE ...)`, so the dense
+// instantiation keeps the code it had (`items` is a trailing argument it never reads).
+enum { V3_DENSE = 0, V3_LIST = 1, V3_ZERO = 2 };
+
+template <typename T, int PX, bool FLAT, bool CLEAN, int MODE = V3_DENSE>
 __global__ void __launch_bounds__(64 * PPP_S1V3_WAVES(PX), PPP_S1V3_MINWAVES(PX))
     consensus_v3_kernel(const T *__restrict__ pred, const uint8_t *__restrict__ ov,
                         float *__restrict__ cons, float *__restrict__ cnt_out, const Geo G,
                         const int n_rows, const int runs_per_line, const int bZ2,
-                        const long long n_waves) {
+                        const long long n_waves, const uint32_t *__restrict__ items) {
     using K = V3<PX, FLAT>;
     constexpr int NIT = K::NIT;
     constexpr int V3_WAVES = PPP_S1V3_WAVES(PX);
     constexpr bool SPLIT = PPP_S1V3_SPLIT(PX);
-    __shared__ v4f lds_bt[V3_WAVES][SPLIT ? 1 : K::NELP];
-    __shared__ v2f lds_bt2[V3_WAVES][SPLIT ? K::NELP : 1];
-    __shared__ uint32_t lds_ct[V3_WAVES][SPLIT ? K::NELP : 1];
-    __shared__ v2f lds_at[V3_WAVES][K::NELP];
-    __shared__ v2f lds_cf[V3_WAVES][K::NC];
-    __shared__ uint8_t lds_valid[V3_WAVES][2][2][K::NT + 2];
+    constexpr bool VOTES = MODE != V3_ZERO;
+    __shared__ v4f lds_bt[V3_WAVES][SPLIT || !VOTES ? 1 : K::NELP];
+    __shared__ v2f lds_bt2[V3_WAVES][SPLIT && VOTES ? K::NELP : 1];
+    __shared__ uint32_t lds_ct[V3_WAVES][SPLIT && VOTES ? K::NELP : 1];
+    __shared__ v2f lds_at[V3_WAVES][VOTES ? K::NELP : 1];
+    __shared__ v2f lds_cf[V3_WAVES][VOTES ? K::NC : 1];
+    __shared__ uint8_t lds_valid[V3_WAVES][2][2][VOTES ? K::NT + 2 : 1];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     // XCD-aware order (as v2): each XCD gets a contiguous range of (x-run, row) work
     long long bid = blockIdx.x;
@@ -345,8 +359,12 @@ __global__ void __launch_bounds__(64 * PPP_S1V3_WAVES(PX), PPP_S1V3_MINWAVES(PX)
         const long long nb = gridDim.x, per = nb / 8, main = per * 8;
         if (bid < main) bid = (bid % 8) * per + bid / 8;
     }
-    const long long wid = bid * V3_WAVES + wave;
-    if (wid >= n_waves) return;
+    const long long pos = bid * V3_WAVES + wave;
+    if (pos >= n_waves) return;
+    // (lists: the XCD-aware order acts on the position in the list, which keeps the items' order)
+    long long wid_;
+    if constexpr (MODE != V3_DENSE) wid_ = (long long)items[pos]; else wid_ = pos;
+    const long long wid = wid_;
     const int row = (int)(wid % n_rows);
     long long run = wid / n_rows;
     int dz, dy;
@@ -394,6 +412,7 @@ __global__ void __launch_bounds__(64 * PPP_S1V3_WAVES(PX), PPP_S1V3_MINWAVES(PX)
     // validity (foreground && !overlap) of the target pixels on the u row and on the w row of
     // both slices; applied when the accumulators are written
     const int ntA = nA + 2 * (PX - 1);
+    if constexpr (VOTES) {
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         uint8_t *uval = lds_valid[wave][s][0], *wval = lds_valid[wave][s][1];
@@ -417,6 +436,7 @@ __global__ void __launch_bounds__(64 * PPP_S1V3_WAVES(PX), PPP_S1V3_MINWAVES(PX)
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
+    }
 
     // Per-lane description of the NIT elements of an operand image this lane stages for every
     // tile (element e = it*64 + lane -> channel column j, centre i); the same for both images
@@ -460,7 +480,7 @@ __global__ void __launch_bounds__(64 * PPP_S1V3_WAVES(PX), PPP_S1V3_MINWAVES(PX)
     v2f *bt2 = lds_bt2[wave];
     uint32_t *ct = lds_ct[wave];
 
-    if (w_row_ok) {
+    if (VOTES && w_row_ok) {
         const int kz_hi = min(G.pz - 1, G.pz - 1 - dz), kz_lo = max(0, -dz);
         const int ky_hi = min(G.py - 1, G.py - 1 - dy), ky_lo = max(0, -dy);
         const long long slice = (long long)G.Y * G.X;
@@ -683,7 +703,7 @@ __global__ void __launch_bounds__(64 * PPP_S1V3_WAVES(PX), PPP_S1V3_MINWAVES(PX)
     for (int s = 0; s < 2; ++s) {
         if (s == 1 && !have_s1) break;
         const uint8_t *uval = lds_valid[wave][s][0], *wval = lds_valid[wave][s][1];
-        const bool u_ok = uval[ti_u] != 0;
+        const bool u_ok = VOTES && uval[ti_u] != 0;
         float val[K::NACC];
 #pragma unroll
         for (int i = 0; i < K::NACC; ++i) {
@@ -691,7 +711,7 @@ __global__ void __launch_bounds__(64 * PPP_S1V3_WAVES(PX), PPP_S1V3_MINWAVES(PX)
             val[i] = 0.0f;
             if (dz == 0 && dy == 0 && dx <= 0) continue;
             const unsigned total = cnt[i] + (tc[i] & 0x00FF00FFu) + ((tc[i] >> 8) & 0x00FF00FFu);
-            const bool ok = u_ok && wval[ti_u + dx] != 0;
+            const bool ok = VOTES && u_ok && wval[ti_u + dx] != 0;
             const unsigned n = ok ? ((s ? total >> 16 : total) & 0xFFFFu) : 0u;
             const float a = ok ? (s ? acc[i].y : acc[i].x) : 0.0f;
             const float c = (float)n;
@@ -824,21 +844,89 @@ static hipError_t launch_v3f(const T *pred, const uint8_t *ov, float *cons, floa
         if (ea != hipSuccess) return ea;
     }
     consensus_v3_kernel<T, PX, FLAT, CLEAN><<<dim3((unsigned)n_blocks), dim3(64 * V3_WAVES), dyn_lds, s>>>(
-        pred, ov, cons, cnt, G, n_rows, runs_per_line, bZ2, n_waves);
+        pred, ov, cons, cnt, G, n_rows, runs_per_line, bZ2, n_waves, nullptr);
     return hipGetLastError();
+}
+
+// the lists' launch: the active items through the kernel, the inactive ones through the zero
+// stores; a list of length 0 is no launch (a grid of 0 blocks is an error)
+template <typename T, int PX, bool FLAT, bool CLEAN>
+static hipError_t launch_v3f_lists(const T *pred, const uint8_t *ov, float *cons, float *cnt, const Geo &G,
+                                   const uint32_t *active, long long n_active, const uint32_t *inactive,
+                                   long long n_inactive, hipStream_t s) {
+    const int n_rows = (G.pz - 1) * G.wy + G.py;
+    const int runs_per_line = FLAT ? (int)(((long long)G.cX * G.cY + 63) / 64) : (G.cX + 63) / 64;
+    const int bZ2 = (G.cZ + 1) / 2;
+    const long long n_waves = (long long)runs_per_line * (FLAT ? 1 : G.cY) * bZ2 * n_rows;
+    constexpr int V3_WAVES = PPP_S1V3_WAVES(PX);
+    if (n_active + n_inactive != n_waves || n_waves >= (1ll << 32)) return hipErrorInvalidValue;   // (items are uint32)
+    if (((long long)(PX - 1) * G.V + 2ll * G.X) * (long long)sizeof(T) >= (1ll << 32)) return hipErrorNotSupported;
+    if (G.layout == PPP_CONS_VOXEL_MAJOR && !G.vm_open) {
+        const hipError_t ez = launch_vm_zero(cons, G, n_rows, s);
+        if (ez != hipSuccess) return ez;
+    }
+    if (n_active > 0) {
+        const long long nb = (n_active + V3_WAVES - 1) / V3_WAVES;
+        PPP_GRID_CHECK(nb, 64 * V3_WAVES);
+        consensus_v3_kernel<T, PX, FLAT, CLEAN, V3_LIST><<<dim3((unsigned)nb), dim3(64 * V3_WAVES), 0, s>>>(
+            pred, ov, cons, cnt, G, n_rows, runs_per_line, bZ2, n_active, active);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (n_inactive > 0) {
+        const long long nb = (n_inactive + V3_WAVES - 1) / V3_WAVES;
+        PPP_GRID_CHECK(nb, 64 * V3_WAVES);
+        // (the zero stores read no prediction: one instantiation per PX and FLAT)
+        consensus_v3_kernel<float, PX, FLAT, true, V3_ZERO><<<dim3((unsigned)nb), dim3(64 * V3_WAVES), 0, s>>>(
+            nullptr, nullptr, cons, cnt, G, n_rows, runs_per_line, bZ2, n_inactive, inactive);
+    }
+    return hipGetLastError();
+}
+
+// FLAT (two lines flattened over y * x into one run) or one line per run: same rule as v2
+static bool v3_flat(const Geo &G) {
+    static EnvSwitch sw("PPP_S1_FLAT");
+    const char *e = sw.get();
+    bool flat = G.cX >= 64 && G.cX % 64 != 0 && G.py >= 3 && G.cY > 1;
+    if (e && e[0] == '0') flat = false;
+    if (e && e[0] == '1' && G.cX >= 64 && G.py >= 3) flat = true;
+    return flat;
+}
+static bool v3_clean(const Geo &G) {
+    static EnvSwitch swc("PPP_S1_CLEAN");      // PPP_S1_CLEAN=0: the general kernel whatever the caller knows
+    const char *ec = swc.get();
+    return G.pred_clean == 1 && !(ec && ec[0] == '0');
+}
+
+// the run / item numbering of the launch these parameters get (what the item pre-pass must share)
+V3Items consensus_v3_items(const Geo &G) {
+    V3Items I;
+    I.flat = v3_flat(G) ? 1 : 0;
+    I.n_rows = (G.pz - 1) * G.wy + G.py;
+    I.runs_per_line = I.flat ? (int)(((long long)G.cX * G.cY + 63) / 64) : (G.cX + 63) / 64;
+    I.bZ2 = (G.cZ + 1) / 2;
+    I.n_runs = (long long)I.runs_per_line * (I.flat ? 1 : G.cY) * I.bZ2;
+    I.n_items = I.n_runs * I.n_rows;
+    return I;
+}
+
+template <typename T, int PX>
+static hipError_t launch_v3_lists(const T *pred, const uint8_t *ov, float *cons, float *cnt, const Geo &G,
+                                  const uint32_t *act, long long na, const uint32_t *ina, long long ni,
+                                  hipStream_t s) {
+    const bool flat = v3_flat(G);
+    if (v3_clean(G))
+        return flat ? launch_v3f_lists<T, PX, true, true>(pred, ov, cons, cnt, G, act, na, ina, ni, s)
+                    : launch_v3f_lists<T, PX, false, true>(pred, ov, cons, cnt, G, act, na, ina, ni, s);
+    return flat ? launch_v3f_lists<T, PX, true, false>(pred, ov, cons, cnt, G, act, na, ina, ni, s)
+                : launch_v3f_lists<T, PX, false, false>(pred, ov, cons, cnt, G, act, na, ina, ni, s);
 }
 
 template <typename T, int PX>
 static hipError_t launch_v3(const T *pred, const uint8_t *ov, float *cons, float *cnt,
                             const Geo &G, hipStream_t s) {
-    static EnvSwitch sw("PPP_S1_FLAT");        // same rule as v2
-    const char *e = sw.get();
-    bool flat = G.cX >= 64 && G.cX % 64 != 0 && G.py >= 3 && G.cY > 1;
-    if (e && e[0] == '0') flat = false;
-    if (e && e[0] == '1' && G.cX >= 64 && G.py >= 3) flat = true;
-    static EnvSwitch swc("PPP_S1_CLEAN");      // PPP_S1_CLEAN=0: the general kernel whatever the caller knows
-    const char *ec = swc.get();
-    const bool clean = G.pred_clean == 1 && !(ec && ec[0] == '0');
+    const bool flat = v3_flat(G);
+    const bool clean = v3_clean(G);
     if (clean)
         return flat ? launch_v3f<T, PX, true, true>(pred, ov, cons, cnt, G, s)
                     : launch_v3f<T, PX, false, true>(pred, ov, cons, cnt, G, s);
@@ -866,6 +954,29 @@ hipError_t launch_consensus_v3(const void *pred, int dtype, const uint8_t *ov, f
         return dtype == PPP_F16                                                                 \
                    ? launch_v3<__half, P>((const __half *)pred, ov, cons, cnt, G, s)            \
                    : launch_v3<float, P>((const float *)pred, ov, cons, cnt, G, s);
+    switch (G.px) {
+        PPP_V3_CASE(3)
+        PPP_V3_CASE(5)
+        PPP_V3_CASE(7)
+        PPP_V3_CASE(9)
+    default:
+        return hipErrorNotSupported;
+    }
+#undef PPP_V3_CASE
+}
+
+// the same consensus with the items taken from two lists (ppp_consensus_sparse.hip makes them)
+hipError_t launch_consensus_v3_lists(const void *pred, int dtype, const uint8_t *ov, float *cons, float *cnt,
+                                     const Geo &G, const uint32_t *active, long long n_active,
+                                     const uint32_t *inactive, long long n_inactive, hipStream_t s) {
+    if (!consensus_v3_supported(G)) return hipErrorNotSupported;
+    if (G.layout == PPP_CONS_VOXEL_MAJOR && (cnt || !cons)) return hipErrorInvalidValue;
+#define PPP_V3_CASE(P)                                                                                       \
+    case P:                                                                                                  \
+        return dtype == PPP_F16 ? launch_v3_lists<__half, P>((const __half *)pred, ov, cons, cnt, G, active, \
+                                                             n_active, inactive, n_inactive, s)              \
+                                : launch_v3_lists<float, P>((const float *)pred, ov, cons, cnt, G, active,   \
+                                                            n_active, inactive, n_inactive, s);
     switch (G.px) {
         PPP_V3_CASE(3)
         PPP_V3_CASE(5)

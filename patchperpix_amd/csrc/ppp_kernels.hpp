@@ -38,6 +38,20 @@ const char *last_consensus_kernel();
 bool consensus_v3_supported(const Geo &G);
 hipError_t launch_consensus_v3(const void *pred, int dtype, const uint8_t *ov, float *cons,
                                float *cnt, const Geo &G, hipStream_t s);
+// S1 over item lists (ppp_consensus_sparse.hip, ppp_consensus_v3.hip).  item = run * n_rows + row
+struct V3Items { int flat, n_rows, runs_per_line, bZ2; long long n_runs, n_items; };
+V3Items consensus_v3_items(const Geo &G);
+hipError_t launch_consensus_v3_lists(const void *pred, int dtype, const uint8_t *ov, float *cons, float *cnt,
+                                     const Geo &G, const uint32_t *active, long long n_active,
+                                     const uint32_t *inactive, long long n_inactive, hipStream_t s);
+size_t consensus_sparse_workspace_bytes(const Geo &G);
+// counts the items (total, active: one device -> host read, synchronises `s`), then launches: the
+// lists when mode = 1, or mode = 0 and the active share is below the measured break-even; the dense
+// kernel otherwise.  took_lists: what it chose.
+hipError_t run_consensus_sparse(const void *pred, int dtype, const uint8_t *ov, float *cons, float *cnt,
+                                const Geo &G, void *work, int mode, long long *total, long long *active,
+                                int *took_lists, hipStream_t s);
+void note_consensus_kernel(const char *name);
 hipError_t launch_consensus_part(const void *pred, int dtype, const uint8_t *ov, float *cons, const Geo &G,
                                  hipStream_t s);
 bool consensus_v4_supported(const Geo &G);

@@ -78,6 +78,49 @@ def two_blobs(shape):
     return lab
 
 
+def tube_labels(shape, n_tubes=14, radius=2.5, seed=0, turn=0.35):
+    """Label volume of thin tubes (neurons, not cells): a few percent foreground.
+
+    Tube k (label k + 1) is a smooth random walk of unit steps: it starts at a random voxel with
+    a random direction, every step adds a Gaussian perturbation of scale ``turn`` to the
+    direction (renormalised) and reflects at the faces; it runs for as many steps as the longest edge is long.
+    Every position is painted with a ball of ``radius``; the first tube to reach a voxel keeps
+    it.  Same seed, same array (``np.random.RandomState``).
+    """
+    shape = tuple(int(s) for s in shape)
+    rs = np.random.RandomState(int(seed) % (1 << 32))
+    lab = np.zeros(shape, dtype=np.int64)
+    hi = np.asarray(shape, dtype=np.float64) - 1.0
+    r = float(radius)
+    ri = int(np.ceil(r))
+    g = np.arange(-ri, ri + 1)
+    bz, by, bx = np.meshgrid(g, g, g, indexing="ij")
+    ball = np.stack([bz, by, bx], axis=-1)[(bz * bz + by * by + bx * bx) <= r * r]
+    n_steps = max(shape)
+    for k in range(int(n_tubes)):
+        pos = rs.uniform(0.0, 1.0, 3) * hi
+        d = rs.normal(size=3)
+        d /= max(np.linalg.norm(d), 1e-9)
+        kicks = rs.normal(scale=float(turn), size=(n_steps, 3))
+        for t in range(n_steps):
+            c = np.rint(pos).astype(np.int64) + ball
+            ok = np.all((c >= 0) & (c < np.asarray(shape)), axis=1)
+            c = c[ok]
+            cur = lab[c[:, 0], c[:, 1], c[:, 2]]
+            free = cur == 0
+            lab[c[free, 0], c[free, 1], c[free, 2]] = k + 1
+            d = d + kicks[t]
+            d /= max(np.linalg.norm(d), 1e-9)
+            pos = pos + d
+            for a in range(3):           # reflect at the faces
+                if pos[a] < 0.0:
+                    pos[a], d[a] = -pos[a], -d[a]
+                elif pos[a] > hi[a]:
+                    pos[a], d[a] = 2.0 * hi[a] - pos[a], -d[a]
+            pos = np.clip(pos, 0.0, hi)
+    return lab
+
+
 def pred_from_labels(lab, patchshape, seed=0, hi=HI, lo=LO, noise=NOISE,
                      dtype=np.float32):
     """Dense patch prediction ``(C, Z, Y, X)`` from a label volume (see module doc)."""
@@ -108,9 +151,13 @@ def pred_from_labels(lab, patchshape, seed=0, hi=HI, lo=LO, noise=NOISE,
 
 
 def make_case(shape, patchshape, seed=0, kind="cells", cell=None, overlap_frac=0.0,
-              noise=NOISE):
-    """Returns dict(pred f32 (C,Z,Y,X), foreground bool, numinst u8, labels)."""
-    if kind == "two_blobs":
+              noise=NOISE, n_tubes=14, radius=2.5):
+    """Returns dict(pred f32 (C,Z,Y,X), foreground bool, numinst u8, labels).
+    kind: "cells" (dense, the default), "two_blobs", "empty", or "tubes" (sparse: ``n_tubes``
+    tubes of ``radius``, see tube_labels)."""
+    if kind == "tubes":
+        lab = tube_labels(shape, n_tubes=n_tubes, radius=radius, seed=seed)
+    elif kind == "two_blobs":
         lab = two_blobs(shape)
     elif kind == "empty":
         lab = np.zeros(tuple(shape), dtype=np.int64)

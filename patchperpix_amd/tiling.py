@@ -971,11 +971,15 @@ def assemble(pred_local, lo, shape, foreground, mask_to_cover, numinst, patchsha
                 ``_sharded_global=True`` -- nothing a rank holds or computes is as large as the
                 whole volume: the ranked list, the cover and the sort are sharded by z (stage B2);
     my_slabs    [(z0, z1), ...] owned by this rank (contiguous, inside [lo, hi) minus halo).
+    ``_s1_sparse`` see below.
     Returns (instances (Z,Y,X) -- complete on every rank; uint16, or uint32 with
     ``_instances_dtype`` --, foreground uint8); with ``_gather_result=False`` the own z-range of
     both only; or (pairs, aff) with return_intermediates, with the reference's early-outs.
     """
-    return _Assembly(pred_local, lo, shape, foreground, mask_to_cover, numinst, patchshape, my_slabs, comm, ops, kw).run()
+    # `_s1_sparse` (None = PPP_S1_SPARSE decides, "auto", True, False): S1 over item lists on sparse
+    # foreground (backend.s1_sparse_scope); the result is identical by construction
+    with backend.s1_sparse_scope(kw.get("_s1_sparse")):
+        return _Assembly(pred_local, lo, shape, foreground, mask_to_cover, numinst, patchshape, my_slabs, comm, ops, kw).run()
 
 
 class _Assembly:

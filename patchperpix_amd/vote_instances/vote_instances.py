@@ -120,6 +120,14 @@ def _pad(a, rad, channels=False):
 
 
 def to_instance_seg(pred_affs, foreground, mask_to_cover, numinst, patchshape, **kwargs):
+    """`_to_instance_seg` (below) under the caller's choice for S1 on sparse foreground: the private
+    kwarg ``_s1_sparse`` (None = PPP_S1_SPARSE decides, "auto", True, False; backend.s1_sparse_scope)
+    travels on to tiling.assemble like ``_ring_z``.  The result is identical by construction."""
+    with backend.s1_sparse_scope(kwargs.get("_s1_sparse")):
+        return _to_instance_seg(pred_affs, foreground, mask_to_cover, numinst, patchshape, **kwargs)
+
+
+def _to_instance_seg(pred_affs, foreground, mask_to_cover, numinst, patchshape, **kwargs):
     """vote_instances.py:150-452.
 
     pred_affs     (C,Z,Y,X) float32/float16 ndarray, or an already-resident device tensor
