@@ -419,6 +419,13 @@ def _stream():
     return ctypes.c_void_p(_torch().cuda.current_stream().cuda_stream)
 
 
+def _workspace(nbytes, device):
+    """The d_work buffer of an entry point, `nbytes` being the answer of its ppp_*_workspace_bytes
+    query: a negative answer is the query's error (ppp_last_error says which)."""
+    check(min(int(nbytes), 0))
+    return _torch().empty(int(nbytes), dtype=_torch().uint8, device=device)
+
+
 # Optional per-kernel timing with HIP events on the stream the kernels are launched on
 # (bench.py switches it on): EVENTS = {} collects name -> [(start, stop), ...].
 EVENTS = None
@@ -654,7 +661,7 @@ def _consensus_sparse(pred, overlap, cons, cnt, P, part, open_rows):
     key = str(pred.device)
     work = _S1_WORK.get(key)
     if work is None or work.numel() < need:
-        work = _S1_WORK[key] = _torch().empty((need,), dtype=_torch().uint8, device=pred.device)
+        work = _S1_WORK[key] = _workspace(need, pred.device)
     check(L.ppp_consensus_sparse(_dev_ptr(pred), pred_dtype_code(pred), _dev_ptr(overlap), _dev_ptr(cons),
                                  _dev_ptr(cnt), ctypes.byref(P), pb, 1 if open_rows else 0, _dev_ptr(work),
                                  mode, _stream()))
@@ -783,10 +790,9 @@ def rank_patches(pred, cons, overlap, P, score_box=None, out=None):
     box = None if score_box is None else ctypes.byref(Box(*[int(v) for v in score_box]))
     if P.cons_layout == CONS_VOXEL_MAJOR:
         nbytes = int(lib().ppp_rank_workspace_bytes(box, ctypes.byref(P)))
-        check(min(nbytes, 0))
         if nbytes == 0:
             raise RuntimeError("libppp_mi355x: no voxel-major ranking kernel for this configuration")
-        work = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
+        work = _workspace(nbytes, pred.device)
         # voxels whose consensus row the launch reads: the score box grown by the patch radius
         sb = (0, 0, 0) + tuple(P.shape) if score_box is None else tuple(int(v) for v in score_box)
         cb = P.cons_box
@@ -1138,8 +1144,7 @@ class LabelState:
         self.n = int(nodes.shape[0])
         V = int(P.Z) * int(P.Y) * int(P.X)
         self.V = V
-        nbytes = int(lib().ppp_label_workspace_bytes(ctypes.byref(P)))
-        self.work = torch.empty((nbytes,), dtype=torch.uint8, device=nodes.device)
+        self.work = _workspace(lib().ppp_label_workspace_bytes(ctypes.byref(P)), nodes.device)
         self.parent = self.work[:4 * V].view(torch.int32)
         self.haspos = self.work[4 * V:8 * V].view(torch.int32)
         self.firstpos = self.work[8 * V:16 * V].view(torch.int64)
@@ -1205,8 +1210,7 @@ def label_components(pairs, aff, nodes, P):
     n = 0 if pairs is None else int(pairs.shape[0])
     k = int(nodes.shape[0])
     keys = torch.empty((k,), dtype=torch.int32, device=nodes.device)
-    nbytes = int(lib().ppp_label_workspace_bytes(ctypes.byref(P)))
-    work = torch.empty((nbytes,), dtype=torch.uint8, device=nodes.device)
+    work = _workspace(lib().ppp_label_workspace_bytes(ctypes.byref(P)), nodes.device)
     with _timed("label_components"):
         check(lib().ppp_label_components(_dev_ptr(pairs), _dev_ptr(aff), n, _dev_ptr(nodes), k,
                                          _dev_ptr(keys), _dev_ptr(work), ctypes.byref(P),
@@ -1415,9 +1419,7 @@ def cover_pass_device(mask, bits, lin, state, pix_th, P, bits_first_voxel=None):
     torch = _torch()
     n = int(state.numel())
     cleared = torch.empty(n, dtype=torch.int32, device=mask.device)
-    nbytes = int(lib().ppp_cover_workspace_bytes(n, ctypes.byref(P)))
-    check(min(nbytes, 0))
-    work = torch.empty(nbytes, dtype=torch.uint8, device=mask.device)
+    work = _workspace(lib().ppp_cover_workspace_bytes(n, ctypes.byref(P)), mask.device)
     rounds = ctypes.c_int32(0)
     with _timed("cover"):
         if bits_first_voxel is None:
@@ -1443,9 +1445,7 @@ def thin_cover_device(mask, bits, lin, P, slice_interior=None):
     keep = torch.zeros(max(n, 1), dtype=torch.uint8, device=mask.device)
     if n == 0:
         return keep[:0].bool()
-    nbytes = int(lib().ppp_thin_workspace_bytes(n, ctypes.byref(P)))
-    check(min(nbytes, 0))
-    work = torch.empty(nbytes, dtype=torch.uint8, device=mask.device)
+    work = _workspace(lib().ppp_thin_workspace_bytes(n, ctypes.byref(P)), mask.device)
     rounds = ctypes.c_int32(0)
     with _timed("thin_cover"):
         if slice_interior is None:
@@ -1474,8 +1474,7 @@ class CoverShard:
         self.lin, self.rank_id, self.bits = lin_local.contiguous(), rank_id.contiguous(), bits
         self.n = int(lin_local.numel())
         self.gz = int(global_z)
-        nbytes = int(lib().ppp_cover_workspace_bytes(self.n, ctypes.byref(P)))
-        self.work = torch.empty((nbytes,), dtype=torch.uint8, device=mask.device)
+        self.work = _workspace(lib().ppp_cover_workspace_bytes(self.n, ctypes.byref(P)), mask.device)
         self.state = self.cleared = None
 
     def open(self, state):
@@ -1523,10 +1522,8 @@ class ThinShard:
         self.lin, self.index = lin_local.contiguous(), index_global.to(torch.int32).contiguous()
         self.n = int(lin_local.numel())
         self.gz = int(global_z)
-        nbytes = int(lib().ppp_thin_shard_workspace_bytes(ctypes.byref(P)))
-        check(min(nbytes, 0))
         dev = mask.device
-        self.work = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        self.work = _workspace(lib().ppp_thin_shard_workspace_bytes(ctypes.byref(P)), dev)
         self.state = torch.empty(max(self.n, 1), dtype=torch.int32, device=dev)
         self.count = torch.empty(max(self.n, 1), dtype=torch.int32, device=dev)
         self.cleared = torch.empty(max(self.n, 1), dtype=torch.int32, device=dev)
@@ -1672,9 +1669,7 @@ def mws_edges_device(rows, aff, nodes, P):
     attractive.  rows / aff / nodes: device tensors as for mws_labels_device (n, k > 0)."""
     torch = _torch()
     n, k = int(rows.shape[0]), int(nodes.shape[0])
-    nbytes = int(lib().ppp_mws_edges_workspace_bytes(n, k, ctypes.byref(P)))
-    check(min(nbytes, 0))
-    work = torch.empty(nbytes, dtype=torch.uint8, device=rows.device)
+    work = _workspace(lib().ppp_mws_edges_workspace_bytes(n, k, ctypes.byref(P)), rows.device)
     eu = torch.empty((n,), dtype=torch.int32, device=rows.device)
     ev = torch.empty((n,), dtype=torch.int32, device=rows.device)
     n_edges = ctypes.c_int64(0)
@@ -1728,9 +1723,7 @@ def rank_order_device(score, foreground, patchshape, to_host=True):
         fg = torch.from_numpy(np.ascontiguousarray(np.asarray(foreground) != 0).astype(np.uint8)
                               ).to(score.device).reshape(-1)
     V = Z * Y * X
-    nbytes = int(lib().ppp_rank_order_workspace_bytes(ctypes.byref(P)))
-    check(min(nbytes, 0))
-    work = torch.empty(nbytes, dtype=torch.uint8, device=score.device)
+    work = _workspace(lib().ppp_rank_order_workspace_bytes(ctypes.byref(P)), score.device)
     # the ranked list has at most one entry per interior voxel
     cap = max(1, (Z - 2 * (P.pz // 2)) * (Y - 2 * (P.py // 2)) * (X - 2 * (P.px // 2)))
     lin = torch.empty((min(cap, V),), dtype=torch.int64, device=score.device)

@@ -287,11 +287,7 @@ int ppp_rank_patches(const void *d_pred, int pred_dtype, const float *d_cons,
     if (sb.z0 < 0 || sb.y0 < 0 || sb.x0 < 0 || sb.z1 > p->Z || sb.y1 > p->Y || sb.x1 > p->X)
         return fail(PPP_ERR_INVALID_ARG, "score_box outside the volume");
     // the consensus tile must hold every base voxel the scored centres read
-    const ppp_box &cb = p->cons_box;
-    auto lo = [](int a, int r) { return a - r < 0 ? 0 : a - r; };
-    auto hi = [](int a, int r, int n) { return a + r > n ? n : a + r; };
-    if (lo(sb.z0, G.rz) < cb.z0 || lo(sb.y0, G.ry) < cb.y0 || lo(sb.x0, G.rx) < cb.x0 ||
-        hi(sb.z1, G.rz, p->Z) > cb.z1 || hi(sb.y1, G.ry, p->Y) > cb.y1 || hi(sb.x1, G.rx, p->X) > cb.x1)
+    if (!ppp::cons_box_covers(G, sb))
         return fail(PPP_ERR_INVALID_ARG, "cons_box does not cover score_box grown by the patch radius");
     PPP_TRY(need_device());
     hipError_t e = ppp::launch_rank(d_pred, pred_dtype, d_cons, d_overlap, d_score, sb, G, (hipStream_t)stream);
@@ -304,11 +300,7 @@ static int rank_box(const ppp_box *score_box, const ppp_params *p, const ppp::Ge
     if (sb->z0 < 0 || sb->y0 < 0 || sb->x0 < 0 || sb->z1 > p->Z || sb->y1 > p->Y || sb->x1 > p->X ||
         sb->z1 <= sb->z0 || sb->y1 <= sb->y0 || sb->x1 <= sb->x0)
         return fail(PPP_ERR_INVALID_ARG, "score_box outside the volume");
-    const ppp_box &cb = p->cons_box;
-    auto lo = [](int a, int r) { return a - r < 0 ? 0 : a - r; };
-    auto hi = [](int a, int r, int n) { return a + r > n ? n : a + r; };
-    if (lo(sb->z0, G.rz) < cb.z0 || lo(sb->y0, G.ry) < cb.y0 || lo(sb->x0, G.rx) < cb.x0 ||
-        hi(sb->z1, G.rz, p->Z) > cb.z1 || hi(sb->y1, G.ry, p->Y) > cb.y1 || hi(sb->x1, G.rx, p->X) > cb.x1)
+    if (!ppp::cons_box_covers(G, *sb))
         return fail(PPP_ERR_INVALID_ARG, "cons_box does not cover score_box grown by the patch radius");
     return PPP_OK;
 }
@@ -323,6 +315,16 @@ int64_t ppp_rank_workspace_bytes(const ppp_box *score_box, const ppp_params *p) 
     if (rank_box(score_box, p, G, &sb) != PPP_OK) return -1;
     return (int64_t)ppp::rank_vm_workspace_bytes(sb, G);
 }
+
+#ifdef PPP_RW_STAMPS
+// diagnostic build only, not in the header: where ppp_rank_patches_vm's workspace holds the stamps (-1: nowhere)
+extern "C" int64_t ppp_rank_wg_stamps_offset(const ppp_box *score_box, const ppp_params *p) {
+    ppp::Geo G;
+    ppp_box sb;
+    if (make_geo(p, &G) != PPP_OK || !ppp::rank_wg_supported(G) || rank_box(score_box, p, G, &sb) != PPP_OK) return -1;
+    return (int64_t)ppp::rank_wg_stamps_offset(sb, G);
+}
+#endif
 
 int ppp_rank_patches_vm(const void *d_pred, int pred_dtype, const float *d_cons_vm,
                         const uint8_t *d_overlap, float *d_score, const ppp_box *score_box,

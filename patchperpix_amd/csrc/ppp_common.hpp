@@ -53,6 +53,26 @@ static inline bool grid_too_big(unsigned long long blocks, unsigned threads) {
 #define PPP_GRID_CHECK(blocks, threads) \
     do { if (::ppp::grid_too_big((unsigned long long)(blocks), (unsigned)(threads))) return hipErrorInvalidConfiguration; } while (0)
 
+// ---- device workspaces (host side) -----------------------------------------------------------
+// A workspace is described ONCE, by a layout function that takes its arrays from a Carver in order: the
+// size query runs it on a null base and reads `used`, the launcher runs it on d_work.
+static inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+struct Carver {                       // bump allocator, 256-byte slots; base == nullptr: measure only
+    char *base;
+    size_t used = 0;
+    explicit Carver(void *work) : base((char *)work) {}
+    void *take_bytes(size_t bytes) { void *p = base ? base + used : nullptr; used += up256(bytes); return p; }
+    template <class T> T *take(size_t count) { return (T *)take_bytes(count * sizeof(T)); }
+};
+
+// the cons box holds every voxel of the volume within the patch radius of the score box (S2 reads them)
+static inline bool cons_box_covers(const Geo &G, const ppp_box &sb) {
+    auto lo = [](int a, int r) { return a - r < 0 ? 0 : a - r; };
+    auto hi = [](int a, int r, int n) { return a + r > n ? n : a + r; };
+    return G.bz0 <= lo(sb.z0, G.rz) && G.by0 <= lo(sb.y0, G.ry) && G.bx0 <= lo(sb.x0, G.rx) &&
+           G.bz0 + G.bZ >= hi(sb.z1, G.rz, G.Z) && G.by0 + G.bY >= hi(sb.y1, G.ry, G.Y) && G.bx0 + G.bX >= hi(sb.x1, G.rx, G.X);
+}
+
 template <typename T>
 __device__ __forceinline__ float ldf(const T *p, long long i);
 template <>

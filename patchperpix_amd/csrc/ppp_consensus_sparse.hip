@@ -29,8 +29,6 @@
 
 namespace ppp {
 
-static size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
 // one wave per word: 64 voxels of a line, lane 0 stores the ballot.  Bits beyond X stay 0.
 template <typename T>
 __global__ void __launch_bounds__(256)
@@ -129,14 +127,25 @@ static size_t partition_temp_bytes(long long n) {
     return up256(a);
 }
 static int words_per_line(const Geo &G) { return (G.X + 63) / 64; }
-static size_t bits_bytes(const Geo &G) { return up256((size_t)G.Z * G.Y * words_per_line(G) * 8); }
 
+static SparseWork consensus_sparse_layout(Carver &c, const Geo &G, const V3Items &I) {
+    SparseWork W;
+    W.bits = c.take<unsigned long long>((size_t)G.Z * G.Y * words_per_line(G));
+    W.flags = c.take<uint8_t>(I.n_items);
+    W.items = c.take<uint32_t>(I.n_items);
+    W.count = (unsigned long long *)c.take_bytes(256);
+    W.temp_bytes = partition_temp_bytes(I.n_items);
+    W.temp = c.take_bytes(W.temp_bytes);
+    return W;
+}
+// 0: not supported (no packed kernel for these parameters, or more items than 32-bit item numbers hold)
 size_t consensus_sparse_workspace_bytes(const Geo &G) {
     if (!consensus_v3_supported(G) || (G.layout != PPP_CONS_COMPACT && G.layout != PPP_CONS_VOXEL_MAJOR)) return 0;
     const V3Items I = consensus_v3_items(G);
     if (I.n_items <= 0 || I.n_items >= (1ll << 31)) return 0;
-    return bits_bytes(G) + up256((size_t)I.n_items) + up256((size_t)I.n_items * 4) + 256 +
-           partition_temp_bytes(I.n_items);
+    Carver c(nullptr);
+    consensus_sparse_layout(c, G, I);
+    return c.used;
 }
 
 // at or above this share of active items the lists gain nothing over the dense launch (auto mode).
@@ -150,16 +159,8 @@ hipError_t run_consensus_sparse(const void *pred, int dtype, const uint8_t *ov, 
                                 int *took_lists, hipStream_t s) {
     const V3Items I = consensus_v3_items(G);
     if (consensus_sparse_workspace_bytes(G) == 0) return hipErrorNotSupported;
-    SparseWork W;
-    {
-        char *p = (char *)work;
-        W.bits = (unsigned long long *)p;  p += bits_bytes(G);
-        W.flags = (uint8_t *)p;            p += up256((size_t)I.n_items);
-        W.items = (uint32_t *)p;           p += up256((size_t)I.n_items * 4);
-        W.count = (unsigned long long *)p; p += 256;
-        W.temp = p;
-        W.temp_bytes = partition_temp_bytes(I.n_items);
-    }
+    Carver carver(work);
+    const SparseWork W = consensus_sparse_layout(carver, G, I);
     const int wpl = words_per_line(G);
     // slices the base voxels and their partners (dz >= 0) lie in
     const int z_lo = G.cz0, z_hi = std::min(G.Z, G.cz0 + G.cZ + G.pz - 1);

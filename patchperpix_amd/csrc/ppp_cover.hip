@@ -446,27 +446,21 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-static size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
-size_t cover_workspace_bytes(long long n, const Geo &G) {
-    (void)n;
-    return 4 * up256((size_t)G.V * 4) + up256((size_t)G.V) + up256((size_t)G.V * 2) +
-           up256((size_t)G.Z * G.Y * row_words(G) * 4) + 256;
-}
-
-static CoverWork carve(void *work, const Geo &G) {
+// (the same layout serves run_cover_pass and the sharded steps; n does not enter it)
+static CoverWork cover_layout(Carver &c, const Geo &G) {
     CoverWork W;
-    char *p = (char *)work;
-    W.rank_vol = (int32_t *)p; p += up256((size_t)G.V * 4);
-    W.nbr_min = (int32_t *)p;  p += up256((size_t)G.V * 4);
-    W.tmp = (int32_t *)p;      p += up256((size_t)G.V * 4);
-    W.dirty = (uint8_t *)p;    p += up256((size_t)G.V);
-    W.mbits = (uint32_t *)p;   p += up256((size_t)G.Z * G.Y * row_words(G) * 4);
-    W.counters = (int32_t *)p; p += 256;
-    W.loc_vol = (int32_t *)p;  p += up256((size_t)G.V * 4);
-    W.witness = (uint16_t *)p;
+    W.rank_vol = c.take<int32_t>(G.V);
+    W.nbr_min = c.take<int32_t>(G.V);
+    W.tmp = c.take<int32_t>(G.V);
+    W.dirty = c.take<uint8_t>(G.V);
+    W.mbits = c.take<uint32_t>((size_t)G.Z * G.Y * row_words(G));
+    W.counters = (int32_t *)c.take_bytes(256);
+    W.loc_vol = c.take<int32_t>(G.V);
+    W.witness = c.take<uint16_t>(G.V);
     return W;
 }
+size_t cover_workspace_bytes(long long, const Geo &G) { Carver c(nullptr); cover_layout(c, G); return c.used; }
+static CoverWork carve(void *work, const Geo &G) { Carver c(work); return cover_layout(c, G); }
 
 // One pass of the cover loop without the stop rule.  Returns the number of rounds in *rounds.
 hipError_t run_cover_pass(uint8_t *mask, const uint32_t *bits, long long bits_vox, const long long *lin,
@@ -545,36 +539,38 @@ hipError_t run_cover_pass(uint8_t *mask, const uint32_t *bits, long long bits_vo
 static constexpr long long THIN_NONE = FilterNone<long long>::value;
 static constexpr long long THIN_MAXC = 1ll << 20;
 
-struct ThinWork {
+// what the one-device thinning and its sharded form both keep per volume; the head of both workspaces
+struct ThinVolumes {
     long long *key_vol, *nbr_min, *tmp;  // [V] each
     uint8_t *dirty;                      // [V]
     uint32_t *mbits;                     // [Z*Y][XW]
     int32_t *counters;                   // [COVER_BATCH]
+};
+static void thin_volumes_layout(Carver &c, const Geo &G, ThinVolumes &W) {
+    W.key_vol = c.take<long long>(G.V);
+    W.nbr_min = c.take<long long>(G.V);
+    W.tmp = c.take<long long>(G.V);
+    W.dirty = c.take<uint8_t>(G.V);
+    W.mbits = c.take<uint32_t>((size_t)G.Z * G.Y * row_words(G));
+    W.counters = (int32_t *)c.take_bytes(256);
+}
+
+struct ThinWork : ThinVolumes {
     unsigned long long *interior;        // [1] set interior voxels of the mask
     int32_t *state, *sel_count, *cleared;  // [n] each
 };
-
-size_t thin_workspace_bytes(long long n, const Geo &G) {
-    return 3 * up256((size_t)G.V * 8) + up256((size_t)G.V) +
-           up256((size_t)G.Z * G.Y * row_words(G) * 4) + 256 + 256 + 3 * up256((size_t)(n > 0 ? n : 1) * 4);
-}
-
-static ThinWork carve_thin(void *work, long long n, const Geo &G) {
+static ThinWork thin_layout(Carver &c, long long n, const Geo &G) {
     ThinWork W;
-    char *p = (char *)work;
-    W.key_vol = (long long *)p; p += up256((size_t)G.V * 8);
-    W.nbr_min = (long long *)p; p += up256((size_t)G.V * 8);
-    W.tmp = (long long *)p;     p += up256((size_t)G.V * 8);
-    W.dirty = (uint8_t *)p;     p += up256((size_t)G.V);
-    W.mbits = (uint32_t *)p;    p += up256((size_t)G.Z * G.Y * row_words(G) * 4);
-    W.counters = (int32_t *)p;  p += 256;
-    W.interior = (unsigned long long *)p; p += 256;
-    const size_t per = up256((size_t)(n > 0 ? n : 1) * 4);
-    W.state = (int32_t *)p;     p += per;
-    W.sel_count = (int32_t *)p; p += per;
-    W.cleared = (int32_t *)p;
+    thin_volumes_layout(c, G, W);
+    W.interior = (unsigned long long *)c.take_bytes(256);
+    const size_t per = (size_t)(n > 0 ? n : 1);
+    W.state = c.take<int32_t>(per);
+    W.sel_count = c.take<int32_t>(per);
+    W.cleared = c.take<int32_t>(per);
     return W;
 }
+size_t thin_workspace_bytes(long long n, const Geo &G) { Carver c(nullptr); thin_layout(c, n, G); return c.used; }
+static ThinWork carve_thin(void *work, long long n, const Geo &G) { Carver c(work); return thin_layout(c, n, G); }
 
 __global__ void __launch_bounds__(256)
     thin_init_kernel(const long long *__restrict__ lin, int n, long long *__restrict__ key_vol) {
@@ -986,29 +982,17 @@ hipError_t cover_zone_import(void *work, int z_lo, int z_hi, const int32_t *in_r
 // patch's position in the GLOBAL selected list (the sequential loop's tie-break, foreground_cover.py:210);
 // loc_vol maps an own centre to its row in the rank's own lists.  The stop rule (foreground_cover.py:
 // 206-216) needs every rank's kept patches: the caller gathers (key at selection, cleared interior voxels).
-struct ThinShardWork {
-    long long *key_vol, *nbr_min, *tmp;  // [V] each
-    uint8_t *dirty;                      // [V]
-    uint32_t *mbits;                     // [Z*Y][XW]
-    int32_t *counters;                   // [COVER_BATCH]
+struct ThinShardWork : ThinVolumes {
     int32_t *loc_vol;                    // [V]
 };
-size_t thin_shard_workspace_bytes(const Geo &G) {
-    return 3 * up256((size_t)G.V * 8) + up256((size_t)G.V) + up256((size_t)G.Z * G.Y * row_words(G) * 4) + 256 +
-           up256((size_t)G.V * 4);
-}
-static ThinShardWork carve_thin_shard(void *work, const Geo &G) {
+static ThinShardWork thin_shard_layout(Carver &c, const Geo &G) {
     ThinShardWork W;
-    char *p = (char *)work;
-    W.key_vol = (long long *)p; p += up256((size_t)G.V * 8);
-    W.nbr_min = (long long *)p; p += up256((size_t)G.V * 8);
-    W.tmp = (long long *)p;     p += up256((size_t)G.V * 8);
-    W.dirty = (uint8_t *)p;     p += up256((size_t)G.V);
-    W.mbits = (uint32_t *)p;    p += up256((size_t)G.Z * G.Y * row_words(G) * 4);
-    W.counters = (int32_t *)p;  p += 256;
-    W.loc_vol = (int32_t *)p;
+    thin_volumes_layout(c, G, W);
+    W.loc_vol = c.take<int32_t>(G.V);
     return W;
 }
+size_t thin_shard_workspace_bytes(const Geo &G) { Carver c(nullptr); thin_shard_layout(c, G); return c.used; }
+static ThinShardWork carve_thin_shard(void *work, const Geo &G) { Carver c(work); return thin_shard_layout(c, G); }
 __global__ void __launch_bounds__(256)
     thin_init_local_kernel(const long long *__restrict__ lin, const int32_t *__restrict__ gidx, int n,
                            long long *__restrict__ key_vol, int32_t *__restrict__ loc_vol) {

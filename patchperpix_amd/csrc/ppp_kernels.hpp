@@ -67,6 +67,9 @@ hipError_t launch_rank_vm(const void *pred, int dtype, const float *S, const uin
                           const ppp_box &sb, void *work, const Geo &G, hipStream_t s);
 bool rank_wg_supported(const Geo &G);
 size_t rank_wg_workspace_bytes(const ppp_box &sb, const Geo &G);
+#ifdef PPP_RW_STAMPS
+size_t rank_wg_stamps_offset(const ppp_box &sb, const Geo &G);   // where the stamps lie in that workspace
+#endif
 hipError_t launch_rank_wg(const void *pred, int dtype, const float *S, const uint8_t *ov, float *score,
                           const ppp_box &sb, void *work, const Geo &G, hipStream_t s);
 hipError_t launch_patch_graph(const void *pred, int dtype, const float *cons,

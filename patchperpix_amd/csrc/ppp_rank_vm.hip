@@ -301,8 +301,6 @@ __global__ void __launch_bounds__(64, PZ * PY * PX <= 343 ? 3 : 2)
     }
 }
 
-static size_t up256r(size_t v) { return (v + 255) / 256 * 256; }
-
 // 0 = no kernel; else an id of the instantiated patch shape
 static int rank_vm_shape(const Geo &G) {
     if (G.pz == G.py && G.py == G.px && (G.px == 3 || G.px == 5 || G.px == 7 || G.px == 9)) return G.px;
@@ -313,13 +311,27 @@ bool rank_vm_supported(const Geo &G) {
     return rank_vm_shape(G) != 0 && !G.count_pos_neg && G.layout == PPP_CONS_VOXEL_MAJOR;
 }
 
-size_t rank_vm_workspace_bytes(const ppp_box &sb, const Geo &G) {
+struct RankVmWork {
+    uint32_t *Pb, *Nb;   // [score box][words]
+    uint32_t *info;      // [score box]
+    uint8_t *valid;      // [V]
+};
+static RankVmWork rank_vm_layout(Carver &c, const ppp_box &sb, const Geo &G) {
     const size_t sbV = (size_t)(sb.x1 - sb.x0) * (sb.y1 - sb.y0) * (sb.z1 - sb.z0);
     const size_t words = (size_t)(G.C + 31) / 32;
-    const size_t one_wave = 2 * up256r(words * sbV * 4) + up256r(sbV * 4) + up256r((size_t)G.V);
+    RankVmWork W;
+    W.Pb = c.take<uint32_t>(words * sbV);
+    W.Nb = c.take<uint32_t>(words * sbV);
+    W.info = c.take<uint32_t>(sbV);
+    W.valid = c.take<uint8_t>(G.V);
+    return W;
+}
+size_t rank_vm_workspace_bytes(const ppp_box &sb, const Geo &G) {
+    Carver c(nullptr);
+    rank_vm_layout(c, sb, G);
     // (either kernel may serve the call: ppp_rank_wg.hip takes the cubic 5 / 7 / 9 patches)
     const size_t wg = rank_wg_supported(G) ? rank_wg_workspace_bytes(sb, G) : 0;
-    return one_wave > wg ? one_wave : wg;
+    return c.used > wg ? c.used : wg;
 }
 
 template <typename T>
@@ -327,19 +339,9 @@ static hipError_t launch_rv(const T *pred, const float *S, const uint8_t *ov, fl
                             const ppp_box &sb, void *work, const Geo &G, hipStream_t s) {
     const int sX = sb.x1 - sb.x0, sY = sb.y1 - sb.y0, sZ = sb.z1 - sb.z0;
     const size_t sbV = (size_t)sX * sY * sZ;
-    const size_t words = (size_t)(G.C + 31) / 32;
-    char *p = (char *)work;
-    uint32_t *Pb = (uint32_t *)p;   p += up256r(words * sbV * 4);
-    uint32_t *Nb = (uint32_t *)p;   p += up256r(words * sbV * 4);
-    uint32_t *info = (uint32_t *)p; p += up256r(sbV * 4);
-    uint8_t *valid = (uint8_t *)p;
-    // the consensus box must hold every voxel of the volume within the radius of the score box
-    if (G.bz0 > (sb.z0 - G.rz > 0 ? sb.z0 - G.rz : 0) || G.by0 > (sb.y0 - G.ry > 0 ? sb.y0 - G.ry : 0) ||
-        G.bx0 > (sb.x0 - G.rx > 0 ? sb.x0 - G.rx : 0) ||
-        G.bz0 + G.bZ < (sb.z1 + G.rz < G.Z ? sb.z1 + G.rz : G.Z) ||
-        G.by0 + G.bY < (sb.y1 + G.ry < G.Y ? sb.y1 + G.ry : G.Y) ||
-        G.bx0 + G.bX < (sb.x1 + G.rx < G.X ? sb.x1 + G.rx : G.X))
-        return hipErrorInvalidValue;
+    Carver carver(work);
+    auto [Pb, Nb, info, valid] = rank_vm_layout(carver, sb, G);
+    if (!cons_box_covers(G, sb)) return hipErrorInvalidValue;
     PPP_GRID_CHECK((G.V + 255) / 256, 256);
     PPP_GRID_CHECK((sbV + 255) / 256, 256);
     rank_valid_kernel<T><<<dim3((unsigned)((G.V + 255) / 256)), dim3(256), 0, s>>>(pred, ov, valid, G);

@@ -880,8 +880,6 @@ __global__ void __launch_bounds__(64 * RW_WAVES, PPP_RW_MINWAVES(PX))
 #endif
 }
 
-static size_t up256w(size_t v) { return (v + 255) / 256 * 256; }
-
 bool rank_wg_supported(const Geo &G) {
     static EnvSwitch wg_sw("PPP_RANK_WG");
     const bool off = wg_sw.get() && wg_sw.get()[0] == '0';
@@ -890,11 +888,33 @@ bool rank_wg_supported(const Geo &G) {
            G.layout == PPP_CONS_VOXEL_MAJOR;
 }
 
-size_t rank_wg_workspace_bytes(const ppp_box &sb, const Geo &G) {
-    const size_t sbV = (size_t)(sb.x1 - sb.x0) * (sb.y1 - sb.y0) * (sb.z1 - sb.z0);
-    return up256w(rw_mask_bytes(sb.z1 - sb.z0, sb.y1 - sb.y0, sb.x1 - sb.x0, G.C)) + up256w(sbV * 4) + up256w((size_t)G.V) + 256 +
-           2 * (size_t)RW_ORDER_MAX * 4 + up256w(rw_deal_bytes(G.px));
+struct RankWgWork {
+    uint32_t *M, *info;       // the masks of the score box (rw_mask_bytes); [score box]
+    uint8_t *valid;           // [V]
+    int *any_e;               // [1] one-bit masks: "a partner equals the threshold somewhere"
+    int32_t *weight, *order;  // [RW_ORDER_MAX] each; a PPP_RW_STAMPS build reuses `weight` for its stamps
+    uint16_t *dealT;          // rw_deal_bytes
+};
+static RankWgWork rank_wg_layout(Carver &c, const ppp_box &sb, const Geo &G) {
+    const int sX = sb.x1 - sb.x0, sY = sb.y1 - sb.y0, sZ = sb.z1 - sb.z0;
+    RankWgWork W;
+    W.M = (uint32_t *)c.take_bytes(rw_mask_bytes(sZ, sY, sX, G.C));
+    W.info = c.take<uint32_t>((size_t)sX * sY * sZ);
+    W.valid = c.take<uint8_t>(G.V);
+    W.any_e = (int *)c.take_bytes(256);
+    W.weight = c.take<int32_t>(RW_ORDER_MAX);
+    W.order = c.take<int32_t>(RW_ORDER_MAX);
+    W.dealT = (uint16_t *)c.take_bytes(rw_deal_bytes(G.px));
+    return W;
 }
+size_t rank_wg_workspace_bytes(const ppp_box &sb, const Geo &G) { Carver c(nullptr); rank_wg_layout(c, sb, G); return c.used; }
+#ifdef PPP_RW_STAMPS
+size_t rank_wg_stamps_offset(const ppp_box &sb, const Geo &G) {      // (tools/s2_wg_times.py reads them back)
+    char base;                                                       // (any base: only the difference counts)
+    Carver c(&base);
+    return (size_t)((char *)rank_wg_layout(c, sb, G).weight - &base);
+}
+#endif
 
 // ---- how many tiles of a launch to split (round 7) ---------------------------------------------
 // Every XCD deals its range of tiles, heaviest first, to the workgroups its 32 CUs hold at a time, and a launch
@@ -939,17 +959,9 @@ static hipError_t launch_rwg(const T *pred, const float *S, const uint8_t *ov, f
                              const ppp_box &sb, void *work, const Geo &G, hipStream_t s) {
     const int sX = sb.x1 - sb.x0, sY = sb.y1 - sb.y0, sZ = sb.z1 - sb.z0;
     const size_t sbV = (size_t)sX * sY * sZ;
-    char *p = (char *)work;
-    uint32_t *M = (uint32_t *)p;    p += up256w(rw_mask_bytes(sZ, sY, sX, G.C));
-    uint32_t *info = (uint32_t *)p; p += up256w(sbV * 4);
-    uint8_t *valid = (uint8_t *)p;  p += up256w((size_t)G.V);
-    int *any_e = (int *)p;          // one-bit masks: "a partner equals the threshold somewhere"
-    if (G.bz0 > (sb.z0 - G.rz > 0 ? sb.z0 - G.rz : 0) || G.by0 > (sb.y0 - G.ry > 0 ? sb.y0 - G.ry : 0) ||
-        G.bx0 > (sb.x0 - G.rx > 0 ? sb.x0 - G.rx : 0) ||
-        G.bz0 + G.bZ < (sb.z1 + G.rz < G.Z ? sb.z1 + G.rz : G.Z) ||
-        G.by0 + G.bY < (sb.y1 + G.ry < G.Y ? sb.y1 + G.ry : G.Y) ||
-        G.bx0 + G.bX < (sb.x1 + G.rx < G.X ? sb.x1 + G.rx : G.X))
-        return hipErrorInvalidValue;
+    Carver carver(work);
+    auto [M, info, valid, any_e, weight, order, dealT] = rank_wg_layout(carver, sb, G);
+    if (!cons_box_covers(G, sb)) return hipErrorInvalidValue;
     PPP_GRID_CHECK((G.V + 255) / 256, 256);
     PPP_GRID_CHECK((sbV + 255) / 256, 256);
     rank_valid2_kernel<T><<<dim3((unsigned)((G.V + 255) / 256)), dim3(256), 0, s>>>(pred, ov, valid, G);
@@ -990,8 +1002,6 @@ static hipError_t launch_rwg(const T *pred, const float *S, const uint8_t *ov, f
     const int per_xcd = (int)((n_tiles + 7) / 8);
     // heavy tiles first (PPP_RANK_ORDER=0: spatial order)
     static EnvSwitch order_sw("PPP_RANK_ORDER");
-    int32_t *weight = (int32_t *)((char *)any_e + 256), *order = weight + RW_ORDER_MAX;
-    uint16_t *dealT = (uint16_t *)(order + RW_ORDER_MAX);
     if (n_tiles > RW_ORDER_MAX || (order_sw.get() && order_sw.get()[0] == '0')) order = nullptr;
     // 8 x 16 x 16 tiles by the rule above: the lightest tiles of every XCD's range are split in two so that the
     // launch's last round runs halves side by side instead of a few whole tiles (rw_choose_splits).

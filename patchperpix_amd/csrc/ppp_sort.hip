@@ -15,8 +15,6 @@
 
 namespace ppp {
 
-static size_t up256s(size_t v) { return (v + 255) / 256 * 256; }
-
 // ---------------------------------------------------------------------------------------------
 // rank order
 // ---------------------------------------------------------------------------------------------
@@ -59,31 +57,29 @@ static size_t rank_temp_bytes(long long V) {
                           (int32_t *)nullptr, (long long *)nullptr, (size_t)V, (hipStream_t)0);
     (void)rocprim::radix_sort_pairs_desc(nullptr, b, (float *)nullptr, (float *)nullptr, (int32_t *)nullptr,
                                          (int32_t *)nullptr, (size_t)V, 0, 32, (hipStream_t)0);
-    return up256s(a > b ? a : b);
+    return up256(a > b ? a : b);
 }
-size_t rank_order_workspace_bytes(const Geo &G) {
-    return up256s((size_t)G.V) + 4 * up256s((size_t)G.V * 4) + 256 + rank_temp_bytes(G.V);
-}
-static RankWork carve_rank(void *work, const Geo &G) {
+static RankWork rank_order_layout(Carver &c, const Geo &G) {
     RankWork W;
-    char *p = (char *)work;
-    W.flags = (uint8_t *)p;  p += up256s((size_t)G.V);
-    W.idx = (int32_t *)p;    p += up256s((size_t)G.V * 4);
-    W.idx2 = (int32_t *)p;   p += up256s((size_t)G.V * 4);
-    W.keys = (float *)p;     p += up256s((size_t)G.V * 4);
-    W.keys2 = (float *)p;    p += up256s((size_t)G.V * 4);
-    W.count = (long long *)p; p += 256;
-    W.temp = p;
+    W.flags = c.take<uint8_t>(G.V);
+    W.idx = c.take<int32_t>(G.V);
+    W.idx2 = c.take<int32_t>(G.V);
+    W.keys = c.take<float>(G.V);
+    W.keys2 = c.take<float>(G.V);
+    W.count = (long long *)c.take_bytes(256);
     W.temp_bytes = rank_temp_bytes(G.V);
+    W.temp = c.take_bytes(W.temp_bytes);
     return W;
 }
+size_t rank_order_workspace_bytes(const Geo &G) { Carver c(nullptr); rank_order_layout(c, G); return c.used; }
 
 // lin i64 [>= count], out_score f32 [>= count] (may be NULL).  Synchronises (the count goes to the host).
 hipError_t run_rank_order(const float *score, const uint8_t *fg, long long *lin, float *out_score,
                           long long *n_out, void *work, const Geo &G, hipStream_t s) {
     PPP_GRID_CHECK((G.V + 255) / 256, 256);
     if (G.V >= (1ll << 31)) return hipErrorInvalidValue;   // voxel indices travel as int32
-    RankWork W = carve_rank(work, G);
+    Carver carver(work);
+    RankWork W = rank_order_layout(carver, G);
     const dim3 vgrid((unsigned)((G.V + 255) / 256)), block(256);
     rank_flags_kernel<<<vgrid, block, 0, s>>>(fg, W.flags, G);
     hipError_t e;
@@ -183,12 +179,37 @@ static size_t mws_temp_bytes(long long n) {
                                     (uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)n, 0, 64, (hipStream_t)0);
     (void)rocprim::radix_sort_pairs_desc(nullptr, b, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
                                          (uint32_t *)nullptr, (size_t)n, 0, 32, (hipStream_t)0);
-    return up256s(a > b ? a : b);
+    return up256(a > b ? a : b);
+}
+struct MwsWork {
+    int32_t *id_vol, *eu, *ev;                                // [V], [n_rows] x 2
+    unsigned long long *firstpos, *key2, *key2b, *counters;   // [n_nodes], [n_rows] x 2, [2]
+    uint32_t *rid, *rid2, *wk, *wk2;                          // [n_rows] each
+    void *temp;
+    size_t temp_bytes;
+};
+static MwsWork mws_edges_layout(Carver &c, long long n_rows, long long n_nodes, const Geo &G) {
+    const size_t n = (size_t)(n_rows > 0 ? n_rows : 1);
+    MwsWork W;
+    W.id_vol = c.take<int32_t>(G.V);
+    W.firstpos = c.take<unsigned long long>(n_nodes > 0 ? n_nodes : 1);
+    W.eu = c.take<int32_t>(n);
+    W.ev = c.take<int32_t>(n);
+    W.key2 = c.take<unsigned long long>(n);
+    W.key2b = c.take<unsigned long long>(n);
+    W.rid = c.take<uint32_t>(n);
+    W.rid2 = c.take<uint32_t>(n);
+    W.wk = c.take<uint32_t>(n);
+    W.wk2 = c.take<uint32_t>(n);
+    W.counters = (unsigned long long *)c.take_bytes(256);
+    W.temp_bytes = mws_temp_bytes((long long)n);
+    W.temp = c.take_bytes(W.temp_bytes);
+    return W;
 }
 size_t mws_edges_workspace_bytes(long long n_rows, long long n_nodes, const Geo &G) {
-    const size_t n = (size_t)(n_rows > 0 ? n_rows : 1);
-    return up256s((size_t)G.V * 4) + up256s((size_t)(n_nodes > 0 ? n_nodes : 1) * 8) + 2 * up256s(n * 4) +
-           2 * up256s(n * 8) + 4 * up256s(n * 4) + 256 + mws_temp_bytes((long long)n);
+    Carver c(nullptr);
+    mws_edges_layout(c, n_rows, n_nodes, G);
+    return c.used;
 }
 
 // out_u / out_v int32 [n_rows] (device): the edges in the order graph_mws.mws visits them, node
@@ -202,45 +223,33 @@ hipError_t run_mws_edges(const uint32_t *rows, const float *aff, long long n_row
     if (n_rows >= (1ll << 32) - 1 || n_nodes >= (1ll << 31)) return hipErrorInvalidValue;
     PPP_GRID_CHECK((n_rows + 255) / 256, 256);
     const size_t n = (size_t)n_rows;
-    char *p = (char *)work;
-    int32_t *id_vol = (int32_t *)p;                      p += up256s((size_t)G.V * 4);
-    unsigned long long *firstpos = (unsigned long long *)p; p += up256s((size_t)(n_nodes > 0 ? n_nodes : 1) * 8);
-    int32_t *eu = (int32_t *)p;                          p += up256s(n * 4);
-    int32_t *ev = (int32_t *)p;                          p += up256s(n * 4);
-    unsigned long long *key2 = (unsigned long long *)p;  p += up256s(n * 8);
-    unsigned long long *key2b = (unsigned long long *)p; p += up256s(n * 8);
-    uint32_t *rid = (uint32_t *)p;                       p += up256s(n * 4);
-    uint32_t *rid2 = (uint32_t *)p;                      p += up256s(n * 4);
-    uint32_t *wk = (uint32_t *)p;                        p += up256s(n * 4);
-    uint32_t *wk2 = (uint32_t *)p;                       p += up256s(n * 4);
-    unsigned long long *counters = (unsigned long long *)p; p += 256;
-    void *temp = p;
-    const size_t temp_bytes = mws_temp_bytes(n_rows);
+    Carver carver(work);
+    const MwsWork W = mws_edges_layout(carver, n_rows, n_nodes, G);
     hipError_t e;
-    if ((e = hipMemsetAsync(id_vol, 0xFF, (size_t)G.V * 4, s)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(firstpos, 0xFF, (size_t)(n_nodes > 0 ? n_nodes : 1) * 8, s)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(counters, 0, 16, s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(W.id_vol, 0xFF, (size_t)G.V * 4, s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(W.firstpos, 0xFF, (size_t)(n_nodes > 0 ? n_nodes : 1) * 8, s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(W.counters, 0, 16, s)) != hipSuccess) return e;
     const dim3 block(256), rgrid((unsigned)((n_rows + 255) / 256));
     if (n_nodes > 0)
-        mws_nodes_kernel<<<dim3((unsigned)((n_nodes + 255) / 256)), block, 0, s>>>(nodes, n_nodes, id_vol, G);
-    mws_first_kernel<<<rgrid, block, 0, s>>>(rows, aff, n_rows, id_vol, firstpos, eu, ev, counters, G);
-    mws_keys_kernel<<<rgrid, block, 0, s>>>(aff, n_rows, eu, ev, firstpos, key2, rid);
+        mws_nodes_kernel<<<dim3((unsigned)((n_nodes + 255) / 256)), block, 0, s>>>(nodes, n_nodes, W.id_vol, G);
+    mws_first_kernel<<<rgrid, block, 0, s>>>(rows, aff, n_rows, W.id_vol, W.firstpos, W.eu, W.ev, W.counters, G);
+    mws_keys_kernel<<<rgrid, block, 0, s>>>(aff, n_rows, W.eu, W.ev, W.firstpos, W.key2, W.rid);
     // stable by (first appearance of the earlier endpoint), rows arrive in row order
     unsigned bits = 2;                                       // keys are <= 2 * n_rows
     while (bits < 64 && (2ull * (unsigned long long)n_rows) >> bits) ++bits;
-    size_t tb = temp_bytes;
-    if ((e = rocprim::radix_sort_pairs(temp, tb, key2, key2b, rid, rid2, n, 0, bits, s)) != hipSuccess)
+    size_t tb = W.temp_bytes;
+    if ((e = rocprim::radix_sort_pairs(W.temp, tb, W.key2, W.key2b, W.rid, W.rid2, n, 0, bits, s)) != hipSuccess)
         return e;
-    mws_wkeys_kernel<<<rgrid, block, 0, s>>>(aff, rid2, n_rows, wk);
-    tb = temp_bytes;
-    if ((e = rocprim::radix_sort_pairs_desc(temp, tb, wk, wk2, rid2, rid, n, 0, 32, s)) != hipSuccess) return e;
+    mws_wkeys_kernel<<<rgrid, block, 0, s>>>(aff, W.rid2, n_rows, W.wk);
+    tb = W.temp_bytes;
+    if ((e = rocprim::radix_sort_pairs_desc(W.temp, tb, W.wk, W.wk2, W.rid2, W.rid, n, 0, 32, s)) != hipSuccess) return e;
     unsigned long long h[2] = {0, 0};
-    if ((e = hipMemcpyAsync(h, counters, 16, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(h, W.counters, 16, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
     if (h[1] != 0) return hipErrorInvalidValue;
     *n_edges = (long long)h[0];
     if (h[0])
-        mws_emit_kernel<<<dim3((unsigned)((h[0] + 255) / 256)), block, 0, s>>>(aff, rid, (long long)h[0], eu, ev,
+        mws_emit_kernel<<<dim3((unsigned)((h[0] + 255) / 256)), block, 0, s>>>(aff, W.rid, (long long)h[0], W.eu, W.ev,
                                                                               out_u, out_v);
     return hipGetLastError();
 }

@@ -25,7 +25,7 @@ CASES = {"wg1024": ((24, 264, 264), (9, 9, 9), (24, 24, 24)), "wg2048": ((40, 26
 RW_ORDER_MAX = 16384
 
 
-def run_launch(args, shape, ps, cell, sbox, sb):
+def run_launch(args, shape, ps, cell, sbox):
     """two launches of S2 on the case's volume; the stamps of the second and its time"""
     import numpy as np
     import torch
@@ -52,13 +52,10 @@ def run_launch(args, shape, ps, cell, sbox, sb):
         b.record()
         torch.cuda.synchronize()
         res["launch_ms"] = round(a.elapsed_time(b), 2)
-    # where the tile-weight array sits in the workspace (rank_wg_workspace_bytes, ppp_rank_wg.hip): after the
-    # masks (48 words per centre at 9^3, rows of 16 x-neighbours), the per-centre info, the validity bytes
-    up = lambda v: (v + 255) // 256 * 256                                           # noqa: E731
-    C = int(np.prod(ps))
-    mw = (((C + 15) // 16) + 3) & ~3
-    sZ, sY, sX = sb[3] - sb[0], sb[4] - sb[1], sb[5] - sb[2]
-    off = up(sZ * sY * ((sX + 15) // 16 * 16) * mw * 4) + up(sZ * sY * sX * 4) + up(int(np.prod(shape))) + 256
+    # where the stamps lie in the workspace: the diagnostic build says (the tile-weight array of its layout)
+    L.ppp_rank_wg_stamps_offset.restype = ctypes.c_int64
+    off = int(L.ppp_rank_wg_stamps_offset(box, ctypes.byref(Pv)))
+    assert off >= 0, "no stamps: the workgroup kernel does not serve this case"
     st = work[off: off + RW_ORDER_MAX * 4].cpu().numpy().view(np.uint32).reshape(-1, 4)
     return st, res
 
@@ -80,7 +77,7 @@ def main():
         st = np.load(args.load)[:, 1:].copy()
         res = {"case": args.case, "lib": "dump", "launch_ms": args.launch_ms}
     else:
-        st, res = run_launch(args, shape, ps, cell, sbox, sb)
+        st, res = run_launch(args, shape, ps, cell, sbox)
     res["workgroups_launched"] = int(np.sum(st[:, 1] != 0))
     if args.dump:
         np.save(args.dump, np.concatenate([np.arange(len(st), dtype=np.uint32)[:, None], st], axis=1))
