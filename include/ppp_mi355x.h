@@ -666,6 +666,37 @@ int ppp_mws_edges(const uint32_t *d_pairs, const float *d_aff, int64_t n_rows, c
                   int64_t n_nodes, int32_t *d_eu, int32_t *d_ev, int64_t *n_edges, void *d_work,
                   const ppp_params *p, void *stream);
 
+/* --- whole-volume post-steps of the label driver (ppp_postprocess.hip) ----------------------
+ * They take no ppp_params: a map is described by its voxel count or its (Z, Y, X) extent.  Maps of
+ * 2^31 voxels or more return PPP_ERR_UNSUPPORTED (the size queries return it as a negative value).
+ * Ids are UNSIGNED: ids >= 2^31 order and index like any other.  All three synchronise the stream.
+ *
+ * ppp_post_compact_ids: remove_small_components + relabel (PatchPerPix/util/postprocess.py:24-37,
+ *   :40-52; the driver's use: stitch_patch_graph.py:831-848), in place on d_ids u32 [n].  max_id
+ *   bounds the ids of the map (a larger id: PPP_ERR_INVALID_ARG, map unchanged); the workspace holds
+ *   two u32 tables of max_id + 2 slots.  Ids with at most `compsize` voxels become 0 (compsize < 0
+ *   removes nothing); with relabel != 0 the surviving non-zero ids become start, start + 1, ... in
+ *   ascending order of the old id (arithmetic modulo 2^32).  *n_kept = number of surviving ids.
+ * ppp_post_dilate: the in-place ascending loop of stitch_patch_graph.py:871-880 (every instance, in
+ *   ascending id order, dilated by one step of the 6-neighbourhood and painted over what is there)
+ *   in closed form: a voxel of id a "survives" iff no face neighbour of smaller non-zero id survives;
+ *   d_out[v] = the largest id among the survivors in v and its six face neighbours, else 0.  d_out
+ *   must not be d_in.  *rounds = 1 + the number of sweeps over the voxels the first pass left open.
+ * ppp_post_clean_mask: clean_mask (stitch_patch_graph.py:46-57: scipy.ndimage.label + bincount):
+ *   d_out u8 [Z][Y][X] = 1 where d_mask != 0 and the voxel's connected component has more than `size`
+ *   voxels, else 0 (d_out may be d_mask).  structure: 27 bits, bit (dz+1)*9 + (dy+1)*3 + (dx+1) set
+ *   when offset (dz, dy, dx) connects; it must be centrosymmetric (scipy demands the same).
+ *   *n_found / *n_kept = components found / kept.                                              */
+int64_t ppp_post_compact_ids_workspace_bytes(int64_t n, uint32_t max_id);
+int ppp_post_compact_ids(uint32_t *d_ids, int64_t n, uint32_t max_id, int64_t compsize, int32_t relabel,
+                         uint32_t start, int64_t *n_kept, void *d_work, void *stream);
+int64_t ppp_post_dilate_workspace_bytes(int32_t Z, int32_t Y, int32_t X);
+int ppp_post_dilate(const uint32_t *d_in, uint32_t *d_out, int32_t Z, int32_t Y, int32_t X, int32_t *rounds,
+                    void *d_work, void *stream);
+int64_t ppp_post_clean_mask_workspace_bytes(int32_t Z, int32_t Y, int32_t X);
+int ppp_post_clean_mask(const uint8_t *d_mask, uint8_t *d_out, int32_t Z, int32_t Y, int32_t X, uint32_t structure,
+                        int64_t size, int64_t *n_found, int64_t *n_kept, void *d_work, void *stream);
+
 /* --- synthetic input (bench / tests only; same hash as patchperpix_amd/synth.py) ------
  * fills d_pred (C,Z,Y,X) from a label volume d_labels int32 (Z,Y,X).  voxel_offset is the
  * linear index of local voxel 0 in the global volume (0 unless the buffers are a slab).    */

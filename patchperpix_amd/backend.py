@@ -303,6 +303,20 @@ _SIGNATURES = {
     "ppp_label_slice_renumber": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(Params),
                                                 ctypes.c_void_p]),
+    # whole-volume post-steps of the label driver (postprocess.py)
+    "ppp_post_compact_ids_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_uint32]),
+    "ppp_post_compact_ids": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32, ctypes.c_int64,
+                                            ctypes.c_int32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int64),
+                                            ctypes.c_void_p, ctypes.c_void_p]),
+    "ppp_post_dilate_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "ppp_post_dilate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                       ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p,
+                                       ctypes.c_void_p]),
+    "ppp_post_clean_mask_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "ppp_post_clean_mask": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                           ctypes.c_int32, ctypes.c_uint32, ctypes.c_int64,
+                                           ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                           ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 
@@ -1737,6 +1751,54 @@ def rank_order_device(score, foreground, patchshape, to_host=True):
     if to_host:
         return lin.cpu().numpy(), sc.cpu().numpy()
     return lin, sc
+
+
+# ----------------------------------------------------------------------------------------
+# whole-volume post-steps of the label driver (ppp_postprocess.hip; callers: postprocess.py)
+# ----------------------------------------------------------------------------------------
+def post_compact_ids(ids, max_id, compsize=-1, relabel=True, start=1):
+    """ppp_post_compact_ids, IN PLACE on a contiguous device tensor of 32-bit ids (int32 storage is
+    read as uint32): ids of at most `compsize` voxels become 0, and with `relabel` the surviving
+    ones become start, start + 1, ... in ascending order of the old id.  `max_id` bounds the ids of
+    the map.  Returns the number of surviving ids."""
+    assert ids.element_size() == 4 and not ids.is_floating_point(), "post_compact_ids needs 32-bit ids"
+    n = int(ids.numel())
+    work = _workspace(lib().ppp_post_compact_ids_workspace_bytes(n, int(max_id)), ids.device)
+    kept = ctypes.c_int64(0)
+    with _timed("post_compact_ids"):
+        check(lib().ppp_post_compact_ids(_dev_ptr(ids), n, int(max_id), int(compsize), 1 if relabel else 0,
+                                         int(start) & 0xFFFFFFFF, ctypes.byref(kept), _dev_ptr(work), _stream()))
+    return int(kept.value)
+
+
+def post_dilate(ids):
+    """ppp_post_dilate on a contiguous (Z, Y, X) device tensor of 32-bit ids: the ascending in-place
+    dilation loop of the reference in closed form.  Returns (new tensor, rounds)."""
+    assert ids.element_size() == 4 and not ids.is_floating_point() and ids.dim() == 3, "post_dilate needs 32-bit ids, 3-d"
+    Z, Y, X = [int(v) for v in ids.shape]
+    work = _workspace(lib().ppp_post_dilate_workspace_bytes(Z, Y, X), ids.device)
+    out = _torch().empty_like(ids)
+    rounds = ctypes.c_int32(0)
+    with _timed("post_dilate"):
+        check(lib().ppp_post_dilate(_dev_ptr(ids), _dev_ptr(out), Z, Y, X, ctypes.byref(rounds), _dev_ptr(work),
+                                    _stream()))
+    return out, int(rounds.value)
+
+
+def post_clean_mask(mask, structure_bits, size):
+    """ppp_post_clean_mask on a contiguous (Z, Y, X) uint8 device tensor: the mask without its connected
+    components (connectivity: the 27 structure bits) of at most `size` voxels.  Returns (uint8 tensor,
+    components found, components kept)."""
+    torch = _torch()
+    assert mask.dtype == torch.uint8 and mask.dim() == 3, "post_clean_mask needs a uint8 (Z, Y, X) mask"
+    Z, Y, X = [int(v) for v in mask.shape]
+    work = _workspace(lib().ppp_post_clean_mask_workspace_bytes(Z, Y, X), mask.device)
+    out = torch.empty_like(mask)
+    found, kept = ctypes.c_int64(0), ctypes.c_int64(0)
+    with _timed("post_clean_mask"):
+        check(lib().ppp_post_clean_mask(_dev_ptr(mask), _dev_ptr(out), Z, Y, X, int(structure_bits), int(size),
+                                        ctypes.byref(found), ctypes.byref(kept), _dev_ptr(work), _stream()))
+    return out, int(found.value), int(kept.value)
 
 
 def host_cover_pass(mask_running, overlap, patchshape, ranked_lin, ranked_score, bits, pix_th,

@@ -372,16 +372,9 @@ def main(pred_file, result_folder=".", **kwargs):
     instances = label_graph(vol, rows, aff, input_shape, kwargs)
     foreground, _ = util.loadFg(in_f, **kwargs)
     foreground = np.squeeze(foreground)
-    if kwargs.get("remove_small_comps", 0) > 0:
-        instances = postprocess.relabel(postprocess.remove_small_components(instances, kwargs["remove_small_comps"]))
     if kwargs.get("output_format", "hdf") == "hdf":
-        masked = instances.copy()
-        masked[foreground == 0] = 0
-        datasets = {res_key: instances.astype(np.uint16), "vote_foreground": np.asarray(foreground).astype(np.uint16),
-                    res_key + "_masked": masked.astype(np.uint16)}
-        if kwargs.get("dilate_instances", False):
-            dil = postprocess.dilate_instances(instances)
-            datasets[res_key + "_dil_1"] = dil.astype(np.uint16)
-            datasets[res_key + "_masked_dil_1"] = np.where(foreground == 0, 0, dil).astype(np.uint16)
+        instances, datasets = postprocess.post_steps(instances, foreground, **dict(kwargs, res_key=res_key))
         write_result(os.path.join(result_folder, sample + ".hdf"), datasets)
+    elif kwargs.get("remove_small_comps", 0) > 0:
+        instances = postprocess.compact(instances, kwargs["remove_small_comps"])
     return instances

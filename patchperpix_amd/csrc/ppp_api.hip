@@ -1150,4 +1150,75 @@ int ppp_thin_zone(int32_t import, void *d_work, int32_t z_lo, int32_t z_hi, int3
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_thin_zone");
 }
 
+/* ---- post-steps of the label driver (ppp_postprocess.hip) ---- */
+static int post_volume(int32_t Z, int32_t Y, int32_t X, long long *V) {
+    if (Z <= 0 || Y <= 0 || X <= 0) return fail(PPP_ERR_INVALID_ARG, "bad volume %d x %d x %d", Z, Y, X);
+    *V = (long long)Z * Y * X;
+    if (*V >= (1ll << 31)) return fail(PPP_ERR_UNSUPPORTED, "volumes of 2^31 voxels or more are not supported");
+    return PPP_OK;
+}
+
+int64_t ppp_post_compact_ids_workspace_bytes(int64_t n, uint32_t max_id) {
+    if (n < 0) return fail(PPP_ERR_INVALID_ARG, "n must be >= 0");
+    if (n >= (1ll << 31)) return fail(PPP_ERR_UNSUPPORTED, "volumes of 2^31 voxels or more are not supported");
+    return (int64_t)ppp::post_compact_workspace_bytes(max_id);
+}
+
+int ppp_post_compact_ids(uint32_t *d_ids, int64_t n, uint32_t max_id, int64_t compsize, int32_t relabel,
+                         uint32_t start, int64_t *n_kept, void *d_work, void *stream) {
+    if (n < 0) return fail(PPP_ERR_INVALID_ARG, "n must be >= 0");
+    if (n >= (1ll << 31)) return fail(PPP_ERR_UNSUPPORTED, "volumes of 2^31 voxels or more are not supported");
+    if (!n_kept || !d_work || (n > 0 && !d_ids) || ((uintptr_t)d_ids & 3))
+        return fail(PPP_ERR_INVALID_ARG, "NULL or misaligned pointer argument");
+    PPP_TRY(need_device());
+    long long kept = 0;
+    hipError_t e = ppp::run_post_compact(d_ids, n, max_id, compsize, relabel, start, &kept, d_work, (hipStream_t)stream);
+    *n_kept = kept;
+    if (e == hipErrorInvalidValue) return fail(PPP_ERR_INVALID_ARG, "ppp_post_compact_ids: the map holds an id above max_id");
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_post_compact_ids");
+}
+
+int64_t ppp_post_dilate_workspace_bytes(int32_t Z, int32_t Y, int32_t X) {
+    long long V;
+    int rc = post_volume(Z, Y, X, &V);
+    return rc != PPP_OK ? rc : (int64_t)ppp::post_dilate_workspace_bytes(V);
+}
+
+int ppp_post_dilate(const uint32_t *d_in, uint32_t *d_out, int32_t Z, int32_t Y, int32_t X, int32_t *rounds,
+                    void *d_work, void *stream) {
+    long long V;
+    PPP_TRY(post_volume(Z, Y, X, &V));
+    if (!d_in || !d_out || !d_work || !rounds) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    if (d_in == d_out) return fail(PPP_ERR_INVALID_ARG, "ppp_post_dilate does not work in place");
+    PPP_TRY(need_device());
+    int r = 0;
+    hipError_t e = ppp::run_post_dilate(d_in, d_out, Z, Y, X, &r, d_work, (hipStream_t)stream);
+    *rounds = r;
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_post_dilate");
+}
+
+int64_t ppp_post_clean_mask_workspace_bytes(int32_t Z, int32_t Y, int32_t X) {
+    long long V;
+    int rc = post_volume(Z, Y, X, &V);
+    return rc != PPP_OK ? rc : (int64_t)ppp::post_clean_mask_workspace_bytes(V);
+}
+
+int ppp_post_clean_mask(const uint8_t *d_mask, uint8_t *d_out, int32_t Z, int32_t Y, int32_t X, uint32_t structure,
+                        int64_t size, int64_t *n_found, int64_t *n_kept, void *d_work, void *stream) {
+    long long V;
+    PPP_TRY(post_volume(Z, Y, X, &V));
+    if (!d_mask || !d_out || !d_work || !n_found || !n_kept) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    if (structure >> 27) return fail(PPP_ERR_INVALID_ARG, "the structure has 27 bits");
+    for (int b = 0; b < 13; ++b)
+        if (((structure >> b) & 1u) != ((structure >> (26 - b)) & 1u))
+            return fail(PPP_ERR_INVALID_ARG, "the structure must be centrosymmetric");
+    PPP_TRY(need_device());
+    long long found = 0, kept = 0;
+    hipError_t e = ppp::run_post_clean_mask(d_mask, d_out, Z, Y, X, structure, size, &found, &kept, d_work,
+                                            (hipStream_t)stream);
+    *n_found = found;
+    *n_kept = kept;
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_post_clean_mask");
+}
+
 }  // extern "C"

@@ -198,4 +198,14 @@ hipError_t thin_zone_export(void *work, int z_lo, int z_hi, int own_lo, int own_
 hipError_t thin_zone_import(void *work, int z_lo, int z_hi, const long long *in_key, const uint8_t *in_mask,
                             const uint8_t *in_clean, const Geo &G, hipStream_t s);
 
+// post-steps of the label driver (ppp_postprocess.hip)
+size_t post_compact_workspace_bytes(uint32_t max_id);
+hipError_t run_post_compact(uint32_t *ids, long long n, uint32_t max_id, long long compsize, int relabel,
+                            uint32_t start, long long *n_kept, void *work, hipStream_t s);
+size_t post_dilate_workspace_bytes(long long V);
+hipError_t run_post_dilate(const uint32_t *in, uint32_t *out, int Z, int Y, int X, int *rounds, void *work, hipStream_t s);
+size_t post_clean_mask_workspace_bytes(long long V);
+hipError_t run_post_clean_mask(const uint8_t *mask, uint8_t *out, int Z, int Y, int X, uint32_t structure,
+                               long long size, long long *n_found, long long *n_kept, void *work, hipStream_t s);
+
 }  // namespace ppp

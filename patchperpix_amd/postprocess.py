@@ -1,8 +1,18 @@
 """Post-steps of the blockwise `label` driver (reference: PatchPerPix/util/postprocess.py:24-52 and
 PatchPerPix/vote_instances/stitch_patch_graph.py:831-894): drop small instances, renumber,
-dilate.  Host NumPy like the reference -- they touch the finished uint16 map once."""
+dilate.
+
+`remove_small_components`, `relabel` and `dilate_instances` are host NumPy like the reference.  Their
+`*_device` forms return the same arrays from the HIP kernels of csrc/ppp_postprocess.hip; `post_steps`
+is the block the drivers run after the assembly and picks between the two (`use_device`)."""
+import logging
+import math
+import os
+
 import numpy as np
 from scipy import ndimage
+
+logger = logging.getLogger(__name__)
 
 
 def remove_small_components(array, compsize=5):
@@ -33,3 +43,167 @@ def dilate_instances(instances, iterations=1):
             continue
         out[ndimage.binary_dilation(out == lbl, iterations=iterations)] = lbl
     return out
+
+
+# ----------------------------------------------------------------------------------------
+# the same steps on the device
+# ----------------------------------------------------------------------------------------
+MAX_TABLE_ID = 1 << 28      # the count table has one slot per id: 1 GiB at 2^28 ids
+
+
+def use_device():
+    """The one dispatch rule of the post-steps: the device when there is one and PPP_POSTPROCESS is
+    not "host", else the host functions above (today's behaviour, not a fallback for a missing
+    kernel: with a device the library must load)."""
+    if os.environ.get("PPP_POSTPROCESS", "") == "host":
+        return False
+    import torch
+    return torch.cuda.is_available()
+
+
+def _is_tensor(a):
+    return type(a).__module__.startswith("torch") and hasattr(a, "is_cuda")
+
+
+def _on_host(fn, array, *args):
+    """the host function on a NumPy array or a tensor, returning the same kind"""
+    if not _is_tensor(array):
+        return fn(array, *args)
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(fn(array.cpu().numpy(), *args))).to(array.device)
+
+
+def _ids_to_device(array):
+    """A map of uint16 / uint32 / int32 ids as a contiguous device tensor with int32 STORAGE (its bits
+    are the uint32 ids), with (lo, hi) = the extremes of that storage; None for any other dtype or
+    an empty map."""
+    import torch
+    if _is_tensor(array):
+        name = str(array.dtype).replace("torch.", "")
+        if name not in ("uint16", "uint32", "int32") or array.numel() == 0:
+            return None
+        t = array if array.is_cuda else array.cuda()
+        t = t.to(torch.int32) if name == "uint16" else t.contiguous().view(torch.int32)
+        if t.data_ptr() == array.data_ptr():
+            t = t.clone()
+    else:
+        array = np.asarray(array)
+        if array.dtype not in (np.uint16, np.uint32, np.int32) or array.size == 0:
+            return None
+        t = torch.from_numpy(np.ascontiguousarray(array).astype(np.uint32, copy=False).view(np.int32)).cuda()
+    lo, hi = torch.aminmax(t)
+    return t.contiguous(), int(lo), int(hi)
+
+
+def _ids_from_device(t, like):
+    """back to the kind and dtype of `like`, wrapping the way the host's astype does"""
+    import torch
+    if _is_tensor(like):
+        name = str(like.dtype).replace("torch.", "")
+        if name == "uint16":
+            t = (t & 0xFFFF).to(torch.uint16)
+        elif name == "uint32":
+            t = t.view(torch.uint32)
+        return t.reshape(like.shape).to(like.device)
+    return t.cpu().numpy().view(np.uint32).astype(np.asarray(like).dtype).reshape(np.shape(like))
+
+
+def _compact_host(array, compsize, do_relabel, start):
+    if compsize is not None:
+        array = remove_small_components(array, compsize)
+    return relabel(array, start) if do_relabel else array
+
+
+def _compact_device(array, compsize, do_relabel, start):
+    """remove_small_components (compsize not None) and / or relabel in ONE pass over the map"""
+    from . import backend
+    dev = _ids_to_device(array)
+    if dev is None or dev[1] < 0 or dev[2] >= MAX_TABLE_ID:
+        # (a negative extreme of the int32 storage: a negative id, or a uint32 id >= 2^31)
+        logger.debug("post-steps: compaction on the host (dtype %s, or ids beyond the %d-slot table)",
+                     getattr(array, "dtype", None), MAX_TABLE_ID)
+        return _on_host(_compact_host, array, compsize, do_relabel, start)
+    t, _, hi = dev
+    size = -1 if compsize is None else int(math.floor(compsize))
+    backend.post_compact_ids(t.reshape(-1), hi, compsize=max(size, -1), relabel=do_relabel,
+                             start=1 if start is None else int(start))
+    return _ids_from_device(t, array)
+
+
+def remove_small_components_device(array, compsize=5):
+    """`remove_small_components` from the device (ppp_post_compact_ids); NumPy array or device tensor
+    in, the same kind and dtype out."""
+    return _compact_device(array, compsize, False, None)
+
+
+def relabel_device(array, start=None):
+    """`relabel` from the device (ppp_post_compact_ids)."""
+    return _compact_device(array, None, True, start)
+
+
+def dilate_instances_device(instances, iterations=1):
+    """`dilate_instances` from the device (ppp_post_dilate: the ascending loop in closed form, no
+    loop over instances)."""
+    from . import backend
+    ndim = len(instances.shape)
+    dev = _ids_to_device(instances) if (iterations == 1 and 1 <= ndim <= 3) else None
+    signed = str(getattr(instances, "dtype", "")).replace("torch.", "") == "int32"
+    if dev is None or (signed and dev[1] < 0):
+        logger.debug("post-steps: dilation on the host (dtype %s, iterations %s)", getattr(instances, "dtype", None), iterations)
+        return _on_host(dilate_instances, instances, iterations)
+    t = dev[0].reshape((1,) * (3 - ndim) + tuple(int(v) for v in instances.shape))
+    out, rounds = backend.post_dilate(t)
+    backend.note("post_dilate_rounds", rounds)
+    return _ids_from_device(out, instances)
+
+
+def clean_mask_device(mask, structure, size):
+    """`vote_instances.stitch_patch_graph.clean_mask` from the device (ppp_post_clean_mask): returns
+    (bool array, components found, components kept), or None when the case is the host's (not 2-d / 3-d,
+    a structure that is not 3 per axis, centred and centrosymmetric, an empty mask)."""
+    from . import backend
+    import torch
+    m = np.asarray(mask)
+    st = np.asarray(structure) != 0
+    if m.ndim not in (2, 3) or m.size == 0 or m.size >= 1 << 31 or st.shape != (3,) * m.ndim:
+        return None
+    if m.ndim == 2:
+        st = np.stack([np.zeros_like(st), st, np.zeros_like(st)])
+    flat = st.reshape(-1)
+    if not flat[13] or not np.array_equal(flat, flat[::-1]):
+        return None
+    bits = int(sum(1 << i for i in np.flatnonzero(flat)))
+    m3 = np.ascontiguousarray(m != 0).astype(np.uint8).reshape((1,) * (3 - m.ndim) + m.shape)
+    out, found, kept = backend.post_clean_mask(torch.from_numpy(m3).cuda(), bits, int(math.floor(size)))
+    return out.cpu().numpy().astype(bool).reshape(m.shape), found, kept
+
+
+def compact(instances, compsize):
+    """relabel(remove_small_components(instances, compsize)), by the dispatch rule"""
+    if use_device():
+        return _compact_device(instances, compsize, True, None)
+    return relabel(remove_small_components(instances, compsize))
+
+
+def post_steps(instances, foreground, res_key, **kw):
+    """What the label drivers do with the assembled uint32 map (stitch_patch_graph.py:831-894): small
+    components removed and the ids compacted when remove_small_comps asks for it, then the datasets of
+    the result file, all uint16 like the reference's astype (ids above 65 535 that survive wrap,
+    :852-870): <res_key>, vote_foreground, <res_key>_masked and -- dilate_instances --
+    <res_key>_dil_1, <res_key>_masked_dil_1.  Returns (instances, datasets)."""
+    foreground = np.asarray(foreground)
+    if kw.get("remove_small_comps", 0) > 0:
+        instances = compact(instances, kw["remove_small_comps"])
+    if int(instances.max(initial=0)) > np.iinfo(np.uint16).max:
+        logger.warning("instance ids up to %d are written as uint16 like the reference does "
+                       "(stitch_patch_graph.py:852-856): set remove_small_comps > 0 to compact "
+                       "them first", int(instances.max()))
+    masked = instances.copy()
+    masked[foreground == 0] = 0
+    datasets = {res_key: instances.astype(np.uint16), "vote_foreground": foreground.astype(np.uint16),
+                res_key + "_masked": masked.astype(np.uint16)}
+    if kw.get("dilate_instances", False):
+        dil = dilate_instances_device(instances) if use_device() else dilate_instances(instances)
+        datasets[res_key + "_dil_1"] = dil.astype(np.uint16)
+        datasets[res_key + "_masked_dil_1"] = np.where(foreground == 0, 0, dil).astype(np.uint16)
+    return instances, datasets

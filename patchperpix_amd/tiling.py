@@ -2327,19 +2327,9 @@ def _stitch_streamed(provider, foreground, numinst, bb, shape, patchshape, pred_
                           patchshape, plan_slabs(bshape[0], n), _yx_tiles=(ny, nx), **kw)
     instances = np.zeros(shape, dtype=np.uint32)
     instances[bb] = inst_bb
-    if kw.get("remove_small_comps", 0) > 0:
-        instances = postprocess.relabel(postprocess.remove_small_components(instances, kw["remove_small_comps"]))
-    masked = instances.copy()
-    masked[foreground == 0] = 0
+    instances, datasets = postprocess.post_steps(instances, foreground, **dict(kw, res_key=kw.get("res_key", "vote_instances")))
     os.makedirs(result_folder, exist_ok=True)
     fn = os.path.splitext(os.path.basename(pred_file.rstrip("/")))[0]
-    res_key = kw.get("res_key", "vote_instances")
-    datasets = {res_key: instances.astype(np.uint16), "vote_foreground": foreground.astype(np.uint16),
-                res_key + "_masked": masked.astype(np.uint16)}
-    if kw.get("dilate_instances", False):
-        dil = postprocess.dilate_instances(instances)
-        datasets[res_key + "_dil_1"] = dil.astype(np.uint16)
-        datasets[res_key + "_masked_dil_1"] = np.where(foreground == 0, 0, dil).astype(np.uint16)
     write_result(os.path.join(result_folder, fn + ".hdf"), datasets)
     return instances
 
@@ -2462,25 +2452,10 @@ def _stitch_main(stack, pred_file, result_folder=".", **kwargs):
     # post-steps of the reference driver (stitch_patch_graph.py:831-894): small components
     # removed and the ids compacted -- on the uint32 map -- when remove_small_comps asks for it;
     # every dataset is then written as uint16 (the reference's astype: ids above 65 535 that
-    # survive wrap, :852-870)
+    # survive wrap, :852-870) -- postprocess.post_steps, on the device when there is one
     from . import postprocess
-    if kw.get("remove_small_comps", 0) > 0:
-        instances = postprocess.relabel(
-            postprocess.remove_small_components(instances, kw["remove_small_comps"]))
-    if int(instances.max(initial=0)) > np.iinfo(np.uint16).max:
-        logger.warning("instance ids up to %d are written as uint16 like the reference does "
-                       "(stitch_patch_graph.py:852-856): set remove_small_comps > 0 to compact "
-                       "them first", int(instances.max()))
-    masked = instances.copy()
-    masked[foreground == 0] = 0
+    instances, datasets = postprocess.post_steps(instances, foreground, **dict(kw, res_key=kw.get("res_key", "vote_instances")))
     os.makedirs(result_folder, exist_ok=True)
     fn = os.path.splitext(os.path.basename(pred_file.rstrip("/")))[0]
-    res_key = kw.get("res_key", "vote_instances")
-    datasets = {res_key: instances.astype(np.uint16), "vote_foreground": foreground.astype(np.uint16),
-                res_key + "_masked": masked.astype(np.uint16)}
-    if kw.get("dilate_instances", False):
-        dil = postprocess.dilate_instances(instances)
-        datasets[res_key + "_dil_1"] = dil.astype(np.uint16)
-        datasets[res_key + "_masked_dil_1"] = np.where(foreground == 0, 0, dil).astype(np.uint16)
     write_result(os.path.join(result_folder, fn + ".hdf"), datasets)
     return instances

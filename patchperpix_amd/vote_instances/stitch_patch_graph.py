@@ -32,7 +32,15 @@ def replace(array, old_values, new_values):
 
 def clean_mask(mask, structure, size):
     """Mask without its connected components of at most `size` voxels
-    (stitch_patch_graph.py:46-57; `structure` is scipy.ndimage's connectivity)."""
+    (stitch_patch_graph.py:46-57; `structure` is scipy.ndimage's connectivity).  On the device
+    (ppp_post_clean_mask) under the dispatch rule of postprocess.use_device."""
+    from .. import postprocess
+    if postprocess.use_device():
+        done = postprocess.clean_mask_device(mask, structure, size)
+        if done is not None:
+            logger.info("removing %i of small components.", done[1] - done[2])
+            return done[0]
+        logger.debug("clean_mask on the host (mask or structure outside the device form)")
     labeled, n = ndimage.label(mask, structure)
     big = np.bincount(labeled.ravel(), minlength=n + 1) > size
     big[0] = False
