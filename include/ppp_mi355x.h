@@ -434,6 +434,14 @@ int ppp_cover_pass_voxel_bits(uint8_t *d_mask, const uint32_t *d_bits_by_voxel, 
                               int32_t *d_cleared, void *d_work, const ppp_params *p, void *stream,
                               int32_t *rounds);
 
+/* The x and y passes of the rounds' neighbourhood minimum on their own (what ppp_cover_pass and
+ * ppp_thin_cover run once per round between their count and select steps): d_out[z][y][x] = the minimum
+ * of d_in over [y - (py-1), y + (py-1)] x [x - (px-1), x + (px-1)] of slice z, clipped to the slice.
+ * elem_bytes 4: int32 ranks ("none" = 0x7F7F7F7F), 8: int64 keys ("none" = 0x7F7F7F7F7F7F7F7F);
+ * d_in, d_out and d_scratch hold Z*Y*X elements each and are distinct.                          */
+int ppp_minfilter_xy(const void *d_in, void *d_out, void *d_scratch, int32_t elem_bytes, const ppp_params *p,
+                     void *stream);
+
 /* --- S4: set-cover thinning on the device -------------------------------------------------
  * replaces thinOutForegroundCover (foreground_cover.py:183-256, sample == 1.0; a host loop in the
  * reference): while the interior of the running mask is not empty, keep the first patch that

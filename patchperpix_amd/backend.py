@@ -87,6 +87,8 @@ _SIGNATURES = {
                                                ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     "ppp_consensus_writes_voxel_major": (ctypes.c_int, [ctypes.POINTER(Params)]),
     "ppp_device_count": (ctypes.c_int, []),
+    "ppp_minfilter_xy": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                        ctypes.POINTER(Params), ctypes.c_void_p]),
     "ppp_cons_planes": (ctypes.c_int64, [ctypes.POINTER(Params)]),
     "ppp_cons_elems": (ctypes.c_int64, [ctypes.POINTER(Params)]),
     "ppp_consensus": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,

@@ -946,6 +946,17 @@ int ppp_cover_pass_voxel_bits(uint8_t *d_mask, const uint32_t *d_bits_by_voxel, 
                            stream, rounds, "ppp_cover_pass_voxel_bits");
 }
 
+int ppp_minfilter_xy(const void *d_in, void *d_out, void *d_scratch, int32_t elem_bytes, const ppp_params *p,
+                     void *stream) {
+    ppp::Geo G;
+    PPP_TRY(make_geo(p, &G));
+    if (elem_bytes != 4 && elem_bytes != 8) return fail(PPP_ERR_INVALID_ARG, "ppp_minfilter_xy: elements of 4 or 8 bytes");
+    if (!d_in || !d_out || !d_scratch || d_in == d_out) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument or d_in == d_out");
+    PPP_TRY(need_device());
+    hipError_t e = ppp::run_minfilter_xy(d_in, d_scratch, d_out, elem_bytes, G, (hipStream_t)stream);
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_minfilter_xy");
+}
+
 int64_t ppp_rank_order_workspace_bytes(const ppp_params *p) {
     ppp::Geo G;
     if (make_geo(p, &G) != PPP_OK) return -1;

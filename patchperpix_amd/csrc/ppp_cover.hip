@@ -24,6 +24,29 @@
 // (the selecting wave marks the (2p-1)^3 box of centres it can affect in a byte volume), the
 // recount stops at the first window row that settles "more than pixTh", and the host only
 // synchronises once per batch of rounds.
+//
+// The sweeps at volumes that fit the caches (140^3, 7^3: 240 cover + 48 thinning rounds per step).
+// profiles/r07_a_*_kernel_stats.txt has a cover round at 31 + 25 + 17 = 73 us and a thinning round at
+// 38 + 31 + 18 = 87 us of kernel time (xy minimum, count, select) for sweeps whose bytes -- 11 to 44 MB,
+// all cache resident -- cost 5-8 us at the rates the same kernels reach on large volumes.  The time was
+// dependent latency inside a workgroup and launches of more than one generation of workgroups:
+//   xy minimum  a staging loop of 14 serial load -> wait -> LDS write trips, 2 r + 1 LDS reads per output
+//               and pass, 36 % of the lanes on padding -> cover_minfilter_xy_cubic_kernel (see there);
+//   count       670 workgroups of 1024 threads, 512 resident -> 512 threads x 8 voxels, all resident, eight
+//               loads in flight per pass; the thinning's count had one voxel per thread (2 680 workgroups)
+//               and now shares the form;
+//   select      one voxel per thread, 10 719 workgroups, each the chain own value -> own slice of the
+//               filtered volume -> eight voxels per thread, both loads of all eight issued together, the
+//               other slices asked nearest first for all of a thread's candidates at once (ready_voxels).
+// The round keeps its three launches and every step leaves the state it left before (tests/test_shard_steps.py
+// compares it step by step, tests/test_cover_sweeps.py the filter alone and the number of rounds):
+//   * the xy minimum is NOT fused into select -- a workgroup would read a neighbour's rank that another
+//     workgroup of the same launch has just retired and select a lower ranked overlapping patch whose
+//     count predates the neighbour's clears; nbr_min is the snapshot that prevents it;
+//   * count is NOT fused into the minimum -- every rejection would unblock its neighbours a round later;
+//   * one persistent launch with a grid barrier per step was tried before and dropped.
+// What a round cannot beat is three dependent launches: tools/ubench/launch_floor.hip times a chain of
+// empty kernels at the grids of the three sweeps.
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -113,18 +136,24 @@ __global__ void __launch_bounds__(256)
 // per-voxel sweep left one or two lanes of almost every wave walking the 49-row window while the
 // others idled -- a few per cent of the voxels are dirty candidates, scattered.  (A global list
 // costs a same-address atomic per wave: 4x slower than no compaction at all.)
-static constexpr int COUNT_THREADS = 1024;
-static constexpr int COUNT_VPT = 4;     // voxels per thread of the cover's count sweep
+// (512 threads x 8 voxels: the 4096 voxels of a workgroup as before, but four workgroups fit a CU, so the
+// 670 workgroups of 140^3 are resident at once -- 1024 x 4 left a second generation that was 30 % full --
+// and a thread has eight loads in flight per pass instead of four)
+static constexpr int COUNT_THREADS = 512;
+static constexpr int COUNT_VPT = 8;     // voxels per thread of the count sweeps
+static inline dim3 count_grid(const Geo &G) {
+    return dim3((unsigned)((G.V + COUNT_THREADS * COUNT_VPT - 1) / (COUNT_THREADS * COUNT_VPT)));
+}
 __global__ void __launch_bounds__(COUNT_THREADS)
     cover_count_kernel(const uint32_t *__restrict__ mbits, const uint32_t *__restrict__ bits,
                        uint8_t *__restrict__ dirty, const int pix_th, int32_t *__restrict__ state,
                        int32_t *__restrict__ rank_vol, int32_t *__restrict__ n_alive,
                        const int32_t *__restrict__ loc_vol, uint16_t *__restrict__ witness,
                        const long long bits_vox, const Geo G) {
-    // COUNT_VPT voxels per thread (v = block base + j * 1024 + thread: every pass stays coalesced).  The
+    // COUNT_VPT voxels per thread (v = block base + j * COUNT_THREADS + thread: every pass stays coalesced).  The
     // sweep is a chain of dependent loads per voxel -- rank, then witness, then one word of the mask --
     // and its time was their latency (1.17 ms for the 134 M voxels of 512^3 with one voxel per thread:
-    // 0.8 TB/s); the loads of a thread's voxels are issued pass by pass, four in flight each.
+    // 0.8 TB/s); the loads of a thread's voxels are issued pass by pass, COUNT_VPT in flight each.
     __shared__ uint16_t s_list[COUNT_THREADS * COUNT_VPT];
     __shared__ int s_n;
     if (threadIdx.x == 0) s_n = 0;
@@ -336,12 +365,132 @@ __global__ void __launch_bounds__(256)
     }
 }
 
+// Running minimum of width W over a register array: a[i] <- min(a[i .. i + W - 1]) for i <= L - W, by
+// doubling (a[i] covers 2, 4, .. P inputs, P the largest power of two <= W; the last step joins two
+// windows of P that overlap by 2 P - W): 4 min per element at W = 13 instead of 12.  In place: every
+// step reads entries above the one it writes.
+template <typename T, int W, int L>
+__device__ __forceinline__ void running_min(T (&a)[L]) {
+    static_assert(W >= 1 && L >= W, "window longer than the run");
+    constexpr int P = W >= 16 ? 16 : W >= 8 ? 8 : W >= 4 ? 4 : W >= 2 ? 2 : 1;
+    static_assert(W < 2 * P, "window of more than 31 elements");
+#pragma unroll
+    for (int st = 1; st < P; st <<= 1) {
+#pragma unroll
+        for (int i = 0; i + st < L; ++i) a[i] = min(a[i], a[i + st]);
+    }
+    if (W > P) {
+#pragma unroll
+        for (int i = 0; i + W - P < L; ++i) a[i] = min(a[i], a[i + W - P]);
+    }
+}
+
+// The same two passes for the cubic patches (radius R = p - 1 a template parameter: 2, 4, 6, 8), built
+// for the SMALL volumes whose rounds are latency, not bytes (140^3: every volume of a round sits in
+// L2 / Infinity Cache).  What the kernel above pays there and this one does not:
+//   * its staging loop is one load, one wait and one LDS write per iteration, 14 dependent round trips
+//     per wave, each with a division by the run-time tile width.  Here the y pass comes FIRST and straight
+//     from global memory: a thread owns one column of the tile and MF_YR + 2 R rows of it, loads them all
+//     (clamped addresses, no branch: every load is issued before the first wait; lanes along x, so every
+//     load instruction is coalesced), takes the running minimum in registers and leaves MF_YR results in LDS;
+//   * 2 r + 1 LDS reads per output and pass.  Here a thread makes a RUN of outputs (MF_YR along y, MF_XR
+//     along x) from run + 2 R inputs, by doubling (running_min): 22 loads and 4 min per output / 10 at 7^3
+//     in the y pass, 20 LDS reads / 8 in the x pass;
+//   * one LDS array instead of two (the x pass reads its run, all threads meet, writes it back in place);
+//     lanes walk the ROWS of the array, whose pitch is odd: reads and writes are free of bank conflicts;
+//   * tiles of 48 x 40 or 64 x 30, whichever pads the slice less: 140 x 140 is 3 x 4 tiles of 48 x 40
+//     (15 % of the launched outputs are padding; 3 x 5 tiles of 64 x 32 made it 36 %) and the 1 680
+//     workgroups of 140^3 are resident at once (at most 72 VGPRs, 21 KB of LDS: seven or eight per CU).
+// All index arithmetic divides by compile-time constants.
+static constexpr int MF_YR = 10, MF_XR = 8;
+template <typename T, int R, int TX, int YG>
+__global__ void __launch_bounds__(256)
+    cover_minfilter_xy_cubic_kernel(const T *__restrict__ in, T *__restrict__ out, const int X, const int Y) {
+    constexpr int W = 2 * R + 1, CW = TX + 2 * R, PITCH = CW | 1, TY = YG * MF_YR;
+    constexpr int LY = MF_YR + 2 * R, LX = MF_XR + 2 * R;
+    constexpr int Y_ITEMS = CW * YG, X_ITEMS = TY * (TX / MF_XR);
+    static_assert(TX % MF_XR == 0 && X_ITEMS <= 256, "one x run per thread");
+    const T NONE = FilterNone<T>::value;
+    __shared__ T tile[TY * PITCH];             // [TY][CW]: minimum along y, then (in place) along x too
+    const int x0 = blockIdx.x * TX, y0 = blockIdx.y * TY;
+    const int zbase = blockIdx.z * Y * X;      // (a volume has fewer than 2^31 voxels)
+#pragma unroll
+    for (int it = 0; it < (Y_ITEMS + 255) / 256; ++it) {
+        const int i = threadIdx.x + it * 256;
+        if (i < Y_ITEMS) {
+            const int c = i % CW, g = i / CW;
+            const int xx = x0 - R + c, yb = y0 + g * MF_YR - R;
+            const bool x_in = xx >= 0 && xx < X;
+            const int col = zbase + min(max(xx, 0), X - 1);
+            T a[LY];
+#pragma unroll
+            for (int k = 0; k < LY; ++k) a[k] = in[col + min(max(yb + k, 0), Y - 1) * X];
+#pragma unroll
+            for (int k = 0; k < LY; ++k)
+                if (!x_in || yb + k < 0 || yb + k >= Y) a[k] = NONE;
+            running_min<T, W, LY>(a);
+#pragma unroll
+            for (int k = 0; k < MF_YR; ++k) tile[(g * MF_YR + k) * PITCH + c] = a[k];
+        }
+    }
+    __syncthreads();
+    const int r = threadIdx.x % TY, j = threadIdx.x / TY;
+    T *run = tile + r * PITCH + j * MF_XR;
+    T b[LX];
+    if (threadIdx.x < X_ITEMS) {
+#pragma unroll
+        for (int k = 0; k < LX; ++k) b[k] = run[k];
+        running_min<T, W, LX>(b);
+    }
+    __syncthreads();
+    if (threadIdx.x < X_ITEMS) {
+#pragma unroll
+        for (int k = 0; k < MF_XR; ++k) run[k] = b[k];       // column c of the tile: its first TX entries
+    }
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < (TY * TX + 255) / 256; ++it) {
+        const int i = threadIdx.x + it * 256;
+        const int rr = i / TX, cc = i % TX;
+        if (i < TY * TX && y0 + rr < Y && x0 + cc < X) out[zbase + (y0 + rr) * X + x0 + cc] = tile[rr * PITCH + cc];
+    }
+}
+
+// the cubic kernel's two tiles; false = the launch does not fit the grid limits (the caller falls back)
+template <typename T, int R>
+static bool minfilter_xy_cubic(const T *in, T *out, const Geo &G, hipStream_t s) {
+    constexpr int YG_NARROW = 4, YG_WIDE = 3;            // 48 x 40 and 64 x 30: both 1920 outputs, <= 256 items a pass
+    auto tiles = [](int n, int t) { return (n + t - 1) / t; };
+    const long long area_narrow = (long long)tiles(G.X, 48) * 48 * tiles(G.Y, YG_NARROW * MF_YR) * (YG_NARROW * MF_YR);
+    const long long area_wide = (long long)tiles(G.X, 64) * 64 * tiles(G.Y, YG_WIDE * MF_YR) * (YG_WIDE * MF_YR);
+    // (the kernel indexes with 32-bit integers)
+    if (G.V >= (1ll << 31) || G.Z > 65535 || tiles(G.Y, YG_WIDE * MF_YR) > 65535) return false;
+    if (area_wide <= area_narrow)
+        cover_minfilter_xy_cubic_kernel<T, R, 64, YG_WIDE><<<dim3((unsigned)tiles(G.X, 64), (unsigned)tiles(G.Y, YG_WIDE * MF_YR), (unsigned)G.Z), dim3(256), 0, s>>>(in, out, G.X, G.Y);
+    else
+        cover_minfilter_xy_cubic_kernel<T, R, 48, YG_NARROW><<<dim3((unsigned)tiles(G.X, 48), (unsigned)tiles(G.Y, YG_NARROW * MF_YR), (unsigned)G.Z), dim3(256), 0, s>>>(in, out, G.X, G.Y);
+    return true;
+}
+
 // x and y passes of the neighbourhood minimum: in -> out (scratch: the x pass when the fused
 // kernel's tile does not fit LDS).  The z pass is NOT a sweep of its own: only the few voxels that
 // hold an undecided patch need the 3-d minimum, and the select kernels take it over the 2 pz - 1
 // slices themselves (one volume write + read and one launch less per round).
+// Cubic 3^3 .. 9^3 patches take the kernel with compile-time radii, every other shape (anisotropic, the
+// 25-wide 2-d patches, anything whose tile does not fit LDS) the run-time one.
 template <typename T>
 static void minfilter_xy(const T *in, T *scratch, T *out, const Geo &G, hipStream_t s) {
+    if (G.px == G.py && G.py == G.pz) {
+        bool done = false;
+        switch (G.px) {
+        case 3: done = minfilter_xy_cubic<T, 2>(in, out, G, s); break;
+        case 5: done = minfilter_xy_cubic<T, 4>(in, out, G, s); break;
+        case 7: done = minfilter_xy_cubic<T, 6>(in, out, G, s); break;
+        case 9: done = minfilter_xy_cubic<T, 8>(in, out, G, s); break;
+        default: break;
+        }
+        if (done) return;
+    }
     const int rx = G.px - 1, ry = G.py - 1;
     constexpr int TYB = MfRows<T>::value, TYS = 8;      // rows per block: the tall tile where it fits LDS
     auto lds_of = [&](int ty) { return (size_t)((ty + 2 * ry) * (MF_TX + 2 * rx) + (ty + 2 * ry) * MF_TX) * sizeof(T); };
@@ -356,6 +505,13 @@ static void minfilter_xy(const T *in, T *scratch, T *out, const Geo &G, hipStrea
         cover_minfilter_kernel<T><<<vgrid, block, 0, s>>>(scratch, out, G.V, G.Y, G.X, ry);
     }
 }
+// the filter alone, on buffers of the caller (ppp_minfilter_xy: what the tests pin the tiling with)
+hipError_t run_minfilter_xy(const void *in, void *scratch, void *out, int elem_bytes, const Geo &G, hipStream_t s) {
+    if (elem_bytes == 4) minfilter_xy<int32_t>((const int32_t *)in, (int32_t *)scratch, (int32_t *)out, G, s);
+    else if (elem_bytes == 8) minfilter_xy<long long>((const long long *)in, (long long *)scratch, (long long *)out, G, s);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
 // minimum over the slices z - (pz-1) .. z + (pz-1) of the xy-filtered volume at voxel v
 template <typename T>
 __device__ __forceinline__ T zmin_at(const T *__restrict__ xy, long long v, const Geo &G) {
@@ -367,25 +523,62 @@ __device__ __forceinline__ T zmin_at(const T *__restrict__ xy, long long v, cons
     return m;
 }
 
-// "is the value `mine` at voxel v the minimum over the slices z - (pz-1) .. z + (pz-1) of the
-// xy-filtered volume": the same answer as zmin_at(...) == mine, but the slices are asked nearest
-// first and a wave stops as soon as every candidate lane has met a smaller value -- on a dense
-// volume a patch has a better ranked undecided neighbour in its own slice in all but a few
-// thousand cases per round, so a wave reads ONE slice instead of 2 pz - 1.
+// The ready test of the select sweeps, SELECT_VPT voxels per thread (v = first + j * 256: every pass is
+// coalesced): "is my value the minimum over the slices z - (pz-1) .. z + (pz-1) of the xy-filtered volume".
+// Returns the voxels j for which it is, one bit each; mine[j] = the thread's own values.
+// The own value and the own slice of the filtered volume are loaded for all of a thread's voxels before
+// anything is tested (one thread per voxel was the dependent chain rank -> nbr_min in 10 719 workgroups of
+// 256 at 140^3: five generations, each two memory latencies long).  The other slices are asked nearest
+// first, all of a thread's remaining candidates together, and a wave stops as soon as every candidate lane
+// has met a smaller value -- on a dense volume a patch has a better ranked undecided neighbour in its own
+// slice in all but a few thousand cases per round, so a wave reads ONE slice instead of 2 pz - 1.
+static constexpr int SELECT_VPT = 8;
+static inline dim3 select_grid(const Geo &G) { return dim3((unsigned)((G.V + 256 * SELECT_VPT - 1) / (256 * SELECT_VPT))); }
 template <typename T>
-__device__ __forceinline__ bool is_zmin(const T *__restrict__ xy, long long v, T mine, bool cand, const Geo &G) {
+__device__ __forceinline__ unsigned ready_voxels(const T *own, const T *__restrict__ xy,
+                                                 const long long first, T (&mine)[SELECT_VPT], const Geo &G) {
+    const T NONE = FilterNone<T>::value;
+    T here[SELECT_VPT];
+#pragma unroll
+    for (int j = 0; j < SELECT_VPT; ++j) {
+        const long long v = min(first + j * 256, G.V - 1);        // (clamped: no branch between the loads)
+        mine[j] = own[v];
+        here[j] = xy[v];
+    }
+    unsigned cand = 0;
+#pragma unroll
+    for (int j = 0; j < SELECT_VPT; ++j)
+        if (first + j * 256 < G.V && mine[j] != NONE && !(here[j] < mine[j])) cand |= 1u << j;
+    if (__ballot(cand != 0u) == 0ull) return 0u;
     const long long plane = (long long)G.X * G.Y;
-    const int z = cand ? (int)(v / plane) : 0;
-    for (int i = 0; i <= 2 * (G.pz - 1); ++i) {
-        if (__ballot(cand) == 0ull) break;
-        const int d = (i & 1) ? -((i + 1) >> 1) : (i >> 1);            // 0, -1, +1, -2, +2, ...
-        if (cand && z + d >= 0 && z + d < G.Z && xy[v + (long long)d * plane] < mine) cand = false;
+    const bool small = G.V < (1ll << 31);                         // (32-bit division where the volume allows it)
+    int z[SELECT_VPT];
+#pragma unroll
+    for (int j = 0; j < SELECT_VPT; ++j) {
+        const long long v = first + j * 256;
+        z[j] = !((cand >> j) & 1u) ? 0 : small ? (int)v / (int)plane : (int)(v / plane);
+    }
+    for (int i = 1; i <= 2 * (G.pz - 1); ++i) {
+        if (__ballot(cand != 0u) == 0ull) break;
+        const int d = (i & 1) ? -((i + 1) >> 1) : (i >> 1);            // -1, +1, -2, +2, ...
+        // (a voxel that does not ask reads its own slice again: a select between addresses, not a branch
+        // around the load, so the loads of a pass are in flight together)
+        T there[SELECT_VPT];
+        unsigned ask = 0;
+#pragma unroll
+        for (int j = 0; j < SELECT_VPT; ++j) {
+            if (((cand >> j) & 1u) && z[j] + d >= 0 && z[j] + d < G.Z) ask |= 1u << j;
+            there[j] = xy[((ask >> j) & 1u) ? first + j * 256 + (long long)d * plane : min(first + j * 256, G.V - 1)];
+        }
+#pragma unroll
+        for (int j = 0; j < SELECT_VPT; ++j)
+            if (((ask >> j) & 1u) && there[j] < mine[j]) cand &= ~(1u << j);
     }
     return cand;
 }
 
-// Thread per voxel: the best ranked undecided patch of its neighbourhood selects itself; its
-// wave clears the voxels (lane per window row) and marks the centres whose counts may have
+// SELECT_VPT voxels per thread: the best ranked undecided patch of its neighbourhood selects itself;
+// its wave clears the voxels (lane per window row) and marks the centres whose counts may have
 // changed.  Selected patches never share a voxel, but they may share a mask word.
 __global__ void __launch_bounds__(256)
     cover_select_kernel(uint32_t *__restrict__ mbits, const uint32_t *__restrict__ bits,
@@ -393,55 +586,62 @@ __global__ void __launch_bounds__(256)
                         int32_t *__restrict__ rank_vol, int32_t *__restrict__ cleared_interior,
                         uint8_t *__restrict__ dirty, const int32_t *__restrict__ loc_vol,
                         const int gZ, const long long bits_vox, const int mark_dirty, const Geo G) {
-    const long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    const long long first = blockIdx.x * (long long)(256 * SELECT_VPT) + threadIdx.x;
     const int lane = threadIdx.x & 63;
-    int k = v < G.V ? rank_vol[v] : RANK_NONE;
-    bool ready = is_zmin<int32_t>(nbr_min, v, k, k != RANK_NONE, G);          // nbr_min: xy-filtered ranks
-    if (loc_vol && ready) { k = loc_vol[v]; ready = k >= 0; }   // own centres only; local index
-    unsigned long long todo = __ballot(ready);
+    int32_t mine[SELECT_VPT];
+    unsigned ready_bits = ready_voxels<int32_t>(rank_vol, nbr_min, first, mine, G);   // nbr_min: xy-filtered ranks
+    if (__ballot(ready_bits != 0u) == 0ull) return;
+    if (loc_vol) {                                              // own centres only
+#pragma unroll
+        for (int j = 0; j < SELECT_VPT; ++j)
+            if (((ready_bits >> j) & 1u) && loc_vol[first + j * 256] < 0) ready_bits &= ~(1u << j);
+    }
     const int words = (G.C + 31) / 32, XW = row_words(G);
-    while (todo) {
-        const int src = __builtin_ctzll(todo);
-        todo &= todo - 1;
-        const int kk = __shfl(k, src);
-        const long long cc = v - lane + src;
-        int cz, cy, cx;
-        centre_of(G, cc, cz, cy, cx);
-        const uint32_t *b = bits + (bits_vox >= 0 ? cc - bits_vox : (long long)kk) * words;
-        const int start = cx - G.rx, sh = start & 31;
-        // window bits whose voxel is an interior x position
-        uint32_t xin = 0;
-        for (int i = 0; i < G.px; ++i)
-            if (start + i >= G.rx && start + i < G.X - G.rx) xin |= 1u << i;
-        int cleared = 0;
-        for (int r = lane; r < G.pz * G.py; r += 64) {
-            const int z = cz + r / G.py - G.rz, y = cy + r % G.py - G.ry;
-            uint32_t *row = mbits + ((long long)z * G.Y + y) * XW;
-            const uint32_t cl = bit_window(row, start, G.px, XW) & bit_window(b, r * G.px, G.px, words);
-            if (cl) {
-                atomicAnd(row + (start >> 5), ~(cl << sh));
-                if (sh && (cl >> (32 - sh))) atomicAnd(row + (start >> 5) + 1, ~(cl >> (32 - sh)));
-                // (interior of the WHOLE volume: gZ slices, this buffer starts at slice G.oz)
-                if (z + G.oz >= G.rz && z + G.oz < gZ - G.rz && y >= G.ry && y < G.Y - G.ry)
-                    cleared += __popc(cl & xin);
+    for (int j = 0; j < SELECT_VPT; ++j) {
+        unsigned long long todo = __ballot((ready_bits >> j) & 1u);
+        while (todo) {
+            const int src = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const long long cc = first + j * 256 - lane + src;
+            const int kk = loc_vol ? loc_vol[cc] : rank_vol[cc];      // (local index; every lane the same word)
+            int cz, cy, cx;
+            centre_of(G, cc, cz, cy, cx);
+            const uint32_t *b = bits + (bits_vox >= 0 ? cc - bits_vox : (long long)kk) * words;
+            const int start = cx - G.rx, sh = start & 31;
+            // window bits whose voxel is an interior x position
+            uint32_t xin = 0;
+            for (int i = 0; i < G.px; ++i)
+                if (start + i >= G.rx && start + i < G.X - G.rx) xin |= 1u << i;
+            int cleared = 0;
+            for (int r = lane; r < G.pz * G.py; r += 64) {
+                const int z = cz + r / G.py - G.rz, y = cy + r % G.py - G.ry;
+                uint32_t *row = mbits + ((long long)z * G.Y + y) * XW;
+                const uint32_t cl = bit_window(row, start, G.px, XW) & bit_window(b, r * G.px, G.px, words);
+                if (cl) {
+                    atomicAnd(row + (start >> 5), ~(cl << sh));
+                    if (sh && (cl >> (32 - sh))) atomicAnd(row + (start >> 5) + 1, ~(cl >> (32 - sh)));
+                    // (interior of the WHOLE volume: gZ slices, this buffer starts at slice G.oz)
+                    if (z + G.oz >= G.rz && z + G.oz < gZ - G.rz && y >= G.ry && y < G.Y - G.ry)
+                        cleared += __popc(cl & xin);
+                }
             }
-        }
-        for (int o = 32; o > 0; o >>= 1) cleared += __shfl_xor(cleared, o);
-        // every centre within p-1 of this one has a window that overlaps the cleared voxels
-        const int z0 = max(cz - (G.pz - 1), 0), z1 = min(cz + G.pz - 1, G.Z - 1);
-        const int y0 = max(cy - (G.py - 1), 0), y1 = min(cy + G.py - 1, G.Y - 1);
-        const int x0 = max(cx - (G.px - 1), 0), x1 = min(cx + G.px - 1, G.X - 1);
-        const int ny = y1 - y0 + 1, nx = x1 - x0 + 1;
-        // (pix_th == 0: the count step asks every undecided patch's witness voxel instead)
-        const int rows = mark_dirty ? (z1 - z0 + 1) * ny : 0;
-        for (int row = lane; row < rows; row += 64) {
-            uint8_t *d = dirty + vox(G, z0 + row / ny, y0 + row % ny, x0);
-            for (int x = 0; x < nx; ++x) d[x] = 1;
-        }
-        if (lane == src) {
-            state[kk] = 1;
-            rank_vol[cc] = RANK_NONE;
-            cleared_interior[kk] = cleared;
+            for (int o = 32; o > 0; o >>= 1) cleared += __shfl_xor(cleared, o);
+            // every centre within p-1 of this one has a window that overlaps the cleared voxels
+            const int z0 = max(cz - (G.pz - 1), 0), z1 = min(cz + G.pz - 1, G.Z - 1);
+            const int y0 = max(cy - (G.py - 1), 0), y1 = min(cy + G.py - 1, G.Y - 1);
+            const int x0 = max(cx - (G.px - 1), 0), x1 = min(cx + G.px - 1, G.X - 1);
+            const int ny = y1 - y0 + 1, nx = x1 - x0 + 1;
+            // (pix_th == 0: the count step asks every undecided patch's witness voxel instead)
+            const int rows = mark_dirty ? (z1 - z0 + 1) * ny : 0;
+            for (int row = lane; row < rows; row += 64) {
+                uint8_t *d = dirty + vox(G, z0 + row / ny, y0 + row % ny, x0);
+                for (int x = 0; x < nx; ++x) d[x] = 1;
+            }
+            if (lane == src) {
+                state[kk] = 1;
+                rank_vol[cc] = RANK_NONE;
+                cleared_interior[kk] = cleared;
+            }
         }
     }
 }
@@ -482,13 +682,13 @@ hipError_t run_cover_pass(uint8_t *mask, const uint32_t *bits, long long bits_vo
     int32_t n_alive = 1;
     while (n_alive > 0) {
         if ((e = hipMemsetAsync(W.counters, 0, COVER_BATCH * 4, s)) != hipSuccess) return e;
-        const dim3 cgrid((unsigned)((G.V + COUNT_THREADS * COUNT_VPT - 1) / (COUNT_THREADS * COUNT_VPT))), cblock(COUNT_THREADS);
+        const dim3 cgrid = count_grid(G), cblock(COUNT_THREADS);
         for (int r = 0; r < COVER_BATCH; ++r) {
             cover_count_kernel<<<cgrid, cblock, 0, s>>>(W.mbits, bits, W.dirty, pix_th, state, W.rank_vol,
                                                        W.counters + r, nullptr, witness_ok(G) ? W.witness : nullptr, bits_vox, G);
             // x, y, z; radius p-1: two windows overlap iff |dc| <= p-1 on every axis
             minfilter_xy<int32_t>(W.rank_vol, W.tmp, W.nbr_min, G, s);
-            cover_select_kernel<<<vgrid, block, 0, s>>>(W.mbits, bits, W.nbr_min, state, W.rank_vol, cleared,
+            cover_select_kernel<<<select_grid(G), block, 0, s>>>(W.mbits, bits, W.nbr_min, state, W.rank_vol, cleared,
                                                         W.dirty, nullptr, G.Z + G.oz, bits_vox, (pix_th != 0 || !witness_ok(G)) ? 1 : 0, G);
         }
         *rounds += COVER_BATCH;
@@ -617,37 +817,55 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-// Thread per voxel: the undecided patches of a workgroup whose neighbourhood changed are compacted
-// in LDS (as in cover_count_kernel), then recounted in full; a patch that covers nothing any more
-// is retired.
+// COUNT_VPT voxels per thread, as in cover_count_kernel (the loads of a thread's voxels issued pass by
+// pass): the undecided patches of a workgroup whose neighbourhood changed are compacted in LDS, then
+// recounted in full; a patch that covers nothing any more is retired.
 __global__ void __launch_bounds__(COUNT_THREADS)
     thin_count_kernel(const uint32_t *__restrict__ mbits, const uint32_t *__restrict__ bits,
                       uint8_t *__restrict__ dirty, int32_t *__restrict__ state,
                       long long *__restrict__ key_vol, int32_t *__restrict__ n_alive,
                       const int32_t *__restrict__ loc_vol, const Geo G) {
-    __shared__ uint16_t s_list[COUNT_THREADS];
+    __shared__ uint16_t s_list[COUNT_THREADS * COUNT_VPT];
     __shared__ int s_n;
     if (threadIdx.x == 0) s_n = 0;
     __syncthreads();
-    const long long v0 = blockIdx.x * (long long)blockDim.x;
+    const long long v0 = blockIdx.x * (long long)(COUNT_THREADS * COUNT_VPT);
     {
-        const long long v = v0 + threadIdx.x;
-        const bool in = v < G.V;
+        long long vv[COUNT_VPT], key[COUNT_VPT];
+        uint8_t mark[COUNT_VPT];
+        bool alive[COUNT_VPT], marked[COUNT_VPT];
+#pragma unroll
+        for (int j = 0; j < COUNT_VPT; ++j) {
+            vv[j] = v0 + j * COUNT_THREADS + threadIdx.x;
+            const long long vc = min(vv[j], G.V - 1);            // (clamped: no branch between the loads)
+            key[j] = key_vol[vc];
+            mark[j] = dirty[vc];
+        }
         // (sharded: loc_vol = local list index of an OWN centre, -1 elsewhere -- the keys a rank sees in
         // its halo slices belong to patches their owner counts)
-        const bool alive = in && key_vol[v] != THIN_NONE && (!loc_vol || loc_vol[v] >= 0);
-        const bool marked = in && dirty[v] != 0;
-        if (marked) dirty[v] = 0;
-        const unsigned long long m = __ballot(alive && marked);
-        if (m != 0ull) {
-            const int lane = threadIdx.x & 63;
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&s_n, __popcll(m));
-            base = __shfl(base, 0);
-            if (alive && marked) s_list[base + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)threadIdx.x;
+#pragma unroll
+        for (int j = 0; j < COUNT_VPT; ++j) {
+            alive[j] = vv[j] < G.V && key[j] != THIN_NONE;
+            if (loc_vol && alive[j]) alive[j] = loc_vol[vv[j]] >= 0;
+            marked[j] = vv[j] < G.V && mark[j] != 0;
+            if (marked[j]) dirty[vv[j]] = 0;
+        }
+        bool rest = false;
+#pragma unroll
+        for (int j = 0; j < COUNT_VPT; ++j) {
+            const unsigned long long m = __ballot(alive[j] && marked[j]);
+            if (m != 0ull) {
+                const int lane = threadIdx.x & 63;
+                int base = 0;
+                if (lane == 0) base = atomicAdd(&s_n, __popcll(m));
+                base = __shfl(base, 0);
+                if (alive[j] && marked[j])
+                    s_list[base + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)(j * COUNT_THREADS + threadIdx.x);
+            }
+            rest = rest || (alive[j] && !marked[j]);
         }
         // undecided after this step: those not recounted now; recounted survivors report below
-        if (__ballot(alive && !marked) != 0 && (threadIdx.x & 63) == 0) *n_alive = 1;
+        if (__ballot(rest) != 0 && (threadIdx.x & 63) == 0) *n_alive = 1;
     }
     __syncthreads();
     const int n = s_n;
@@ -689,7 +907,7 @@ __global__ void __launch_bounds__(COUNT_THREADS)
     }
 }
 
-// Thread per voxel: the patch with the best key of its neighbourhood keeps itself; its wave
+// SELECT_VPT voxels per thread: the patch with the best key of its neighbourhood keeps itself; its wave
 // clears the voxels and marks the centres whose counts may have changed.
 __global__ void __launch_bounds__(256)
     thin_select_kernel(uint32_t *__restrict__ mbits, const uint32_t *__restrict__ bits,
@@ -697,54 +915,61 @@ __global__ void __launch_bounds__(256)
                        long long *__restrict__ key_vol, int32_t *__restrict__ sel_count,
                        int32_t *__restrict__ cleared_interior, uint8_t *__restrict__ dirty,
                        const int32_t *__restrict__ loc_vol, const int oz, const int gZ, const Geo G) {
-    const long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    const long long first = blockIdx.x * (long long)(256 * SELECT_VPT) + threadIdx.x;
     const int lane = threadIdx.x & 63;
-    const long long key = v < G.V ? key_vol[v] : THIN_NONE;
-    bool ready = is_zmin<long long>(nbr_min, v, key, key != THIN_NONE, G);      // (xy-filtered keys)
-    int k = (int)(key & 0xFFFFFFFFll);
-    if (loc_vol && ready) { k = loc_vol[v]; ready = k >= 0; }                   // own centres only; local index
-    unsigned long long todo = __ballot(ready);
+    long long mine[SELECT_VPT];
+    unsigned ready_bits = ready_voxels<long long>(key_vol, nbr_min, first, mine, G);      // (xy-filtered keys)
+    if (__ballot(ready_bits != 0u) == 0ull) return;
+    if (loc_vol) {                                              // own centres only
+#pragma unroll
+        for (int j = 0; j < SELECT_VPT; ++j)
+            if (((ready_bits >> j) & 1u) && loc_vol[first + j * 256] < 0) ready_bits &= ~(1u << j);
+    }
     const int words = (G.C + 31) / 32, XW = row_words(G);
-    while (todo) {
-        const int src = __builtin_ctzll(todo);
-        todo &= todo - 1;
-        const int kk = __shfl(k, src);
-        const long long cc = v - lane + src;
-        int cz, cy, cx;
-        centre_of(G, cc, cz, cy, cx);
-        const uint32_t *b = bits + (long long)kk * words;
-        const int start = cx - G.rx, sh = start & 31;
-        uint32_t xin = 0;
-        for (int i = 0; i < G.px; ++i)
-            if (start + i >= G.rx && start + i < G.X - G.rx) xin |= 1u << i;
-        int cleared = 0;
-        for (int r = lane; r < G.pz * G.py; r += 64) {
-            const int z = cz + r / G.py - G.rz, y = cy + r % G.py - G.ry;
-            uint32_t *row = mbits + ((long long)z * G.Y + y) * XW;
-            const uint32_t cl = bit_window(row, start, G.px, XW) & bit_window(b, r * G.px, G.px, words);
-            if (cl) {
-                atomicAnd(row + (start >> 5), ~(cl << sh));
-                if (sh && (cl >> (32 - sh))) atomicAnd(row + (start >> 5) + 1, ~(cl >> (32 - sh)));
-                // (interior of the WHOLE volume: gZ slices, this buffer starts at its slice oz)
-                if (z + oz >= G.rz && z + oz < gZ - G.rz && y >= G.ry && y < G.Y - G.ry)
-                    cleared += __popc(cl & xin);
+    for (int j = 0; j < SELECT_VPT; ++j) {
+        unsigned long long todo = __ballot((ready_bits >> j) & 1u);
+        while (todo) {
+            const int src = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const long long cc = first + j * 256 - lane + src;
+            const long long key = key_vol[cc];                        // (every lane the same word)
+            const int kk = loc_vol ? loc_vol[cc] : (int)(key & 0xFFFFFFFFll);     // local index
+            int cz, cy, cx;
+            centre_of(G, cc, cz, cy, cx);
+            const uint32_t *b = bits + (long long)kk * words;
+            const int start = cx - G.rx, sh = start & 31;
+            uint32_t xin = 0;
+            for (int i = 0; i < G.px; ++i)
+                if (start + i >= G.rx && start + i < G.X - G.rx) xin |= 1u << i;
+            int cleared = 0;
+            for (int r = lane; r < G.pz * G.py; r += 64) {
+                const int z = cz + r / G.py - G.rz, y = cy + r % G.py - G.ry;
+                uint32_t *row = mbits + ((long long)z * G.Y + y) * XW;
+                const uint32_t cl = bit_window(row, start, G.px, XW) & bit_window(b, r * G.px, G.px, words);
+                if (cl) {
+                    atomicAnd(row + (start >> 5), ~(cl << sh));
+                    if (sh && (cl >> (32 - sh))) atomicAnd(row + (start >> 5) + 1, ~(cl >> (32 - sh)));
+                    // (interior of the WHOLE volume: gZ slices, this buffer starts at its slice oz)
+                    if (z + oz >= G.rz && z + oz < gZ - G.rz && y >= G.ry && y < G.Y - G.ry)
+                        cleared += __popc(cl & xin);
+                }
             }
-        }
-        for (int o = 32; o > 0; o >>= 1) cleared += __shfl_xor(cleared, o);
-        const int z0 = max(cz - (G.pz - 1), 0), z1 = min(cz + G.pz - 1, G.Z - 1);
-        const int y0 = max(cy - (G.py - 1), 0), y1 = min(cy + G.py - 1, G.Y - 1);
-        const int x0 = max(cx - (G.px - 1), 0), x1 = min(cx + G.px - 1, G.X - 1);
-        const int ny = y1 - y0 + 1, nx = x1 - x0 + 1;
-        const int rows = (z1 - z0 + 1) * ny;
-        for (int row = lane; row < rows; row += 64) {
-            uint8_t *d = dirty + vox(G, z0 + row / ny, y0 + row % ny, x0);
-            for (int x = 0; x < nx; ++x) d[x] = 1;
-        }
-        if (lane == src) {
-            state[kk] = 1;
-            key_vol[cc] = THIN_NONE;
-            sel_count[kk] = (int32_t)(THIN_MAXC - (key >> 32));
-            cleared_interior[kk] = cleared;
+            for (int o = 32; o > 0; o >>= 1) cleared += __shfl_xor(cleared, o);
+            const int z0 = max(cz - (G.pz - 1), 0), z1 = min(cz + G.pz - 1, G.Z - 1);
+            const int y0 = max(cy - (G.py - 1), 0), y1 = min(cy + G.py - 1, G.Y - 1);
+            const int x0 = max(cx - (G.px - 1), 0), x1 = min(cx + G.px - 1, G.X - 1);
+            const int ny = y1 - y0 + 1, nx = x1 - x0 + 1;
+            const int rows = (z1 - z0 + 1) * ny;
+            for (int row = lane; row < rows; row += 64) {
+                uint8_t *d = dirty + vox(G, z0 + row / ny, y0 + row % ny, x0);
+                for (int x = 0; x < nx; ++x) d[x] = 1;
+            }
+            if (lane == src) {
+                state[kk] = 1;
+                key_vol[cc] = THIN_NONE;
+                sel_count[kk] = (int32_t)(THIN_MAXC - (key >> 32));
+                cleared_interior[kk] = cleared;
+            }
         }
     }
 }
@@ -775,10 +1000,10 @@ hipError_t run_thin_cover(const uint8_t *mask, const uint32_t *bits, const long 
     while (n_alive > 0) {
         if ((e = hipMemsetAsync(W.counters, 0, COVER_BATCH * 4, s)) != hipSuccess) return e;
         for (int r = 0; r < COVER_BATCH; ++r) {
-            thin_count_kernel<<<dim3((unsigned)((G.V + COUNT_THREADS - 1) / COUNT_THREADS)), dim3(COUNT_THREADS), 0, s>>>(
+            thin_count_kernel<<<count_grid(G), dim3(COUNT_THREADS), 0, s>>>(
                 W.mbits, bits, W.dirty, W.state, W.key_vol, W.counters + r, nullptr, G);
             minfilter_xy<long long>(W.key_vol, W.tmp, W.nbr_min, G, s);
-            thin_select_kernel<<<vgrid, block, 0, s>>>(W.mbits, bits, W.nbr_min, W.state, W.key_vol,
+            thin_select_kernel<<<select_grid(G), block, 0, s>>>(W.mbits, bits, W.nbr_min, W.state, W.key_vol,
                                                        W.sel_count, W.cleared, W.dirty, nullptr, 0, G.Z, G);
         }
         *rounds += COVER_BATCH;
@@ -881,7 +1106,7 @@ hipError_t cover_step_count(const uint32_t *bits, int pix_th, int32_t *state, vo
     CoverWork W = carve(work, G);
     hipError_t e;
     if ((e = hipMemsetAsync(W.counters, 0, 4, s)) != hipSuccess) return e;
-    cover_count_kernel<<<dim3((unsigned)((G.V + COUNT_THREADS * COUNT_VPT - 1) / (COUNT_THREADS * COUNT_VPT))), dim3(COUNT_THREADS), 0, s>>>(
+    cover_count_kernel<<<count_grid(G), dim3(COUNT_THREADS), 0, s>>>(
         W.mbits, bits, W.dirty, pix_th, state, W.rank_vol, W.counters, W.loc_vol, witness_ok(G) ? W.witness : nullptr, -1ll, G);
     return hipGetLastError();
 }
@@ -895,7 +1120,7 @@ hipError_t cover_step_filter(void *work, const Geo &G, hipStream_t s) {
 hipError_t cover_step_select(const uint32_t *bits, int pix_th, int32_t *state, int32_t *cleared, void *work,
                              int gZ, const Geo &G, hipStream_t s) {
     CoverWork W = carve(work, G);
-    cover_select_kernel<<<dim3((unsigned)((G.V + 255) / 256)), dim3(256), 0, s>>>(
+    cover_select_kernel<<<select_grid(G), dim3(256), 0, s>>>(
         W.mbits, bits, W.nbr_min, state, W.rank_vol, cleared, W.dirty, W.loc_vol, gZ, -1ll, (pix_th != 0 || !witness_ok(G)) ? 1 : 0, G);
     return hipGetLastError();
 }
@@ -1026,7 +1251,7 @@ hipError_t thin_step_count(const uint32_t *bits, int32_t *state, void *work, con
     ThinShardWork W = carve_thin_shard(work, G);
     hipError_t e;
     if ((e = hipMemsetAsync(W.counters, 0, 4, s)) != hipSuccess) return e;
-    thin_count_kernel<<<dim3((unsigned)((G.V + COUNT_THREADS - 1) / COUNT_THREADS)), dim3(COUNT_THREADS), 0, s>>>(
+    thin_count_kernel<<<count_grid(G), dim3(COUNT_THREADS), 0, s>>>(
         W.mbits, bits, W.dirty, state, W.key_vol, W.counters, W.loc_vol, G);
     return hipGetLastError();
 }
@@ -1038,7 +1263,7 @@ hipError_t thin_step_filter(void *work, const Geo &G, hipStream_t s) {
 hipError_t thin_step_select(const uint32_t *bits, int32_t *state, int32_t *sel_count, int32_t *cleared, void *work,
                             int gZ, const Geo &G, hipStream_t s) {
     ThinShardWork W = carve_thin_shard(work, G);
-    thin_select_kernel<<<dim3((unsigned)((G.V + 255) / 256)), dim3(256), 0, s>>>(
+    thin_select_kernel<<<select_grid(G), dim3(256), 0, s>>>(
         W.mbits, bits, W.nbr_min, state, W.key_vol, sel_count, cleared, W.dirty, W.loc_vol, G.oz, gZ, G);
     return hipGetLastError();
 }

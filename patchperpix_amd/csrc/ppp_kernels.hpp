@@ -153,6 +153,9 @@ hipError_t run_cover_pass(uint8_t *mask, const uint32_t *bits, long long bits_vo
                           long long n, int pix_th, int32_t *state, int32_t *cleared, void *work,
                           const Geo &G, hipStream_t s, int *rounds);
 
+// x and y passes of the rounds' neighbourhood minimum (radius p - 1) on caller-owned volumes of 4- or 8-byte elements
+hipError_t run_minfilter_xy(const void *in, void *scratch, void *out, int elem_bytes, const Geo &G, hipStream_t s);
+
 size_t rank_order_workspace_bytes(const Geo &G);
 hipError_t run_rank_order(const float *score, const uint8_t *fg, long long *lin, float *out_score,
                           long long *n_out, void *work, const Geo &G, hipStream_t s);
