@@ -630,6 +630,13 @@ int64_t ppp_host_thin_cover(const uint8_t *h_mask, const int32_t *vol, const int
  * h_mask uint8 (Z,Y,X) 0 / non-zero, vol = {Z,Y,X}, h_out uint8 (Z,Y,X) 0 / 1; returns the number
  * of voxels kept or -1. */
 int64_t ppp_host_skeletonize_3d(const uint8_t *h_mask, const int32_t *vol, uint8_t *h_out);
+/* ppp_host_skel_rule_mismatches: the deletion rule of the thinning exists twice -- the predicates of
+ * ppp_host_skeletonize_3d and the function of a 27-bit neighbourhood word that the device kernels
+ * evaluate (csrc/ppp_skel_rule.hpp).  Neighbour pattern k < 2^26 enumerates the 26 neighbour bits (the
+ * word without its centre bit 13, higher bits moved down; the centre is set).  Returns the number of
+ * patterns in [first, first + count) on which the two disagree (0 over all 2^26), -1 when the range
+ * leaves [0, 2^26].  Host only; large ranges are split over up to 16 threads. */
+int64_t ppp_host_skel_rule_mismatches(uint32_t first, uint32_t count);
 /* ppp_host_patch_pairs: computeAndStorePatchPairs (aff_patch_graph.py:43-110) with a grid
  *   hash instead of cKDTree; canonical row order (see file header of ppp_host.cpp).
  *   pairs == NULL returns the row count only.                                               */
@@ -704,6 +711,23 @@ int ppp_post_dilate(const uint32_t *d_in, uint32_t *d_out, int32_t Z, int32_t Y,
 int64_t ppp_post_clean_mask_workspace_bytes(int32_t Z, int32_t Y, int32_t X);
 int ppp_post_clean_mask(const uint8_t *d_mask, uint8_t *d_out, int32_t Z, int32_t Y, int32_t X, uint32_t structure,
                         int64_t size, int64_t *n_found, int64_t *n_kept, void *d_work, void *stream);
+
+/* --- 3-d thinning of the foreground on the device (csrc/ppp_skeleton.hip) ----------------------
+ * `skeletonize_foreground` (vote_instances.py:219-224, stitch_patch_graph.py:756-759: the cover mask, or
+ * the bounding box in blockwise mode, is the 3-d skeleton of the foreground).  The result is DEFINED as
+ * that of ppp_host_skeletonize_3d on the same mask, voxel for voxel (Lee / Kashyap / Chu 1994, the host
+ * function's sequential re-check in its exact priority-parallel form); parity with scikit-image's
+ * skeletonize_3d stays UNPINNED, as for the host function.
+ * d_mask u8 [Z][Y][X], 0 / non-zero; d_out u8 [Z][Y][X], 0 / 1 (d_out may be d_mask).  *n_kept = voxels
+ * kept; stats[3] = passes over the border directions, sub-iterations, rounds that had candidates to
+ * decide.  The call synchronises the stream.  PPP_ERR_NO_DEVICE without a device (there is no CPU path
+ * behind it); maps of 2^31 voxels or more, of more than 65535 slices or more than 262140 rows per slice:
+ * PPP_ERR_UNSUPPORTED (the size query returns it as a negative value).  The workspace holds two bit
+ * images of the padded volume, three lists of about Z*Y*X / 2 u32 entries and the round counters. */
+int64_t ppp_skeletonize_3d_workspace_bytes(int32_t Z, int32_t Y, int32_t X);
+int ppp_skeletonize_3d(const uint8_t *d_mask, uint8_t *d_out, int32_t Z, int32_t Y, int32_t X,
+                       int64_t *n_kept, int32_t *stats /* [3]: passes, sub-iterations, rounds */,
+                       void *d_work, void *stream);
 
 /* --- synthetic input (bench / tests only; same hash as patchperpix_amd/synth.py) ------
  * fills d_pred (C,Z,Y,X) from a label volume d_labels int32 (Z,Y,X).  voxel_offset is the

@@ -273,6 +273,7 @@ _SIGNATURES = {
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                              ctypes.c_void_p]),
     "ppp_host_skeletonize_3d": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "ppp_host_skel_rule_mismatches": (ctypes.c_int64, [ctypes.c_uint32, ctypes.c_uint32]),
     "ppp_host_patch_pairs": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                               ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
                                               ctypes.c_void_p]),
@@ -319,6 +320,11 @@ _SIGNATURES = {
                                            ctypes.c_int32, ctypes.c_uint32, ctypes.c_int64,
                                            ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
                                            ctypes.c_void_p, ctypes.c_void_p]),
+    # 3-d thinning of the foreground on the device (ppp_skeleton.hip)
+    "ppp_skeletonize_3d_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "ppp_skeletonize_3d": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                          ctypes.c_int32, ctypes.POINTER(ctypes.c_int64),
+                                          ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 
@@ -1837,6 +1843,46 @@ def host_skeletonize_3d(mask):
     if lib().ppp_host_skeletonize_3d(_np_ptr(m3), _np_ptr(_i32(m3.shape)), _np_ptr(out)) < 0:
         raise RuntimeError("libppp_mi355x: ppp_host_skeletonize_3d: bad arguments")
     return out.reshape(shape).astype(bool)
+
+
+def skeletonize_3d(mask):
+    """ppp_skeletonize_3d: the thinning of host_skeletonize_3d on the device, the same result voxel for
+    voxel.  `mask` is a (Z, Y, X) or (Y, X) NumPy array or device tensor, 0 / non-zero; the bool result
+    is of the same kind and shape.  NOTES["skeleton_stats"] = (passes, sub-iterations, rounds)."""
+    torch = _torch()
+    is_tensor = torch.is_tensor(mask)
+    if not torch.cuda.is_available():
+        raise RuntimeError("libppp_mi355x: ppp_skeletonize_3d: no HIP device available (this library has no CPU path)")
+    if is_tensor:
+        assert mask.is_cuda, "skeletonize_3d takes a NumPy array or a DEVICE tensor"
+        m = (mask != 0).to(torch.uint8).contiguous()
+    else:
+        m = torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0).astype(np.uint8)).cuda()
+    shape = tuple(m.shape)
+    assert 2 <= len(shape) <= 3, "skeletonize_3d needs a (Z, Y, X) or (Y, X) mask"
+    Z, Y, X = (1,) * (3 - len(shape)) + shape
+    if Z * Y * X == 0:
+        out = m
+    else:
+        work = _workspace(lib().ppp_skeletonize_3d_workspace_bytes(Z, Y, X), m.device)
+        kept = ctypes.c_int64(0)
+        stats = (ctypes.c_int32 * 3)()
+        with _timed("skeletonize_3d"):
+            check(lib().ppp_skeletonize_3d(_dev_ptr(m), _dev_ptr(m), Z, Y, X, ctypes.byref(kept), stats,
+                                           _dev_ptr(work), _stream()))
+        NOTES["skeleton_stats"] = tuple(int(v) for v in stats)
+        NOTES["skeleton_kept"] = int(kept.value)
+        out = m
+    return out.bool() if is_tensor else out.cpu().numpy().astype(bool)
+
+
+def host_skel_rule_mismatches(first, count):
+    """ppp_host_skel_rule_mismatches: neighbour patterns in [first, first + count) on which the rule the
+    device kernels evaluate (csrc/ppp_skel_rule.hpp) and the host thinning's predicates disagree."""
+    n = int(lib().ppp_host_skel_rule_mismatches(int(first), int(count)))
+    if n < 0:
+        raise ValueError("ppp_host_skel_rule_mismatches: the range leaves [0, 2^26]")
+    return n
 
 
 def host_patch_pairs(sel_zyx, patchshape, max_ps_dist=2, include_single=True):

@@ -1232,4 +1232,32 @@ int ppp_post_clean_mask(const uint8_t *d_mask, uint8_t *d_out, int32_t Z, int32_
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_post_clean_mask");
 }
 
+/* ---- 3-d thinning of the foreground (ppp_skeleton.hip) ---- */
+static int skeleton_volume(int32_t Z, int32_t Y, int32_t X) {
+    long long V;
+    PPP_TRY(post_volume(Z, Y, X, &V));
+    // one workgroup row per slice and per four rows of a slice
+    if (Z > 65535 || Y > 4 * 65535)
+        return fail(PPP_ERR_UNSUPPORTED, "ppp_skeletonize_3d: at most 65535 slices of at most 262140 rows");
+    return PPP_OK;
+}
+
+int64_t ppp_skeletonize_3d_workspace_bytes(int32_t Z, int32_t Y, int32_t X) {
+    int rc = skeleton_volume(Z, Y, X);
+    return rc != PPP_OK ? rc : (int64_t)ppp::skeleton_workspace_bytes(Z, Y, X);
+}
+
+int ppp_skeletonize_3d(const uint8_t *d_mask, uint8_t *d_out, int32_t Z, int32_t Y, int32_t X, int64_t *n_kept,
+                       int32_t *stats, void *d_work, void *stream) {
+    PPP_TRY(skeleton_volume(Z, Y, X));
+    if (!d_mask || !d_out || !d_work || !n_kept || !stats) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    PPP_TRY(need_device());
+    long long kept = 0;
+    int st[3] = {0, 0, 0};
+    hipError_t e = ppp::run_skeletonize_3d(d_mask, d_out, Z, Y, X, &kept, st, d_work, (hipStream_t)stream);
+    *n_kept = kept;
+    stats[0] = st[0]; stats[1] = st[1]; stats[2] = st[2];
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_skeletonize_3d");
+}
+
 }  // extern "C"

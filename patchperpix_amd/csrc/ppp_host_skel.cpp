@@ -165,3 +165,56 @@ int64_t ppp_host_skeletonize_3d(const uint8_t *mask, const int32_t *vol, uint8_t
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// The rule as one function of a 27-bit word (ppp_skel_rule.hpp, what the device kernels evaluate)
+// against the predicates above.
+// ---------------------------------------------------------------------------------------------
+#include <thread>
+
+#include "ppp_skel_rule.hpp"
+
+namespace {
+
+// neighbour pattern k (26 bits: the neighbourhood word without its centre bit, higher bits moved down)
+// -> the word with the centre set
+inline uint32_t rule_word(uint32_t k) { return (k & 0x1FFFu) | ((k >> 13) << 14) | ppp_skel::kCentre; }
+
+int64_t rule_mismatches_range(uint32_t first, uint32_t count) {
+    int64_t bad = 0;
+    uint8_t nb[27];
+    for (uint64_t k = first; k < (uint64_t)first + count; ++k) {
+        const uint32_t w = rule_word((uint32_t)k);
+        int n = 0;
+        for (int i = 0; i < 27; ++i) { nb[i] = (w >> i) & 1u; n += nb[i]; }
+        // the composition of `removable` in ppp_host_skeletonize_3d
+        const bool want = n != 2 && euler_delta(nb) == 0 && one_component(nb);
+        bad += want != ppp_skel::removable(w);
+    }
+    return bad;
+}
+
+}  // namespace
+
+extern "C" {
+
+// The number of neighbour patterns k in [first, first + count) -- k < 2^26 enumerates the 26 neighbour
+// bits, the centre is set -- on which ppp_skel::removable and this file's predicates disagree; -1 when
+// the range leaves [0, 2^26].  Ranges of 2^20 patterns or more are split over up to 16 threads.
+int64_t ppp_host_skel_rule_mismatches(uint32_t first, uint32_t count) {
+    if ((uint64_t)first + count > (1ull << 26)) return -1;
+    const uint32_t n_threads = count >= (1u << 20) ? 16u : 1u;
+    if (n_threads == 1u) return rule_mismatches_range(first, count);
+    std::vector<int64_t> part(n_threads, 0);
+    std::vector<std::thread> pool;
+    const uint32_t per = (count + n_threads - 1) / n_threads;
+    for (uint32_t t = 0; t < n_threads; ++t) {
+        const uint32_t lo = t * per < count ? t * per : count, hi = lo + per < count ? lo + per : count;
+        pool.emplace_back([&part, t, first, lo, hi] { part[t] = rule_mismatches_range(first + lo, hi - lo); });
+    }
+    int64_t bad = 0;
+    for (uint32_t t = 0; t < n_threads; ++t) { pool[t].join(); bad += part[t]; }
+    return bad;
+}
+
+}  // extern "C"

@@ -211,4 +211,9 @@ size_t post_clean_mask_workspace_bytes(long long V);
 hipError_t run_post_clean_mask(const uint8_t *mask, uint8_t *out, int Z, int Y, int X, uint32_t structure,
                                long long size, long long *n_found, long long *n_kept, void *work, hipStream_t s);
 
+// 3-d thinning of the foreground (ppp_skeleton.hip)
+size_t skeleton_workspace_bytes(int Z, int Y, int X);
+hipError_t run_skeletonize_3d(const uint8_t *mask, uint8_t *out, int Z, int Y, int X, long long *n_kept, int *stats,
+                              void *work, hipStream_t s);
+
 }  // namespace ppp

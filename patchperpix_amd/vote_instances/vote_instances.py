@@ -89,13 +89,16 @@ def _skeletonize(mask, backend_name=None):
     Kashyap / Chu 1994; csrc/ppp_host_skel.cpp) but is PARITY UNPINNED against scikit-image, which
     this image lacks, and deliberately deviates in its sequential re-check (all three deletion
     conditions instead of the simple-point test alone, which erases plates two voxels thick) --
-    so the cover mask / bounding box may differ from a scikit-image run.  The choice is logged at
-    WARNING and recorded in ``SKELETONIZE_SERVED_BY`` (the drivers copy it into the output attrs)."""
+    so the cover mask / bounding box may differ from a scikit-image run.  ``"ppp_device"`` is the
+    same thinning on the device (``ppp_skeletonize_3d``, csrc/ppp_skeleton.hip): the host function's
+    result voxel for voxel, and an error without a device -- it never takes the host loop.  The choice
+    is logged at WARNING and recorded in ``SKELETONIZE_SERVED_BY`` (the drivers copy it into the output
+    attrs)."""
     global SKELETONIZE_SERVED_BY
     import os
     choice = backend_name or os.environ.get("PPP_SKELETONIZE") or "skimage"
-    if choice not in ("skimage", "ppp"):
-        raise ValueError("skeletonize_backend must be 'skimage' or 'ppp', not %r" % (choice,))
+    if choice not in ("skimage", "ppp", "ppp_device"):
+        raise ValueError("skeletonize_backend must be 'skimage', 'ppp' or 'ppp_device', not %r" % (choice,))
     if choice == "skimage":
         try:
             from skimage.morphology import skeletonize_3d
@@ -106,6 +109,11 @@ def _skeletonize(mask, backend_name=None):
                 "whose result is not pinned to scikit-image's") from e
         SKELETONIZE_SERVED_BY = "skimage.morphology.skeletonize_3d"
         return skeletonize_3d(mask) > 0
+    if choice == "ppp_device":
+        logger.warning("skeletonize_foreground: thinning with ppp_skeletonize_3d (skeletonize_backend='ppp_device'); "
+                       "not pinned to scikit-image's skeletonize_3d -- the cover mask / bounding box may differ")
+        SKELETONIZE_SERVED_BY = "ppp_skeletonize_3d"
+        return backend.skeletonize_3d(mask)
     logger.warning("skeletonize_foreground: thinning with ppp_host_skeletonize_3d (skeletonize_backend='ppp'); "
                    "not pinned to scikit-image's skeletonize_3d -- the cover mask / bounding box may differ")
     SKELETONIZE_SERVED_BY = "ppp_host_skeletonize_3d"
