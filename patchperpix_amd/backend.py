@@ -1591,9 +1591,35 @@ def synth_pred(labels, P, seed=0, hi=0.95, lo=0.05, noise=0.04, f16=True, voxel_
 
 def decode_tail(x, w1, b1, w2, b2, w3, b3, dst, pred, patchshape):
     """ppp_decode_tail: x float32 [n, 64, 4, 4, 4] (decoder features), dst int64 [n] voxel indices,
-    pred (C, ...) float16 / float32 device block -- written in place at pred[:, dst]."""
+    pred (C, ...) float16 / float32 device block -- written in place at pred[:, dst].  The kernel
+    trusts every extent it is given, so the arguments are checked here first (shapes, dtypes and
+    devices only: no device synchronisation; the VALUES of dst, each in [0, voxels of pred), stay
+    the caller's promise): a mismatch raises ValueError before the library is touched."""
     torch = _torch()
+    patchshape = tuple(int(p) for p in patchshape)
+    if x.dim() < 1 or pred.dim() < 1:
+        raise ValueError("decode_tail: x and pred need a leading batch / channel dimension")
     n = int(x.shape[0])
+    if patchshape == (7, 7, 7) and tuple(x.shape[1:]) != (64, 4, 4, 4):
+        raise ValueError("decode_tail: 7^3 patches are decoded from features (n, 64, 4, 4, 4), got %s" %
+                         (tuple(x.shape),))
+    if int(dst.numel()) != n:
+        raise ValueError("decode_tail: %d destination indices for %d patches" % (int(dst.numel()), n))
+    if dst.is_floating_point() or dst.is_complex() or dst.dtype == torch.bool:
+        raise ValueError("decode_tail: dst must hold integer voxel indices, got %s" % dst.dtype)
+    if pred.dtype not in (torch.float16, torch.float32):
+        raise ValueError("decode_tail: pred must be float16 or float32, got %s" % pred.dtype)
+    if not pred.is_contiguous():
+        raise ValueError("decode_tail: pred must be contiguous (it is written through its base pointer)")
+    if int(pred.shape[0]) != int(np.prod(patchshape)):
+        raise ValueError("decode_tail: pred has %d channels, patches of %s have %d" %
+                         (int(pred.shape[0]), patchshape, int(np.prod(patchshape))))
+    for name, w, count in (("w1", w1, int(x.shape[1]) * 27 if x.dim() > 1 else 27), ("w2", w2, 27), ("w3", w3, 27)):
+        if int(w.numel()) != count:
+            raise ValueError("decode_tail: %s has %d elements, expected %d" % (name, int(w.numel()), count))
+    if len({t.device for t in (x, dst, pred, w1, w2, w3)}) != 1:
+        raise ValueError("decode_tail: x, dst, pred and the weights must be on one device, got %s" %
+                         sorted({str(t.device) for t in (x, dst, pred, w1, w2, w3)}))
     if n == 0:
         return pred
     P = Params()
@@ -1602,7 +1628,7 @@ def decode_tail(x, w1, b1, w2, b2, w3, b3, dst, pred, patchshape):
     while len(vol) < 3:
         vol = [1] + vol
     P.Z, P.Y, P.X = vol
-    P.pz, P.py, P.px = [int(p) for p in patchshape]
+    P.pz, P.py, P.px = patchshape
     P.th = P.thi = 0.5
     P.bg_rule, P.value_rule = BG_LESS_THAN_TH, VAL_COUNT
     P.cons_box = Box(0, 0, 0, P.Z, P.Y, P.X)

@@ -27,7 +27,14 @@
 // PARITY: the decoder's arithmetic is unpinned by the reference (funlib.learn.torch absent, no
 // checkpoint); this kernel is checked against the torch restatement of the same layers
 // (patchperpix_amd/decode.py PatchDecoder) within a float tolerance (summation order differs from
-// MIOpen's), tests/test_decode.py.
+// MIOpen's), tests/test_decode.py, and pinned to a float64 evaluation of the literal layers
+// (tests/decode_ref.py) by tests/test_decode_exact.py: on exactly representable operands (every
+// float32 summation order exact) the block holds the float16 rounding of the float64 result bit
+// for bit, over the batch edges of a 64-patch group, both destination dtypes and scatter offsets
+// past 2^32, with every other column of a sentinel-filled block untouched; on realistic weights
+// every value is one of the two float16 neighbours of the float64 result, and the correctly
+// rounded one wherever that result is further from a float16 rounding boundary than the derived
+// float32 forward-error bound.
 #include "ppp_kernels.hpp"
 
 namespace ppp {
