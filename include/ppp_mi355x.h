@@ -335,6 +335,33 @@ int ppp_paint_instances(const void *d_pred, int pred_dtype, const uint32_t *d_no
                         const uint32_t *d_labels, uint64_t n_nodes, uint32_t *d_instances,
                         const ppp_params *p, void *stream);
 
+/* --- `no_overlap_per_channel` without the loop over components (ppp_pack_channels.hip) -------
+ * Replaces graph_to_labeling.py:57-115 (per component: a zeroed volume, the paint, np.sum, a masked
+ * test per channel tried) by sizes + overlap pairs (below), ppp_host_pack_channels and one paint.
+ * Labels are 1 .. n_labels; `own` is the sub-box of the frame (Z,Y,X of ppp_params) whose voxels the
+ * call counts (NULL = the whole frame): a tile counts its own voxels and reads patch centres from
+ * its frame, grown by the patch radius.  Nodes must lie inside the frame.
+ * ppp_pack_scan_count: d_sizes u64 [n_labels + 1] += the number of own voxels each label covers
+ *   (slot 0 unused; the caller zeroes the table once and may sum several boxes into it);
+ *   *n_pairs = the keys ppp_pack_scan_fill will write.  Synchronises the stream.
+ * ppp_pack_scan_fill: after the count, on the same workspace, prediction, frame and box: d_pairs
+ *   u64 [n_pairs] = (b << 32) | a for every own voxel and every two labels a < b that cover it (a
+ *   pair comes once per shared voxel -- the caller dedupes; exact, nothing dropped, no cap on the
+ *   labels that meet in a voxel).
+ * ppp_paint_instances_channels: ppp_paint_instances into d_out u32 (n_channels, Z, Y, X):
+ *   label l is painted into channel d_chan[l] (u32 [n_labels + 1], slot 0 unused), the largest
+ *   label of a channel wins a voxel (graph_to_labeling.py:93-106 given the assignment).       */
+int64_t ppp_pack_scan_workspace_bytes(const ppp_params *p, const ppp_box *own);
+int ppp_pack_scan_count(const void *d_pred, int pred_dtype, const uint32_t *d_nodes, const uint32_t *d_labels,
+                        uint64_t n_nodes, uint32_t n_labels, const ppp_box *own, uint64_t *d_sizes,
+                        int64_t *n_pairs, void *d_work, const ppp_params *p, void *stream);
+int ppp_pack_scan_fill(const void *d_pred, int pred_dtype, const ppp_box *own, uint64_t *d_pairs, int64_t n_pairs,
+                       void *d_work, const ppp_params *p, void *stream);
+int ppp_paint_instances_channels(const void *d_pred, int pred_dtype, const uint32_t *d_nodes,
+                                 const uint32_t *d_labels, uint64_t n_nodes, const uint32_t *d_chan,
+                                 uint32_t n_labels, uint32_t n_channels, uint32_t *d_out,
+                                 const ppp_params *p, void *stream);
+
 /* ppp_paint_patch_rows: the same painting with the patches given as a table instead of a dense
  * prediction block: d_rows [n_nodes][C] (float16 / float32), row k = pred[:, node k].  Serves
  * affGraphToInstances(sparse_labels=True) of the blockwise driver (graph_to_labeling.py:66-72,
@@ -661,6 +688,18 @@ int64_t ppp_host_mws(const uint32_t *pairs, const float *aff, int64_t n_rows, co
  *   ids issued (emptied components included).                                               */
 int64_t ppp_host_mws_sorted(const int32_t *eu, const int32_t *ev, int64_t n_edges, int64_t n_nodes,
                             int32_t *labels);
+
+/* ppp_host_pack_channels: the channel assignment of `no_overlap_per_channel`
+ *   (graph_to_labeling.py:86-106: one painted volume, one .sum() and one masked test per component
+ *   and channel) as a greedy walk over sizes and overlap pairs (closed form: ppp_pack_channels.hip).
+ *   sizes int64 [n_labels]: voxels of component k (label k + 1); pairs u64 [n_pairs]: keys
+ *   (b << 32) | a of overlapping labels 1 <= a < b <= n_labels, any order, repeats allowed.
+ *   Component 0 and every component of at most min_voxels voxels (2000 in the reference) go to
+ *   channel 0; any other goes to the first channel none of whose earlier components overlaps it,
+ *   a new one if there is none.  chan_out int32 [n_labels], *n_channels_out = channels opened (0
+ *   without components).  Returns the number of channels, -1 on bad arguments.              */
+int64_t ppp_host_pack_channels(int64_t n_labels, const int64_t *sizes, const uint64_t *pairs, int64_t n_pairs,
+                               int64_t min_voxels, int32_t *chan_out, int32_t *n_channels_out);
 
 /* --- order-defining stages as device sorts (rocPRIM inside the library) ------------------
  * ppp_rank_order: all_patches + rank_patches_by_score (vote_instances.py:276,286-287,

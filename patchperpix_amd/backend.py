@@ -325,6 +325,19 @@ _SIGNATURES = {
     "ppp_skeletonize_3d": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                                           ctypes.c_int32, ctypes.POINTER(ctypes.c_int64),
                                           ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_void_p]),
+    # no_overlap_per_channel without the loop over components (ppp_pack_channels.hip, ppp_host_pack.cpp)
+    "ppp_pack_scan_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(Params), ctypes.POINTER(Box)]),
+    "ppp_pack_scan_count": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(Box), ctypes.c_void_p,
+                                           ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p, ctypes.POINTER(Params),
+                                           ctypes.c_void_p]),
+    "ppp_pack_scan_fill": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Box), ctypes.c_void_p,
+                                          ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(Params), ctypes.c_void_p]),
+    "ppp_paint_instances_channels": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
+                                                    ctypes.c_void_p, ctypes.POINTER(Params), ctypes.c_void_p]),
+    "ppp_host_pack_channels": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]),
 }
 
 
@@ -1261,6 +1274,67 @@ def paint_instances(pred, nodes, labels, instances, P):
                                         _dev_ptr(labels), int(nodes.shape[0]),
                                         _dev_ptr(instances), ctypes.byref(P), _stream()))
     return instances
+
+
+# ---- no_overlap_per_channel: sizes + overlap pairs, the greedy walk, the paint by channel ----------
+PACK_MIN_VOXELS = 2000      # graph_to_labeling.py:98
+
+
+def pack_scan(pred, nodes, labels, n_labels, P, own=None, sizes=None):
+    """Sizes and overlap pairs of the components (ppp_pack_scan_count / _fill).  nodes int32 [K, 3] and
+    labels int32 [K] (1 .. n_labels) in the frame of P; own = (z0, y0, x0, z1, y1, x1) of the frame's
+    voxels to count (None: all).  Returns (sizes int64 [n_labels + 1] on the device, slot 0 unused --
+    `sizes` given: added to in place -- and pair keys int64 [n], (b << 32) | a with a < b, one per
+    pair and shared voxel: not yet unique)."""
+    torch = _torch()
+    dev = pred.device
+    if sizes is None:
+        sizes = torch.zeros((int(n_labels) + 1,), dtype=torch.int64, device=dev)
+    box = Box(*[int(v) for v in own]) if own is not None else Box(0, 0, 0, P.Z, P.Y, P.X)
+    work = _workspace(lib().ppp_pack_scan_workspace_bytes(ctypes.byref(P), ctypes.byref(box)), dev)
+    n_pairs = ctypes.c_int64(0)
+    with _timed("pack_scan"):
+        check(lib().ppp_pack_scan_count(_dev_ptr(pred), pred_dtype_code(pred), _dev_ptr(nodes), _dev_ptr(labels),
+                                        int(nodes.shape[0]), int(n_labels), ctypes.byref(box), _dev_ptr(sizes),
+                                        ctypes.byref(n_pairs), _dev_ptr(work), ctypes.byref(P), _stream()))
+        pairs = torch.empty((int(n_pairs.value),), dtype=torch.int64, device=dev)
+        check(lib().ppp_pack_scan_fill(_dev_ptr(pred), pred_dtype_code(pred), ctypes.byref(box), _dev_ptr(pairs),
+                                       int(n_pairs.value), _dev_ptr(work), ctypes.byref(P), _stream()))
+    return sizes, pairs
+
+
+def host_pack_channels(sizes, pairs, min_voxels=PACK_MIN_VOXELS):
+    """ppp_host_pack_channels.  sizes: voxels of component k (label k + 1), host array [K]; pairs: host
+    array of keys (b << 32) | a of overlapping labels a < b.  Returns (chan int32 [K], n_channels)."""
+    sizes = np.ascontiguousarray(sizes, dtype=np.int64)
+    pairs = np.ascontiguousarray(pairs).astype(np.uint64, copy=False)
+    chan = np.zeros(len(sizes), dtype=np.int32)
+    n_ch = ctypes.c_int32(0)
+    if lib().ppp_host_pack_channels(len(sizes), _np_ptr(sizes), _np_ptr(pairs), len(pairs), int(min_voxels),
+                                    _np_ptr(chan), ctypes.byref(n_ch)) < 0:
+        raise RuntimeError("libppp_mi355x: ppp_host_pack_channels: bad arguments")
+    return chan, int(n_ch.value)
+
+
+def paint_instances_channels(pred, nodes, labels, chan, n_channels, out, P):
+    """S6 (paint by channel).  chan int32 [n_labels + 1] on the device (slot 0 unused): label l goes to
+    out[chan[l]]; out int32 (n_channels, Z, Y, X) in place, the largest label of a channel wins."""
+    with _timed("paint_instances"):
+        check(lib().ppp_paint_instances_channels(_dev_ptr(pred), pred_dtype_code(pred), _dev_ptr(nodes),
+                                                 _dev_ptr(labels), int(nodes.shape[0]), _dev_ptr(chan),
+                                                 int(chan.numel()) - 1, int(n_channels), _dev_ptr(out),
+                                                 ctypes.byref(P), _stream()))
+    return out
+
+
+def pack_channels(sizes, pairs):
+    """sizes (device, [n_labels + 1]) and pair keys (device, any order, repeats allowed) -> (chan int32
+    [n_labels + 1] on the device, slot 0 unused, and the channel count): unique, then the host walk."""
+    torch = _torch()
+    uniq = torch.unique(pairs) if pairs.numel() else pairs
+    chan, n_ch = host_pack_channels(sizes[1:].cpu().numpy(), uniq.cpu().numpy())
+    chan_dev = torch.from_numpy(np.concatenate([np.zeros(1, np.int32), chan])).to(sizes.device)
+    return chan_dev, n_ch
 
 
 # ---- the reference's NumPy-semantics stages (cuda=False) -------------------------------------------

@@ -718,6 +718,75 @@ int ppp_paint_instances(const void *d_pred, int pred_dtype, const uint32_t *d_no
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_paint_instances");
 }
 
+// ---- no_overlap_per_channel (ppp_pack_channels.hip) ----------------------------------------------
+static int pack_own_box(const ppp_box *own, const ppp::Geo &G, ppp_box *b) {
+    if (own) *b = *own;
+    else { b->z0 = b->y0 = b->x0 = 0; b->z1 = G.Z; b->y1 = G.Y; b->x1 = G.X; }
+    if (b->z0 < 0 || b->y0 < 0 || b->x0 < 0 || b->z1 > G.Z || b->y1 > G.Y || b->x1 > G.X ||
+        b->z1 < b->z0 || b->y1 < b->y0 || b->x1 < b->x0)
+        return fail(PPP_ERR_INVALID_ARG, "own box outside the frame");
+    return PPP_OK;
+}
+
+int64_t ppp_pack_scan_workspace_bytes(const ppp_params *p, const ppp_box *own) {
+    ppp::Geo G;
+    ppp_box b;
+    int rc = make_geo(p, &G);
+    if (rc == PPP_OK) rc = pack_own_box(own, G, &b);
+    return rc != PPP_OK ? rc : (int64_t)ppp::pack_scan_workspace_bytes(G, b);
+}
+
+int ppp_pack_scan_count(const void *d_pred, int pred_dtype, const uint32_t *d_nodes, const uint32_t *d_labels,
+                        uint64_t n_nodes, uint32_t n_labels, const ppp_box *own, uint64_t *d_sizes,
+                        int64_t *n_pairs, void *d_work, const ppp_params *p, void *stream) {
+    ppp::Geo G;
+    ppp_box b;
+    PPP_TRY(make_geo(p, &G));
+    PPP_TRY(check_dtype(pred_dtype));
+    PPP_TRY(pack_own_box(own, G, &b));
+    if (!n_pairs || !d_work || !d_sizes || (n_nodes > 0 && (!d_pred || !d_nodes || !d_labels)))
+        return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    PPP_TRY(need_device());
+    long long np = 0;
+    hipError_t e = ppp::run_pack_scan_count(d_pred, pred_dtype, d_nodes, d_labels, n_nodes, n_labels, b,
+                                            (unsigned long long *)d_sizes, &np, d_work, G, (hipStream_t)stream);
+    *n_pairs = np;
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_pack_scan_count");
+}
+
+int ppp_pack_scan_fill(const void *d_pred, int pred_dtype, const ppp_box *own, uint64_t *d_pairs, int64_t n_pairs,
+                       void *d_work, const ppp_params *p, void *stream) {
+    ppp::Geo G;
+    ppp_box b;
+    PPP_TRY(make_geo(p, &G));
+    PPP_TRY(check_dtype(pred_dtype));
+    PPP_TRY(pack_own_box(own, G, &b));
+    if (n_pairs < 0) return fail(PPP_ERR_INVALID_ARG, "n_pairs must be >= 0");
+    if (n_pairs == 0) return PPP_OK;
+    if (!d_pred || !d_pairs || !d_work) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    PPP_TRY(need_device());
+    hipError_t e = ppp::run_pack_scan_fill(d_pred, pred_dtype, b, (unsigned long long *)d_pairs, n_pairs, d_work, G,
+                                           (hipStream_t)stream);
+    if (e == hipErrorInvalidValue)
+        return fail(PPP_ERR_INVALID_ARG, "ppp_pack_scan_fill: n_pairs / workspace are not those of ppp_pack_scan_count");
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_pack_scan_fill");
+}
+
+int ppp_paint_instances_channels(const void *d_pred, int pred_dtype, const uint32_t *d_nodes,
+                                 const uint32_t *d_labels, uint64_t n_nodes, const uint32_t *d_chan,
+                                 uint32_t n_labels, uint32_t n_channels, uint32_t *d_out,
+                                 const ppp_params *p, void *stream) {
+    ppp::Geo G;
+    PPP_TRY(make_geo(p, &G));
+    PPP_TRY(check_dtype(pred_dtype));
+    if (n_nodes == 0 || n_channels == 0) return PPP_OK;
+    if (!d_pred || !d_nodes || !d_labels || !d_chan || !d_out) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    PPP_TRY(need_device());
+    hipError_t e = ppp::launch_paint_channels(d_pred, pred_dtype, d_nodes, d_labels, n_nodes, d_chan, n_labels, n_channels,
+                                              d_out, G, (hipStream_t)stream);
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_paint_instances_channels");
+}
+
 // ---- the reference's NumPy-semantics stages (cuda=False) -----------------------------------------
 int64_t ppp_np_vote_planes(const ppp_params *p) {
     ppp::Geo G;

@@ -124,6 +124,16 @@ hipError_t launch_paint_rows(const void *rows, int dtype, const uint32_t *nodes,
 hipError_t launch_paint(const void *pred, int dtype, const uint32_t *nodes,
                         const uint32_t *labels, uint64_t n, uint32_t *inst, const Geo &G,
                         hipStream_t s);
+// no_overlap_per_channel: sizes + overlap pairs, paint by channel (ppp_pack_channels.hip)
+size_t pack_scan_workspace_bytes(const Geo &G, const ppp_box &own);
+hipError_t run_pack_scan_count(const void *pred, int dtype, const uint32_t *nodes, const uint32_t *labels, uint64_t n_nodes,
+                               uint32_t n_labels, const ppp_box &own, unsigned long long *sizes, long long *n_pairs,
+                               void *work, const Geo &G, hipStream_t s);
+hipError_t run_pack_scan_fill(const void *pred, int dtype, const ppp_box &own, unsigned long long *pairs, long long n_pairs,
+                              void *work, const Geo &G, hipStream_t s);
+hipError_t launch_paint_channels(const void *pred, int dtype, const uint32_t *nodes, const uint32_t *labels, uint64_t n,
+                                 const uint32_t *chan, uint32_t n_labels, uint32_t n_channels, uint32_t *out,
+                                 const Geo &G, hipStream_t s);
 hipError_t launch_cons_to_voxel_major(const float *compact, float *S, const Geo &G,
                                       hipStream_t s);
 hipError_t launch_cons_planes_to_rows(const float *planes, const ppp_box &pb, float *S, const Geo &G,

@@ -679,6 +679,12 @@ class DeviceOps:
     def paint(self, pred, nodes, labels, inst, P):
         return backend.paint_instances(pred, nodes, labels, inst, P)
 
+    def pack_scan(self, pred, nodes, labels, n_labels, P, own, sizes):
+        return backend.pack_scan(pred, nodes, labels, n_labels, P, own=own, sizes=sizes)
+
+    def paint_channels(self, pred, nodes, labels, chan, n_channels, out, P):
+        return backend.paint_instances_channels(pred, nodes, labels, chan, n_channels, out, P)
+
 
 # ------------------------------------------------------------------------------------------
 # the greedy cover, sharded by z over the ranks
@@ -1023,9 +1029,14 @@ class _Assembly:
         # to_instance_seg -- applies skeletonize_foreground to the mask before it gets here)
         for opt in ("skipConsensus", "skipRanking", "termAfterThinCover", "termAfterPatchGraph",
                     "save_consensus", "graphToInst", "debug", "isbiHack", "pad_with_ps",
-                    "one_instance_per_channel", "no_overlap_per_channel", "sparse_labels"):
+                    "one_instance_per_channel", "sparse_labels"):
             if self.kw.get(opt, False):
                 raise NotImplementedError("%s is not supported by the tiled / multi-rank assembly" % opt)
+        # no_overlap_per_channel: sizes and overlap pairs per own tile, summed / united over the ranks,
+        # the same channel walk on every rank, one paint by channel per tile (label_and_paint)
+        self.packed = bool(self.kw.get("no_overlap_per_channel", False))
+        if self.packed and self.ops is not None and not hasattr(self.ops, "pack_scan"):
+            raise NotImplementedError("no_overlap_per_channel needs the device kernels (DeviceOps)")
         # the two optional branches of the greedy cover (foreground_cover.py:53-85, 141-168) leave marks
         # anywhere in a slice: a sequential walk of the ranked list -- served on ONE rank (below)
         self.seq_cover = bool(self.kw.get("mark_close_neighboorhood", False) or self.kw.get("select_patches_overlap_neighborhood", False))
@@ -1958,53 +1969,16 @@ class _Assembly:
             backend.note("ids_issued", n_labels)
             # painted on the own slabs only; `inst_g` is the whole map when it is gathered
             gz0, gz1 = (0, self.Z) if self.gather_result else (self.oz0, self.oz1)
+            if self.packed:
+                return self.paint_packed(lab_nodes, labels, n_labels, gz0, gz1)
             inst_g = torch.zeros((gz1 - gz0, self.Y, self.X), dtype=torch.int32, device=self.dev)
-            if self.whole is not None:
-                Pl = self.params(self.whole)
-                for (z0, z1) in self.my_slabs:
-                    near = torch.nonzero((lab_nodes[:, 0] >= z0 - self.rz) & (lab_nodes[:, 0] < z1 + self.rz)).reshape(-1)
-                    if near.numel() == 0:
-                        continue
-                    inst_l = torch.zeros(self.whole.shape, dtype=torch.int32, device=self.dev)
-                    self.ops.paint(self.whole.pred, self.to_local(lab_nodes[near], self.whole), labels[near].contiguous(), inst_l, Pl)
-                    inst_g[z0 - gz0:z1 - gz0] = inst_l[z0 - self.lo:z1 - self.lo]
-                    del inst_l
-            else:
-                # nodes sorted by z once: a tile looks at the nodes of its own z-range (+ radius) only
-                # instead of scanning the whole list (640 tiles x 3.6 M nodes at 1024^3); the painting
-                # keeps the largest label per voxel, so the order of the nodes does not matter
-                if len(self.my_tiles) > 1 and lab_nodes.shape[0] > 0:
-                    z_order = torch.argsort(lab_nodes[:, 0].contiguous(), stable=True)
-                    lab_nodes, labels = lab_nodes[z_order].contiguous(), labels[z_order].contiguous()
-                    node_z = lab_nodes[:, 0].contiguous()
-                    del z_order
-                else:
-                    node_z = None
-                for t in self.my_tiles:
-                    z0, z1, y0, y1, x0, x1 = t
-                    if node_z is not None:
-                        za = int(torch.searchsorted(node_z, torch.tensor([z0 - self.rz], dtype=node_z.dtype, device=self.dev)).item())
-                        zb = int(torch.searchsorted(node_z, torch.tensor([z1 + self.rz], dtype=node_z.dtype, device=self.dev)).item())
-                        part = lab_nodes[za:zb]
-                        near = (part[:, 1] >= y0 - int(self.rad[1])) & (part[:, 1] < y1 + int(self.rad[1]))
-                        near &= (part[:, 2] >= x0 - int(self.rad[2])) & (part[:, 2] < x1 + int(self.rad[2]))
-                        near = torch.nonzero(near).reshape(-1) + za
-                        del part
-                    else:
-                        near = (lab_nodes[:, 0] >= z0 - self.rz) & (lab_nodes[:, 0] < z1 + self.rz)
-                        near &= (lab_nodes[:, 1] >= y0 - int(self.rad[1])) & (lab_nodes[:, 1] < y1 + int(self.rad[1]))
-                        near &= (lab_nodes[:, 2] >= x0 - int(self.rad[2])) & (lab_nodes[:, 2] < x1 + int(self.rad[2]))
-                        near = torch.nonzero(near).reshape(-1)
-                    if near.numel() == 0:
-                        continue
-                    nxt = self.next_of(t)
-                    fr = self.frame_for(self.grow(t, self.rad), self.grow(nxt, self.rad) if nxt is not None else None)
-                    o = fr.origin
-                    inst_l = torch.zeros(fr.shape, dtype=torch.int32, device=self.dev)
-                    self.ops.paint(fr.pred, self.to_local(lab_nodes[near], fr), labels[near].contiguous(), inst_l, self.params(fr))
-                    inst_g[z0 - gz0:z1 - gz0, y0:y1, x0:x1] = \
-                        inst_l[z0 - o[0]:z1 - o[0], y0 - o[1]:y1 - o[1], x0 - o[2]:x1 - o[2]]
-                    del inst_l, fr
+            for fr, Pl, nodes_l, labels_l, (z0, z1, y0, y1, x0, x1) in self.own_frames(lab_nodes, labels):
+                o = fr.origin
+                inst_l = torch.zeros(fr.shape, dtype=torch.int32, device=self.dev)
+                self.ops.paint(fr.pred, nodes_l, labels_l, inst_l, Pl)
+                inst_g[z0 - gz0:z1 - gz0, y0:y1, x0:x1] = \
+                    inst_l[z0 - o[0]:z1 - o[0], y0 - o[1]:y1 - o[1], x0 - o[2]:x1 - o[2]]
+                del inst_l, fr
             if not self.gather_result:
                 instances = inst_g.cpu().numpy().view(np.uint32).astype(self.id_dtype, copy=False)
                 return instances, self.fg_out(self.oz0, self.oz1)
@@ -2028,6 +2002,100 @@ class _Assembly:
                         inst16 = inst32.to(torch.int16)
                 instances = inst16.cpu().numpy().view(np.uint16)
         return instances, self.full_fg()
+
+
+    def own_frames(self, lab_nodes, labels):
+        """What the painting of one own box needs, box after box: (frame, its parameters, the labelled
+        nodes whose windows reach the box in frame coordinates, their labels, the box as global
+        (z0, z1, y0, y1, x0, x1)).  Boxes no labelled node reaches are left out."""
+        import torch
+        if self.whole is not None:
+            Pl = self.params(self.whole)
+            for (z0, z1) in self.my_slabs:
+                near = torch.nonzero((lab_nodes[:, 0] >= z0 - self.rz) & (lab_nodes[:, 0] < z1 + self.rz)).reshape(-1)
+                if near.numel() == 0:
+                    continue
+                yield (self.whole, Pl, self.to_local(lab_nodes[near], self.whole), labels[near].contiguous(),
+                       (z0, z1, 0, self.Y, 0, self.X))
+            return
+        # nodes sorted by z once: a tile looks at the nodes of its own z-range (+ radius) only
+        # instead of scanning the whole list (640 tiles x 3.6 M nodes at 1024^3); the painting
+        # keeps the largest label per voxel, so the order of the nodes does not matter
+        if len(self.my_tiles) > 1 and lab_nodes.shape[0] > 0:
+            z_order = torch.argsort(lab_nodes[:, 0].contiguous(), stable=True)
+            lab_nodes, labels = lab_nodes[z_order].contiguous(), labels[z_order].contiguous()
+            node_z = lab_nodes[:, 0].contiguous()
+            del z_order
+        else:
+            node_z = None
+        for t in self.my_tiles:
+            z0, z1, y0, y1, x0, x1 = t
+            if node_z is not None:
+                za = int(torch.searchsorted(node_z, torch.tensor([z0 - self.rz], dtype=node_z.dtype, device=self.dev)).item())
+                zb = int(torch.searchsorted(node_z, torch.tensor([z1 + self.rz], dtype=node_z.dtype, device=self.dev)).item())
+                part = lab_nodes[za:zb]
+                near = (part[:, 1] >= y0 - int(self.rad[1])) & (part[:, 1] < y1 + int(self.rad[1]))
+                near &= (part[:, 2] >= x0 - int(self.rad[2])) & (part[:, 2] < x1 + int(self.rad[2]))
+                near = torch.nonzero(near).reshape(-1) + za
+                del part
+            else:
+                near = (lab_nodes[:, 0] >= z0 - self.rz) & (lab_nodes[:, 0] < z1 + self.rz)
+                near &= (lab_nodes[:, 1] >= y0 - int(self.rad[1])) & (lab_nodes[:, 1] < y1 + int(self.rad[1]))
+                near &= (lab_nodes[:, 2] >= x0 - int(self.rad[2])) & (lab_nodes[:, 2] < x1 + int(self.rad[2]))
+                near = torch.nonzero(near).reshape(-1)
+            if near.numel() == 0:
+                continue
+            nxt = self.next_of(t)
+            fr = self.frame_for(self.grow(t, self.rad), self.grow(nxt, self.rad) if nxt is not None else None)
+            yield fr, self.params(fr), self.to_local(lab_nodes[near], fr), labels[near].contiguous(), t
+
+    def paint_packed(self, lab_nodes, labels, n_labels, gz0, gz1):
+        """no_overlap_per_channel (graph_to_labeling.py:57-115): the (channels, Z, Y, X) map.  Every own
+        box counts its voxels per label and lists the label pairs that share one of them; the sizes are
+        summed and the pairs united over boxes and ranks; the channel walk is deterministic, so every
+        rank holds the same assignment; every own box is then painted by channel."""
+        import torch
+        sizes = torch.zeros((n_labels + 1,), dtype=torch.int64, device=self.dev)
+        parts = []
+        with backend.host_timer("s6_pack_scan"):
+            for fr, Pl, nodes_l, labels_l, (z0, z1, y0, y1, x0, x1) in self.own_frames(lab_nodes, labels):
+                o = fr.origin
+                own = (z0 - o[0], y0 - o[1], x0 - o[2], z1 - o[0], y1 - o[1], x1 - o[2])
+                _, keys = self.ops.pack_scan(fr.pred, nodes_l, labels_l, n_labels, Pl, own, sizes)
+                parts.append(torch.unique(keys))
+                del fr, keys
+            pairs = torch.unique(torch.cat(parts)) if parts else torch.zeros((0,), dtype=torch.int64, device=self.dev)
+            if self.comm.world > 1:
+                self.comm.all_reduce_sum(sizes)
+                longest = torch.tensor([int(pairs.numel())], dtype=torch.int64, device=self.dev)
+                longest = int(self.comm.all_reduce_max(longest).item())
+                padded = torch.full((longest,), -1, dtype=torch.int64, device=self.dev)      # (keys are >= 0)
+                padded[:pairs.numel()] = pairs
+                every = self.comm.all_gather(padded).reshape(-1)
+                pairs = torch.unique(every[every >= 0])
+            chan, n_ch = backend.pack_channels(sizes, pairs)
+        backend.note("pack_channels", n_ch)
+        inst_g = torch.zeros((n_ch, gz1 - gz0, self.Y, self.X), dtype=torch.int32, device=self.dev)
+        if n_ch:
+            for fr, Pl, nodes_l, labels_l, (z0, z1, y0, y1, x0, x1) in self.own_frames(lab_nodes, labels):
+                o = fr.origin
+                inst_l = torch.zeros((n_ch,) + tuple(fr.shape), dtype=torch.int32, device=self.dev)
+                self.ops.paint_channels(fr.pred, nodes_l, labels_l, chan, n_ch, inst_l, Pl)
+                inst_g[:, z0 - gz0:z1 - gz0, y0:y1, x0:x1] = \
+                    inst_l[:, z0 - o[0]:z1 - o[0], y0 - o[1]:y1 - o[1], x0 - o[2]:x1 - o[2]]
+                del inst_l, fr
+        if not self.gather_result:
+            return inst_g.cpu().numpy().view(np.uint32).astype(self.id_dtype, copy=False), self.fg_out(self.oz0, self.oz1)
+        if self.comm.world > 1 and n_ch:
+            # z-major on the wire: a rank's share is one contiguous range of slices of every channel
+            zm = inst_g.permute(1, 0, 2, 3).contiguous()
+            del inst_g
+            if self.rank_ranges is not None:
+                self.comm.all_gather_slabs(zm, self.rank_ranges)
+            else:
+                self.comm.all_reduce_sum(zm)
+            inst_g = zm.permute(1, 0, 2, 3).contiguous()
+        return inst_g.cpu().numpy().view(np.uint32).astype(self.id_dtype, copy=False), self.full_fg()
 
 
 def slabs_needed(shape, patchshape, free_bytes, safety=0.6, copies=3.0):

@@ -1,6 +1,7 @@
 """Step 6: patch graph -> instance labels
 (reference: PatchPerPix/vote_instances/graph_to_labeling.py)."""
 import logging
+import os
 
 import numpy as np
 
@@ -50,6 +51,51 @@ def component_labels(affinity_graph, shape, device, P, **kwargs):
     return nodes[valid], labels.astype(np.int64)
 
 
+def paint_channels(pred_affs, nodes_dev, labels_dev, n_comp, shape, P, per_channel=False, packed=True):
+    """graph_to_labeling.py:57-115: the (channels, Z, Y, X) map, int32 on the device, of the components
+    1 .. n_comp (nodes_dev int32 [K, 3], labels_dev int32 [K]).  one_instance_per_channel: a volume per
+    component.  no_overlap_per_channel: a component of more than 2000 voxels goes into the first channel
+    it does not overlap (a new one if none), every smaller one into channel 0 (whatever is there)."""
+    import torch
+    dev = pred_affs.device
+    shape = tuple(int(v) for v in shape)
+    if n_comp == 0:
+        return torch.zeros((0,) + shape, dtype=torch.int32, device=dev)
+    if packed and not per_channel and os.environ.get("PPP_PACK_CHANNELS", "pass") != "loop":
+        # without the loop over components: sizes and overlapping label pairs in one device pass, the
+        # greedy channel walk on the host, one paint by channel (closed form: csrc/ppp_pack_channels.hip).
+        # PPP_PACK_CHANNELS=loop keeps the loop below reachable: it is what this path is held equal to.
+        sizes, pairs = backend.pack_scan(pred_affs, nodes_dev, labels_dev, n_comp, P)
+        chan, n_ch = backend.pack_channels(sizes, pairs)
+        out = torch.zeros((n_ch,) + shape, dtype=torch.int32, device=dev)
+        backend.paint_instances_channels(pred_affs, nodes_dev, labels_dev, chan, n_ch, out, P)
+        return out
+    # every component is painted into a volume of its own
+    channels = []
+    for value in range(1, n_comp + 1):
+        own = torch.nonzero(labels_dev == value).reshape(-1)
+        cur = torch.zeros(shape, dtype=torch.int32, device=dev)
+        if own.numel():
+            backend.paint_instances(pred_affs, nodes_dev[own].contiguous(), labels_dev[own].contiguous(), cur, P)
+        if per_channel:
+            channels.append(cur)
+        if packed:
+            if not channels:
+                channels.append(cur)
+                continue
+            m = cur > 0
+            if int(m.sum().item()) > backend.PACK_MIN_VOXELS:
+                for ch in channels:
+                    if not bool((ch[m] != 0).any().item()):
+                        ch[m] = value
+                        break
+                else:
+                    channels.append(cur)
+            else:
+                channels[0][m] = value
+    return torch.stack(channels, 0)
+
+
 def affGraphToInstances(affinity_graph, pred_affs, patchshape, rad, debug_output1,
                         debug_output2, instances, foreground, **kwargs):
     """graph_to_labeling.py:34-155.  ``instances`` gives shape and dtype of the output
@@ -75,41 +121,13 @@ def affGraphToInstances(affinity_graph, pred_affs, patchshape, rad, debug_output
     per_channel = kwargs.get("one_instance_per_channel", False)
     packed = kwargs.get("no_overlap_per_channel", False)
     if per_channel or packed:
-        # graph_to_labeling.py:57-115: every component is painted into a volume of its own;
-        # one_instance_per_channel stacks them, no_overlap_per_channel puts a component of more
-        # than 2000 voxels into the first channel it does not overlap (a new one if none) and
-        # every smaller one into channel 0 (whatever is there)
         nodes_dev = torch.from_numpy(np.ascontiguousarray(nodes)).to(dev)
         labels_dev = torch.from_numpy(labels.astype(np.int32)).to(dev)
-        channels = []
         n_comp = int(labels.max()) if len(labels) else 0
-        for value in range(1, n_comp + 1):
-            own = torch.nonzero(labels_dev == value).reshape(-1)
-            cur = torch.zeros(instances.shape, dtype=torch.int32, device=dev)
-            if own.numel():
-                backend.paint_instances(pred_affs, nodes_dev[own].contiguous(), labels_dev[own].contiguous(), cur, P)
-            if per_channel:
-                channels.append(cur)
-            if packed:
-                if not channels:
-                    channels.append(cur)
-                    continue
-                m = cur > 0
-                if int(m.sum().item()) > 2000:
-                    for ch in channels:
-                        if not bool((ch[m] != 0).any().item()):
-                            ch[m] = value
-                            break
-                    else:
-                        channels.append(cur)
-                else:
-                    channels[0][m] = value
-        if channels:
-            instances = torch.stack(channels, 0).cpu().numpy().astype(out_dtype)
-        else:
-            # (np.stack of an empty list raises in the reference; a volume without components
-            # leaves the early-outs of to_instance_seg before it gets here)
-            instances = np.zeros((0,) + tuple(instances.shape), dtype=out_dtype)
+        # (no component: np.stack of an empty list raises in the reference; a volume without
+        # components leaves the early-outs of to_instance_seg before it gets here)
+        instances = paint_channels(pred_affs, nodes_dev, labels_dev, n_comp, instances.shape, P,
+                                   per_channel=per_channel, packed=packed).cpu().numpy().astype(out_dtype)
     else:
         inst_dev = torch.from_numpy(np.ascontiguousarray(instances).astype(np.int32)).to(dev)
         if len(nodes):
