@@ -461,6 +461,40 @@ int ppp_cover_pass_voxel_bits(uint8_t *d_mask, const uint32_t *d_bits_by_voxel, 
                               int32_t *d_cleared, void *d_work, const ppp_params *p, void *stream,
                               int32_t *rounds);
 
+/* --- the cover's two optional branches on the device ---------------------------------------
+ * ppp_cover_pass_marked: ppp_cover_pass with `mark_close_neighboorhood` (foreground_cover.py:141-143,
+ * 162-168).  d_mark_bits u32 [Z*Y][(X+31)/32 + 1] (ppp_cover_mark_bits_bytes(p) bytes; bit x%32 of word
+ * x/32 of row z*Y+y), in/out, shared by the passes of one cover and its ring cover: a patch whose centre is
+ * marked is skipped (before the count), a selected patch marks marked[cz, cy-3:cy+4, cx-3:cx+4] with
+ * NumPy's slice rules -- the high end clips, a negative start (cy < 3 or cx < 3) marks nothing.  Exact:
+ * the rounds' ready test uses the y/x radius max(p-1, 3).  As in ppp_cover_pass the stop rule is the
+ * caller's; marks may only come from patches that survive its cut, so the caller rebuilds the volume from
+ * the surviving set (ppp_cover_marks_from_selected) after the pass.  y or x axes shorter than 7 (the
+ * slice would wrap to the far end): PPP_ERR_UNSUPPORTED.                                      */
+int ppp_cover_pass_marked(uint8_t *d_mask, const uint32_t *d_bits, const int64_t *d_lin, int64_t n,
+                          int32_t pix_th, int32_t *d_state, int32_t *d_cleared, uint32_t *d_mark_bits,
+                          void *d_work, const ppp_params *p, void *stream, int32_t *rounds);
+/* ... with the patch bits in a row per voxel, see ppp_cover_pass_voxel_bits (foreground_cover.py:141-143,
+ * 162-168)                                                                                   */
+int ppp_cover_pass_marked_voxel_bits(uint8_t *d_mask, const uint32_t *d_bits_by_voxel, int64_t first_voxel,
+                                     const int64_t *d_lin, int64_t n, int32_t pix_th, int32_t *d_state,
+                                     int32_t *d_cleared, uint32_t *d_mark_bits, void *d_work,
+                                     const ppp_params *p, void *stream, int32_t *rounds);
+int64_t ppp_cover_mark_bits_bytes(const ppp_params *p);
+/* ppp_cover_marks_from_selected: the mark volume of a set of selected centres, rebuilt from nothing
+ * (foreground_cover.py:162-168 applied to each): d_lin i64 [n] linear centres, d_selected u8 [n] (NULL:
+ * all n) picks among them.                                                                    */
+int ppp_cover_marks_from_selected(const int64_t *d_lin, const uint8_t *d_selected, int64_t n,
+                                  uint32_t *d_mark_bits, const ppp_params *p, void *stream);
+/* ppp_mask_dilate: scipy.ndimage.binary_dilation(d_in != 0, iterations=k) with the default 6-neighbour
+ * cross (foreground_cover.py:57-60, `select_patches_overlap_neighborhood`: the ring between 2 and 5
+ * dilations of the overlap voxels); use_z = 0 leaves the z neighbours out (a stack of independent
+ * slices).  d_in, d_out u8 [Z][Y][X] (d_out 0 / 1; may be d_in), d_work
+ * ppp_mask_dilate_workspace_bytes(p) bytes.                                                   */
+int64_t ppp_mask_dilate_workspace_bytes(const ppp_params *p);
+int ppp_mask_dilate(const uint8_t *d_in, uint8_t *d_out, int32_t iterations, int32_t use_z, void *d_work,
+                    const ppp_params *p, void *stream);
+
 /* The x and y passes of the rounds' neighbourhood minimum on their own (what ppp_cover_pass and
  * ppp_thin_cover run once per round between their count and select steps): d_out[z][y][x] = the minimum
  * of d_in over [y - (py-1), y + (py-1)] x [x - (px-1), x + (px-1)] of slice z, clipped to the slice.

@@ -197,6 +197,23 @@ _SIGNATURES = {
                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.POINTER(Params), ctypes.c_void_p,
                                                  ctypes.POINTER(ctypes.c_int32)]),
+    "ppp_cover_pass_marked": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.POINTER(Params), ctypes.c_void_p,
+                                             ctypes.POINTER(ctypes.c_int32)]),
+    "ppp_cover_pass_marked_voxel_bits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                        ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                        ctypes.c_void_p, ctypes.POINTER(Params),
+                                                        ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]),
+    "ppp_cover_mark_bits_bytes": (ctypes.c_int64, [ctypes.POINTER(Params)]),
+    "ppp_cover_marks_from_selected": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                     ctypes.c_void_p, ctypes.POINTER(Params),
+                                                     ctypes.c_void_p]),
+    "ppp_mask_dilate_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(Params)]),
+    "ppp_mask_dilate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                       ctypes.c_void_p, ctypes.POINTER(Params), ctypes.c_void_p]),
     "ppp_host_mws_sorted": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                              ctypes.c_int64, ctypes.c_void_p]),
     "ppp_rank_order_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(Params)]),
@@ -1505,12 +1522,14 @@ def patch_bits(pred, centres, thresh, P, scratch=None):
     return bits
 
 
-def cover_pass_device(mask, bits, lin, state, pix_th, P, bits_first_voxel=None):
+def cover_pass_device(mask, bits, lin, state, pix_th, P, bits_first_voxel=None, mark_bits=None):
     """One pass of the greedy cover on the device (foreground_cover.py:111-180 without the stop
     rule, see ppp_cover_pass).  mask uint8 (Z,Y,X) is cleared in place; state int32 [n]
     (0 = takes part; ends 1 selected / 2 not) is updated in place.  bits: int32 [n, words] in
     list order, or -- bits_first_voxel given -- a table with a row per voxel whose first row
-    belongs to that linear voxel index (ppp_cover_pass_voxel_bits).
+    belongs to that linear voxel index (ppp_cover_pass_voxel_bits).  mark_bits (cover_mark_bits):
+    the pass with `mark_close_neighboorhood`, marks read and written in place
+    (ppp_cover_pass_marked[_voxel_bits]).
     Returns (cleared int32 [n], rounds)."""
     torch = _torch()
     n = int(state.numel())
@@ -1518,7 +1537,16 @@ def cover_pass_device(mask, bits, lin, state, pix_th, P, bits_first_voxel=None):
     work = _workspace(lib().ppp_cover_workspace_bytes(n, ctypes.byref(P)), mask.device)
     rounds = ctypes.c_int32(0)
     with _timed("cover"):
-        if bits_first_voxel is None:
+        if mark_bits is not None and bits_first_voxel is None:
+            check(lib().ppp_cover_pass_marked(_dev_ptr(mask), _dev_ptr(bits), _dev_ptr(lin), n, int(pix_th),
+                                              _dev_ptr(state), _dev_ptr(cleared), _dev_ptr(mark_bits),
+                                              _dev_ptr(work), ctypes.byref(P), _stream(), ctypes.byref(rounds)))
+        elif mark_bits is not None:
+            check(lib().ppp_cover_pass_marked_voxel_bits(_dev_ptr(mask), _dev_ptr(bits), int(bits_first_voxel),
+                                                         _dev_ptr(lin), n, int(pix_th), _dev_ptr(state),
+                                                         _dev_ptr(cleared), _dev_ptr(mark_bits), _dev_ptr(work),
+                                                         ctypes.byref(P), _stream(), ctypes.byref(rounds)))
+        elif bits_first_voxel is None:
             check(lib().ppp_cover_pass(_dev_ptr(mask), _dev_ptr(bits), _dev_ptr(lin), n, int(pix_th),
                                        _dev_ptr(state), _dev_ptr(cleared), _dev_ptr(work),
                                        ctypes.byref(P), _stream(), ctypes.byref(rounds)))
@@ -1528,6 +1556,43 @@ def cover_pass_device(mask, bits, lin, state, pix_th, P, bits_first_voxel=None):
                                                   _dev_ptr(cleared), _dev_ptr(work), ctypes.byref(P),
                                                   _stream(), ctypes.byref(rounds)))
     return cleared, int(rounds.value)
+
+
+def cover_mark_bits(P, device):
+    """An empty mark volume of `mark_close_neighboorhood` (int32 words, ppp_cover_mark_bits_bytes)."""
+    torch = _torch()
+    nbytes = int(lib().ppp_cover_mark_bits_bytes(ctypes.byref(P)))
+    if nbytes < 0:
+        raise RuntimeError("ppp_cover_mark_bits_bytes: invalid parameters")
+    return torch.zeros(nbytes // 4, dtype=torch.int32, device=device)
+
+
+def cover_marks_from_selected(lin, selected, mark_bits, P):
+    """Rebuild mark_bits from the centres lin int64 [n] with selected bool / uint8 [n] set (None: all);
+    foreground_cover.py:162-168 for each of them (ppp_cover_marks_from_selected)."""
+    torch = _torch()
+    lin = lin.contiguous()
+    sel = None if selected is None else selected.to(torch.uint8).contiguous()
+    with _timed("cover"):
+        check(lib().ppp_cover_marks_from_selected(_dev_ptr(lin), None if sel is None else _dev_ptr(sel),
+                                                  int(lin.numel()), _dev_ptr(mark_bits), ctypes.byref(P),
+                                                  _stream()))
+    return mark_bits
+
+
+def mask_dilate(mask, iterations, P, use_z=True):
+    """scipy.ndimage.binary_dilation(mask != 0, iterations=iterations) on the device, uint8 0 / 1 out;
+    use_z=False: every slice on its own (ppp_mask_dilate; foreground_cover.py:57-60)."""
+    torch = _torch()
+    mask = mask.contiguous()
+    if mask.dtype != torch.uint8:
+        mask = (mask != 0).to(torch.uint8)
+    out = torch.empty_like(mask)
+    work = _workspace(lib().ppp_mask_dilate_workspace_bytes(ctypes.byref(P)), mask.device)
+    with _timed("cover"):
+        check(lib().ppp_mask_dilate(_dev_ptr(mask), _dev_ptr(out), int(iterations), 1 if use_z else 0,
+                                    _dev_ptr(work), ctypes.byref(P), _stream()))
+    return out
 
 
 def thin_cover_device(mask, bits, lin, P, slice_interior=None):

@@ -982,10 +982,14 @@ int64_t ppp_cover_workspace_bytes(int64_t n, const ppp_params *p) {
 
 static int cover_pass_impl(uint8_t *d_mask, const uint32_t *d_bits, int64_t first_voxel, const int64_t *d_lin,
                            int64_t n, int32_t pix_th, int32_t *d_state, int32_t *d_cleared, void *d_work,
-                           const ppp_params *p, void *stream, int32_t *rounds, const char *who) {
+                           const ppp_params *p, void *stream, int32_t *rounds, const char *who,
+                           uint32_t *d_mark_bits = nullptr, bool marked = false) {
     ppp::Geo G;
     PPP_TRY(make_geo(p, &G));
     if (rounds) *rounds = 0;
+    if (marked && !d_mark_bits) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    if (marked && (G.Y < 7 || G.X < 7))
+        return fail(PPP_ERR_UNSUPPORTED, "%s needs y and x axes of at least 7 voxels (the mark box wraps on shorter ones)", who);
     if (n <= 0) return PPP_OK;
     if (n > 0x7F000000LL) return fail(PPP_ERR_INVALID_ARG, "too many ranked patches for one cover pass");
     if (G.px > 32) return fail(PPP_ERR_UNSUPPORTED, "%s needs patch rows of at most 32 voxels", who);
@@ -994,7 +998,7 @@ static int cover_pass_impl(uint8_t *d_mask, const uint32_t *d_bits, int64_t firs
     PPP_TRY(need_device());
     int r = 0;
     hipError_t e = ppp::run_cover_pass(d_mask, d_bits, first_voxel, (const long long *)d_lin, n, pix_th, d_state,
-                                       d_cleared, d_work, G, (hipStream_t)stream, &r);
+                                       d_cleared, d_work, G, (hipStream_t)stream, &r, d_mark_bits);
     if (rounds) *rounds = r;
     return e == hipSuccess ? PPP_OK : hip_fail(e, who);
 }
@@ -1013,6 +1017,58 @@ int ppp_cover_pass_voxel_bits(uint8_t *d_mask, const uint32_t *d_bits_by_voxel, 
     if (first_voxel < 0) return fail(PPP_ERR_INVALID_ARG, "first_voxel must be >= 0");
     return cover_pass_impl(d_mask, d_bits_by_voxel, first_voxel, d_lin, n, pix_th, d_state, d_cleared, d_work, p,
                            stream, rounds, "ppp_cover_pass_voxel_bits");
+}
+
+int ppp_cover_pass_marked(uint8_t *d_mask, const uint32_t *d_bits, const int64_t *d_lin, int64_t n,
+                          int32_t pix_th, int32_t *d_state, int32_t *d_cleared, uint32_t *d_mark_bits,
+                          void *d_work, const ppp_params *p, void *stream, int32_t *rounds) {
+    return cover_pass_impl(d_mask, d_bits, -1, d_lin, n, pix_th, d_state, d_cleared, d_work, p, stream, rounds,
+                           "ppp_cover_pass_marked", d_mark_bits, true);
+}
+
+int ppp_cover_pass_marked_voxel_bits(uint8_t *d_mask, const uint32_t *d_bits_by_voxel, int64_t first_voxel,
+                                     const int64_t *d_lin, int64_t n, int32_t pix_th, int32_t *d_state,
+                                     int32_t *d_cleared, uint32_t *d_mark_bits, void *d_work,
+                                     const ppp_params *p, void *stream, int32_t *rounds) {
+    if (first_voxel < 0) return fail(PPP_ERR_INVALID_ARG, "first_voxel must be >= 0");
+    return cover_pass_impl(d_mask, d_bits_by_voxel, first_voxel, d_lin, n, pix_th, d_state, d_cleared, d_work, p,
+                           stream, rounds, "ppp_cover_pass_marked_voxel_bits", d_mark_bits, true);
+}
+
+int64_t ppp_cover_mark_bits_bytes(const ppp_params *p) {
+    ppp::Geo G;
+    if (make_geo(p, &G) != PPP_OK) return -1;
+    return (int64_t)ppp::cover_mark_bits_bytes(G);
+}
+
+int ppp_cover_marks_from_selected(const int64_t *d_lin, const uint8_t *d_selected, int64_t n,
+                                  uint32_t *d_mark_bits, const ppp_params *p, void *stream) {
+    ppp::Geo G;
+    PPP_TRY(make_geo(p, &G));
+    if (G.Y < 7 || G.X < 7)
+        return fail(PPP_ERR_UNSUPPORTED, "ppp_cover_marks_from_selected needs y and x axes of at least 7 voxels");
+    if (!d_mark_bits || (n > 0 && !d_lin)) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    PPP_TRY(need_device());
+    hipError_t e = ppp::run_cover_marks_from_selected((const long long *)d_lin, d_selected, n < 0 ? 0 : n,
+                                                      d_mark_bits, G, (hipStream_t)stream);
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_cover_marks_from_selected");
+}
+
+int64_t ppp_mask_dilate_workspace_bytes(const ppp_params *p) {
+    ppp::Geo G;
+    if (make_geo(p, &G) != PPP_OK) return -1;
+    return (int64_t)ppp::mask_dilate_workspace_bytes(G);
+}
+
+int ppp_mask_dilate(const uint8_t *d_in, uint8_t *d_out, int32_t iterations, int32_t use_z, void *d_work,
+                    const ppp_params *p, void *stream) {
+    ppp::Geo G;
+    PPP_TRY(make_geo(p, &G));
+    if (iterations < 0) return fail(PPP_ERR_INVALID_ARG, "ppp_mask_dilate: iterations must be >= 0");
+    if (!d_in || !d_out || !d_work) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    PPP_TRY(need_device());
+    hipError_t e = ppp::run_mask_dilate(d_in, d_out, iterations, use_z ? 1 : 0, d_work, G, (hipStream_t)stream);
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_mask_dilate");
 }
 
 int ppp_minfilter_xy(const void *d_in, void *d_out, void *d_scratch, int32_t elem_bytes, const ppp_params *p,

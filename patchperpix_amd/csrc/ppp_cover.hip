@@ -478,9 +478,11 @@ static bool minfilter_xy_cubic(const T *in, T *out, const Geo &G, hipStream_t s)
 // slices themselves (one volume write + read and one launch less per round).
 // Cubic 3^3 .. 9^3 patches take the kernel with compile-time radii, every other shape (anisotropic, the
 // 25-wide 2-d patches, anything whose tile does not fit LDS) the run-time one.
+// (rx, ry: the radii -- p - 1 for the cover and the thinning, max(p - 1, 3) for a cover with marks; the
+// cubic kernel serves radius p - 1 only)
 template <typename T>
-static void minfilter_xy(const T *in, T *scratch, T *out, const Geo &G, hipStream_t s) {
-    if (G.px == G.py && G.py == G.pz) {
+static void minfilter_xy(const T *in, T *scratch, T *out, const Geo &G, const int rx, const int ry, hipStream_t s) {
+    if (G.px == G.py && G.py == G.pz && rx == G.px - 1 && ry == G.py - 1) {
         bool done = false;
         switch (G.px) {
         case 3: done = minfilter_xy_cubic<T, 2>(in, out, G, s); break;
@@ -491,7 +493,6 @@ static void minfilter_xy(const T *in, T *scratch, T *out, const Geo &G, hipStrea
         }
         if (done) return;
     }
-    const int rx = G.px - 1, ry = G.py - 1;
     constexpr int TYB = MfRows<T>::value, TYS = 8;      // rows per block: the tall tile where it fits LDS
     auto lds_of = [&](int ty) { return (size_t)((ty + 2 * ry) * (MF_TX + 2 * rx) + (ty + 2 * ry) * MF_TX) * sizeof(T); };
     auto grid_of = [&](int ty) { return dim3((unsigned)((G.X + MF_TX - 1) / MF_TX), (unsigned)((G.Y + ty - 1) / ty), (unsigned)G.Z); };
@@ -504,6 +505,10 @@ static void minfilter_xy(const T *in, T *scratch, T *out, const Geo &G, hipStrea
         cover_minfilter_kernel<T><<<vgrid, block, 0, s>>>(in, scratch, G.V, G.X, 1, rx);
         cover_minfilter_kernel<T><<<vgrid, block, 0, s>>>(scratch, out, G.V, G.Y, G.X, ry);
     }
+}
+template <typename T>
+static void minfilter_xy(const T *in, T *scratch, T *out, const Geo &G, hipStream_t s) {
+    minfilter_xy<T>(in, scratch, out, G, G.px - 1, G.py - 1, s);
 }
 // the filter alone, on buffers of the caller (ppp_minfilter_xy: what the tests pin the tiling with)
 hipError_t run_minfilter_xy(const void *in, void *scratch, void *out, int elem_bytes, const Geo &G, hipStream_t s) {
@@ -577,15 +582,86 @@ __device__ __forceinline__ unsigned ready_voxels(const T *own, const T *__restri
     return cand;
 }
 
+// ---- `mark_close_neighboorhood` (foreground_cover.py:141-143, 162-168) ------------------------------
+// The mark volume has the layout of the running mask bits ([Z*Y][row_words]).  A ranked patch whose centre
+// is marked is skipped; a selected patch sets marked[cz, cy-3:cy+4, cx-3:cx+4] with NumPy's slice rules:
+// the high end clips, a NEGATIVE start (cy < 3 or cx < 3) on an axis of at least 7 voxels gives an empty
+// slice -- that patch marks nothing at all.  (On a shorter axis the slice wraps to the far end: such
+// volumes keep the host loop, the entry points refuse them.)
+// The fate of patch i then also depends on the selected patches of higher rank whose centre lies within
+// (0, +-3, +-3) of i, so the ready test's y/x radius becomes max(p - 1, 3) (the z radius stays p_z - 1:
+// marks never leave the centre's slice) -- a lower ranked patch within that radius of an undecided one is
+// never ready, so no mark reaches a centre before its turn that the sequential loop would not have set.
+// The 7 x 7 box is wider than the dirty box of a 3^3 selection and witnesses suppress recounts at
+// pix_th == 0, so the mark test is a sweep of its own over every undecided patch, before every count.
+static constexpr int MARK_R = 3;
+__host__ __device__ __forceinline__ int mark_radius(int p) { return p - 1 > MARK_R ? p - 1 : MARK_R; }
+
+// row `dy` (0..6) of the mark box of a patch selected at (cz, cy, cx).  Ready patches of one round can touch
+// the same word: atomic OR.
+__device__ __forceinline__ void mark_box_row(uint32_t *__restrict__ mark_bits, int cz, int cy, int cx, int dy,
+                                             const Geo &G) {
+    if (cy < MARK_R || cx < MARK_R) return;                   // negative slice start: empty slice
+    const int y = cy - MARK_R + dy;
+    if (y >= G.Y) return;                                     // the high end clips
+    const int x0 = cx - MARK_R, nb = min(cx + MARK_R + 1, G.X) - x0, sh = x0 & 31;
+    const uint32_t m = (1u << nb) - 1u;                       // nb in 1..7
+    uint32_t *row = mark_bits + ((long long)cz * G.Y + y) * row_words(G) + (x0 >> 5);
+    atomicOr(row, m << sh);
+    if (sh && (m >> (32 - sh))) atomicOr(row + 1, m >> (32 - sh));   // (the row's spare word keeps this in bounds)
+}
+
+// the mark test: every undecided patch whose centre is marked is decided "not selected"
+static constexpr int MARKTEST_VPT = 4;
+__global__ void __launch_bounds__(256)
+    cover_marktest_kernel(const uint32_t *__restrict__ mark_bits, int32_t *__restrict__ state,
+                          int32_t *__restrict__ rank_vol, const Geo G) {
+    const long long v0 = blockIdx.x * (long long)(256 * MARKTEST_VPT) + threadIdx.x;
+    int kk[MARKTEST_VPT];
+#pragma unroll
+    for (int j = 0; j < MARKTEST_VPT; ++j) {
+        const long long v = v0 + j * 256;
+        kk[j] = v < G.V ? rank_vol[v] : RANK_NONE;
+    }
+#pragma unroll
+    for (int j = 0; j < MARKTEST_VPT; ++j) {
+        if (kk[j] == RANK_NONE) continue;
+        const long long v = v0 + j * 256;
+        const int x = (int)(v % G.X);
+        if ((mark_bits[(v / G.X) * row_words(G) + (x >> 5)] >> (x & 31)) & 1u) {
+            state[kk[j]] = 2;
+            rank_vol[v] = RANK_NONE;
+        }
+    }
+}
+
+// the marks of a list of centres (sel == nullptr: all of them, else those with sel[k] != 0): thread per
+// (centre, box row)
+__global__ void __launch_bounds__(256)
+    cover_marks_from_list_kernel(const long long *__restrict__ lin, const uint8_t *__restrict__ sel, long long n,
+                                 uint32_t *__restrict__ mark_bits, const Geo G) {
+    const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (t >= n * 7) return;
+    const long long k = t / 7;
+    if (sel && !sel[k]) return;
+    int cz, cy, cx;
+    centre_of(G, lin[k], cz, cy, cx);
+    mark_box_row(mark_bits, cz, cy, cx, (int)(t % 7), G);
+}
+
 // SELECT_VPT voxels per thread: the best ranked undecided patch of its neighbourhood selects itself;
 // its wave clears the voxels (lane per window row) and marks the centres whose counts may have
 // changed.  Selected patches never share a voxel, but they may share a mask word.
-__global__ void __launch_bounds__(256)
-    cover_select_kernel(uint32_t *__restrict__ mbits, const uint32_t *__restrict__ bits,
-                        const int32_t *__restrict__ nbr_min, int32_t *__restrict__ state,
-                        int32_t *__restrict__ rank_vol, int32_t *__restrict__ cleared_interior,
-                        uint8_t *__restrict__ dirty, const int32_t *__restrict__ loc_vol,
-                        const int gZ, const long long bits_vox, const int mark_dirty, const Geo G) {
+// (MARKS: `mark_close_neighboorhood` -- a selected patch also sets the (0, +-3, +-3) box around its centre
+// in the mark bits, see mark_box_row)
+template <bool MARKS>
+__device__ __forceinline__ void
+    cover_select_body(uint32_t *__restrict__ mbits, const uint32_t *__restrict__ bits,
+                      const int32_t *__restrict__ nbr_min, int32_t *__restrict__ state,
+                      int32_t *__restrict__ rank_vol, int32_t *__restrict__ cleared_interior,
+                      uint8_t *__restrict__ dirty, const int32_t *__restrict__ loc_vol,
+                      const int gZ, const long long bits_vox, const int mark_dirty,
+                      uint32_t *__restrict__ mark_bits, const Geo &G) {
     const long long first = blockIdx.x * (long long)(256 * SELECT_VPT) + threadIdx.x;
     const int lane = threadIdx.x & 63;
     int32_t mine[SELECT_VPT];
@@ -637,6 +713,7 @@ __global__ void __launch_bounds__(256)
                 uint8_t *d = dirty + vox(G, z0 + row / ny, y0 + row % ny, x0);
                 for (int x = 0; x < nx; ++x) d[x] = 1;
             }
+            if (MARKS && lane < 7) mark_box_row(mark_bits, cz, cy, cx, lane, G);
             if (lane == src) {
                 state[kk] = 1;
                 rank_vol[cc] = RANK_NONE;
@@ -644,6 +721,24 @@ __global__ void __launch_bounds__(256)
             }
         }
     }
+}
+__global__ void __launch_bounds__(256)
+    cover_select_kernel(uint32_t *__restrict__ mbits, const uint32_t *__restrict__ bits,
+                        const int32_t *__restrict__ nbr_min, int32_t *__restrict__ state,
+                        int32_t *__restrict__ rank_vol, int32_t *__restrict__ cleared_interior,
+                        uint8_t *__restrict__ dirty, const int32_t *__restrict__ loc_vol,
+                        const int gZ, const long long bits_vox, const int mark_dirty, const Geo G) {
+    cover_select_body<false>(mbits, bits, nbr_min, state, rank_vol, cleared_interior, dirty, loc_vol, gZ, bits_vox,
+                             mark_dirty, nullptr, G);
+}
+__global__ void __launch_bounds__(256)
+    cover_select_marked_kernel(uint32_t *__restrict__ mbits, const uint32_t *__restrict__ bits,
+                               const int32_t *__restrict__ nbr_min, int32_t *__restrict__ state,
+                               int32_t *__restrict__ rank_vol, int32_t *__restrict__ cleared_interior,
+                               uint8_t *__restrict__ dirty, const long long bits_vox, const int mark_dirty,
+                               uint32_t *__restrict__ mark_bits, const Geo G) {
+    cover_select_body<true>(mbits, bits, nbr_min, state, rank_vol, cleared_interior, dirty, nullptr, G.Z + G.oz,
+                            bits_vox, mark_dirty, mark_bits, G);
 }
 
 // (the same layout serves run_cover_pass and the sharded steps; n does not enter it)
@@ -665,10 +760,11 @@ static CoverWork carve(void *work, const Geo &G) { Carver c(work); return cover_
 // One pass of the cover loop without the stop rule.  Returns the number of rounds in *rounds.
 hipError_t run_cover_pass(uint8_t *mask, const uint32_t *bits, long long bits_vox, const long long *lin,
                           long long n, int pix_th, int32_t *state, int32_t *cleared, void *work,
-                          const Geo &G, hipStream_t s, int *rounds) {
+                          const Geo &G, hipStream_t s, int *rounds, uint32_t *mark_bits) {
     *rounds = 0;
     if (n <= 0) return hipSuccess;
     PPP_GRID_CHECK((G.V + 255) / 256, 256);
+    if (mark_bits && (G.Y < 2 * MARK_R + 1 || G.X < 2 * MARK_R + 1)) return hipErrorNotSupported;
     CoverWork W = carve(work, G);
     hipError_t e;
     if ((e = hipMemsetD32Async((hipDeviceptr_t)W.rank_vol, RANK_NONE, (size_t)G.V, s)) != hipSuccess) return e;
@@ -683,13 +779,24 @@ hipError_t run_cover_pass(uint8_t *mask, const uint32_t *bits, long long bits_vo
     while (n_alive > 0) {
         if ((e = hipMemsetAsync(W.counters, 0, COVER_BATCH * 4, s)) != hipSuccess) return e;
         const dim3 cgrid = count_grid(G), cblock(COUNT_THREADS);
+        const int mark_dirty = (pix_th != 0 || !witness_ok(G)) ? 1 : 0;
         for (int r = 0; r < COVER_BATCH; ++r) {
+            if (mark_bits)
+                cover_marktest_kernel<<<dim3((unsigned)((G.V + 256 * MARKTEST_VPT - 1) / (256 * MARKTEST_VPT))), block, 0, s>>>(
+                    mark_bits, state, W.rank_vol, G);
             cover_count_kernel<<<cgrid, cblock, 0, s>>>(W.mbits, bits, W.dirty, pix_th, state, W.rank_vol,
                                                        W.counters + r, nullptr, witness_ok(G) ? W.witness : nullptr, bits_vox, G);
             // x, y, z; radius p-1: two windows overlap iff |dc| <= p-1 on every axis
-            minfilter_xy<int32_t>(W.rank_vol, W.tmp, W.nbr_min, G, s);
-            cover_select_kernel<<<select_grid(G), block, 0, s>>>(W.mbits, bits, W.nbr_min, state, W.rank_vol, cleared,
-                                                        W.dirty, nullptr, G.Z + G.oz, bits_vox, (pix_th != 0 || !witness_ok(G)) ? 1 : 0, G);
+            if (!mark_bits) {
+                minfilter_xy<int32_t>(W.rank_vol, W.tmp, W.nbr_min, G, s);
+                cover_select_kernel<<<select_grid(G), block, 0, s>>>(W.mbits, bits, W.nbr_min, state, W.rank_vol, cleared,
+                                                            W.dirty, nullptr, G.Z + G.oz, bits_vox, mark_dirty, G);
+            } else {
+                // (with marks: y / x radius max(p - 1, 3), see mark_box_row)
+                minfilter_xy<int32_t>(W.rank_vol, W.tmp, W.nbr_min, G, mark_radius(G.px), mark_radius(G.py), s);
+                cover_select_marked_kernel<<<select_grid(G), block, 0, s>>>(W.mbits, bits, W.nbr_min, state, W.rank_vol,
+                                                                   cleared, W.dirty, bits_vox, mark_dirty, mark_bits, G);
+            }
         }
         *rounds += COVER_BATCH;
         // "any patch undecided" at the start of the batch's last round; if none, that round
@@ -708,6 +815,82 @@ hipError_t run_cover_pass(uint8_t *mask, const uint32_t *bits, long long bits_vo
         }
     }
     cover_unpack_kernel<<<vgrid, block, 0, s>>>(W.mbits, mask, G);
+    return hipGetLastError();
+}
+
+// bytes of a mark volume
+size_t cover_mark_bits_bytes(const Geo &G) { return (size_t)G.Z * G.Y * row_words(G) * sizeof(uint32_t); }
+
+// The mark volume of a set of selected centres, rebuilt from nothing: what the marks are after the stop
+// rule has cut a pass's selections (marks may only come from patches that survive the cut), and what a
+// second pass or the ring cover starts from.
+hipError_t run_cover_marks_from_selected(const long long *lin, const uint8_t *sel, long long n, uint32_t *mark_bits,
+                                         const Geo &G, hipStream_t s) {
+    if (G.Y < 2 * MARK_R + 1 || G.X < 2 * MARK_R + 1) return hipErrorNotSupported;
+    hipError_t e;
+    if ((e = hipMemsetAsync(mark_bits, 0, cover_mark_bits_bytes(G), s)) != hipSuccess) return e;
+    if (n <= 0) return hipSuccess;
+    PPP_GRID_CHECK((n * 7 + 255) / 256, 256);
+    cover_marks_from_list_kernel<<<dim3((unsigned)((n * 7 + 255) / 256)), dim3(256), 0, s>>>(lin, sel, n, mark_bits, G);
+    return hipGetLastError();
+}
+
+// ---- `select_patches_overlap_neighborhood` (foreground_cover.py:53-85): binary dilation ----------------
+// One round of 6-neighbour dilation on bit rows (scipy.ndimage.binary_dilation's default cross, border
+// value 0): a word ORs itself shifted by one bit either way (with the carry of the neighbouring words),
+// the same word of the rows y - 1 and y + 1 and -- use_z -- of the slices z - 1 and z + 1.  Bits past the
+// end of a row stay clear.
+__global__ void __launch_bounds__(256)
+    mask_dilate_bits_kernel(const uint32_t *__restrict__ in, uint32_t *__restrict__ out, const int use_z, const Geo G) {
+    const int XW = row_words(G);
+    const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (t >= (long long)G.Z * G.Y * XW) return;
+    const int w = (int)(t % XW);
+    const long long row = t / XW;
+    const int y = (int)(row % G.Y), z = (int)(row / G.Y);
+    const uint32_t c = in[t], l = w > 0 ? in[t - 1] : 0u, r = w + 1 < XW ? in[t + 1] : 0u;
+    uint32_t v = c | (c << 1) | (l >> 31) | (c >> 1) | (r << 31);
+    if (y > 0) v |= in[t - XW];
+    if (y + 1 < G.Y) v |= in[t + XW];
+    if (use_z) {
+        const long long plane = (long long)G.Y * XW;
+        if (z > 0) v |= in[t - plane];
+        if (z + 1 < G.Z) v |= in[t + plane];
+    }
+    const int left = G.X - w * 32;                            // voxels of the row from this word on
+    out[t] = left >= 32 ? v : left <= 0 ? 0u : (v & ((1u << left) - 1u));
+}
+__global__ void __launch_bounds__(256)
+    mask_bits_to_bytes_kernel(const uint32_t *__restrict__ mbits, uint8_t *__restrict__ mask, const Geo G) {
+    const long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (v >= G.V) return;
+    const int x = (int)(v % G.X);
+    mask[v] = (uint8_t)((mbits[(v / G.X) * row_words(G) + (x >> 5)] >> (x & 31)) & 1u);
+}
+
+struct DilateWork { uint32_t *a, *b; };
+static DilateWork dilate_layout(Carver &c, const Geo &G) {
+    DilateWork W;
+    W.a = c.take<uint32_t>((size_t)G.Z * G.Y * row_words(G));
+    W.b = c.take<uint32_t>((size_t)G.Z * G.Y * row_words(G));
+    return W;
+}
+size_t mask_dilate_workspace_bytes(const Geo &G) { Carver c(nullptr); dilate_layout(c, G); return c.used; }
+
+// out = `iterations` rounds of dilation of (in != 0), one byte per voxel (0 / 1); in == out is allowed
+hipError_t run_mask_dilate(const uint8_t *in, uint8_t *out, int iterations, int use_z, void *work, const Geo &G,
+                           hipStream_t s) {
+    const long long n_words = (long long)G.Z * G.Y * row_words(G);
+    PPP_GRID_CHECK((G.V + 255) / 256, 256);
+    Carver c(work);
+    DilateWork W = dilate_layout(c, G);
+    const dim3 wgrid((unsigned)((n_words + 255) / 256)), vgrid((unsigned)((G.V + 255) / 256)), block(256);
+    cover_pack_kernel<<<wgrid, block, 0, s>>>(in, W.a, G);
+    for (int i = 0; i < iterations; ++i) {
+        mask_dilate_bits_kernel<<<wgrid, block, 0, s>>>(W.a, W.b, use_z, G);
+        std::swap(W.a, W.b);
+    }
+    mask_bits_to_bytes_kernel<<<vgrid, block, 0, s>>>(W.a, out, G);
     return hipGetLastError();
 }
 

@@ -161,7 +161,15 @@ hipError_t launch_decode_tail(const float *X, long long B, int F, int S, const f
 size_t cover_workspace_bytes(long long n, const Geo &G);
 hipError_t run_cover_pass(uint8_t *mask, const uint32_t *bits, long long bits_vox, const long long *lin,
                           long long n, int pix_th, int32_t *state, int32_t *cleared, void *work,
-                          const Geo &G, hipStream_t s, int *rounds);
+                          const Geo &G, hipStream_t s, int *rounds, uint32_t *mark_bits = nullptr);
+// `mark_close_neighboorhood`: the mark volume (bits, [Z*Y][row words] like the running mask) and its rebuild
+// from a list of selected centres; `select_patches_overlap_neighborhood`: rounds of 6-neighbour dilation
+size_t cover_mark_bits_bytes(const Geo &G);
+hipError_t run_cover_marks_from_selected(const long long *lin, const uint8_t *sel, long long n, uint32_t *mark_bits,
+                                         const Geo &G, hipStream_t s);
+size_t mask_dilate_workspace_bytes(const Geo &G);
+hipError_t run_mask_dilate(const uint8_t *in, uint8_t *out, int iterations, int use_z, void *work, const Geo &G,
+                           hipStream_t s);
 
 // x and y passes of the rounds' neighbourhood minimum (radius p - 1) on caller-owned volumes of 4- or 8-byte elements
 hipError_t run_minfilter_xy(const void *in, void *scratch, void *out, int elem_bytes, const Geo &G, hipStream_t s);

@@ -662,6 +662,15 @@ class DeviceOps:
                                         bits_first_voxel=bits_first_voxel)
         return sel
 
+    def cover_options(self, mask_to_cover, overlap, bits, lin, scores, pix_ths, radslice, P, kw,
+                      bits_first_voxel=None):
+        """The greedy cover with `mark_close_neighboorhood` / `select_patches_overlap_neighborhood`
+        (foreground_cover.py:53-85, 141-168), marks, ring and second pass on the device.  Returns the
+        result as indices into the ranked list, in the result's order (device tensor)."""
+        from .vote_instances import foreground_cover as fc
+        return fc.cover_options_device(mask_to_cover, overlap, bits, lin, scores, pix_ths, radslice, P, kw,
+                                       bits_first_voxel=bits_first_voxel)
+
     def thin_cover(self, mask_to_cover, bits, lin, P):
         return backend.thin_cover_device(mask_to_cover, bits, lin, P)
 
@@ -1038,7 +1047,8 @@ class _Assembly:
         if self.packed and self.ops is not None and not hasattr(self.ops, "pack_scan"):
             raise NotImplementedError("no_overlap_per_channel needs the device kernels (DeviceOps)")
         # the two optional branches of the greedy cover (foreground_cover.py:53-85, 141-168) leave marks
-        # anywhere in a slice: a sequential walk of the ranked list -- served on ONE rank (below)
+        # anywhere in a slice: served on ONE rank (below) -- on the device where the ops object has the
+        # marked cover, else by a sequential walk of the ranked list on the host
         self.seq_cover = bool(self.kw.get("mark_close_neighboorhood", False) or self.kw.get("select_patches_overlap_neighborhood", False))
         if self.kw.get("aff_graph") is not None:
             raise NotImplementedError("aff_graph input is not supported by the tiled assembly")
@@ -1659,11 +1669,32 @@ class _Assembly:
                 lin_t, rscores_t = self.ops.rank_order(self.score_f, self.fg_d, self.ps)
             if self.debug_crc:
                 backend.note("crc_ranked", zlib.crc32(lin_t.cpu().numpy().tobytes()))
-            scores_host = self.score_f.cpu().numpy() if self.seq_cover and self.kw.get("select_patches_overlap_neighborhood") else None
+            # (marks and ring on the device: DeviceOps.cover_options; an ops object without it, the host
+            # switch, patch rows wider than a word and axes a mark box wraps around on keep the loop)
+            dev_options = self.seq_cover and hasattr(self.ops, "cover_options") and \
+                os.environ.get("PPP_COVER", "device") != "host" and self.ps[2] <= 32 and \
+                fc.marks_on_device(self.shape, self.kw)
+            scores_host = self.score_f.cpu().numpy() if self.seq_cover and not dev_options and \
+                self.kw.get("select_patches_overlap_neighborhood") else None
             del self.score_f
             self.coords_t = coords_of(lin_t)
             if self.kw.get("skipSelection", False):
                 self.sel_coords = self.coords_t.cpu().numpy()
+            elif dev_options:
+                # ---- the marked cover and the ring on the device: nothing of the volume's size goes to
+                # the host, only the selected centres come back
+                with backend.host_timer("s3_cover"):
+                    radslice = tuple(slice(int(self.rad[i]), self.shape[i] - int(self.rad[i])) for i in range(3))
+                    ov = self.ov_d if self.any_overlap else None
+                    if self.provider and self.comm.world == 1 and hasattr(self.ops, "voxel_major_pool"):
+                        order = self.ops.cover_options(self.mask_d, ov, self.bits_own, lin_t, rscores_t, pix_ths, radslice,
+                                                       self.Pg, self.kw, bits_first_voxel=self.oz0 * self.plane)
+                    else:
+                        bits = self.gathered_bits(self.coords_t, self.kw["fc_threshold"], True)
+                        order = self.ops.cover_options(self.mask_d, ov, bits, lin_t, rscores_t, pix_ths, radslice,
+                                                       self.Pg, self.kw)
+                        del bits
+                    self.sel_coords = np.ascontiguousarray(self.coords_t[order].cpu().numpy(), dtype=np.int32).reshape(-1, 3)
             elif self.seq_cover:
                 # ---- sequential native cover with marks (one rank; the ranked list goes to the host,
                 # the patch bits of a chunk of centres come from wherever the prediction lives)

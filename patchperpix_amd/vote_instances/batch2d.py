@@ -13,8 +13,10 @@ neighbourhood reaches another slice):
   S3        the device cover's rounds are slice-local; what is not is the loop's stop rule ("the
             interior is empty") -- applied per slice here, and a slice that is done takes no part in
             the later pixTh passes.  The score_threshold break is a cut of a list sorted by score,
-            the same in every subsequence.  The sequential variants (mark_close_neighboorhood,
-            select_patches_overlap_neighborhood) run per slice;
+            the same in every subsequence.  mark_close_neighboorhood (marks never leave the
+            centre's slice) and select_patches_overlap_neighborhood (in-plane dilation) ride the same
+            batched rounds (foreground_cover.cover_options_device, per_slice); the host loop, where
+            it is asked for, runs per slice;
   S4        ppp_thin_cover_slices: the same rounds, the stop rule per slice;
   pairs     the selected list sorted by (z, x), partners in the same slice only
             (ppp_patch_pairs_*_slices): the rows of slice k in its own canonical order;
@@ -33,7 +35,8 @@ import numpy as np
 from .. import backend
 from .aff_patch_graph import PatchPairs
 from .consensus_array import loadOrComputeConsensus
-from .foreground_cover import (_bits_for, _pix_thresholds, cover_sequential, never_selected)
+from .foreground_cover import (_bits_for, _pix_thresholds, cover_options_device, cover_sequential, marks_on_device,
+                               never_selected)
 from .ranked_patches import PatchList, loadOrComputePatchRanking
 
 logger = logging.getLogger(__name__)
@@ -219,7 +222,24 @@ def _cover(overlap_mask, mask_to_cover, patchshape, ranked, radslice, pred, scor
     near_overlap = bool(kw.get("select_patches_overlap_neighborhood", False))
     if len(ranked) == 0:
         return ranked
-    if os.environ.get("PPP_COVER", "device") == "host" or int(patchshape[2]) > 32 or mark or near_overlap:
+    on_device = os.environ.get("PPP_COVER", "device") != "host" and int(patchshape[2]) <= 32
+    if on_device and (mark or near_overlap) and marks_on_device(mask_to_cover.shape, kw):
+        # marks stay in their slice and p_z - 1 = 0: one batched cover serves them; the stop rule, the
+        # score break, the ring's pixel threshold and its (in-plane) dilation are per slice
+        dev = pred.device
+        mask = torch.from_numpy(np.ascontiguousarray(mask_to_cover != 0).astype(np.uint8)).to(dev)
+        ov = np.asarray(overlap_mask)
+        overlap = torch.from_numpy(np.ascontiguousarray(ov != 0).astype(np.uint8)).to(dev) if ov.any() else None
+        bits = backend.patch_bits(pred, torch.from_numpy(ranked.coords).to(dev), kw["fc_threshold"], P)
+        order = cover_options_device(mask, overlap, bits, torch.from_numpy(ranked.lin(mask.shape)).to(dev),
+                                     torch.from_numpy(np.ascontiguousarray(ranked.scores)).to(dev),
+                                     _pix_thresholds(patchshape, kw), radslice, P, kw, per_slice=True)
+        sel = ranked[order.cpu().numpy()]
+        if near_overlap and len(sel):
+            # the reference rebuilds the list from the score volume (foreground_cover.py:83-85)
+            sel = PatchList(sel.coords, np.asarray(scores_array)[tuple(sel.coords.T)])
+        return sel
+    if not on_device or mark or near_overlap:
         # the sequential loop (and its marks) per slice, on the slice's subsequence of the ranked list
         parts = []
         z = ranked.coords[:, 0]
