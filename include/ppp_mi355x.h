@@ -273,6 +273,26 @@ int ppp_patch_graph_by_patch_lcg(const void *d_pred, int pred_dtype, const float
                                  int32_t n_groups, int64_t n_blocks, int32_t chunk, float *d_aff,
                                  const int64_t *d_drop_off, const uint64_t *d_drops,
                                  const ppp_params *p, void *stream);
+/* The foreground bits of a patch made once per patch.  The per-patch kernel needs, for patch A and
+ * for the patch B of every pair row, the C = pz*py*px bits  mid[u_r] > th && pred[r][c] > th  (u_r =
+ * the r-th voxel of the window of centre c; th as in the patch graph); built inside the kernel they
+ * cost 2 C scattered loads per row.  ppp_patch_fg_bits writes ceil(C / 32) uint32 words per centre
+ * (bit r of the patch = bit r % 32 of word r / 32) for
+ *   d_centres   int64 [n] linear voxel indices (z*Y + y)*X + x, ASCENDING, windows inside the volume
+ * ppp_patch_graph_by_patch_bits = ppp_patch_graph_by_patch_lcg (slices != 0: its _slices form) that
+ * reads the bits of A and of every B from that table (a binary search per row in d_bits_centres,
+ * which must hold the centre of every patch of the dispatched rows) -- d_bits NULL: built in the
+ * kernel, as by the entry points above.  Same bits.  The table depends on d_pred and the patch shape
+ * only, not on cons_box or ring_z. */
+int ppp_patch_fg_bits(const void *d_pred, int pred_dtype, const int64_t *d_centres, int64_t n,
+                      uint32_t *d_bits, const ppp_params *p, void *stream);
+int ppp_patch_graph_by_patch_bits(const void *d_pred, int pred_dtype, const float *d_cons_vm,
+                                  const uint32_t *d_pairs, const uint32_t *d_order,
+                                  const int64_t *d_group_start, const int64_t *d_chunk_offsets,
+                                  int32_t n_groups, int64_t n_blocks, int32_t chunk, float *d_aff,
+                                  const int64_t *d_drop_off, const uint64_t *d_drops,
+                                  const int64_t *d_bits_centres, int64_t n_bits, const uint32_t *d_bits,
+                                  int32_t slices, const ppp_params *p, void *stream);
 int ppp_patch_graph_by_patch(const void *d_pred, int pred_dtype, const float *d_cons_vm,
                              const uint32_t *d_pairs, const uint32_t *d_order,
                              const int64_t *d_group_start, const int64_t *d_chunk_offsets,

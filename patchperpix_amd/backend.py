@@ -140,6 +140,15 @@ _SIGNATURES = {
                                                     ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
                                                     ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                                     ctypes.c_void_p, ctypes.POINTER(Params), ctypes.c_void_p]),
+    "ppp_patch_fg_bits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                         ctypes.c_void_p, ctypes.POINTER(Params), ctypes.c_void_p]),
+    "ppp_patch_graph_by_patch_bits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
+                                                     ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                     ctypes.c_void_p, ctypes.c_int32,
+                                                     ctypes.POINTER(Params), ctypes.c_void_p]),
     "ppp_label_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Params)]),
     "ppp_label_components": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                             ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
@@ -903,7 +912,8 @@ def patch_graph_prepare(pred, pairs, Pv, ahead=False):
     import types
     torch = _torch()
     n = int(pairs.shape[0])
-    job = types.SimpleNamespace(n=n, n_live=0, plan=None, bufs=[None, None], masks_done=set())
+    job = types.SimpleNamespace(n=n, n_live=0, plan=None, bufs=[None, None], masks_done=set(),
+                                bits_centres=None, bits=None)
     job.aff = torch.zeros((n,), dtype=torch.float32, device=pred.device)
     if n == 0:
         return job
@@ -937,6 +947,15 @@ def patch_graph_prepare(pred, pairs, Pv, ahead=False):
     job.chunk_offsets = torch.cat([zero, torch.cumsum((counts + chunk - 1) // chunk, 0)])
     job.n_groups = int(counts.shape[0])
     job.order32 = order.to(torch.int32)
+    oom = getattr(torch, "OutOfMemoryError", None) or torch.cuda.OutOfMemoryError
+    # the foreground bits of every patch of the dispatched rows, once per patch (PPP_PA_BITS=0: built
+    # inside the per-patch kernel, for every row; so they are when memory runs out in here)
+    if os.environ.get("PPP_PA_BITS", "1") != "0":
+        try:
+            job.bits_centres, job.bits = patch_fg_bits(pred, pairs[order], Pv)
+        except oom:
+            job.bits_centres = job.bits = None
+            torch.cuda.empty_cache()
     del order
     # thinning masks beforehand: the groups are cut into batches whose masks fit the budget (one
     # buffer, filled and read batch after batch; a second buffer when a batch's masks are made
@@ -944,7 +963,6 @@ def patch_graph_prepare(pred, pairs, Pv, ahead=False):
     # The plan's temporaries (about eight int64 per dispatched row) and the mask buffers are not
     # part of the tile planner's budget: the mask budget is capped by what is free right now, and
     # running out of memory anywhere in here falls back to the generator inside the kernel.
-    oom = getattr(torch, "OutOfMemoryError", None) or torch.cuda.OutOfMemoryError
     plan = drops = None
     try:
         plan = _lcg_plan(dkey, job.group_start, Pv)
@@ -960,6 +978,25 @@ def patch_graph_prepare(pred, pairs, Pv, ahead=False):
     job.co_host = dict(zip(job.cuts, co_host))    # blocks before each cut: ONE copy for all batches
     job.bufs = [drops, drops]
     return job
+
+
+def patch_fg_bits(pred, rows, Pv):
+    """The foreground bits of every patch that occurs in `rows` (device int32 [n, 6]: centre of A,
+    centre of B), once per patch (ppp_patch_fg_bits).  Returns (centres: int64 [m] ascending linear
+    voxel indices in the frame of `pred`, bits: int32 [m, ceil(C / 32)])."""
+    torch = _torch()
+    rows = rows.to(torch.int64)
+    lin = torch.cat([(rows[:, 0] * Pv.Y + rows[:, 1]) * Pv.X + rows[:, 2],
+                     (rows[:, 3] * Pv.Y + rows[:, 4]) * Pv.X + rows[:, 5]])
+    del rows
+    centres = torch.unique(lin)                   # (sorted)
+    del lin
+    words = (Pv.pz * Pv.py * Pv.px + 31) // 32
+    bits = torch.empty((int(centres.shape[0]), words), dtype=torch.int32, device=pred.device)
+    with _timed("patch_graph_bits"):
+        check(lib().ppp_patch_fg_bits(_dev_ptr(pred), pred_dtype_code(pred), _dev_ptr(centres),
+                                      int(centres.shape[0]), _dev_ptr(bits), ctypes.byref(Pv), _stream()))
+    return centres, bits
 
 
 def _pa_masks(job, pred, pairs, Pv, b, slices=False):
@@ -995,14 +1032,15 @@ def patch_graph_by_patch(pred, cons_vm, pairs, Pv, job=None, slices=False):
             _pa_masks(job, pred, pairs, Pv, b, slices)
         co = job.chunk_offsets[g0:g1 + 1]
         n_blocks = int(job.co_host[g1] - job.co_host[g0])
-        fn = lib().ppp_patch_graph_by_patch_lcg_slices if slices else lib().ppp_patch_graph_by_patch_lcg
         with _timed("patch_graph"):
-            check(fn(
+            check(lib().ppp_patch_graph_by_patch_bits(
                 _dev_ptr(pred), pred_dtype_code(pred), _dev_ptr(cons_vm), _dev_ptr(pairs),
                 _dev_ptr(job.order32), _dev_ptr(job.group_start[g0:g1 + 1].contiguous()),
                 _dev_ptr((co - co[0]).contiguous()), g1 - g0, n_blocks, job.chunk, _dev_ptr(aff),
                 _dev_ptr(plan["drop_off"]) if plan is not None else None,
-                _dev_ptr(job.bufs[b % 2]) if plan is not None else None, ctypes.byref(Pv), _stream()))
+                _dev_ptr(job.bufs[b % 2]) if plan is not None else None,
+                _dev_ptr(job.bits_centres), 0 if job.bits is None else int(job.bits_centres.shape[0]),
+                _dev_ptr(job.bits), 1 if slices else 0, ctypes.byref(Pv), _stream()))
     return aff
 
 

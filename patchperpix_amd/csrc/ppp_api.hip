@@ -451,6 +451,7 @@ static int patch_graph_by_patch_impl(const void *d_pred, int pred_dtype, const f
                                      const int64_t *d_group_start, const int64_t *d_chunk_offsets,
                                      int32_t n_groups, int64_t n_blocks, int32_t chunk, float *d_aff,
                                      const int64_t *d_drop_off, const uint64_t *d_drops,
+                                     const int64_t *d_bits_centres, int64_t n_bits, const uint32_t *d_bits,
                                      const ppp_params *p, void *stream, int slices) {
     ppp::Geo G;
     PPP_TRY(slices_geo(p, slices, &G));
@@ -462,12 +463,16 @@ static int patch_graph_by_patch_impl(const void *d_pred, int pred_dtype, const f
         return fail(PPP_ERR_INVALID_ARG, "ppp_patch_graph_by_patch reads the VOXEL_MAJOR layout");
     if ((d_drop_off == nullptr) != (d_drops == nullptr))
         return fail(PPP_ERR_INVALID_ARG, "d_drop_off and d_drops go together");
+    if (d_bits && (!d_bits_centres || n_bits <= 0 || n_bits >= (1ll << 31)))
+        return fail(PPP_ERR_INVALID_ARG, "d_bits needs its sorted centre list");
     PPP_TRY(need_device());
     hipError_t e = ppp::launch_patch_graph_pa(d_pred, pred_dtype, d_cons_vm, d_pairs, d_order,
                                               (const long long *)d_group_start,
                                               (const long long *)d_chunk_offsets, n_groups, n_blocks,
                                               chunk, d_aff, (const long long *)d_drop_off,
-                                              (const unsigned long long *)d_drops, G, (hipStream_t)stream);
+                                              (const unsigned long long *)d_drops,
+                                              d_bits ? (const long long *)d_bits_centres : nullptr,
+                                              d_bits ? (int)n_bits : 0, d_bits, G, (hipStream_t)stream);
     if (e == hipErrorNotSupported)
         return fail(PPP_ERR_UNSUPPORTED, "no per-patch kernel for this patch shape / chunk size");
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_patch_graph_by_patch");
@@ -481,7 +486,33 @@ int ppp_patch_graph_by_patch_lcg(const void *d_pred, int pred_dtype, const float
                                  const ppp_params *p, void *stream) {
     return patch_graph_by_patch_impl(d_pred, pred_dtype, d_cons_vm, d_pairs, d_order, d_group_start,
                                      d_chunk_offsets, n_groups, n_blocks, chunk, d_aff, d_drop_off, d_drops,
-                                     p, stream, 0);
+                                     nullptr, 0, nullptr, p, stream, 0);
+}
+
+int ppp_patch_graph_by_patch_bits(const void *d_pred, int pred_dtype, const float *d_cons_vm,
+                                  const uint32_t *d_pairs, const uint32_t *d_order,
+                                  const int64_t *d_group_start, const int64_t *d_chunk_offsets,
+                                  int32_t n_groups, int64_t n_blocks, int32_t chunk, float *d_aff,
+                                  const int64_t *d_drop_off, const uint64_t *d_drops,
+                                  const int64_t *d_bits_centres, int64_t n_bits, const uint32_t *d_bits,
+                                  int32_t slices, const ppp_params *p, void *stream) {
+    return patch_graph_by_patch_impl(d_pred, pred_dtype, d_cons_vm, d_pairs, d_order, d_group_start,
+                                     d_chunk_offsets, n_groups, n_blocks, chunk, d_aff, d_drop_off, d_drops,
+                                     d_bits_centres, n_bits, d_bits, p, stream, slices ? 1 : 0);
+}
+
+int ppp_patch_fg_bits(const void *d_pred, int pred_dtype, const int64_t *d_centres, int64_t n,
+                      uint32_t *d_bits, const ppp_params *p, void *stream) {
+    ppp::Geo G;
+    PPP_TRY(make_geo(p, &G));
+    PPP_TRY(check_dtype(pred_dtype));
+    if (n <= 0) return PPP_OK;
+    if (!d_pred || !d_centres || !d_bits) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    PPP_TRY(need_device());
+    hipError_t e = ppp::launch_patch_fg_bits(d_pred, pred_dtype, (const long long *)d_centres, (long long)n,
+                                             d_bits, G, (hipStream_t)stream);
+    if (e == hipErrorNotSupported) return fail(PPP_ERR_UNSUPPORTED, "too many centres for one launch");
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_patch_fg_bits");
 }
 
 int ppp_patch_graph_by_patch_lcg_slices(const void *d_pred, int pred_dtype, const float *d_cons_vm,
@@ -492,7 +523,7 @@ int ppp_patch_graph_by_patch_lcg_slices(const void *d_pred, int pred_dtype, cons
                                         const ppp_params *p, void *stream) {
     return patch_graph_by_patch_impl(d_pred, pred_dtype, d_cons_vm, d_pairs, d_order, d_group_start,
                                      d_chunk_offsets, n_groups, n_blocks, chunk, d_aff, d_drop_off, d_drops,
-                                     p, stream, 1);
+                                     nullptr, 0, nullptr, p, stream, 1);
 }
 
 int ppp_patch_graph_by_patch(const void *d_pred, int pred_dtype, const float *d_cons_vm,

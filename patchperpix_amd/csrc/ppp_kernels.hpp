@@ -80,7 +80,10 @@ hipError_t launch_patch_graph_pa(const void *pred, int dtype, const float *S, co
                                  const uint32_t *order, const long long *group_start,
                                  const long long *chunk_offsets, int n_groups, long long n_blocks,
                                  int chunk, float *aff, const long long *drop_off,
-                                 const unsigned long long *drops, const Geo &G, hipStream_t s);
+                                 const unsigned long long *drops, const long long *bits_centres, int n_bits,
+                                 const uint32_t *bits, const Geo &G, hipStream_t s);
+hipError_t launch_patch_fg_bits(const void *pred, int dtype, const long long *centres, long long n,
+                                uint32_t *table, const Geo &G, hipStream_t s);
 long long patch_graph_lcg_words(const Geo &G, int dz, int dy, int dx);
 hipError_t launch_patch_graph_lcg(const void *pred, int dtype, const uint32_t *rows, const uint32_t *order,
                                   const long long *lcg_pos, long long n, const long long *drop_off,

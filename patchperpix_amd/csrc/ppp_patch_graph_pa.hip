@@ -32,6 +32,29 @@
 // is fetched into registers while the current one is consumed.  One LDS row buffer and two
 // barriers per pixel from 7^3 on, two buffers and one barrier below.
 //
+// The adds of a candidate row.  A lane adds the row's PX staged values under its own PX-bit mask;
+// about one slot in ten is useful, so the instructions per slot are what counts: see
+// PPP_PA_EXEC_ADD below (7^3 small kernel: the add runs under a lane mask instead of masking the
+// value).
+//
+// Measured and dropped (140^3 / 7^3 benchmark, thinned list, S5 kernel per step against 48.2 ms):
+// the rows 65.. of a patch as a SECOND PASS of the same wave over the row already staged (a lane
+// carries rows pos and pos + 64, 128 rows per workgroup, instead of a second one-wave workgroup
+// that stages every row of A again; 38 % of the workgroups exist for 8.6 % of the rows).  The
+// second set of B-patch bits takes the CU from 13 to 11 workgroups, the second pair's state does
+// not fit the 128-VGPR budget (18 spilled with its axis masks made anew per pixel, 27 with them
+// kept): 62.7 ms; with a 3-waves-per-SIMD budget (152 VGPRs, no spills) 50.9 ms.  The kernel is
+// bound by vector issue and by waves per CU, not by the staging reads (they hit in L2), and the
+// second pass walks the same union of candidate rows the second workgroup walked.
+//
+// The foreground bits of the patches (round 10).  A and every B need their C bits
+// mid[u_r] > th && pred[r][c] > th; built here they are 2 C scattered loads per pair row, and a
+// selected patch is B in ~64 rows.  patch_fg_bits_kernel (below) makes them once per distinct centre
+// of the dispatched rows, into a table ordered by linear voxel index; a lane finds its patch by a
+// binary search in the sorted centre list and loads ceil(C / 32) words.  Callers without a table
+// (bits == nullptr) get them built here as before.  patch_graph_lcg_wave_kernel gathers only the
+// bits inside a pair's intersection box and is not a plain substitution: it keeps its own gather.
+//
 // The per-pair float sum, the candidate order (r1 raster, then z2o, y2o, x2o ascending) and the
 // LCG stream are exactly those of the reference: results are bit-identical to the other kernels.
 #include "ppp_kernels.hpp"
@@ -105,6 +128,30 @@ static constexpr int PA_MASKS_MAX_PX = PPP_PA_MASKS_MAX_PX;
 #ifndef PPP_PA_MASK_AHEAD
 #define PPP_PA_MASK_AHEAD 1
 #endif
+// The masked add of a candidate row, 7^3 small kernel (140^3 benchmark, thinned list, S5 kernel per
+// step, parent and variants alternating in one call, three runs each; profiles/r10_a_bench_ab.txt):
+//   0  acc += rowq[t] & sel(t): bit-field extract, and, add per slot               47.9-48.0 ms
+//   1  the slot's bit as the carry of a doubling of the reversed row mask, the add under that lane
+//      mask (v_add_co, exec <- saved & carry, v_add_f32): 2 vector + 1 scalar instruction per slot,
+//      all seven carries made before the first add                                  46.0 ms
+//   (measured and dropped: the same with ONE carry in VCC per slot and EXEC restored after every
+//   add -- each add waits for its own vector -> scalar -> EXEC round trip: 50.1-50.2 ms.  In the
+//   256-thread kernel the fourteen scalar registers of form 1 cost 8 more spilled VGPRs at its
+//   64-VGPR budget: it keeps form 0.)
+// Registers of patch_graph_pa_kernel<__half, 7, 64> with form 0 and with form 1 alike: 114 VGPRs,
+// 106 SGPRs, nothing spilled (profiles/r10_a_kernel_regs.txt).
+// Not done: the row's seven LDS reads are still issued for every lane ahead of the statement (lanes
+// without work read slot 0); reading under the slot's lane mask as well would need the reads and
+// their wait inside the statement.
+// Why the bits are the same: a skipped slot leaves acc as it is, form 0 adds +0.0f there.  The two
+// differ only for acc == -0.0f, which cannot occur: acc starts at +0.0f (`float acc = 0.0f`
+// below), and in round-to-nearest -- the mode the kernel runs in -- a sum is -0.0f only
+// when both operands are.  It also needs f32 denormals kept (the HIP default, and what this library
+// is built with): with them flushed, form 0's `acc + 0.0f` would flush a denormal acc that a skipped
+// slot leaves alone.
+#ifndef PPP_PA_EXEC_ADD
+#define PPP_PA_EXEC_ADD 1
+#endif
 static constexpr int PA_PAD = 8;       // floats of slack either side of the staged row (a masked row read overshoots by < PX)
 
 // bits b in [0, n) with lo <= b <= hi
@@ -146,7 +193,9 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
                           const long long *__restrict__ group_start,
                           const long long *__restrict__ chunk_offsets, const int n_groups,
                           float *__restrict__ aff, const long long *__restrict__ drop_off,
-                          const unsigned long long *__restrict__ drops, const Geo G) {
+                          const unsigned long long *__restrict__ drops,
+                          const long long *__restrict__ bits_centres, const int n_bits,
+                          const uint32_t *__restrict__ bits, const Geo G) {
     extern __shared__ uint32_t lds_raw[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int words = (G.C + 31) / 32;
@@ -213,7 +262,23 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
               ax = (int)rows[(size_t)first_row * 6 + 2];
     const T *mid = pred + (long long)G.mid * G.V;
 
-    // ---- foreground bits of patch A (shared) and of this lane's patch B
+    // ---- foreground bits of patch A (shared) and of this lane's patch B: from the table made once
+    // per patch by patch_fg_bits_kernel (below) where the caller has one -- a selected patch is B
+    // in ~64 rows and A in 1.6 workgroups, and its 343 bits cost 2 x 343 scattered loads each time
+    // they are built here -- else built here.  bits_slot: position of a centre in the sorted list
+    // (the caller lists every centre of its rows; the search stays inside the list regardless).
+    auto bits_slot = [&](const long long lin) -> long long {
+        int lo = 0, hi = n_bits;
+        while (hi - lo > 1) {
+            const int m = (lo + hi) >> 1;
+            if (bits_centres[m] <= lin) lo = m; else hi = m;
+        }
+        return lo;
+    };
+    if (bits != nullptr) {
+        const uint32_t *src = bits + bits_slot(vox(G, az, ay, ax)) * words;
+        for (int w = tid; w < words; w += PA_THREADS) faw[w] = src[w];
+    } else
     for (int base = 0; base < G.C; base += PA_THREADS) {
         const int r = base + tid;
         bool on = false;
@@ -247,6 +312,10 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
         rnd = pair_seed(G, az, ay, ax, bz, by, bx);
         const long long lb = vox(G, bz, by, bx);
         int r = 0;
+        if (bits != nullptr) {
+            const uint32_t *src = bits + bits_slot(lb) * words;
+            for (int w = 0; w < words; ++w) fbw[w * PA_THREADS + tid] = src[w];
+        } else
         for (int w = 0; w < words; ++w) {
             uint32_t bits = 0;
             for (int b = 0; b < 32 && r < G.C; ++b, ++r) {
@@ -298,7 +367,7 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
         const int z1o = r1 / (G.py * PX), y1o = (r1 / PX) % G.py, x1o = r1 % PX;
         return S + (baseA + (long long)row_slice(G, az + z1o - G.rz) * sZ + (long long)(y1o - G.ry) * sY + (x1o - PX / 2)) * W;
     };
-    float acc = 0.0f;
+    float acc = 0.0f;               // (+0.0f: the masked add of PPP_PA_EXEC_ADD relies on it)
     unsigned fg_cnt = 0;
 #ifdef PA_STATS
     unsigned long long st_0 = 0, st_1 = 0, st_2 = 0, st_3 = 0, st_4 = 0, st_5 = 0;
@@ -588,11 +657,46 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
                         // lanes with nothing to add on this row may point anywhere: they read
                         // slot 0 (one broadcast address; what they read is masked to zero)
                         const float *rowq = cur + (rb != 0u ? idx0 + y2o * G.wx : 0);
+                        if constexpr (PPP_PA_EXEC_ADD != 0 && PX == 7 && PA_THREADS != PaCfg<PX>::THREADS) {
+                            // Two vector instructions per add slot instead of three (bit-field
+                            // extract, and, add): the row's mask is reversed once, every doubling
+                            // of it shifts one slot's bit out as the lane's carry, and the add runs
+                            // under that lane mask (skipping a slot = adding +0.0: acc is never
+                            // -0.0).  EXEC is changed and restored inside the one statement; the
+                            // row's values are its inputs.  See PPP_PA_EXEC_ADD above.
+                            uint32_t m = __builtin_bitreverse32(rb);      // slot t = bit 31 - t
+                            const float v0 = rowq[0], v1 = rowq[1], v2 = rowq[2], v3 = rowq[3], v4 = rowq[4],
+                                        v5 = rowq[5], v6 = rowq[6];
+                            // the seven lane masks first (scalar register pairs), then the adds
+                            u64 sv, c0, c1, c2, c3, c4, c5, c6;
+                            float a = acc;
+#define PPP_PA_CARRY(C) "v_add_co_u32 %[m], %[" #C "], %[m], %[m]\n\t"
+#define PPP_PA_SLOT(C, V)                                \
+    "s_and_b64 exec, %[sv], %[" #C "]\n\t"               \
+    "v_add_f32 %[acc], %[acc], %[" #V "]\n\t"
+                            asm volatile("s_mov_b64 %[sv], exec\n\t"
+                                         PPP_PA_CARRY(c0) PPP_PA_CARRY(c1) PPP_PA_CARRY(c2) PPP_PA_CARRY(c3)
+                                         PPP_PA_CARRY(c4) PPP_PA_CARRY(c5) PPP_PA_CARRY(c6)
+                                         PPP_PA_SLOT(c0, v0) PPP_PA_SLOT(c1, v1) PPP_PA_SLOT(c2, v2)
+                                         PPP_PA_SLOT(c3, v3) PPP_PA_SLOT(c4, v4) PPP_PA_SLOT(c5, v5)
+                                         PPP_PA_SLOT(c6, v6)
+                                         "s_mov_b64 exec, %[sv]\n\t"
+                                         : [acc] "+v"(a), [m] "+v"(m), [sv] "=&s"(sv), [c0] "=&s"(c0),
+                                           [c1] "=&s"(c1), [c2] "=&s"(c2), [c3] "=&s"(c3), [c4] "=&s"(c4),
+                                           [c5] "=&s"(c5), [c6] "=&s"(c6)
+                                         : [v0] "v"(v0), [v1] "v"(v1), [v2] "v"(v2), [v3] "v"(v3), [v4] "v"(v4),
+                                           [v5] "v"(v5), [v6] "v"(v6)
+                                         : "scc");                 // (s_and_b64 writes SCC)
+#undef PPP_PA_CARRY
+#undef PPP_PA_SLOT
+                            acc = a;
+                        } else {
 #pragma unroll
                         for (int t = 0; t < PX; ++t) {
                             // acc += bit t of rb ? rowq[t] : 0.0f
                             const int sel = ((int)(rb << (31 - t))) >> 31;
                             acc += __int_as_float(__float_as_int(rowq[t]) & sel);
+                        }
                         }
                     }
                     }
@@ -962,7 +1066,8 @@ template <typename T, int PX, int THREADS>
 static hipError_t launch_pa(const T *pred, const float *S, const uint32_t *rows, const uint32_t *order,
                             const long long *group_start, const long long *chunk_offsets, int n_groups,
                             long long n_blocks, float *aff, const long long *drop_off,
-                            const unsigned long long *drops, const Geo &G, size_t lds, hipStream_t s) {
+                            const unsigned long long *drops, const long long *bits_centres, int n_bits,
+                            const uint32_t *bits, const Geo &G, size_t lds, hipStream_t s) {
     // (dynamic LDS above 64 KB -- the 9^3 rows -- is an opt-in per kernel)
     if (lds > 64 * 1024) {
         hipError_t ea = hipFuncSetAttribute((const void *)patch_graph_pa_kernel<T, PX, THREADS>,
@@ -970,7 +1075,50 @@ static hipError_t launch_pa(const T *pred, const float *S, const uint32_t *rows,
         if (ea != hipSuccess) return ea;
     }
     patch_graph_pa_kernel<T, PX, THREADS><<<dim3((unsigned)n_blocks), dim3(THREADS), lds, s>>>(
-        pred, S, rows, order, group_start, chunk_offsets, n_groups, aff, drop_off, drops, G);
+        pred, S, rows, order, group_start, chunk_offsets, n_groups, aff, drop_off, drops, bits_centres, n_bits,
+        bits, G);
+    return hipGetLastError();
+}
+
+// ---- The foreground bits of a patch, once per patch: bit r of the ceil(C / 32) words of centre c
+// is  mid[u_r] > th_gt && pred[r][c] > th_gt  (u_r = the r-th voxel of c's window) -- the expression
+// the per-patch kernel evaluates for A and for every B.  A wave per centre; centres[] holds linear
+// voxel indices of the frame `pred` lives in, windows inside the volume.
+template <typename T>
+__global__ void __launch_bounds__(64)
+    patch_fg_bits_kernel(const T *__restrict__ pred, const long long *__restrict__ centres, const long long n,
+                         uint32_t *__restrict__ table, const Geo G) {
+    const long long i = blockIdx.x;
+    if (i >= n) return;
+    const int lane = threadIdx.x, words = (G.C + 31) / 32;
+    const long long lin = centres[i];
+    const int cz = (int)(lin / ((long long)G.Y * G.X)), cy = (int)((lin / G.X) % G.Y), cx = (int)(lin % G.X);
+    const T *mid = pred + (long long)G.mid * G.V;
+    for (int base = 0; base < G.C; base += 64) {
+        const int r = base + lane;
+        bool on = false;
+        if (r < G.C) {
+            const int z = cz + r / (G.py * G.px) - G.rz, y = cy + (r / G.px) % G.py - G.ry,
+                      x = cx + r % G.px - G.px / 2;
+            on = ldf(mid, vox(G, z, y, x)) > G.th_gt && ldf(pred, (long long)r * G.V + lin) > G.th_gt;
+        }
+        const unsigned long long m = __ballot(on);
+        if (lane == 0) {
+            const int w = base >> 5;
+            if (w < words) table[i * words + w] = (uint32_t)m;
+            if (w + 1 < words) table[i * words + w + 1] = (uint32_t)(m >> 32);
+        }
+    }
+}
+
+hipError_t launch_patch_fg_bits(const void *pred, int dtype, const long long *centres, long long n,
+                                uint32_t *table, const Geo &G, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (n >= (1ll << 31) || grid_too_big((unsigned long long)n, 64)) return hipErrorNotSupported;
+    if (dtype == PPP_F16)
+        patch_fg_bits_kernel<__half><<<dim3((unsigned)n), dim3(64), 0, s>>>((const __half *)pred, centres, n, table, G);
+    else
+        patch_fg_bits_kernel<float><<<dim3((unsigned)n), dim3(64), 0, s>>>((const float *)pred, centres, n, table, G);
     return hipGetLastError();
 }
 
@@ -978,8 +1126,10 @@ hipError_t launch_patch_graph_pa(const void *pred, int dtype, const float *S, co
                                  const uint32_t *order, const long long *group_start,
                                  const long long *chunk_offsets, int n_groups, long long n_blocks,
                                  int chunk, float *aff, const long long *drop_off,
-                                 const unsigned long long *drops, const Geo &G, hipStream_t s) {
+                                 const unsigned long long *drops, const long long *bits_centres, int n_bits,
+                                 const uint32_t *bits, const Geo &G, hipStream_t s) {
     if (n_groups <= 0 || n_blocks <= 0) return hipSuccess;
+    if (bits != nullptr && (bits_centres == nullptr || n_bits <= 0)) return hipErrorInvalidValue;
     const int threads = chunk;
     if (threads == 0 || (threads != patch_graph_pa_chunk(G, false) && threads != patch_graph_pa_chunk(G, true)))
         return hipErrorNotSupported;
@@ -999,10 +1149,10 @@ hipError_t launch_patch_graph_pa(const void *pred, int dtype, const float *S, co
 #define PPP_PA_CASE(P)                                                                                  \
     case P:                                                                                             \
         if (dtype == PPP_F16)                                                                           \
-            return small ? launch_pa<__half, P, PaCfg<P>::THREADS_SMALL>((const __half *)pred, S, rows, order, group_start, chunk_offsets, n_groups, n_blocks, aff, drop_off, drops, G, lds, s) \
-                         : launch_pa<__half, P, PaCfg<P>::THREADS>((const __half *)pred, S, rows, order, group_start, chunk_offsets, n_groups, n_blocks, aff, drop_off, drops, G, lds, s); \
-        return small ? launch_pa<float, P, PaCfg<P>::THREADS_SMALL>((const float *)pred, S, rows, order, group_start, chunk_offsets, n_groups, n_blocks, aff, drop_off, drops, G, lds, s) \
-                     : launch_pa<float, P, PaCfg<P>::THREADS>((const float *)pred, S, rows, order, group_start, chunk_offsets, n_groups, n_blocks, aff, drop_off, drops, G, lds, s);
+            return small ? launch_pa<__half, P, PaCfg<P>::THREADS_SMALL>((const __half *)pred, S, rows, order, group_start, chunk_offsets, n_groups, n_blocks, aff, drop_off, drops, bits_centres, n_bits, bits, G, lds, s) \
+                         : launch_pa<__half, P, PaCfg<P>::THREADS>((const __half *)pred, S, rows, order, group_start, chunk_offsets, n_groups, n_blocks, aff, drop_off, drops, bits_centres, n_bits, bits, G, lds, s); \
+        return small ? launch_pa<float, P, PaCfg<P>::THREADS_SMALL>((const float *)pred, S, rows, order, group_start, chunk_offsets, n_groups, n_blocks, aff, drop_off, drops, bits_centres, n_bits, bits, G, lds, s) \
+                     : launch_pa<float, P, PaCfg<P>::THREADS>((const float *)pred, S, rows, order, group_start, chunk_offsets, n_groups, n_blocks, aff, drop_off, drops, bits_centres, n_bits, bits, G, lds, s);
     switch (G.px) {
         PPP_PA_CASE(3)
         PPP_PA_CASE(5)
