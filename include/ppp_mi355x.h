@@ -60,7 +60,13 @@ enum ppp_error {
     PPP_ERR_WORKSPACE = -5
 };
 
-enum ppp_dtype { PPP_F32 = 0, PPP_F16 = 1 };
+/* Element type of a prediction buffer.  PPP_BF16 (bfloat16: 1 sign, 8 exponent, 7 mantissa bits) is
+ * read by every entry point that READS a prediction; a value widens to float32 exactly (its 16 bits
+ * are the float's upper half), so every result is that of the float32 buffer holding the same
+ * values.  The entry points that WRITE a prediction or serve benches only (ppp_synth_pred,
+ * ppp_synth_pred_box, ppp_decode_tail, ppp_counter_calibration) take PPP_F32 / PPP_F16 only.
+ * ppp_pred_dtype_supported() tells what a given library reads. */
+enum ppp_dtype { PPP_F32 = 0, PPP_F16 = 1, PPP_BF16 = 2 };
 
 /* background rule for the second pixel of a pair: -DUSE_INV_TH / -DUSE_HALF_TH /
  * -DUSE_LESS_THAN_TH (utilVoteInstances.py:389-406) */
@@ -127,6 +133,9 @@ const char *ppp_consensus_kernel_name(void);
 void ppp_reload_env(void);
 /* number of HIP devices visible; 0 if none (never fails) */
 int ppp_device_count(void);
+/* 1 if this library reads predictions of the ppp_dtype code `dtype`, else 0 (needs no device; a
+ * caller that may hold an older library asks before it hands over a PPP_BF16 buffer) */
+int ppp_pred_dtype_supported(int dtype);
 
 /* number of consensus planes and floats of a consensus buffer for these params */
 int64_t ppp_cons_planes(const ppp_params *p);

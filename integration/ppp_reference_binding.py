@@ -21,7 +21,7 @@ _LIB_PATH = os.environ.get("PPP_LIB") or os.path.join(
     os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "patchperpix_amd", "csrc", "libppp_mi355x.so")
 _lib = ctypes.CDLL(_LIB_PATH)
 _lib.ppp_last_error.restype = ctypes.c_char_p
-PPP_F32, PPP_F16 = 0, 1
+PPP_F32, PPP_F16, PPP_BF16 = 0, 1, 2
 PPP_CONS_REFERENCE = 1
 
 

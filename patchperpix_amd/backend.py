@@ -13,7 +13,7 @@ import numpy as np
 
 from . import build as _build
 
-F32, F16 = 0, 1
+F32, F16, BF16 = 0, 1, 2
 BG_INV_TH, BG_HALF_TH, BG_LESS_THAN_TH = 0, 1, 2
 VAL_COUNT, VAL_PROB_PRODUCT, VAL_NORM_PROB_PRODUCT = 0, 1, 2
 CONS_COMPACT, CONS_REFERENCE, CONS_VOXEL_MAJOR = 0, 1, 2
@@ -87,6 +87,7 @@ _SIGNATURES = {
                                                ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     "ppp_consensus_writes_voxel_major": (ctypes.c_int, [ctypes.POINTER(Params)]),
     "ppp_device_count": (ctypes.c_int, []),
+    "ppp_pred_dtype_supported": (ctypes.c_int, [ctypes.c_int]),
     "ppp_minfilter_xy": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
                                         ctypes.POINTER(Params), ctypes.c_void_p]),
     "ppp_cons_planes": (ctypes.c_int64, [ctypes.POINTER(Params)]),
@@ -556,7 +557,9 @@ def pred_dtype_code(t):
         return F32
     if t.dtype == torch.float16:
         return F16
-    raise TypeError("pred must be float32 or float16, got %s" % t.dtype)
+    if t.dtype == torch.bfloat16:
+        return BF16
+    raise TypeError("pred must be float32, float16 or bfloat16, got %s" % t.dtype)
 
 
 def counter_calibration(src, n_read, dst, n_write):
@@ -611,18 +614,21 @@ def reload_env():
 
 
 def to_device_pred(pred, device="cuda", keep_f16=True):
-    """Host ndarray / tensor -> contiguous device tensor (f16 stays f16: widening is exact
-    and happens in registers)."""
+    """Host ndarray / tensor -> contiguous device tensor (f16 and bf16 stay as they are: widening
+    is exact and happens in registers; a contiguous tensor already on `device` is returned itself).
+    NOTES["pred_dtype"] names the element type the kernels are given."""
     torch = _torch()
     if isinstance(pred, np.ndarray):
         if pred.dtype not in (np.float32, np.float16):
             pred = pred.astype(np.float32)
         pred = torch.from_numpy(np.ascontiguousarray(pred))
-    if pred.dtype not in (torch.float32, torch.float16):
+    if pred.dtype not in (torch.float32, torch.float16, torch.bfloat16):
         pred = pred.float()
     if pred.dtype == torch.float16 and not keep_f16:
         pred = pred.float()
-    return pred.to(device).contiguous()
+    pred = pred.to(device).contiguous()
+    note("pred_dtype", str(pred.dtype).replace("torch.", ""))
+    return pred
 
 
 # ----------------------------------------------------------------------------------------
@@ -1431,7 +1437,7 @@ def np_patch_graph(pred, mask, votes, rows, P):
 
 
 def paint_patch_rows(rows, nodes, labels, instances, P):
-    """S6 (paint) from a patch table: rows float16 / float32 [K, C] (row k = pred[:, node k]),
+    """S6 (paint) from a patch table: rows float16 / bfloat16 / float32 [K, C] (row k = pred[:, node k]),
     nodes int32 [K, 3], labels int32 [K], instances int32 (Z, Y, X) in place."""
     assert rows.is_contiguous() and rows.shape[0] == nodes.shape[0]
     with _timed("paint_instances"):

@@ -112,8 +112,14 @@ int need_device() {
 }
 
 int check_dtype(int dt) {
-    if (dt != PPP_F32 && dt != PPP_F16) return fail(PPP_ERR_INVALID_ARG, "bad pred dtype %d", dt);
+    if (dt != PPP_F32 && dt != PPP_F16 && dt != PPP_BF16) return fail(PPP_ERR_INVALID_ARG, "bad pred dtype %d", dt);
     return PPP_OK;
+}
+// the entry points that write a prediction, or exist for benches and profiles only
+int check_dtype_f32_f16(int dt, const char *who) {
+    if (dt == PPP_BF16)
+        return fail(PPP_ERR_INVALID_ARG, "%s: pred dtype %d (bfloat16) is not supported here, float32 / float16 only", who, dt);
+    return check_dtype(dt);
 }
 
 }  // namespace
@@ -143,6 +149,8 @@ int ppp_device_count(void) {
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
 }
+
+int ppp_pred_dtype_supported(int dtype) { return check_dtype(dtype) == PPP_OK ? 1 : 0; }
 
 int64_t ppp_cons_planes(const ppp_params *p) {
     if (!p) return -1;
@@ -941,7 +949,7 @@ int ppp_synth_pred(const int32_t *d_labels, void *d_pred, int pred_dtype, uint32
                    void *stream) {
     ppp::Geo G;
     PPP_TRY(make_geo(p, &G));
-    PPP_TRY(check_dtype(pred_dtype));
+    PPP_TRY(check_dtype_f32_f16(pred_dtype, "ppp_synth_pred"));
     if (!d_labels || !d_pred) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
     PPP_TRY(need_device());
     hipError_t e = ppp::launch_synth(d_labels, d_pred, pred_dtype, seed, hi, lo, noise, voxel_offset, G, (hipStream_t)stream);
@@ -953,7 +961,7 @@ int ppp_synth_pred_box(const int32_t *d_labels, const int32_t *label_box, void *
                        const ppp_params *p, void *stream) {
     ppp::Geo G;
     PPP_TRY(make_geo(p, &G));
-    PPP_TRY(check_dtype(pred_dtype));
+    PPP_TRY(check_dtype_f32_f16(pred_dtype, "ppp_synth_pred_box"));
     if (!d_labels || !d_pred || !label_box || !global_dims) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
     const int lo3[3] = {G.oz, G.oy, G.ox}, ext[3] = {G.Z, G.Y, G.X}, rad[3] = {G.rz, G.ry, G.rx};
     for (int a = 0; a < 3; ++a) {
@@ -970,7 +978,7 @@ int ppp_synth_pred_box(const int32_t *d_labels, const int32_t *label_box, void *
 
 int ppp_counter_calibration(const void *d_src, int src_dtype, int64_t n_read, float *d_dst, int64_t n_write,
                             void *stream) {
-    PPP_TRY(check_dtype(src_dtype));
+    PPP_TRY(check_dtype_f32_f16(src_dtype, "ppp_counter_calibration"));
     if ((n_read > 0 && !d_src) || !d_dst || n_read < 0 || n_write < 0) return fail(PPP_ERR_INVALID_ARG, "bad argument");
     PPP_TRY(need_device());
     hipError_t e = ppp::launch_counter_calibration(d_src, src_dtype, n_read, d_dst, n_write, (hipStream_t)stream);
@@ -993,7 +1001,7 @@ int ppp_decode_tail(const float *d_x, int64_t n, int32_t fmaps, int32_t side, co
                     void *d_pred, int pred_dtype, const ppp_params *p, void *stream) {
     ppp::Geo G;
     PPP_TRY(make_geo(p, &G));
-    PPP_TRY(check_dtype(pred_dtype));
+    PPP_TRY(check_dtype_f32_f16(pred_dtype, "ppp_decode_tail"));
     if (n <= 0) return PPP_OK;
     if (!d_x || !d_w1 || !d_w2 || !d_w3 || !d_dst || !d_pred) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
     PPP_TRY(need_device());

@@ -34,12 +34,12 @@ hipError_t launch_patch_bits(const void *pred, int dtype, const uint32_t *centre
     for (uint64_t k0 = 0; k0 < n; k0 += (1ull << 24)) {
         const uint64_t m = n - k0 < (1ull << 24) ? n - k0 : (1ull << 24);
         const dim3 grid((unsigned)((m + 3) / 4));
-        if (dtype == PPP_F16)
-            patch_bits_kernel<__half><<<grid, dim3(256), 0, s>>>((const __half *)pred, centres + k0 * 3, m, thresh,
-                                                                bits + k0 * words, G);
-        else
-            patch_bits_kernel<float><<<grid, dim3(256), 0, s>>>((const float *)pred, centres + k0 * 3, m, thresh,
-                                                               bits + k0 * words, G);
+        const hipError_t e = with_pred_type(dtype, [&](auto tag) {
+            using T = PPP_PRED_T(tag);
+            patch_bits_kernel<T><<<grid, dim3(256), 0, s>>>((const T *)pred, centres + k0 * 3, m, thresh, bits + k0 * words, G);
+            return hipSuccess;
+        });
+        if (e != hipSuccess) return e;
     }
     return hipGetLastError();
 }
@@ -69,11 +69,11 @@ hipError_t launch_patch_bits_volume(const void *pred, int dtype, float thresh, u
                                     const Geo &G, hipStream_t s) {
     PPP_GRID_CHECK((G.V + 255) / 256, 256);
     const dim3 grid((unsigned)((G.V + 255) / 256));
-    if (dtype == PPP_F16)
-        patch_bits_volume_kernel<__half><<<grid, dim3(256), 0, s>>>((const __half *)pred, thresh, bits_vol, G);
-    else
-        patch_bits_volume_kernel<float><<<grid, dim3(256), 0, s>>>((const float *)pred, thresh, bits_vol, G);
-    return hipGetLastError();
+    return with_pred_type(dtype, [&](auto tag) {
+        using T = PPP_PRED_T(tag);
+        patch_bits_volume_kernel<T><<<grid, dim3(256), 0, s>>>((const T *)pred, thresh, bits_vol, G);
+        return hipGetLastError();
+    });
 }
 
 // ---- synthetic prediction (patchperpix_amd/synth.py::pred_from_labels) ------------------
@@ -106,7 +106,8 @@ __global__ void __launch_bounds__(256)
     const float u = (float)(hash_u32(ctr) >> 8) * (1.0f / 16777216.0f);
     const float val = base + noise * (2.0f * u - 1.0f);
     const __half h = __float2half_rn(val);  // through float16, like the zarr on disk
-    if constexpr (sizeof(T) == 2) pred[(long long)r * G.V + v] = h;
+    static_assert(std::is_same<T, __half>::value || std::is_same<T, float>::value, "the generator writes float16 / float32");
+    if constexpr (std::is_same<T, __half>::value) pred[(long long)r * G.V + v] = h;
     else pred[(long long)r * G.V + v] = __half2float(h);
 }
 
@@ -142,7 +143,8 @@ __global__ void __launch_bounds__(256)
     const float u = (float)(hash_u32(ctr) >> 8) * (1.0f / 16777216.0f);
     const float val = base + noise * (2.0f * u - 1.0f);
     const __half h = __float2half_rn(val);
-    if constexpr (sizeof(T) == 2) pred[(long long)r * G.V + v] = h;
+    static_assert(std::is_same<T, __half>::value || std::is_same<T, float>::value, "the generator writes float16 / float32");
+    if constexpr (std::is_same<T, __half>::value) pred[(long long)r * G.V + v] = h;
     else pred[(long long)r * G.V + v] = __half2float(h);
 }
 
@@ -152,13 +154,12 @@ hipError_t launch_synth_box(const int32_t *labels, const int *lb, void *pred, in
     const dim3 grid((unsigned)((G.V + 255) / 256), (unsigned)G.C);
     const uint32_t seed_mix = (uint32_t)(((unsigned long long)seed * 0x9E3779B1ull) & 0xFFFFFFFFull);
     const int lY = lb[4] - lb[1], lX = lb[5] - lb[2];
-    if (dtype == PPP_F16)
-        synth_box_kernel<__half><<<grid, dim3(256), 0, s>>>(labels, (__half *)pred, seed_mix, hi, lo, noise,
-                                                           lb[0], lb[1], lb[2], lY, lX, gdim[0], gdim[1], gdim[2], G);
-    else
-        synth_box_kernel<float><<<grid, dim3(256), 0, s>>>(labels, (float *)pred, seed_mix, hi, lo, noise,
-                                                          lb[0], lb[1], lb[2], lY, lX, gdim[0], gdim[1], gdim[2], G);
-    return hipGetLastError();
+    return with_f32_f16_type(dtype, [&](auto tag) {
+        using T = PPP_PRED_T(tag);
+        synth_box_kernel<T><<<grid, dim3(256), 0, s>>>(labels, (T *)pred, seed_mix, hi, lo, noise,
+                                                       lb[0], lb[1], lb[2], lY, lX, gdim[0], gdim[1], gdim[2], G);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_synth(const int32_t *labels, void *pred, int dtype, uint32_t seed, float hi,
@@ -167,11 +168,11 @@ hipError_t launch_synth(const int32_t *labels, void *pred, int dtype, uint32_t s
     PPP_GRID_CHECK((G.V + 255) / 256, 256);
     const dim3 grid((unsigned)((G.V + 255) / 256), (unsigned)G.C);
     const uint32_t seed_mix = (uint32_t)(((unsigned long long)seed * 0x9E3779B1ull) & 0xFFFFFFFFull);
-    if (dtype == PPP_F16)
-        synth_kernel<__half><<<grid, dim3(256), 0, s>>>(labels, (__half *)pred, seed_mix, hi, lo, noise, voxel_offset, G);
-    else
-        synth_kernel<float><<<grid, dim3(256), 0, s>>>(labels, (float *)pred, seed_mix, hi, lo, noise, voxel_offset, G);
-    return hipGetLastError();
+    return with_f32_f16_type(dtype, [&](auto tag) {
+        using T = PPP_PRED_T(tag);
+        synth_kernel<T><<<grid, dim3(256), 0, s>>>(labels, (T *)pred, seed_mix, hi, lo, noise, voxel_offset, G);
+        return hipGetLastError();
+    });
 }
 
 // ---- counter calibration (bench / profiles only) ---------------------------------------------
@@ -196,8 +197,12 @@ hipError_t launch_counter_calibration(const void *src, int dtype, long long n_re
                                       hipStream_t s) {
     const dim3 grid(256 * 32), block(256);
     if (n_read > 0) {
-        if (dtype == PPP_F16) calib_read_kernel<__half><<<grid, block, 0, s>>>((const __half *)src, n_read, dst);
-        else calib_read_kernel<float><<<grid, block, 0, s>>>((const float *)src, n_read, dst);
+        const hipError_t e = with_f32_f16_type(dtype, [&](auto tag) {
+            using T = PPP_PRED_T(tag);
+            calib_read_kernel<T><<<grid, block, 0, s>>>((const T *)src, n_read, dst);
+            return hipSuccess;
+        });
+        if (e != hipSuccess) return e;
     }
     if (n_write > 0) calib_write_kernel<<<grid, block, 0, s>>>(dst, n_write);
     return hipGetLastError();
@@ -215,6 +220,12 @@ template <> struct PredBits<__half> {
     static constexpr unsigned ONE = 0x3C00u;
     static __device__ __forceinline__ float val(unsigned short h) { return (float)__builtin_bit_cast(_Float16, h); }
 };
+template <> struct PredBits<bf16_t> {
+    static constexpr int PER16 = 8;
+    static __device__ __forceinline__ unsigned bits(unsigned short h) { return h; }
+    static constexpr unsigned ONE = 0x3F80u;
+    static __device__ __forceinline__ float val(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
+};
 template <typename T>
 __device__ __forceinline__ unsigned pred_check_one(float v, unsigned bits, unsigned one, float th_gt, float bg_lt) {
     return (bits > one ? 1u : 0u) | ((!(v > th_gt) && !(v < bg_lt)) ? 2u : 0u);
@@ -225,11 +236,11 @@ __global__ void __launch_bounds__(256)
                       int *__restrict__ unclean) {
     unsigned bad = 0u;
     const long long tid = blockIdx.x * (long long)blockDim.x + threadIdx.x, nth = (long long)gridDim.x * blockDim.x;
-    if constexpr (sizeof(T) == 2) {
+    if constexpr (std::is_same<T, __half>::value || std::is_same<T, bf16_t>::value) {
         // head up to the first 16-byte boundary, body as uint4, tail
         const long long head = min(n, (long long)(((16 - ((uintptr_t)src & 15)) & 15) / 2));
         const unsigned short *s16 = reinterpret_cast<const unsigned short *>(src);
-        for (long long i = tid; i < head; i += nth) bad |= pred_check_one<T>(PredBits<__half>::val(s16[i]), s16[i], 0x3C00u, th_gt, bg_lt);
+        for (long long i = tid; i < head; i += nth) bad |= pred_check_one<T>(PredBits<T>::val(s16[i]), s16[i], PredBits<T>::ONE, th_gt, bg_lt);
         const long long nv = (n - head) / 8;
         const uint4 *s128 = reinterpret_cast<const uint4 *>(s16 + head);
         for (long long i = tid; i < nv; i += nth) {
@@ -238,12 +249,13 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const unsigned short a = (unsigned short)(w[k] & 0xFFFFu), b = (unsigned short)(w[k] >> 16);
-                bad |= pred_check_one<T>(PredBits<__half>::val(a), a, 0x3C00u, th_gt, bg_lt);
-                bad |= pred_check_one<T>(PredBits<__half>::val(b), b, 0x3C00u, th_gt, bg_lt);
+                bad |= pred_check_one<T>(PredBits<T>::val(a), a, PredBits<T>::ONE, th_gt, bg_lt);
+                bad |= pred_check_one<T>(PredBits<T>::val(b), b, PredBits<T>::ONE, th_gt, bg_lt);
             }
         }
-        for (long long i = head + nv * 8 + tid; i < n; i += nth) bad |= pred_check_one<T>(PredBits<__half>::val(s16[i]), s16[i], 0x3C00u, th_gt, bg_lt);
+        for (long long i = head + nv * 8 + tid; i < n; i += nth) bad |= pred_check_one<T>(PredBits<T>::val(s16[i]), s16[i], PredBits<T>::ONE, th_gt, bg_lt);
     } else {
+        static_assert(std::is_same<T, float>::value, "pred_check_kernel: float32, float16 or bfloat16");
         const long long head = min(n, (long long)(((16 - ((uintptr_t)src & 15)) & 15) / 4));
         const unsigned *s32 = reinterpret_cast<const unsigned *>(src);
         for (long long i = tid; i < head; i += nth) bad |= pred_check_one<T>(__uint_as_float(s32[i]), s32[i], 0x3F800000u, th_gt, bg_lt);
@@ -266,9 +278,11 @@ hipError_t launch_pred_check(const void *pred, int dtype, long long n, const Geo
     hipError_t e = hipMemsetAsync(unclean, 0, sizeof(int), s);
     if (e != hipSuccess || n <= 0) return e;
     const dim3 grid(256 * 16), block(256);
-    if (dtype == PPP_F16) pred_check_kernel<__half><<<grid, block, 0, s>>>((const __half *)pred, n, G.th_gt, G.bg_lt, unclean);
-    else pred_check_kernel<float><<<grid, block, 0, s>>>((const float *)pred, n, G.th_gt, G.bg_lt, unclean);
-    return hipGetLastError();
+    return with_pred_type(dtype, [&](auto tag) {
+        using T = PPP_PRED_T(tag);
+        pred_check_kernel<T><<<grid, block, 0, s>>>((const T *)pred, n, G.th_gt, G.bg_lt, unclean);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace ppp

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/ppp_mi355x.h"
 
 namespace ppp {
@@ -73,6 +75,35 @@ static inline bool cons_box_covers(const Geo &G, const ppp_box &sb) {
            G.bz0 + G.bZ >= hi(sb.z1, G.rz, G.Z) && G.by0 + G.bY >= hi(sb.y1, G.ry, G.Y) && G.bx0 + G.bX >= hi(sb.x1, G.rx, G.X);
 }
 
+// bfloat16 element (PPP_BF16): the 16 raw bits and NOTHING else -- no conversion operator, no
+// arithmetic.  A site that was not taught the type fails to compile instead of reading wrong bits.
+// Its float32 value is the bits shifted up by 16 (exact), so everything downstream of a load works
+// on the same float the float32 tensor of these values holds.
+struct bf16_t {
+    unsigned short bits;
+};
+static_assert(sizeof(bf16_t) == 2 && alignof(bf16_t) == 2, "bf16_t is a bare 16-bit element");
+
+// The ONE place a ppp_dtype code becomes an element type: f is a generic callable taking PredType<T>.
+// There is no default branch -- a code that is none of the three is an error, never "float".
+template <typename T> struct PredType { using type = T; };
+template <typename F>
+static inline hipError_t with_pred_type(int dtype, F &&f) {
+    if (dtype == PPP_F32) return f(PredType<float>{});
+    if (dtype == PPP_F16) return f(PredType<__half>{});
+    if (dtype == PPP_BF16) return f(PredType<bf16_t>{});
+    return hipErrorInvalidValue;
+}
+// The kernels that WRITE a prediction (synthetic generator, decoder tail) and the ones built for
+// benches and profiles only have float32 / float16 forms; bfloat16 is refused, not mapped.
+template <typename F>
+static inline hipError_t with_f32_f16_type(int dtype, F &&f) {
+    if (dtype == PPP_F32) return f(PredType<float>{});
+    if (dtype == PPP_F16) return f(PredType<__half>{});
+    return hipErrorInvalidValue;
+}
+#define PPP_PRED_T(tag) typename decltype(tag)::type
+
 template <typename T>
 __device__ __forceinline__ float ldf(const T *p, long long i);
 template <>
@@ -82,6 +113,10 @@ __device__ __forceinline__ float ldf<float>(const float *p, long long i) {
 template <>
 __device__ __forceinline__ float ldf<__half>(const __half *p, long long i) {
     return __half2float(p[i]);
+}
+template <>
+__device__ __forceinline__ float ldf<bf16_t>(const bf16_t *p, long long i) {
+    return __uint_as_float((unsigned)p[i].bits << 16);
 }
 
 __device__ __forceinline__ long long vox(const Geo &G, int z, int y, int x) {

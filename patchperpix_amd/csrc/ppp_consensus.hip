@@ -139,10 +139,14 @@ hipError_t launch_consensus(const void *pred, int dtype, const uint8_t *ov, floa
         }
     }
     g_s1_kernel = "consensus_gather_kernel";
-    if (dtype == PPP_F16)
-        consensus_gather_kernel<__half><<<grid, block, 0, s>>>((const __half *)pred, ov, cons, cnt, G);
-    else
-        consensus_gather_kernel<float><<<grid, block, 0, s>>>((const float *)pred, ov, cons, cnt, G);
+    {
+        const hipError_t e_ = with_pred_type(dtype, [&](auto tag) {
+            using T = PPP_PRED_T(tag);
+            consensus_gather_kernel<T><<<grid, block, 0, s>>>((const T *)pred, ov, cons, cnt, G);
+            return hipSuccess;
+        });
+        if (e_ != hipSuccess) return e_;
+    }
     return hipGetLastError();
 }
 

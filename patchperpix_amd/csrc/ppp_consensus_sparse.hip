@@ -168,12 +168,14 @@ hipError_t run_consensus_sparse(const void *pred, int dtype, const uint8_t *ov, 
     PPP_GRID_CHECK((n_words + 3) / 4, 256);
     PPP_GRID_CHECK((I.n_items + 255) / 256, 256);
     const dim3 bgrid((unsigned)((n_words + 3) / 4)), block(256);
-    if (dtype == PPP_F16)
-        valid_bits_kernel<__half><<<bgrid, block, 0, s>>>((const __half *)pred + (long long)G.mid * G.V, ov, W.bits, G,
-                                                          wpl, z_lo, n_words);
-    else
-        valid_bits_kernel<float><<<bgrid, block, 0, s>>>((const float *)pred + (long long)G.mid * G.V, ov, W.bits, G,
-                                                         wpl, z_lo, n_words);
+    {
+        const hipError_t e_ = with_pred_type(dtype, [&](auto tag) {
+            using T = PPP_PRED_T(tag);
+            valid_bits_kernel<T><<<bgrid, block, 0, s>>>((const T *)pred + (long long)G.mid * G.V, ov, W.bits, G, wpl, z_lo, n_words);
+            return hipSuccess;
+        });
+        if (e_ != hipSuccess) return e_;
+    }
     const dim3 igrid((unsigned)((I.n_items + 255) / 256));
     if (I.flat)
         item_flags_kernel<true><<<igrid, block, 0, s>>>(W.bits, W.flags, G, wpl, I.n_rows, I.runs_per_line, I.n_items);

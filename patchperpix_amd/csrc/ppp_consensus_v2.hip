@@ -639,9 +639,10 @@ hipError_t launch_consensus_v2(const void *pred, int dtype, const uint8_t *ov, f
                                float *cnt, const Geo &G, hipStream_t s) {
 #define PPP_V2_CASE(P)                                                                          \
     case P:                                                                                     \
-        return dtype == PPP_F16                                                                 \
-                   ? launch_v2<__half, P>((const __half *)pred, ov, cons, cnt, G, s)            \
-                   : launch_v2<float, P>((const float *)pred, ov, cons, cnt, G, s);
+        return with_pred_type(dtype, [&](auto tag) {                                            \
+            using T = PPP_PRED_T(tag);                                                          \
+            return launch_v2<T, P>((const T *)pred, ov, cons, cnt, G, s);                       \
+        });
     switch (G.px) {
         PPP_V2_CASE(3)
         PPP_V2_CASE(5)
@@ -651,8 +652,10 @@ hipError_t launch_consensus_v2(const void *pred, int dtype, const uint8_t *ov, f
         // (2-d patches only: a 25-wide 3-d patch has 15 625 channels)
         static EnvSwitch wide("PPP_S1_WIDE");
         if (G.pz != 1 || (wide.get() && wide.get()[0] == '0')) return hipErrorNotSupported;
-        return dtype == PPP_F16 ? launch_wide<__half, 25>((const __half *)pred, ov, cons, cnt, G, s)
-                                : launch_wide<float, 25>((const float *)pred, ov, cons, cnt, G, s);
+        return with_pred_type(dtype, [&](auto tag) {
+            using T = PPP_PRED_T(tag);
+            return launch_wide<T, 25>((const T *)pred, ov, cons, cnt, G, s);
+        });
     default:
         return hipErrorNotSupported;
     }

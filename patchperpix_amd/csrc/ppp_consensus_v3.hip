@@ -281,6 +281,10 @@ template <>
 __device__ __forceinline__ unsigned buf_ldraw<__half>(BufRsrc r, unsigned voff, unsigned soff) {
     return (unsigned)__builtin_amdgcn_raw_buffer_load_b16(r, (int)voff, (int)soff, 0);
 }
+template <>
+__device__ __forceinline__ unsigned buf_ldraw<bf16_t>(BufRsrc r, unsigned voff, unsigned soff) {
+    return (unsigned)__builtin_amdgcn_raw_buffer_load_b16(r, (int)voff, (int)soff, 0);
+}
 // (experiment switch PPP_S1V3_BUFLOAD=0: the same bits by global loads, saddr + 32-bit voffset)
 template <typename T>
 __device__ __forceinline__ unsigned glb_ldraw(const T *base, unsigned voff, unsigned soff);
@@ -299,6 +303,11 @@ __device__ __forceinline__ unsigned glb_ldraw<__half>(const __half *base, unsign
     asm volatile("" : "+v"(voff));
     return (unsigned)*reinterpret_cast<const unsigned short *>(reinterpret_cast<const char *>(base) + soff + voff);
 }
+template <>
+__device__ __forceinline__ unsigned glb_ldraw<bf16_t>(const bf16_t *base, unsigned voff, unsigned soff) {
+    asm volatile("" : "+v"(voff));
+    return (unsigned)*reinterpret_cast<const unsigned short *>(reinterpret_cast<const char *>(base) + soff + voff);
+}
 template <typename T>
 __device__ __forceinline__ float widen(unsigned raw);
 template <>
@@ -307,6 +316,9 @@ template <>
 __device__ __forceinline__ float widen<__half>(unsigned raw) {
     return (float)__builtin_bit_cast(_Float16, (unsigned short)raw);
 }
+// bfloat16: the 16 bits are the float's upper half (the load zero-extends, so one shift; exact)
+template <>
+__device__ __forceinline__ float widen<bf16_t>(unsigned raw) { return __uint_as_float(raw << 16); }
 
 template <typename T>
 __device__ __forceinline__ float ldf_at3(const T *base, unsigned byte_off) {
@@ -951,9 +963,10 @@ hipError_t launch_consensus_v3(const void *pred, int dtype, const uint8_t *ov, f
     if (G.layout == PPP_CONS_VOXEL_MAJOR && (cnt || !cons)) return hipErrorInvalidValue;
 #define PPP_V3_CASE(P)                                                                          \
     case P:                                                                                     \
-        return dtype == PPP_F16                                                                 \
-                   ? launch_v3<__half, P>((const __half *)pred, ov, cons, cnt, G, s)            \
-                   : launch_v3<float, P>((const float *)pred, ov, cons, cnt, G, s);
+        return with_pred_type(dtype, [&](auto tag) {                                            \
+            using T = PPP_PRED_T(tag);                                                          \
+            return launch_v3<T, P>((const T *)pred, ov, cons, cnt, G, s);                       \
+        });
     switch (G.px) {
         PPP_V3_CASE(3)
         PPP_V3_CASE(5)
@@ -973,10 +986,11 @@ hipError_t launch_consensus_v3_lists(const void *pred, int dtype, const uint8_t 
     if (G.layout == PPP_CONS_VOXEL_MAJOR && (cnt || !cons)) return hipErrorInvalidValue;
 #define PPP_V3_CASE(P)                                                                                       \
     case P:                                                                                                  \
-        return dtype == PPP_F16 ? launch_v3_lists<__half, P>((const __half *)pred, ov, cons, cnt, G, active, \
-                                                             n_active, inactive, n_inactive, s)              \
-                                : launch_v3_lists<float, P>((const float *)pred, ov, cons, cnt, G, active,   \
-                                                            n_active, inactive, n_inactive, s);
+        return with_pred_type(dtype, [&](auto tag) {                                                         \
+            using T = PPP_PRED_T(tag);                                                                       \
+            return launch_v3_lists<T, P>((const T *)pred, ov, cons, cnt, G, active, n_active, inactive,      \
+                                         n_inactive, s);                                                     \
+        });
     switch (G.px) {
         PPP_V3_CASE(3)
         PPP_V3_CASE(5)

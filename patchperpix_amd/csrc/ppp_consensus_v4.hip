@@ -612,8 +612,10 @@ hipError_t launch_consensus_v4(const void *pred, int dtype, const uint8_t *ov, f
     }
 #define PPP_V4_CASE(P)                                                                          \
     case P:                                                                                     \
-        return dtype == PPP_F16 ? s1v4::launch_v4<__half, P>((const __half *)pred, ov, cons, cnt, G, s) \
-                                : s1v4::launch_v4<float, P>((const float *)pred, ov, cons, cnt, G, s);
+        return with_f32_f16_type(dtype, [&](auto tag) {  /* (no bfloat16 form of the experiment: refused) */ \
+            using T = PPP_PRED_T(tag);                                                          \
+            return s1v4::launch_v4<T, P>((const T *)pred, ov, cons, cnt, G, s);                 \
+        });
     switch (G.px) {
         PPP_V4_CASE(5)
         PPP_V4_CASE(7)

@@ -149,7 +149,7 @@ __global__ void __launch_bounds__(64 * DT_WAVES)
     for (int r = wave; r < C; r += DT_WAVES) {
         if (ok) {
             const __half hv = tile[r][lane];
-            if constexpr (sizeof(T) == 2) pred[(long long)r * V + d] = hv;
+            if constexpr (std::is_same<T, __half>::value) pred[(long long)r * V + d] = hv;
             else pred[(long long)r * V + d] = __half2float(hv);
         }
     }
@@ -164,19 +164,15 @@ hipError_t launch_decode_tail(const float *X, long long B, int F, int S, const f
     PPP_GRID_CHECK(groups, 64 * DT_WAVES);
     const size_t lds = (size_t)(DT_F * 32 + DT_WAVES * DT_NV * DT_ZS + 2 * DT_WAVES * DT_NO + 2 * 27 + 2) * 4 +
                        (size_t)343 * DT_GROUP * 2;
-    hipError_t e;
-    if (dtype == PPP_F16) {
-        if ((e = hipFuncSetAttribute((const void *)decode_tail_kernel<__half, 7>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
-        decode_tail_kernel<__half, 7><<<dim3((unsigned)groups), dim3(64 * DT_WAVES), lds, s>>>(
-            X, B, W1, b1, W2, b2, W3, b3, dst, (__half *)pred, G.V);
-    } else {
-        if ((e = hipFuncSetAttribute((const void *)decode_tail_kernel<float, 7>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
-        decode_tail_kernel<float, 7><<<dim3((unsigned)groups), dim3(64 * DT_WAVES), lds, s>>>(
-            X, B, W1, b1, W2, b2, W3, b3, dst, (float *)pred, G.V);
-    }
-    return hipGetLastError();
+    return with_f32_f16_type(dtype, [&](auto tag) {
+        using T = PPP_PRED_T(tag);
+        const hipError_t e = hipFuncSetAttribute((const void *)decode_tail_kernel<T, 7>,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        decode_tail_kernel<T, 7><<<dim3((unsigned)groups), dim3(64 * DT_WAVES), lds, s>>>(
+            X, B, W1, b1, W2, b2, W3, b3, dst, (T *)pred, G.V);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace ppp

@@ -266,10 +266,14 @@ hipError_t launch_paint_rows(const void *rows, int dtype, const uint32_t *nodes,
     for (uint64_t k0 = 0; k0 < n; k0 += per) {
         const uint64_t m = n - k0 < per ? n - k0 : per;
         const dim3 grid((unsigned)((m * (uint64_t)G.C + 255) / 256));
-        if (dtype == PPP_F16)
-            paint_rows_kernel<__half><<<grid, dim3(256), 0, s>>>((const __half *)rows + k0 * G.C, nodes + k0 * 3, labels + k0, m, inst, G.th_rn, G);
-        else
-            paint_rows_kernel<float><<<grid, dim3(256), 0, s>>>((const float *)rows + k0 * G.C, nodes + k0 * 3, labels + k0, m, inst, G.th_rn, G);
+        {
+            const hipError_t e_ = with_pred_type(dtype, [&](auto tag) {
+                using T = PPP_PRED_T(tag);
+                paint_rows_kernel<T><<<grid, dim3(256), 0, s>>>((const T *)rows + k0 * G.C, nodes + k0 * 3, labels + k0, m, inst, G.th_rn, G);
+                return hipSuccess;
+            });
+            if (e_ != hipSuccess) return e_;
+        }
     }
     return hipGetLastError();
 }
@@ -284,10 +288,14 @@ hipError_t launch_paint(const void *pred, int dtype, const uint32_t *nodes,
         const uint64_t m = n - k0 < per ? n - k0 : per;
         const uint64_t total = m * (uint64_t)G.C;
         const dim3 grid((unsigned)((total + 255) / 256));
-        if (dtype == PPP_F16)
-            paint_kernel<__half><<<grid, dim3(256), 0, s>>>((const __half *)pred, nodes + k0 * 3, labels + k0, m, inst, G.th_rn, G);
-        else
-            paint_kernel<float><<<grid, dim3(256), 0, s>>>((const float *)pred, nodes + k0 * 3, labels + k0, m, inst, G.th_rn, G);
+        {
+            const hipError_t e_ = with_pred_type(dtype, [&](auto tag) {
+                using T = PPP_PRED_T(tag);
+                paint_kernel<T><<<grid, dim3(256), 0, s>>>((const T *)pred, nodes + k0 * 3, labels + k0, m, inst, G.th_rn, G);
+                return hipSuccess;
+            });
+            if (e_ != hipSuccess) return e_;
+        }
     }
     return hipGetLastError();
 }

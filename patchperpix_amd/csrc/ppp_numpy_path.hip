@@ -191,8 +191,14 @@ hipError_t launch_np_consensus(const void *pred, int dtype, const uint8_t *fg, i
     const long long total = (long long)(g.n_planes + 1) * g.V;
     PPP_GRID_CHECK((total + 255) / 256, 256);
     const dim3 grid((unsigned)((total + 255) / 256));
-    if (dtype == PPP_F16) np_consensus_kernel<__half><<<grid, dim3(256), 0, s>>>((const __half *)pred, fg, cons, g);
-    else np_consensus_kernel<float><<<grid, dim3(256), 0, s>>>((const float *)pred, fg, cons, g);
+    {
+        const hipError_t e_ = with_pred_type(dtype, [&](auto tag) {
+            using T = PPP_PRED_T(tag);
+            np_consensus_kernel<T><<<grid, dim3(256), 0, s>>>((const T *)pred, fg, cons, g);
+            return hipSuccess;
+        });
+        if (e_ != hipSuccess) return e_;
+    }
     return hipGetLastError();
 }
 
@@ -202,8 +208,14 @@ hipError_t launch_np_rank(const void *pred, int dtype, const uint8_t *fg, const 
     PPP_GRID_CHECK(g.V, 64);
     const dim3 grid((unsigned)g.V);
     const size_t lds = (size_t)g.C;
-    if (dtype == PPP_F16) np_rank_kernel<__half><<<grid, dim3(64), lds, s>>>((const __half *)pred, fg, cons, score, g);
-    else np_rank_kernel<float><<<grid, dim3(64), lds, s>>>((const float *)pred, fg, cons, score, g);
+    {
+        const hipError_t e_ = with_pred_type(dtype, [&](auto tag) {
+            using T = PPP_PRED_T(tag);
+            np_rank_kernel<T><<<grid, dim3(64), lds, s>>>((const T *)pred, fg, cons, score, g);
+            return hipSuccess;
+        });
+        if (e_ != hipSuccess) return e_;
+    }
     return hipGetLastError();
 }
 
@@ -215,10 +227,14 @@ hipError_t launch_np_graph(const void *pred, int dtype, const uint8_t *mask, con
     PPP_GRID_CHECK(n, 64);
     const dim3 grid((unsigned)n);
     const size_t lds = 2 * (size_t)g.C;
-    if (dtype == PPP_F16)
-        np_graph_kernel<__half><<<grid, dim3(64), lds, s>>>((const __half *)pred, mask, cons, rows, weight, count, g);
-    else
-        np_graph_kernel<float><<<grid, dim3(64), lds, s>>>((const float *)pred, mask, cons, rows, weight, count, g);
+    {
+        const hipError_t e_ = with_pred_type(dtype, [&](auto tag) {
+            using T = PPP_PRED_T(tag);
+            np_graph_kernel<T><<<grid, dim3(64), lds, s>>>((const T *)pred, mask, cons, rows, weight, count, g);
+            return hipSuccess;
+        });
+        if (e_ != hipSuccess) return e_;
+    }
     return hipGetLastError();
 }
 

@@ -243,10 +243,14 @@ hipError_t run_pack_scan_count(const void *pred, int dtype, const uint32_t *node
     for (uint64_t k0 = 0; k0 < n_nodes; k0 += per) {
         const uint64_t m = n_nodes - k0 < per ? n_nodes - k0 : per;
         const dim3 grid((unsigned)((m * (uint64_t)G.C + 255) / 256));
-        if (dtype == PPP_F16)
-            flag_kernel<__half><<<grid, dim3(256), 0, s>>>((const __half *)pred, nodes + k0 * 3, labels + k0, m, W.L1, W.flag, G.th_rn, G);
-        else
-            flag_kernel<float><<<grid, dim3(256), 0, s>>>((const float *)pred, nodes + k0 * 3, labels + k0, m, W.L1, W.flag, G.th_rn, G);
+        {
+            const hipError_t e_ = with_pred_type(dtype, [&](auto tag) {
+                using T = PPP_PRED_T(tag);
+                flag_kernel<T><<<grid, dim3(256), 0, s>>>((const T *)pred, nodes + k0 * 3, labels + k0, m, W.L1, W.flag, G.th_rn, G);
+                return hipSuccess;
+            });
+            if (e_ != hipSuccess) return e_;
+        }
     }
     PPP_GRID_CHECK((n_own + 255) / 256, 256);
     sweep_kernel<<<dim3((unsigned)((n_own + 255) / 256)), dim3(256), 0, s>>>(W.L1, W.flag, own, n_own, n_labels, sizes, W.list,
@@ -257,12 +261,14 @@ hipError_t run_pack_scan_count(const void *pred, int dtype, const uint32_t *node
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
     if ((long long)n_list > W.cap) return hipErrorInvalidValue;       // (cannot happen: a voxel is listed once)
     if (n_list == 0) return hipSuccess;
-    if (dtype == PPP_F16)
-        peel_kernel<__half, false><<<dim3(wave_blocks((long long)n_list)), dim3(256), 0, s>>>(
-            (const __half *)pred, W.Lc, W.L1, W.list, (long long)n_list, n_labels, sizes, W.cnt, nullptr, nullptr, 0, G.th_rn, G);
-    else
-        peel_kernel<float, false><<<dim3(wave_blocks((long long)n_list)), dim3(256), 0, s>>>(
-            (const float *)pred, W.Lc, W.L1, W.list, (long long)n_list, n_labels, sizes, W.cnt, nullptr, nullptr, 0, G.th_rn, G);
+    {
+        const hipError_t e_ = with_pred_type(dtype, [&](auto tag) {
+            using T = PPP_PRED_T(tag);
+            peel_kernel<T, false><<<dim3(wave_blocks((long long)n_list)), dim3(256), 0, s>>>( (const T *)pred, W.Lc, W.L1, W.list, (long long)n_list, n_labels, sizes, W.cnt, nullptr, nullptr, 0, G.th_rn, G);
+            return hipSuccess;
+        });
+        if (e_ != hipSuccess) return e_;
+    }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if ((e = hipMemsetAsync(W.cnt + n_list, 0, 8, s)) != hipSuccess) return e;
     size_t tb = W.temp_bytes;
@@ -290,12 +296,14 @@ hipError_t run_pack_scan_fill(const void *pred, int dtype, const ppp_box &own, u
     if ((e = hipMemcpyAsync(&total, W.off + n_list, 8, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
     if (total != n_pairs) return hipErrorInvalidValue;               // not the workspace of the count
-    if (dtype == PPP_F16)
-        peel_kernel<__half, true><<<dim3(wave_blocks((long long)n_list)), dim3(256), 0, s>>>(
-            (const __half *)pred, W.Lc, W.L1, W.list, (long long)n_list, 0u, nullptr, nullptr, W.off, pairs, n_pairs, G.th_rn, G);
-    else
-        peel_kernel<float, true><<<dim3(wave_blocks((long long)n_list)), dim3(256), 0, s>>>(
-            (const float *)pred, W.Lc, W.L1, W.list, (long long)n_list, 0u, nullptr, nullptr, W.off, pairs, n_pairs, G.th_rn, G);
+    {
+        const hipError_t e_ = with_pred_type(dtype, [&](auto tag) {
+            using T = PPP_PRED_T(tag);
+            peel_kernel<T, true><<<dim3(wave_blocks((long long)n_list)), dim3(256), 0, s>>>( (const T *)pred, W.Lc, W.L1, W.list, (long long)n_list, 0u, nullptr, nullptr, W.off, pairs, n_pairs, G.th_rn, G);
+            return hipSuccess;
+        });
+        if (e_ != hipSuccess) return e_;
+    }
     return hipGetLastError();
 }
 
@@ -332,12 +340,14 @@ hipError_t launch_paint_channels(const void *pred, int dtype, const uint32_t *no
     for (uint64_t k0 = 0; k0 < n; k0 += per) {
         const uint64_t m = n - k0 < per ? n - k0 : per;
         const dim3 grid((unsigned)((m * (uint64_t)G.C + 255) / 256));
-        if (dtype == PPP_F16)
-            paint_channels_kernel<__half><<<grid, dim3(256), 0, s>>>((const __half *)pred, nodes + k0 * 3, labels + k0, m, chan,
-                                                                     n_labels, n_channels, out, G.th_rn, G);
-        else
-            paint_channels_kernel<float><<<grid, dim3(256), 0, s>>>((const float *)pred, nodes + k0 * 3, labels + k0, m, chan,
-                                                                    n_labels, n_channels, out, G.th_rn, G);
+        {
+            const hipError_t e_ = with_pred_type(dtype, [&](auto tag) {
+                using T = PPP_PRED_T(tag);
+                paint_channels_kernel<T><<<grid, dim3(256), 0, s>>>((const T *)pred, nodes + k0 * 3, labels + k0, m, chan, n_labels, n_channels, out, G.th_rn, G);
+                return hipSuccess;
+            });
+            if (e_ != hipSuccess) return e_;
+        }
     }
     return hipGetLastError();
 }

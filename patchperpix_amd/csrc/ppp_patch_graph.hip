@@ -440,13 +440,12 @@ hipError_t launch_patch_graph(const void *pred, int dtype, const float *cons,
         (G.px == 3 || G.px == 5 || G.px == 7 || G.px == 9)) {
 #define PPP_PG_CASE(P)                                                                                          \
     case P:                                                                                                     \
-        if (dtype == PPP_F16)                                                                                   \
-            patch_graph_vm2_kernel<__half, P><<<grid, dim3(64 * PG_WAVES), lds_bytes, s>>>(                     \
-                (const __half *)pred, cons, pairs, order, n, aff, G);                                           \
-        else                                                                                                    \
-            patch_graph_vm2_kernel<float, P><<<grid, dim3(64 * PG_WAVES), lds_bytes, s>>>(                      \
-                (const float *)pred, cons, pairs, order, n, aff, G);                                            \
-        return hipGetLastError();
+        return with_pred_type(dtype, [&](auto tag) {                                                            \
+            using T = PPP_PRED_T(tag);                                                                          \
+            patch_graph_vm2_kernel<T, P><<<grid, dim3(64 * PG_WAVES), lds_bytes, s>>>(                          \
+                (const T *)pred, cons, pairs, order, n, aff, G);                                                \
+            return hipGetLastError();                                                                           \
+        });
         switch (G.px) {
             PPP_PG_CASE(3)
             PPP_PG_CASE(5)
@@ -456,16 +455,24 @@ hipError_t launch_patch_graph(const void *pred, int dtype, const float *cons,
 #undef PPP_PG_CASE
     }
     if (G.layout == PPP_CONS_VOXEL_MAJOR) {
-        if (dtype == PPP_F16)
-            patch_graph_vm_kernel<__half><<<grid, dim3(64 * PG_WAVES), lds_bytes, s>>>((const __half *)pred, cons, pairs, order, n, aff, G);
-        else
-            patch_graph_vm_kernel<float><<<grid, dim3(64 * PG_WAVES), lds_bytes, s>>>((const float *)pred, cons, pairs, order, n, aff, G);
+        {
+            const hipError_t e_ = with_pred_type(dtype, [&](auto tag) {
+                using T = PPP_PRED_T(tag);
+                patch_graph_vm_kernel<T><<<grid, dim3(64 * PG_WAVES), lds_bytes, s>>>((const T *)pred, cons, pairs, order, n, aff, G);
+                return hipSuccess;
+            });
+            if (e_ != hipSuccess) return e_;
+        }
         return hipGetLastError();
     }
-    if (dtype == PPP_F16)
-        patch_graph_kernel<__half><<<grid, dim3(64 * PG_WAVES), lds_bytes, s>>>((const __half *)pred, cons, pairs, order, n, aff, G);
-    else
-        patch_graph_kernel<float><<<grid, dim3(64 * PG_WAVES), lds_bytes, s>>>((const float *)pred, cons, pairs, order, n, aff, G);
+    {
+        const hipError_t e_ = with_pred_type(dtype, [&](auto tag) {
+            using T = PPP_PRED_T(tag);
+            patch_graph_kernel<T><<<grid, dim3(64 * PG_WAVES), lds_bytes, s>>>((const T *)pred, cons, pairs, order, n, aff, G);
+            return hipSuccess;
+        });
+        if (e_ != hipSuccess) return e_;
+    }
     return hipGetLastError();
 }
 

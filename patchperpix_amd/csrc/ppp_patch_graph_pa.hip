@@ -1037,8 +1037,10 @@ hipError_t launch_patch_graph_lcg(const void *pred, int dtype, const uint32_t *r
         return hipErrorNotSupported;
 #define PPP_LCG_CASE(P)                                                                                  \
     case P:                                                                                              \
-        return dtype == PPP_F16 ? launch_lcg<__half, P>((const __half *)pred, rows, order, lcg_pos, n, drop_off, drops, G, s) \
-                                : launch_lcg<float, P>((const float *)pred, rows, order, lcg_pos, n, drop_off, drops, G, s);
+        return with_pred_type(dtype, [&](auto tag) {                                                     \
+            using T = PPP_PRED_T(tag);                                                                   \
+            return launch_lcg<T, P>((const T *)pred, rows, order, lcg_pos, n, drop_off, drops, G, s);    \
+        });
     switch (G.px) {
         PPP_LCG_CASE(3)
         PPP_LCG_CASE(5)
@@ -1115,10 +1117,14 @@ hipError_t launch_patch_fg_bits(const void *pred, int dtype, const long long *ce
                                 uint32_t *table, const Geo &G, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     if (n >= (1ll << 31) || grid_too_big((unsigned long long)n, 64)) return hipErrorNotSupported;
-    if (dtype == PPP_F16)
-        patch_fg_bits_kernel<__half><<<dim3((unsigned)n), dim3(64), 0, s>>>((const __half *)pred, centres, n, table, G);
-    else
-        patch_fg_bits_kernel<float><<<dim3((unsigned)n), dim3(64), 0, s>>>((const float *)pred, centres, n, table, G);
+    {
+        const hipError_t e_ = with_pred_type(dtype, [&](auto tag) {
+            using T = PPP_PRED_T(tag);
+            patch_fg_bits_kernel<T><<<dim3((unsigned)n), dim3(64), 0, s>>>((const T *)pred, centres, n, table, G);
+            return hipSuccess;
+        });
+        if (e_ != hipSuccess) return e_;
+    }
     return hipGetLastError();
 }
 
@@ -1148,11 +1154,11 @@ hipError_t launch_patch_graph_pa(const void *pred, int dtype, const float *S, co
         return hipErrorNotSupported;
 #define PPP_PA_CASE(P)                                                                                  \
     case P:                                                                                             \
-        if (dtype == PPP_F16)                                                                           \
-            return small ? launch_pa<__half, P, PaCfg<P>::THREADS_SMALL>((const __half *)pred, S, rows, order, group_start, chunk_offsets, n_groups, n_blocks, aff, drop_off, drops, bits_centres, n_bits, bits, G, lds, s) \
-                         : launch_pa<__half, P, PaCfg<P>::THREADS>((const __half *)pred, S, rows, order, group_start, chunk_offsets, n_groups, n_blocks, aff, drop_off, drops, bits_centres, n_bits, bits, G, lds, s); \
-        return small ? launch_pa<float, P, PaCfg<P>::THREADS_SMALL>((const float *)pred, S, rows, order, group_start, chunk_offsets, n_groups, n_blocks, aff, drop_off, drops, bits_centres, n_bits, bits, G, lds, s) \
-                     : launch_pa<float, P, PaCfg<P>::THREADS>((const float *)pred, S, rows, order, group_start, chunk_offsets, n_groups, n_blocks, aff, drop_off, drops, bits_centres, n_bits, bits, G, lds, s);
+        return with_pred_type(dtype, [&](auto tag) {                                                    \
+            using T = PPP_PRED_T(tag);                                                                  \
+            return small ? launch_pa<T, P, PaCfg<P>::THREADS_SMALL>((const T *)pred, S, rows, order, group_start, chunk_offsets, n_groups, n_blocks, aff, drop_off, drops, bits_centres, n_bits, bits, G, lds, s) \
+                         : launch_pa<T, P, PaCfg<P>::THREADS>((const T *)pred, S, rows, order, group_start, chunk_offsets, n_groups, n_blocks, aff, drop_off, drops, bits_centres, n_bits, bits, G, lds, s); \
+        });
     switch (G.px) {
         PPP_PA_CASE(3)
         PPP_PA_CASE(5)

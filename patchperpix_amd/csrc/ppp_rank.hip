@@ -90,10 +90,14 @@ hipError_t launch_rank(const void *pred, int dtype, const float *cons, const uin
     }
     PPP_GRID_CHECK((n + 255) / 256, 256);
     const dim3 grid((unsigned)((n + 255) / 256));
-    if (dtype == PPP_F16)
-        rank_kernel<__half><<<grid, dim3(256), 0, s>>>((const __half *)pred, cons, ov, score, sb, G);
-    else
-        rank_kernel<float><<<grid, dim3(256), 0, s>>>((const float *)pred, cons, ov, score, sb, G);
+    {
+        const hipError_t e_ = with_pred_type(dtype, [&](auto tag) {
+            using T = PPP_PRED_T(tag);
+            rank_kernel<T><<<grid, dim3(256), 0, s>>>((const T *)pred, cons, ov, score, sb, G);
+            return hipSuccess;
+        });
+        if (e_ != hipSuccess) return e_;
+    }
     return hipGetLastError();
 }
 

@@ -227,8 +227,10 @@ hipError_t launch_rank_v2(const void *pred, int dtype, const float *cons, const 
                           float *score, const ppp_box &sb, const Geo &G, hipStream_t s) {
 #define PPP_R2_CASE(P)                                                                          \
     case P:                                                                                     \
-        return dtype == PPP_F16 ? launch_r2<__half, P>((const __half *)pred, cons, ov, score, sb, G, s) \
-                                : launch_r2<float, P>((const float *)pred, cons, ov, score, sb, G, s);
+        return with_pred_type(dtype, [&](auto tag) {                                            \
+            using T = PPP_PRED_T(tag);                                                          \
+            return launch_r2<T, P>((const T *)pred, cons, ov, score, sb, G, s);                 \
+        });
     switch (G.px) {
         PPP_R2_CASE(3)
         PPP_R2_CASE(5)

@@ -1077,8 +1077,10 @@ static hipError_t launch_rwg(const T *pred, const float *S, const uint8_t *ov, f
 hipError_t launch_rank_wg(const void *pred, int dtype, const float *S, const uint8_t *ov, float *score,
                           const ppp_box &sb, void *work, const Geo &G, hipStream_t s) {
     if (!rank_wg_supported(G)) return hipErrorNotSupported;
-    return dtype == PPP_F16 ? launch_rwg<__half>((const __half *)pred, S, ov, score, sb, work, G, s)
-                            : launch_rwg<float>((const float *)pred, S, ov, score, sb, work, G, s);
+    return with_pred_type(dtype, [&](auto tag) {
+        using T = PPP_PRED_T(tag);
+        return launch_rwg<T>((const T *)pred, S, ov, score, sb, work, G, s);
+    });
 }
 
 }  // namespace ppp

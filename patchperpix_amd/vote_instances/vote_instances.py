@@ -139,6 +139,7 @@ def _to_instance_seg(pred_affs, foreground, mask_to_cover, numinst, patchshape, 
     """vote_instances.py:150-452.
 
     pred_affs     (C,Z,Y,X) float32/float16 ndarray, or an already-resident device tensor
+                  (float32, float16 or bfloat16: read as it is, never widened in memory)
     foreground    (Z,Y,X) bool       mask_to_cover (Z,Y,X) bool, modified in place (:226)
     numinst       (Z,Y,X) integer    patchshape    int[3]
     (the three fields may also be device tensors, resident like the prediction)

@@ -1,10 +1,14 @@
 """Time the scoring kernel S1 alone (kernel experiments; not the benchmark).
 
-    python tools/time_s1.py [--case 140p7|slab9|...] [--reps N]
+    python tools/time_s1.py [--case 140p7|slab9|...] [--reps N] [--dtype f16|bf16|f16,bf16]
 
 Cases: 140p7 = the whole 140^3 / 7^3 benchmark volume; slab9 = 16 slices of base voxels of a
 (48, 512, 512) / 9^3 volume (the slab shape of the north-star pass); slab7 likewise at 7^3.
-PPP_LIB / PPP_S1_* select library and kernel variants.  Prints one JSON line."""
+PPP_LIB / PPP_S1_* select library and kernel variants.  Prints one JSON line.
+--dtype: the element type of the prediction; bf16 = the float16 case rounded once to bfloat16 (other
+values than the float16 run votes on: a timing, not a comparison of results).  Several types, comma
+separated, are timed INTERLEAVED in one process (repeat r of every type before repeat r + 1), the
+line then carries ms / min_ms / checksum per type."""
 import argparse
 import json
 import os
@@ -27,6 +31,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", default="140p7")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--dtype", default="f16")
     args = ap.parse_args()
     import torch
     import bench
@@ -38,23 +43,39 @@ def main():
     pred = backend.synth_pred(labels, P, seed=0, f16=True)
     ov = torch.zeros(shape, dtype=torch.uint8, device="cuda")
     Pb = backend.make_params(shape, ps, cons_box=box, **kw)
-    times = []
-    crc = None
+    dtypes = args.dtype.split(",")
+    preds = {}
+    for d in dtypes:
+        if d not in ("f16", "bf16"):
+            raise SystemExit("--dtype: f16, bf16 or both, comma separated")
+        preds[d] = pred if d == "f16" else pred.to(torch.bfloat16)
+    times = {d: [] for d in dtypes}
+    crc, kernel = {}, {}
     for r in range(args.reps + 1):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(torch.cuda.current_stream())
-        cons = backend.consensus(pred, ov, Pb)
-        b.record(torch.cuda.current_stream())
-        torch.cuda.synchronize()
-        if r:
-            times.append(a.elapsed_time(b))
-        else:
-            crc = int(cons.view(torch.int32).sum(dtype=torch.int64).item()) & 0xFFFFFFFF
-        del cons
-    print(json.dumps({"case": args.case, "lib": os.path.basename(backend.library_path()),
-                      "env": {k: v for k, v in os.environ.items() if k.startswith("PPP_S1")},
-                      "ms": [round(t, 2) for t in times], "min_ms": round(min(times), 2),
-                      "checksum": crc}))
+        for d in dtypes:
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(torch.cuda.current_stream())
+            cons = backend.consensus(preds[d], ov, Pb)
+            b.record(torch.cuda.current_stream())
+            torch.cuda.synchronize()
+            if r:
+                times[d].append(a.elapsed_time(b))
+            else:
+                crc[d] = int(cons.view(torch.int32).sum(dtype=torch.int64).item()) & 0xFFFFFFFF
+                kernel[d] = backend.NOTES.get("s1_kernel")
+            del cons
+    out = {"case": args.case, "lib": os.path.basename(backend.library_path()),
+           "env": {k: v for k, v in os.environ.items() if k.startswith("PPP_S1")}}
+    if len(dtypes) == 1:
+        t = times[dtypes[0]]
+        out.update(ms=[round(v, 2) for v in t], min_ms=round(min(t), 2), checksum=crc[dtypes[0]])
+        if dtypes[0] != "f16":
+            out["dtype"] = dtypes[0]
+    else:
+        for d in dtypes:
+            out[d] = {"ms": [round(v, 2) for v in times[d]], "min_ms": round(min(times[d]), 2),
+                      "spread_ms": round(max(times[d]) - min(times[d]), 2), "checksum": crc[d], "kernel": kernel[d]}
+    print(json.dumps(out))
 
 
 if __name__ == "__main__":
