@@ -127,6 +127,12 @@ const char *ppp_last_error(void);
 /* name of the kernel the last ppp_consensus call launched (which generation / specialisation
  * served the shape): "consensus_v3_kernel", "consensus_v2_kernel" or "consensus_gather_kernel" */
 const char *ppp_consensus_kernel_name(void);
+/* the same for the last S2 call (ppp_rank_patches: "rank_v2_kernel" or "rank_kernel"; ppp_rank_patches_vm:
+ * "rank_wg_kernel", "rank_wg_kernel<p1>" or "rank_vm_kernel") and the last S5 call (ppp_patch_graph:
+ * "patch_graph_kernel", "patch_graph_vm_kernel" or "patch_graph_vm2_kernel"; ppp_patch_graph_by_patch*:
+ * "patch_graph_pa_kernel", or "patch_graph_pa_kernel<small>" with the small chunk); "none" before the first */
+const char *ppp_rank_kernel_name(void);
+const char *ppp_patch_graph_kernel_name(void);
 /* Development switches (PPP_* environment variables naming a kernel variant or a tile shape)
  * are read once per process, at their first use; ppp_reload_env() makes the next use read them
  * again (tests that compare variants within one process).                                   */

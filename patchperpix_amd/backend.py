@@ -71,6 +71,8 @@ _SIGNATURES = {
                                       ctypes.POINTER(Params), ctypes.c_void_p]),
     "ppp_last_error": (ctypes.c_char_p, []),
     "ppp_consensus_kernel_name": (ctypes.c_char_p, []),
+    "ppp_rank_kernel_name": (ctypes.c_char_p, []),
+    "ppp_patch_graph_kernel_name": (ctypes.c_char_p, []),
     "ppp_reload_env": (None, []),
     "ppp_np_vote_planes": (ctypes.c_int64, [ctypes.POINTER(Params)]),
     "ppp_np_consensus": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,

@@ -141,6 +141,8 @@ extern "C" {
 int ppp_abi_version(void) { return PPP_ABI_VERSION; }
 const char *ppp_last_error(void) { return g_err; }
 const char *ppp_consensus_kernel_name(void) { return ppp::last_consensus_kernel(); }
+const char *ppp_rank_kernel_name(void) { return ppp::last_rank_kernel(); }
+const char *ppp_patch_graph_kernel_name(void) { return ppp::last_patch_graph_kernel(); }
 
 void ppp_reload_env(void) { ppp::env_reload(); }
 

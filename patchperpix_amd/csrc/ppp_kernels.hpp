@@ -52,6 +52,11 @@ hipError_t run_consensus_sparse(const void *pred, int dtype, const uint8_t *ov, 
                                 const Geo &G, void *work, int mode, long long *total, long long *active,
                                 int *took_lists, hipStream_t s);
 void note_consensus_kernel(const char *name);
+// the S2 / S5 kernel the last launch took (ppp_rank_kernel_name, ppp_patch_graph_kernel_name)
+const char *last_rank_kernel();
+void note_rank_kernel(const char *name);
+const char *last_patch_graph_kernel();
+void note_patch_graph_kernel(const char *name);
 hipError_t launch_consensus_part(const void *pred, int dtype, const uint8_t *ov, float *cons, const Geo &G,
                                  hipStream_t s);
 bool consensus_v4_supported(const Geo &G);

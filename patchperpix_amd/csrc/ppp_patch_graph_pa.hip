@@ -1152,6 +1152,7 @@ hipError_t launch_patch_graph_pa(const void *pred, int dtype, const float *S, co
     const size_t lds = (size_t)(row_bufs * WB + ((words + 3) & ~3) + ((words * threads + 1) & ~1)) * 4;
     if (lds > 80 * 1024 || n_blocks >= (1ll << 31) || grid_too_big((unsigned long long)n_blocks, threads))
         return hipErrorNotSupported;
+    note_patch_graph_kernel(small ? "patch_graph_pa_kernel<small>" : "patch_graph_pa_kernel");
 #define PPP_PA_CASE(P)                                                                                  \
     case P:                                                                                             \
         return with_pred_type(dtype, [&](auto tag) {                                                    \

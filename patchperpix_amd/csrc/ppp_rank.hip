@@ -77,6 +77,10 @@ __global__ void __launch_bounds__(256)
     score[lc] = G.norm_rank ? acc / (float)(fg_cnt > 1u ? fg_cnt : 1u) : acc;
 }
 
+static const char *g_s2_kernel = "none";
+const char *last_rank_kernel() { return g_s2_kernel; }
+void note_rank_kernel(const char *name) { g_s2_kernel = name; }
+
 hipError_t launch_rank(const void *pred, int dtype, const float *cons, const uint8_t *ov,
                        float *score, const ppp_box &sb, const Geo &G, hipStream_t s) {
     const long long n = (long long)(sb.x1 - sb.x0) * (sb.y1 - sb.y0) * (sb.z1 - sb.z0);
@@ -86,10 +90,11 @@ hipError_t launch_rank(const void *pred, int dtype, const float *cons, const uin
     const bool force_generic = generic_sw.get() != nullptr;
     if (!force_generic) {
         const hipError_t e2 = launch_rank_v2(pred, dtype, cons, ov, score, sb, G, s);
-        if (e2 != hipErrorNotSupported) return e2;
+        if (e2 != hipErrorNotSupported) { g_s2_kernel = "rank_v2_kernel"; return e2; }
     }
     PPP_GRID_CHECK((n + 255) / 256, 256);
     const dim3 grid((unsigned)((n + 255) / 256));
+    g_s2_kernel = "rank_kernel";
     {
         const hipError_t e_ = with_pred_type(dtype, [&](auto tag) {
             using T = PPP_PRED_T(tag);

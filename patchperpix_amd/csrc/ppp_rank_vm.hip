@@ -406,6 +406,7 @@ hipError_t launch_rank_vm(const void *pred, int dtype, const float *S, const uin
                           const ppp_box &sb, void *work, const Geo &G, hipStream_t s) {
     if (!rank_vm_supported(G)) return hipErrorNotSupported;
     if (rank_wg_supported(G)) return launch_rank_wg(pred, dtype, S, ov, score, sb, work, G, s);
+    note_rank_kernel("rank_vm_kernel");
     return with_pred_type(dtype, [&](auto tag) {
         using T = PPP_PRED_T(tag);
         return launch_rv<T>((const T *)pred, S, ov, score, sb, work, G, s);

@@ -974,6 +974,7 @@ static hipError_t launch_rwg(const T *pred, const float *S, const uint8_t *ov, f
     // not waiting for its masks.
     static EnvSwitch p1_sw("PPP_RANK_P1");
     const bool p1 = G.bg_lt >= G.th_gt && p1_sw.get() && p1_sw.get()[0] == '1';
+    note_rank_kernel(p1 ? "rank_wg_kernel<p1>" : "rank_wg_kernel");
     if (p1) {
         hipError_t em = hipMemsetAsync(any_e, 0, 4, s);
         if (em != hipSuccess) return em;

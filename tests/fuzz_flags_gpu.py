@@ -4,8 +4,9 @@ under tests/ because it calls the oracle; the fixed cases are tests/test_gpu_par
 
 Every trial draws a volume (3-d, or one slice with 2-d patches), a patch shape (cubic, anisotropic, 2-d up
 to 25 wide), thresholds, the background rule, the value / normalisation / ranking switches, cover and
-labelling options and a prediction (float16-exact or perturbed in float32, some values pinned to the
-threshold, to 0 and to 1), runs ``vote_instances.to_instance_seg`` on the GPU and the oracle on the
+labelling options and a prediction (float16-exact or perturbed in float32, or with values pinned to 0, 1 and
+the float32 neighbours of the threshold and of the drawn rule's background threshold -- the value set of
+tests/flag_matrix_cases.py), runs ``vote_instances.to_instance_seg`` on the GPU and the oracle on the
 host, and compares pair rows, pair affinities (bit patterns) and the instance map.
 
   python tests/fuzz_flags_gpu.py [--trials 40] [--seed 1]
@@ -48,7 +49,7 @@ def draw(rng):
         if int(np.prod(shape)) <= vmax:
             break
         long_x = long_x and rng.integers(0, 4) != 0
-    th = float(rng.choice([0.5, 0.5, 0.5, 0.6, 0.8, 0.9]))
+    th = float(rng.choice([0.5, 0.5, 0.5, 0.3, 0.6, 0.8, 0.9]))
     bg = str(rng.choice(["less", "inv", "half"]))
     flags = dict(patch_threshold=th, fc_threshold=float(rng.choice([0.5, 0.5, 0.7])),
                  vi_bg_use_less_than_th=bg == "less", vi_bg_use_inv_th=bg == "inv", vi_bg_use_half_th=bg == "half",
@@ -77,13 +78,19 @@ def make_pred(cfg, synth):
     if cfg["perturb"] == "f32":
         pred = (pred * rng.uniform(0.97, 1.0, size=pred.shape)).astype(np.float32)
     elif cfg["perturb"] == "pinned":
-        th = np.float32(cfg["flags"]["patch_threshold"])
+        # 0, 1, and float32(t) with both neighbours for t = the threshold and the background threshold of the drawn
+        # rule (as the kernels get them: an inv rule below 0.5 is the less-than rule)
+        from oracle import ppp_oracle as orc
+        import flag_matrix_cases as fm
+        from patchperpix_amd.flags import FLYLIGHT
+        P = orc.make_params(cfg["shape"], cfg["ps"], **dict(FLYLIGHT, **cfg["flags"]))
+        bg = {orc.BG_INV_TH: P.thi, orc.BG_HALF_TH: P.th / 2, orc.BG_LESS_THAN_TH: P.th}[P.bg_rule]
+        half = bool(cfg.get("half_input"))        # (float16-exact inputs: the neighbours in that format)
+        vals = sorted({0.0, 1.0} | {float(v) for t in (P.th, bg) for v in fm.around(t, "float16" if half else "float32")})
         r = rng.uniform(size=pred.shape)
-        pred = pred.copy()
-        pred[r < 0.02] = th
-        pred[(r >= 0.02) & (r < 0.04)] = 0.0
-        pred[(r >= 0.04) & (r < 0.06)] = 1.0
-        pred[(r >= 0.06) & (r < 0.07)] = np.float32(1.0) - th
+        pred = np.clip(pred, 0.0, 1.0).astype(np.float32)
+        for k, v in enumerate(vals):
+            pred[(r >= 0.01 * k) & (r < 0.01 * (k + 1))] = np.float32(v)
     if cfg.get("half_input") and cfg["perturb"] != "f32":
         # float16-exact values: the oracle sees their widening
         pred = pred.astype(np.float16).astype(np.float32)
