@@ -837,6 +837,28 @@ int ppp_skeletonize_3d(const uint8_t *d_mask, uint8_t *d_out, int32_t Z, int32_t
                        int64_t *n_kept, int32_t *stats /* [3]: passes, sub-iterations, rounds */,
                        void *d_work, void *stream);
 
+/* --- the 3-d skeleton of EVERY instance of an id map in one pass (csrc/ppp_skeleton.hip) --------
+ * The reference's `postprocess` task (util/postprocess.py:105-119, export_skeleton_nrrds) thins
+ * `inst == label` once per instance.  Instances are disjoint and a verdict of the thinning reads voxels
+ * of its own instance only, so the kernels of ppp_skeletonize_3d run over the whole map at once with
+ * "neighbour present" = "alive and of the centre's id".
+ * DEFINITION of the result: for every id L, { v : d_out[v] == L } equals
+ * ppp_host_skeletonize_3d(d_labels == L) on the whole volume; parity with scikit-image's skeletonize_3d
+ * stays UNPINNED, as for ppp_skeletonize_3d.
+ * d_labels u32 [Z][Y][X]: 0 is background, every other 32-bit value is an id (ids of 2^31 and above
+ * included: only equality is used, there is no table and no id limit).  d_out u32 [Z][Y][X]:
+ * d_out[v] = d_labels[v] where v survives, else 0 (d_out may be d_labels).  *n_kept = voxels kept;
+ * stats[3] as ppp_skeletonize_3d (a map with one id gives that function's counts).  The call
+ * synchronises the stream.  Size limits, PPP_ERR_NO_DEVICE and PPP_ERR_UNSUPPORTED as
+ * ppp_skeletonize_3d.  The workspace holds the two bit images, one u32 word per voxel (which of the 26
+ * neighbours carry the voxel's id), three lists of Z*Y*X u32 entries and the round counters: about
+ * 16 bytes per voxel.
+ * (PPP_ABI_VERSION counts changes to ppp_params and to existing signatures; new entry points leave it.) */
+int64_t ppp_skeletonize_labels_workspace_bytes(int32_t Z, int32_t Y, int32_t X);
+int ppp_skeletonize_labels(const uint32_t *d_labels, uint32_t *d_out, int32_t Z, int32_t Y, int32_t X,
+                           int64_t *n_kept, int32_t *stats /* [3] as ppp_skeletonize_3d */,
+                           void *d_work, void *stream);
+
 /* --- synthetic input (bench / tests only; same hash as patchperpix_amd/synth.py) ------
  * fills d_pred (C,Z,Y,X) from a label volume d_labels int32 (Z,Y,X).  voxel_offset is the
  * linear index of local voxel 0 in the global volume (0 unless the buffers are a slab).    */

@@ -354,6 +354,10 @@ _SIGNATURES = {
     "ppp_skeletonize_3d": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                                           ctypes.c_int32, ctypes.POINTER(ctypes.c_int64),
                                           ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_void_p]),
+    "ppp_skeletonize_labels_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "ppp_skeletonize_labels": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.c_int32, ctypes.POINTER(ctypes.c_int64),
+                                              ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_void_p]),
     # no_overlap_per_channel without the loop over components (ppp_pack_channels.hip, ppp_host_pack.cpp)
     "ppp_pack_scan_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(Params), ctypes.POINTER(Box)]),
     "ppp_pack_scan_count": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
@@ -2085,6 +2089,44 @@ def skeletonize_3d(mask):
         NOTES["skeleton_kept"] = int(kept.value)
         out = m
     return out.bool() if is_tensor else out.cpu().numpy().astype(bool)
+
+
+def skeletonize_labels(ids):
+    """ppp_skeletonize_labels: the 3-d skeleton of every instance of an id map in ONE device pass.  For
+    every id L the voxels that keep L are host_skeletonize_3d(ids == L); every other voxel is 0.  `ids` is a
+    (Z, Y, X) or (Y, X) NumPy array or device tensor of uint16 / uint32 / int32 ids (0: background; only
+    equality of the 32 bits is used); the result is of the same kind, dtype and shape, the input is left
+    as it was.  Parity with scikit-image's skeletonize_3d is unpinned, as for skeletonize_3d.
+    NOTES["skeleton_stats"] = (passes, sub-iterations, rounds), NOTES["skeleton_kept"] = voxels kept."""
+    torch = _torch()
+    is_tensor = torch.is_tensor(ids)
+    if not torch.cuda.is_available():
+        raise RuntimeError("libppp_mi355x: ppp_skeletonize_labels: no HIP device available (this library has no CPU path)")
+    if is_tensor:
+        assert ids.is_cuda, "skeletonize_labels takes a NumPy array or a DEVICE tensor"
+        name = str(ids.dtype).replace("torch.", "")
+        assert name in ("uint16", "uint32", "int32"), "skeletonize_labels takes uint16 / uint32 / int32 ids"
+        t = ids.to(torch.int32) if name == "uint16" else ids.contiguous().view(torch.int32).clone()
+    else:
+        a = np.asarray(ids)
+        name = a.dtype.name
+        assert name in ("uint16", "uint32", "int32"), "skeletonize_labels takes uint16 / uint32 / int32 ids"
+        t = torch.from_numpy(np.ascontiguousarray(a).astype(np.uint32).view(np.int32)).cuda()
+    shape = tuple(t.shape)
+    assert 2 <= len(shape) <= 3, "skeletonize_labels needs a (Z, Y, X) or (Y, X) map"
+    Z, Y, X = (1,) * (3 - len(shape)) + shape
+    if Z * Y * X != 0:
+        work = _workspace(lib().ppp_skeletonize_labels_workspace_bytes(Z, Y, X), t.device)
+        kept = ctypes.c_int64(0)
+        stats = (ctypes.c_int32 * 3)()
+        with _timed("skeletonize_labels"):
+            check(lib().ppp_skeletonize_labels(_dev_ptr(t), _dev_ptr(t), Z, Y, X, ctypes.byref(kept), stats,
+                                               _dev_ptr(work), _stream()))
+        NOTES["skeleton_stats"] = tuple(int(v) for v in stats)
+        NOTES["skeleton_kept"] = int(kept.value)
+    if is_tensor:
+        return (t & 0xFFFF).to(torch.uint16) if name == "uint16" else t.view(ids.dtype)
+    return t.cpu().numpy().view(np.uint32).astype(a.dtype)
 
 
 def host_skel_rule_mismatches(first, count):

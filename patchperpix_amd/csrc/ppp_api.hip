@@ -1426,4 +1426,22 @@ int ppp_skeletonize_3d(const uint8_t *d_mask, uint8_t *d_out, int32_t Z, int32_t
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_skeletonize_3d");
 }
 
+int64_t ppp_skeletonize_labels_workspace_bytes(int32_t Z, int32_t Y, int32_t X) {
+    int rc = skeleton_volume(Z, Y, X);
+    return rc != PPP_OK ? rc : (int64_t)ppp::skeleton_labels_workspace_bytes(Z, Y, X);
+}
+
+int ppp_skeletonize_labels(const uint32_t *d_labels, uint32_t *d_out, int32_t Z, int32_t Y, int32_t X, int64_t *n_kept,
+                           int32_t *stats, void *d_work, void *stream) {
+    PPP_TRY(skeleton_volume(Z, Y, X));
+    if (!d_labels || !d_out || !d_work || !n_kept || !stats) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    PPP_TRY(need_device());
+    long long kept = 0;
+    int st[3] = {0, 0, 0};
+    hipError_t e = ppp::run_skeletonize_labels(d_labels, d_out, Z, Y, X, &kept, st, d_work, (hipStream_t)stream);
+    *n_kept = kept;
+    stats[0] = st[0]; stats[1] = st[1]; stats[2] = st[2];
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_skeletonize_labels");
+}
+
 }  // extern "C"

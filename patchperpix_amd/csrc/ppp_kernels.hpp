@@ -241,5 +241,9 @@ hipError_t run_post_clean_mask(const uint8_t *mask, uint8_t *out, int Z, int Y, 
 size_t skeleton_workspace_bytes(int Z, int Y, int X);
 hipError_t run_skeletonize_3d(const uint8_t *mask, uint8_t *out, int Z, int Y, int X, long long *n_kept, int *stats,
                               void *work, hipStream_t s);
+// the same thinning of every instance of an id map in one pass (the kernels instantiated with labels)
+size_t skeleton_labels_workspace_bytes(int Z, int Y, int X);
+hipError_t run_skeletonize_labels(const uint32_t *labels, uint32_t *out, int Z, int Y, int X, long long *n_kept, int *stats,
+                                  void *work, hipStream_t s);
 
 }  // namespace ppp

@@ -4,7 +4,11 @@ dilate.
 
 `remove_small_components`, `relabel` and `dilate_instances` are host NumPy like the reference.  Their
 `*_device` forms return the same arrays from the HIP kernels of csrc/ppp_postprocess.hip; `post_steps`
-is the block the drivers run after the assembly and picks between the two (`use_device`)."""
+is the block the drivers run after the assembly and picks between the two (`use_device`).
+
+`postprocess_instances` is the reference driver's `postprocess` task (postprocess.py:77-119): the instance
+map cleaned again and one 3-d skeleton per instance -- `skeletonize_instances` (host loop, the definition)
+or `skeletonize_instances_device` (all instances in one pass, csrc/ppp_skeleton.hip)."""
 import logging
 import math
 import os
@@ -183,6 +187,114 @@ def compact(instances, compsize):
     if use_device():
         return _compact_device(instances, compsize, True, None)
     return relabel(remove_small_components(instances, compsize))
+
+
+# ----------------------------------------------------------------------------------------
+# the `postprocess` task: one 3-d skeleton per instance (postprocess.py:77-119)
+# ----------------------------------------------------------------------------------------
+def skeletonize_instances(instances, crop=True):
+    """The 3-d skeleton of every instance of a (Z, Y, X) or (Y, X) id map, as a map of the same dtype
+    and shape: a voxel keeps its id L where ``backend.host_skeletonize_3d(instances == L)`` keeps it, every
+    other voxel is 0 -- the loop of postprocess.py:110-112 with the library's own thinning (Lee / Kashyap /
+    Chu 1994; parity with scikit-image's skeletonize_3d is UNPINNED, as for skeletonize_backend="ppp").
+    This is the host DEFINITION of `skeletonize_instances_device`.
+
+    crop: thin each instance inside its bounding box instead of the whole volume -- the same result (the
+    thinning reads a voxel's 26 neighbours only, everything outside the box is empty either way and the
+    raster order inside it is the volume's); the box keeps two slices where the volume has more than
+    one, because the thinning peels the z borders of a volume of several slices only."""
+    from . import backend
+    inst = np.asarray(instances)
+    shape = inst.shape
+    if inst.ndim not in (2, 3):
+        raise ValueError("skeletonize_instances needs a (Z, Y, X) or (Y, X) map")
+    inst3 = inst.reshape((1,) * (3 - inst.ndim) + shape)
+    out = np.zeros_like(inst3)
+    labels, inverse = np.unique(inst3, return_inverse=True)
+    if not crop:
+        for lbl in labels[labels != 0]:
+            out[backend.host_skeletonize_3d(inst3 == lbl)] = lbl
+        return out.reshape(shape)
+    dense = inverse.reshape(inst3.shape).astype(np.int32)       # position in `labels`: find_objects wants small ids
+    Z = inst3.shape[0]
+    for k, box in enumerate(ndimage.find_objects(dense + 1)):
+        lbl = labels[k]
+        if lbl == 0 or box is None:
+            continue
+        if Z > 1 and box[0].stop - box[0].start == 1:
+            z0 = min(box[0].start, Z - 2)
+            box = (slice(z0, z0 + 2),) + tuple(box[1:])
+        out[box][backend.host_skeletonize_3d(inst3[box] == lbl)] = lbl
+    return out.reshape(shape)
+
+
+def skeletonize_instances_device(instances):
+    """`skeletonize_instances` from the device in ONE pass over the map, whatever the number of instances
+    (backend.skeletonize_labels = ppp_skeletonize_labels, csrc/ppp_skeleton.hip): the same map, voxel for
+    voxel.  uint16 / uint32 / int32 maps (NumPy or device tensor) go as they are; a NumPy map of another
+    integer dtype goes as uint32 when its ids fit, and comes back in its own dtype."""
+    from . import backend
+    if _is_tensor(instances) or np.asarray(instances).dtype in (np.uint16, np.uint32, np.int32):
+        return backend.skeletonize_labels(instances)
+    inst = np.asarray(instances)
+    if inst.dtype.kind not in "iu" or (inst.size and (int(inst.min()) < 0 or int(inst.max()) >= 1 << 32)):
+        raise ValueError("skeletonize_instances_device: ids must be integers that fit 32 bits (dtype %s)" % inst.dtype)
+    return backend.skeletonize_labels(inst.astype(np.uint32)).astype(inst.dtype)
+
+
+def instance_skeletons(instances):
+    """skeletonize_instances, by the dispatch rule; returns (map, the implementation's name)"""
+    if use_device():
+        return skeletonize_instances_device(instances), "ppp_skeletonize_labels"
+    return skeletonize_instances(instances), "ppp_host_skeletonize_3d"
+
+
+def postprocess_instances(samples, output_folder, **kwargs):
+    """The `process_instances` branch of the reference's `postprocess` task (postprocess.py:77-119,
+    called from run_ppp.py:2246-2259).  For every result file ``sample`` (.hdf, opened "a"):
+
+    - ``res_key`` is read, ids with ``counts <= remove_small_comps`` are dropped and the rest renumbered
+      (`compact`: device or host), and the map is written as dataset ``<res_key>_rm_<remove_small_comps>``
+      (gzip), uint16 when its maximum is < 65535, else uint32 -- the reference's rule.  An existing
+      dataset of that name is replaced (the reference's create_dataset fails on a second run).
+    - ``export_skeleton_nrrds``: the skeleton of every instance of the cleaned map, from ONE
+      `instance_skeletons` call instead of one thinning per instance, each written as
+      ``<output_folder>/<sample>_<label>.nrrd`` (mininrrd: the payload and sizes of the reference's
+      ``nrrd.write(mask.transpose(2, 1, 0))``).
+    - ``export_skeleton_labels`` (this project's own option, not the reference's): the skeleton label
+      map as ONE dataset ``<res_key>_rm_<n>_skeleton`` instead of one file per instance.
+
+    The thinning is the library's own (Lee / Kashyap / Chu 1994): parity with scikit-image's
+    skeletonize_3d, which the reference calls, is UNPINNED; the datasets carry the attribute
+    ``skeletonize_instances`` naming the implementation that made the skeletons."""
+    from . import minihdf5, mininrrd
+    comp_thresh = kwargs["remove_small_comps"]
+    res_key = kwargs["res_key"]
+    want_nrrds = bool(kwargs.get("export_skeleton_nrrds", False))
+    want_labels = bool(kwargs.get("export_skeleton_labels", False))
+    for sample in samples:
+        with minihdf5.File(sample, "a") as inf:
+            cleaned = np.asarray(compact(np.asarray(inf[res_key]), comp_thresh))
+            dtype = np.uint16 if int(cleaned.max(initial=0)) < 65535 else np.uint32
+            cleaned = cleaned.astype(dtype)
+            new_key = res_key + ("_rm_%s" % comp_thresh)
+            ds = inf.create_dataset(new_key, data=cleaned, dtype=dtype, compression="gzip")
+            if not (want_nrrds or want_labels):
+                continue
+            skel, served_by = instance_skeletons(cleaned)
+            logger.warning("postprocess: instance skeletons by %s; not pinned to scikit-image's skeletonize_3d",
+                           served_by)
+            ds.attrs["skeletonize_instances"] = served_by
+            if want_labels:
+                sk = inf.create_dataset(new_key + "_skeleton", data=skel, dtype=dtype, compression="gzip")
+                sk.attrs["skeletonize_instances"] = served_by
+            if want_nrrds:
+                os.makedirs(output_folder, exist_ok=True)
+                sample_name = os.path.basename(sample).split(".")[0]
+                vol = skel.reshape((1,) * (3 - skel.ndim) + skel.shape)
+                for lbl in np.unique(cleaned):
+                    if lbl > 0:
+                        mininrrd.write(os.path.join(output_folder, sample_name + ("_%i.nrrd" % lbl)), vol == lbl)
 
 
 def post_steps(instances, foreground, res_key, **kw):

@@ -1,16 +1,17 @@
 #!/usr/bin/env python3
-"""`label` and `decode` tasks with the reference driver's interface
+"""`label`, `decode` and `postprocess` tasks with the reference driver's interface
 (reference: experiments/run_ppp.py -- argument names :157-267, task dispatch :1974-2293,
-``decode`` :682-746, ``vote_instances`` / ``vote_instances_sample`` :1054-1190).
+``decode`` :682-746, ``vote_instances`` / ``vote_instances_sample`` :1054-1190, ``postprocess``
+:2230-2259 -- its ``process_instances`` branch; ``process_fg_prediction`` is refused).
 
-Only the two tasks on this repository's path are provided; training, prediction and evaluation
+Only the tasks on this repository's path are provided; training, prediction and evaluation
 stay with the reference.  Usage, as in the reference README:
 
     python -m patchperpix_amd.run_ppp --setup setup01 --config default.toml --do label \
         --pred-folder <dir with *.zarr|*.hdf|*.npy> --output-folder <dir> [--sample NAME]
 
 Config: the reference's TOML files are read unchanged ([vote_instances], [model], [prediction],
-[visualize], [general], [data], [evaluation]).
+[visualize], [general], [data], [evaluation], [postprocessing]).
 """
 import argparse
 import glob
@@ -119,6 +120,25 @@ def decode(args, config):
                **config["model"], **config["prediction"], **config.get("data", {}))
 
 
+def postprocess(args, config):
+    """run_ppp.py:2230-2259: the result files ``*.<vote_instances.output_format>`` of --output-folder,
+    ``res_key`` from [evaluation], everything else from [postprocessing]."""
+    from . import postprocess as post
+    cfg = config.get("postprocessing", {})
+    if cfg.get("process_fg_prediction", False):
+        # its max_distance_to_fg branch needs an exact Euclidean distance transform: not provided
+        raise NotImplementedError("[postprocessing] process_fg_prediction = true is not provided by this "
+                                  "repository (postprocess_fg stays with the reference); unset it to run "
+                                  "process_instances")
+    if cfg.get("process_instances", False):
+        fmt = config["vote_instances"].get("output_format", "hdf")
+        samples = [os.path.join(args.output_folder, s + "." + fmt)
+                   for s in get_list_samples(args.output_folder, fmt, args.sample)]
+        t0 = time.time()
+        post.postprocess_instances(samples, args.output_folder, res_key=config["evaluation"]["res_key"], **cfg)
+        logger.info("time postprocess_instances (%d samples): %.2fs", len(samples), time.time() - t0)
+
+
 def main(argv=None):
     from patchperpix_amd import backend as _backend
     _backend.tune_host_allocator(cli=True)     # (main(argv) IS the program, also behind a console script)
@@ -126,7 +146,7 @@ def main(argv=None):
     ap.add_argument("-c", "--config", action="append", required=True)
     ap.add_argument("-a", "--app", default="flylight")
     ap.add_argument("-s", "--setup", default="setup01")
-    ap.add_argument("-d", "--do", nargs="+", default=["label"], choices=["label", "decode"])
+    ap.add_argument("-d", "--do", nargs="+", default=["label"], choices=["label", "decode", "postprocess"])
     ap.add_argument("--pred-folder", required=True)
     ap.add_argument("--output-folder", required=True)
     ap.add_argument("--checkpoint", default=None)
@@ -135,7 +155,7 @@ def main(argv=None):
     logging.basicConfig(level=logging.INFO)
     config = load_config(args.config)
     for task in args.do:
-        {"label": label, "decode": decode}[task](args, config)
+        {"label": label, "decode": decode, "postprocess": postprocess}[task](args, config)
 
 
 if __name__ == "__main__":
