@@ -127,6 +127,13 @@ const char *ppp_last_error(void);
 /* name of the kernel the last ppp_consensus call launched (which generation / specialisation
  * served the shape): "consensus_v3_kernel", "consensus_v2_kernel" or "consensus_gather_kernel" */
 const char *ppp_consensus_kernel_name(void);
+/* 1 when the last S1 call (ppp_consensus, ppp_consensus_rows, ppp_consensus_part, ppp_consensus_sparse)
+ * chose the packed kernel's CLEAN instantiation, the one with the short operand classification, for the votes
+ * it launched (pred_clean == 1 in its parameters and the development switch PPP_S1_CLEAN not "0"); 0 after any
+ * other S1 call -- one over item lists without an active item included: it launches zero stores only -- and
+ * before the first.  A host variable set at launch, like the kernel names: what tests assert to know which
+ * form they compared.                                                                              */
+int ppp_consensus_short_form(void);
 /* the same for the last S2 call (ppp_rank_patches: "rank_v2_kernel" or "rank_kernel"; ppp_rank_patches_vm:
  * "rank_wg_kernel", "rank_wg_kernel<p1>" or "rank_vm_kernel") and the last S5 call (ppp_patch_graph:
  * "patch_graph_kernel", "patch_graph_vm_kernel" or "patch_graph_vm2_kernel"; ppp_patch_graph_by_patch*:

@@ -71,6 +71,7 @@ _SIGNATURES = {
                                       ctypes.POINTER(Params), ctypes.c_void_p]),
     "ppp_last_error": (ctypes.c_char_p, []),
     "ppp_consensus_kernel_name": (ctypes.c_char_p, []),
+    "ppp_consensus_short_form": (ctypes.c_int, []),
     "ppp_rank_kernel_name": (ctypes.c_char_p, []),
     "ppp_patch_graph_kernel_name": (ctypes.c_char_p, []),
     "ppp_reload_env": (None, []),
@@ -839,6 +840,7 @@ def consensus(pred, overlap, P, want_count=False, out=None, open_rows=False):
             check(L.ppp_consensus(_dev_ptr(pred), pred_dtype_code(pred), _dev_ptr(overlap),
                                   _dev_ptr(cons), _dev_ptr(cnt), ctypes.byref(P), _stream()))
     note("s1_kernel", L.ppp_consensus_kernel_name().decode())
+    note("s1_short_form", int(L.ppp_consensus_short_form()))
     return (cons, cnt) if want_count else cons
 
 
@@ -1486,6 +1488,7 @@ def consensus_part(pred, overlap, P, part, out):
             check(lib().ppp_consensus_part(_dev_ptr(pred), pred_dtype_code(pred), _dev_ptr(overlap), _dev_ptr(out),
                                            ctypes.byref(P), ctypes.byref(b), _stream()))
     note("s1_kernel", lib().ppp_consensus_kernel_name().decode())
+    note("s1_short_form", int(lib().ppp_consensus_short_form()))
 
 
 def cons_planes_to_rows(planes, planes_box, P, out=None):

@@ -141,6 +141,7 @@ extern "C" {
 int ppp_abi_version(void) { return PPP_ABI_VERSION; }
 const char *ppp_last_error(void) { return g_err; }
 const char *ppp_consensus_kernel_name(void) { return ppp::last_consensus_kernel(); }
+int ppp_consensus_short_form(void) { return ppp::last_consensus_short_form(); }
 const char *ppp_rank_kernel_name(void) { return ppp::last_rank_kernel(); }
 const char *ppp_patch_graph_kernel_name(void) { return ppp::last_patch_graph_kernel(); }
 

@@ -95,9 +95,14 @@ __global__ void __launch_bounds__(256)
 static const char *g_s1_kernel = "none";
 const char *last_consensus_kernel() { return g_s1_kernel; }
 void note_consensus_kernel(const char *name) { g_s1_kernel = name; }
+// 1: the last S1 launch was a CLEAN = true instantiation of the packed kernel (host variable only)
+static int g_s1_short_form = 0;
+int last_consensus_short_form() { return g_s1_short_form; }
+void note_consensus_short_form(int on) { g_s1_short_form = on; }
 
 hipError_t launch_consensus(const void *pred, int dtype, const uint8_t *ov, float *cons,
                             float *cnt, const Geo &G, hipStream_t s) {
+    g_s1_short_form = 0;                // (the packed kernel's launch sets it)
     if (G.layout == PPP_CONS_VOXEL_MAJOR) {
         // only the packed two-slice kernel writes the voxel-major rows directly
         if (!consensus_v3_supported(G)) return hipErrorNotSupported;
@@ -154,6 +159,7 @@ hipError_t launch_consensus(const void *pred, int dtype, const uint8_t *ov, floa
 hipError_t launch_consensus_part(const void *pred, int dtype, const uint8_t *ov, float *cons, const Geo &G,
                                  hipStream_t s) {
     g_s1_kernel = "consensus_v3_kernel";
+    g_s1_short_form = 0;
     return launch_consensus_v3(pred, dtype, ov, cons, nullptr, G, s);
 }
 

@@ -158,6 +158,7 @@ hipError_t run_consensus_sparse(const void *pred, int dtype, const uint8_t *ov, 
                                 const Geo &G, void *work, int mode, long long *total, long long *active,
                                 int *took_lists, hipStream_t s) {
     const V3Items I = consensus_v3_items(G);
+    note_consensus_short_form(0);
     if (consensus_sparse_workspace_bytes(G) == 0) return hipErrorNotSupported;
     Carver carver(work);
     const SparseWork W = consensus_sparse_layout(carver, G, I);

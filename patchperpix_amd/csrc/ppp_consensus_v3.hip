@@ -927,7 +927,10 @@ static hipError_t launch_v3_lists(const T *pred, const uint8_t *ov, float *cons,
                                   const uint32_t *act, long long na, const uint32_t *ina, long long ni,
                                   hipStream_t s) {
     const bool flat = v3_flat(G);
-    if (v3_clean(G))
+    const bool clean = v3_clean(G);
+    // (without an active item only the zero stores run: nothing is classified)
+    note_consensus_short_form(clean && na > 0 ? 1 : 0);
+    if (clean)
         return flat ? launch_v3f_lists<T, PX, true, true>(pred, ov, cons, cnt, G, act, na, ina, ni, s)
                     : launch_v3f_lists<T, PX, false, true>(pred, ov, cons, cnt, G, act, na, ina, ni, s);
     return flat ? launch_v3f_lists<T, PX, true, false>(pred, ov, cons, cnt, G, act, na, ina, ni, s)
@@ -939,6 +942,7 @@ static hipError_t launch_v3(const T *pred, const uint8_t *ov, float *cons, float
                             const Geo &G, hipStream_t s) {
     const bool flat = v3_flat(G);
     const bool clean = v3_clean(G);
+    note_consensus_short_form(clean ? 1 : 0);
     if (clean)
         return flat ? launch_v3f<T, PX, true, true>(pred, ov, cons, cnt, G, s)
                     : launch_v3f<T, PX, false, true>(pred, ov, cons, cnt, G, s);

@@ -52,6 +52,10 @@ hipError_t run_consensus_sparse(const void *pred, int dtype, const uint8_t *ov, 
                                 const Geo &G, void *work, int mode, long long *total, long long *active,
                                 int *took_lists, hipStream_t s);
 void note_consensus_kernel(const char *name);
+// 1 when the last S1 launch was the packed kernel's short classification (CLEAN = true), else 0
+// (ppp_consensus_short_form)
+int last_consensus_short_form();
+void note_consensus_short_form(int on);
 // the S2 / S5 kernel the last launch took (ppp_rank_kernel_name, ppp_patch_graph_kernel_name)
 const char *last_rank_kernel();
 void note_rank_kernel(const char *name);

@@ -3,7 +3,11 @@ at the thresholds, pair rows and the oracle's stage outputs (plain module, no GP
 tests/test_flag_matrix_rule.py and tests/test_flag_matrix_gpu.py).
 
 A CELL is (shape name, flag set name, dtype).  Everything here is a pure function of the cell, computed
-once per process and shared by all families that meet the cell."""
+once per process and shared by all families that meet the cell.
+
+Two VARIANTS of the prediction: "pinned" holds the thresholds themselves (so ppp_pred_check calls it unclean and
+the packed S1 kernel classifies in its general form), "clean" holds their neighbours and no value the check
+objects to (the short form; S1 outputs only; tests/test_s1_clean_gpu.py)."""
 import functools
 import hashlib
 
@@ -105,6 +109,21 @@ def v3_serves(name):
     """the packed S1 kernel (and the item lists): th 0.5, normalised product, bg test at 0.5"""
     g = geo_flags(name)
     return g["th"] == 0.5 and g["bg"] == 0.5 and g["value_rule"] == orc.VAL_NORM_PROB_PRODUCT
+
+
+def v3_flat_form(shape_name, env=None, part=None):
+    """The packed kernel's form for a compute box (the whole volume, or part = (z0, y0, x0, z1, y1, x1)): True for
+    FLAT (64 base voxels flattened over two lines), False for one line per run.  The rule of v3_flat in
+    csrc/ppp_consensus_v3.hip with its switch PPP_S1_FLAT (env: the family's development switches)."""
+    ps, vol, _, _ = SHAPES[shape_name]
+    cY, cX = (vol[1], vol[2]) if part is None else (part[4] - part[1], part[5] - part[2])
+    flat = cX >= 64 and cX % 64 != 0 and ps[1] >= 3 and cY > 1
+    e = (env or {}).get("PPP_S1_FLAT")
+    if e == "0":
+        flat = False
+    if e == "1" and cX >= 64 and ps[1] >= 3:
+        flat = True
+    return flat
 
 
 def th05_variant(name):
@@ -218,9 +237,12 @@ def _pin_slots(shape_name):
 
 
 @functools.lru_cache(maxsize=4)
-def _prediction(shape_name, dtype, pins):
+def _prediction(shape_name, dtype, pins, clean):      # (no default: one cache key per array)
     b = base_case(shape_name)
     pred = to_dtype(b["pred"], dtype).copy()
+    if clean:
+        # (the clean variant only: the existing predictions and their cached oracle outputs keep their bits)
+        pred[pred == 0] = np.float32(0.0)        # -0.0 -> +0.0: "pred.min() >= 0" does not see it, the check does
     slots = _pin_slots(shape_name)
     assert len(pins) <= MAX_PINS
     for k in range(len(pins)):                   # (share first, the mid channel's fixed voxels last: they hold)
@@ -232,9 +254,66 @@ def _prediction(shape_name, dtype, pins):
     return pred
 
 
-def prediction(shape_name, flag_name, dtype="float32"):
+def _pins(flag_name, dtype, variant):
+    assert variant in VARIANTS
+    if variant == CLEAN:
+        assert v3_serves(flag_name), "nothing but the packed S1 kernel reads pred_clean"
+        return tuple(float(v) for v in clean_pins(dtype))
+    return tuple(float(v) for v in pinned_values(flag_name, dtype))
+
+
+def prediction(shape_name, flag_name, dtype="float32", variant="pinned"):
     """float32 [C, Z, Y, X]: the exact widening of what the device gets for this cell"""
-    return _prediction(shape_name, dtype, tuple(float(v) for v in pinned_values(flag_name, dtype)))
+    return _prediction(shape_name, dtype, _pins(flag_name, dtype, variant), variant == CLEAN)
+
+
+# ---- the clean variant: what ppp_pred_check passes, with the values next to the threshold ---------------------------
+PINNED, CLEAN = "pinned", "clean"
+VARIANTS = (PINNED, CLEAN)
+
+
+def smallest(dtype):
+    """(smallest positive subnormal, smallest positive normal) of the format, as float32"""
+    sub = _step(np.float32(0.0), dtype, True)
+    normal = {"float32": 2.0 ** -126, "float16": 2.0 ** -14, "bfloat16": 2.0 ** -126}[dtype]
+    return np.float32(sub), np.float32(normal)
+
+
+def clean_pins(dtype):
+    """The nine pinned values of the clean variant, ascending: 0, the smallest subnormal and normal, the two
+    representable values below 0.5 and the two above it (never 0.5 itself), the largest value below 1, and 1."""
+    a = around(0.5, dtype)
+    assert len(a) == 3 and float(a[1]) == 0.5
+    sub, normal = smallest(dtype)
+    vals = {0.0, float(sub), float(normal), float(_step(a[0], dtype, False)), float(a[0]), float(a[2]),
+            float(_step(a[2], dtype, True)), float(_step(np.float32(1.0), dtype, False)), 1.0}
+    assert len(vals) == 9 and 0.5 not in vals
+    return [np.float32(v) for v in sorted(vals)]
+
+
+def dtype_patterns(a, dtype):
+    """(unsigned bit patterns of the float32 array `a` narrowed exactly to `dtype`, the pattern of 1.0)"""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if dtype == "float32":
+        return a.view(np.uint32), 0x3F800000
+    if dtype == "float16":
+        return a.astype(np.float16).view(np.uint16), 0x3C00
+    assert dtype == "bfloat16"
+    return (a.view(np.uint32) >> np.uint32(16)).astype(np.uint16), 0x3F80
+
+
+def is_clean(pred_f32, dtype, th, bg):
+    """NumPy restatement of ppp_pred_check (csrc/ppp_aux.hip): the bits it returns for a buffer of `dtype` values
+    (given widened to float32) under the class tests v > th / v < bg.  0 = clean.
+    Bit 1: a value whose unsigned pattern in the format exceeds that of 1.0 (above 1, inf, nan, every negative value
+    and -0).  Bit 2: a value that is neither > th nor < bg -- the oracle's two compares, in doubles (make_geo rounds
+    the kernels' float thresholds, th down and bg up, so that their float compares agree)."""
+    a = np.ascontiguousarray(pred_f32, dtype=np.float32)
+    pat, one = dtype_patterns(a, dtype)
+    v = a.astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        between = ~(v > float(th)) & ~(v < float(bg))
+    return (1 if bool((pat > one).any()) else 0) | (2 if bool(between.any()) else 0)
 
 
 # ---- the oracle's stage outputs --------------------------------------------------------------------------------
@@ -250,7 +329,7 @@ def _oracle_s1(shape_name, dtype, pins, key, rep):
     """The oracle's consensus in the reference layout for (prediction, S1 flags); `rep`: a flag set with these S1
     flags.  With the array at hand, the scores and affinities of EVERY flag set that shares it are made too."""
     b = base_case(shape_name)
-    pred = _prediction(shape_name, dtype, pins)
+    pred = _prediction(shape_name, dtype, pins, False)
     # (the gather form of the oracle's S1: the same array as orc.consensus bit for bit -- tests/test_oracle_golden.py
     # and test_flag_matrix_rule.py hold it to that -- on all cores instead of one: 0.4 s instead of 10 s at 9^3)
     cons = orc.consensus_planes(pred, b["overlap"], b["ps"], **FLAG_SETS[rep])
@@ -273,8 +352,31 @@ def _s1_args(shape_name, flag_name, dtype):
     return (shape_name, dtype, tuple(float(v) for v in pinned_values(flag_name, dtype)), s1_key(flag_name), flag_name)
 
 
-def oracle(shape_name, flag_name, dtype="float32"):
-    """dict(cons_hash: bits_hash of the positive offset planes, score (Z, Y, X), aff [rows]) of the cell"""
+@functools.lru_cache(maxsize=1)
+def _oracle_s1_clean(shape_name, dtype, key, rep):
+    """The clean variant's S1 only: the positive offset planes of the oracle's consensus, their hash noted for every
+    served flag set with these S1 flags.  No scores, no affinities: S2 and S5 do not read pred_clean."""
+    b = base_case(shape_name)
+    pred = _prediction(shape_name, dtype, tuple(float(v) for v in clean_pins(dtype)), True)
+    planes = orc.positive_planes(orc.consensus_planes(pred, b["overlap"], b["ps"], **FLAG_SETS[rep]), b["ps"])
+    h = bits_hash(planes)
+    for name in FLAG_SETS:
+        if v3_serves(name) and s1_key(name) == key:
+            _OUT[(shape_name, name, dtype, CLEAN)] = dict(cons_hash=h)
+    planes.setflags(write=False)
+    return planes
+
+
+def oracle(shape_name, flag_name, dtype="float32", variant="pinned"):
+    """dict(cons_hash: bits_hash of the positive offset planes, score (Z, Y, X), aff [rows]) of the cell; the clean
+    variant: cons_hash only"""
+    if variant == CLEAN:
+        k = (shape_name, flag_name, dtype, CLEAN)
+        if k not in _OUT:
+            assert v3_serves(flag_name)
+            _oracle_s1_clean(shape_name, dtype, s1_key(flag_name), _representative(s1_key(flag_name)))
+        return _OUT[k]
+    assert variant == PINNED
     k = (shape_name, flag_name, dtype)
     if k not in _OUT:
         a = _s1_args(*k)
@@ -287,8 +389,12 @@ def _representative(key):
     return next(n for n in FLAG_SETS if s1_key(n) == key)
 
 
-def oracle_cons_planes(shape_name, flag_name, dtype="float32"):
+def oracle_cons_planes(shape_name, flag_name, dtype="float32", variant="pinned"):
     """the positive offset planes [planes, Z, Y, X] (the compact device layout) of the cell's consensus"""
+    if variant == CLEAN:
+        assert v3_serves(flag_name)
+        return _oracle_s1_clean(shape_name, dtype, s1_key(flag_name), _representative(s1_key(flag_name)))
+    assert variant == PINNED
     a = _s1_args(shape_name, flag_name, dtype)
     return orc.positive_planes(_oracle_s1(*a[:4], _representative(a[3])), SHAPES[shape_name][0])
 

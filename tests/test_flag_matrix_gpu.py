@@ -37,6 +37,8 @@ S1 = {
     "v3_vm": dict(env={}, cells={"p5": ALL}, rot="p5", v3=True),
     "lists": dict(env={}, cells={"p5": ALL}, rot="p5", v3=True),
     "wide": dict(env={}, cells={"w25": ALL}, rot="w25"),
+    # the packed kernel's one-line-per-run form (every matrix shape takes the flat form by the rule)
+    "v3_line": dict(env={"PPP_S1_FLAT": "0"}, cells={s: ALL for s in CUBIC + ("p357",)}, rot="p7", v3=True),
 }
 S2 = {
     "rank_generic": dict(env={"PPP_RANK_GENERIC": "1"}, cells={"p3": ALL}, rot="p3"),
@@ -162,14 +164,14 @@ def test_s1_family_matches_oracle(fam, shape, flag, dtype, torch_cuda, monkeypat
     name = lambda: L.ppp_consensus_kernel_name().decode()      # noqa: E731
     Pv = P.copy()
     Pv.cons_layout = backend.CONS_VOXEL_MAJOR
-    if fam in ("v3", "v3_vm", "lists"):
+    if fam in ("v3", "v3_line", "v3_vm", "lists"):
         assert L.ppp_consensus_writes_voxel_major(ctypes.byref(Pv)) == (1 if fm.v3_serves(flag) else 0)
     if fam in ("gather", "gather11", "v2_line", "v2_flat", "v2_general", "wide"):
         cons = backend.consensus(pred, ov, P)
         assert name() == {"gather": "consensus_gather_kernel", "gather11": "consensus_gather_kernel",
                           "wide": "consensus_wide_kernel"}.get(fam, "consensus_v2_kernel")
         _same_cons(torch, cons, shape, flag, dtype, what)
-    elif fam == "v3":
+    elif fam in ("v3", "v3_line"):
         cons = backend.consensus(pred, ov, P)
         # refused: the general kernel of the line-run family serves, and is the oracle's too
         assert name() == ("consensus_v3_kernel" if fm.v3_serves(flag) else "consensus_v2_kernel")

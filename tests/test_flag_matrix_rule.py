@@ -170,3 +170,151 @@ def test_the_oracle_tells_the_flag_sets_apart(shape_name):
             # entry -q of voxel v is entry +q of voxel v - q
             q, L = (1, -2, 1), (1 * 5 + -2) * 5 + 1
             assert np.array_equal(vm[1:, :-2, 1:, W // 2 - L], vm[:-1, 2:, :-1, W // 2 + L])
+
+
+# ---- the clean variant (tests/test_s1_clean_gpu.py) -----------------------------------------------------------------
+SERVED = [n for n in fm.FLAG_SETS if fm.v3_serves(n)]
+V3_SHAPES = [s for s in fm.SHAPES if fm.SHAPES[s][0][2] in (3, 5, 7, 9)]
+
+
+@pytest.mark.parametrize("shape_name", list(fm.SHAPES))
+def test_existing_predictions_are_unclean(shape_name):
+    """Every existing prediction holds a value the float 0.5 of the packed kernel's class tests calls unclean, and
+    every existing cell that kernel serves is unclean under its own thresholds (ppp_pred_check by its model): the
+    existing cells of the packed kernel keep running its general classification.  (A set whose threshold no float
+    equals -- inv03: 0.3 -- can be clean under its own tests; nothing that serves it reads pred_clean.)"""
+    for dtype in fm.DTYPES:
+        for name in SERVED + ["half05"]:         # every set with a class test at 0.5
+            g = fm.geo_flags(name, shape_name)
+            assert 0.5 in (g["th"], g["bg"])
+            bits = fm.is_clean(fm.prediction(shape_name, name, dtype), dtype, g["th"], g["bg"])
+            assert bits == (3 if shape_name == "p9" else 2), (name, dtype, bits)       # (p9: the one negative zero)
+    assert [n for n in fm.FLAG_SETS if 0.5 in (fm.geo_flags(n)["th"], fm.geo_flags(n)["bg"])] == \
+        [n for n in fm.FLAG_SETS if n in SERVED + ["half05"]]
+
+
+def test_the_model_of_the_check_knows_its_classes():
+    for dtype in fm.DTYPES:
+        up, down = (lambda v: fm._step(np.float32(v), dtype, True)), (lambda v: fm._step(np.float32(v), dtype, False))
+        one = lambda v, th=0.5, bg=0.5: fm.is_clean(np.array([0.75, v, 0.125], dtype=np.float32), dtype, th, bg)   # noqa: E731
+        for v in (0.0, fm.smallest(dtype)[0], fm.smallest(dtype)[1], down(0.5), up(0.5), down(1.0), 1.0):
+            assert one(v) == 0, (dtype, v)
+        for v in (up(1.0), 2.0, np.inf, -0.0, -fm.smallest(dtype)[0], -1.0, -np.inf):
+            assert one(v) == 1, (dtype, v)
+        assert one(0.5) == 2 and one(np.nan) == 3 and one(-np.nan) == 3
+        assert [one(v, 0.5, 0.25) for v in (down(0.25), 0.25, 0.375, down(0.5), 0.5, up(0.5))] == [0, 2, 2, 2, 2, 0]
+
+
+@pytest.mark.parametrize("dtype", fm.DTYPES)
+def test_clean_pins_are_what_the_short_classification_can_get_wrong(dtype):
+    pins = [float(v) for v in fm.clean_pins(dtype)]
+    assert len(pins) == 9 <= fm.MAX_PINS and pins == sorted(pins) and 0.5 not in pins
+    st = lambda v, up: float(fm._step(np.float32(v), dtype, up))       # noqa: E731
+    sub, normal = (float(v) for v in fm.smallest(dtype))
+    assert set(pins) == {0.0, sub, normal, st(st(0.5, False), False), st(0.5, False), st(0.5, True),
+                         st(st(0.5, True), True), st(1.0, False), 1.0}
+    assert 0.0 < sub < normal and st(0.0, True) == sub and st(normal, False) < normal
+    man = {"float32": 23, "float16": 10, "bfloat16": 7}[dtype]
+    assert st(normal, False) == normal - sub and sub == normal * 2.0 ** -man          # the largest subnormal precedes it
+    assert all(float(fm.to_dtype(np.array([v], dtype=np.float32), dtype)[0]) == v for v in pins)      # representable
+
+
+@pytest.mark.parametrize("shape_name", V3_SHAPES)
+def test_clean_predictions_are_clean_and_hold_the_pins(shape_name):
+    inner = fm.interior_mask(shape_name)
+    mid_ch = int(np.prod(fm.SHAPES[shape_name][0])) // 2
+    for dtype in fm.DTYPES:
+        pred = fm.prediction(shape_name, "default", dtype, fm.CLEAN)
+        for name in SERVED:                     # (one prediction per shape and dtype, whatever the served set)
+            assert fm.prediction(shape_name, name, dtype, fm.CLEAN) is pred
+            g = fm.geo_flags(name, shape_name)
+            assert (g["th"], g["bg"]) == (0.5, 0.5)
+        assert fm.is_clean(pred, dtype, 0.5, 0.5) == 0
+        assert pred.dtype == np.float32 and not np.signbit(pred).any() and pred.max() <= 1
+        assert np.array_equal(_bits(pred), _bits(fm.to_dtype(pred, dtype)))                # narrows exactly
+        pat, one = fm.dtype_patterns(pred, dtype)
+        assert pat.max() == one
+        mid, rest = pred[mid_ch], np.delete(pred, mid_ch, axis=0)        # (rest: every other channel)
+        for v in fm.clean_pins(dtype):
+            assert np.count_nonzero(mid[inner] == v) >= 20, (dtype, v)
+            assert np.count_nonzero(rest == v) >= 20, (dtype, v)
+        # apart from the pins (and the sign of zero) it is the existing cells' base prediction
+        base = fm.to_dtype(fm.base_case(shape_name)["pred"], dtype)
+        same = _bits(pred) == _bits(base)
+        assert 0.85 < np.count_nonzero(same) / same.size < 0.95
+    with pytest.raises(AssertionError):
+        fm.prediction(shape_name, "half05", "float32", fm.CLEAN)          # nothing but the packed kernel reads pred_clean
+    # the existing variant keeps its bits: the one negative zero of the 9^3 base included
+    neg0 = sum(int(np.count_nonzero(np.signbit(fm.base_case(s)["pred"]))) for s in fm.SHAPES)
+    assert neg0 == 1 and np.count_nonzero(np.signbit(fm.base_case("p9")["pred"])) == 1
+
+
+def _moved(shape_name, dtype, src, dst):
+    """the clean-variant hash for `default` with every value src of the prediction replaced by dst"""
+    b = fm.base_case(shape_name)
+    pred = np.array(fm.prediction(shape_name, "default", dtype, fm.CLEAN))
+    assert np.count_nonzero(pred == src) >= 40
+    pred[pred == src] = dst
+    cons = orc.consensus_planes(pred, b["overlap"], b["ps"], **fm.FLAG_SETS["default"])
+    return fm.bits_hash(orc.positive_planes(cons, b["ps"]))
+
+
+@pytest.mark.parametrize("shape_name", ("p3", "p5", "p357"))
+def test_the_neighbours_of_the_threshold_matter(shape_name):
+    """A kernel that puts the nearest value below 0.5 on the other side (or the nearest above) cannot pass: the
+    oracle's hash changes.  And the four S1 flag keys among the served sets give four hashes."""
+    for dtype in fm.DTYPES:
+        below, above = fm.around(0.5, dtype)[0], fm.around(0.5, dtype)[2]
+        h = fm.oracle(shape_name, "default", dtype, fm.CLEAN)["cons_hash"]
+        assert set(fm.oracle(shape_name, "default", dtype, fm.CLEAN)) == {"cons_hash"}      # S1 only
+        planes = fm.oracle_cons_planes(shape_name, "default", dtype, fm.CLEAN)
+        assert fm.bits_hash(planes) == h and np.count_nonzero(planes) >= 1000
+        assert _moved(shape_name, dtype, below, above) != h, (dtype, "below -> above")
+        assert _moved(shape_name, dtype, above, below) != h, (dtype, "above -> below")
+        by_key = {}
+        for name in SERVED:
+            by_key.setdefault(fm.s1_key(name), set()).add(fm.oracle(shape_name, name, dtype, fm.CLEAN)["cons_hash"])
+        assert len(by_key) == 4 and all(len(v) == 1 for v in by_key.values())
+        assert len(set.union(*by_key.values())) == 4
+        assert {fm.s1_key(n) for n in ("default", "raw", "noov", "nonorm_s1")} == set(by_key)
+        assert fm.oracle(shape_name, "inv05", dtype, fm.CLEAN)["cons_hash"] == h
+        # ... and is another array than the existing cell's
+        if dtype == "float32":
+            assert fm.oracle(shape_name, "default", dtype)["cons_hash"] != h
+    # the serial scatter form of the oracle agrees on the clean prediction too
+    b = fm.base_case(shape_name)
+    serial = orc.consensus(fm.prediction(shape_name, "default", "bfloat16", fm.CLEAN), b["overlap"], b["ps"], **fm.FLAG_SETS["default"])
+    assert fm.bits_hash(orc.positive_planes(serial, b["ps"])) == fm.oracle(shape_name, "default", "bfloat16", fm.CLEAN)["cons_hash"]
+
+
+def test_every_instantiation_of_the_packed_kernel_is_met():
+    """consensus_v3_kernel<T, PX, FLAT, CLEAN, dense / lists>: every combination with CLEAN = true meets a cell of
+    tests/test_s1_clean_gpu.py, every (PX, FLAT) with CLEAN = false a cell of the existing matrix."""
+    import test_flag_matrix_gpu as mg
+    import test_s1_clean_gpu as cg
+    want = set(itertools.product(fm.DTYPES, (3, 5, 7, 9), (True, False), (False, True)))
+    forms = [cg.cell_form(c) for c in cg.CELLS]
+    clean = {f[:4] for f in forms if f[4]}
+    assert clean == want
+    assert len(cg.CELLS) == len(set(cg.CELLS)) and 250 <= len(cg.CELLS) <= 320
+    assert all(fm.v3_serves(c[2]) for c in cg.CELLS)
+    # the general classification on every clean prediction: every shape, every dtype
+    assert {(c[1], c[3]) for c, f in zip(cg.CELLS, forms) if not f[4]} == set(itertools.product(cg.FIVE, fm.DTYPES))
+    # the four S1 keys under both dense forms and the lists, in every dtype and at every shape
+    keys = {fm.s1_key(n) for n in cg.SERVED}
+    assert len(keys) == 4 and {fm.s1_key(n) for n in cg.KEYS} == keys and len(cg.KEYS) == 4 and len(cg.SERVED) == 8
+    for fam in ("v3c_flat", "v3c_line", "lists_c"):
+        have = {(c[1], c[3], fm.s1_key(c[2])) for c in cg.CELLS if c[0] == fam}
+        assert have == set(itertools.product(cg.FIVE, fm.DTYPES, keys)), fam
+    assert {c[2] for c in cg.CELLS if c[0] == "v3c_flat" and c[3] == "float32"} == set(cg.SERVED)
+    # the boxes that take their form by the rule
+    assert {cg.part_form(*c)[1:4] for c in cg.PART_CELLS} == set(itertools.product((5, 7), (True, False), (False,)))
+    # CLEAN = false: the existing matrix's cells of the packed kernel (all unclean, see above)
+    unclean = set()
+    for fam, shape, name, dtype in mg.S1_CELLS:
+        if fam in ("v3", "v3_line", "v3_vm", "lists") and fm.v3_serves(name):
+            unclean.add((fm.SHAPES[shape][0][2], fm.v3_flat_form(shape, mg.S1[fam]["env"])))
+    assert unclean == set(itertools.product((3, 5, 7, 9), (True, False)))
+    # ... and its earlier ids are all still there
+    assert len(mg.S1_CELLS) == len(set(mg.S1_CELLS))
+    assert sum(c[0] == "v3_line" for c in mg.S1_CELLS) == 5 * len(fm.FLAG_SETS) + 4
