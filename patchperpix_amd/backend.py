@@ -1676,68 +1676,86 @@ def thin_cover_device(mask, bits, lin, P, slice_interior=None):
     return keep[:n].bool()
 
 
-class CoverShard:
+class _RoundShard:
+    """What one rank's share of the cover rounds and of the thinning rounds have in common: the steps of a
+    round, the zones and the end, over the entry points ppp_<ENTRY>_step / _alive / _zone / _close."""
+    COUNT, FILTER, SELECT = 0, 1, 2
+    ENTRY = TIMER = None
+
+    def __init__(self, mask, lin_local, bits, P, global_z, work_bytes):
+        self.P, self.mask, self.bits = P, mask, bits
+        self.lin = lin_local.contiguous()
+        self.n = int(lin_local.numel())
+        self.gz = int(global_z)
+        self.work = _workspace(work_bytes, mask.device)
+
+    def _entry(self, name):
+        return getattr(lib(), "ppp_%s_%s" % (self.ENTRY, name))
+
+    def step(self, what, *args):
+        """what: COUNT / FILTER / SELECT; args: the subclass's (_step_lists)"""
+        with _timed(self.TIMER):
+            check(self._entry("step")(int(what), _dev_ptr(self.bits), *self._step_lists(*args), _dev_ptr(self.work),
+                                      self.gz, ctypes.byref(self.P), _stream()))
+
+    def alive(self):
+        a = ctypes.c_int32(0)
+        check(self._entry("alive")(_dev_ptr(self.work), ctypes.byref(self.P), _stream(), ctypes.byref(a)))
+        return a.value != 0
+
+    def zone(self, imp, z_lo, z_hi, own, key=None, mask=None, clean=None, rank=None):
+        """key (int32 ranks in the cover, int64 keys in the thinning) or mask + clean: the buffers of the local
+        slices [z_lo, z_hi), written (imp false; key "not mine" outside the own slices `own`) or read.
+        rank: the cover's earlier name of `key`, still accepted."""
+        key = rank if key is None else key
+        with _timed(self.TIMER):
+            check(self._entry("zone")(1 if imp else 0, _dev_ptr(self.work), int(z_lo), int(z_hi), int(own[0]),
+                                      int(own[1]), _dev_ptr(key), _dev_ptr(mask), _dev_ptr(clean),
+                                      ctypes.byref(self.P), _stream()))
+
+    def close(self):
+        with _timed(self.TIMER):
+            check(self._entry("close")(_dev_ptr(self.mask), _dev_ptr(self.work), ctypes.byref(self.P), _stream()))
+
+
+class CoverShard(_RoundShard):
     """One rank's share of the greedy cover rounds (ppp_cover_open / _step / _zone / _close):
     local mask uint8 (Zl, Y, X) device tensor (own slices + halo), the own ranked patches (local
     linear indices, global ranks, local bit table), local params with origin_z = first slice."""
-    COUNT, FILTER, SELECT = 0, 1, 2
+    ENTRY, TIMER = "cover", "cover"
 
     def __init__(self, mask, lin_local, rank_id, bits, P, global_z):
-        torch = _torch()
-        self.torch, self.P, self.mask = torch, P, mask
-        self.lin, self.rank_id, self.bits = lin_local.contiguous(), rank_id.contiguous(), bits
-        self.n = int(lin_local.numel())
-        self.gz = int(global_z)
-        self.work = _workspace(lib().ppp_cover_workspace_bytes(self.n, ctypes.byref(P)), mask.device)
+        super().__init__(mask, lin_local, bits, P, global_z,
+                         lib().ppp_cover_workspace_bytes(int(lin_local.numel()), ctypes.byref(P)))
+        self.rank_id = rank_id.contiguous()
         self.state = self.cleared = None
 
     def open(self, state):
         """state int32 [n]: 0 takes part, 1 selected in an earlier pass, 2 never."""
+        torch = _torch()
         self.state = state.contiguous()
-        self.cleared = self.torch.empty(max(self.n, 1), dtype=self.torch.int32, device=self.mask.device)
+        self.cleared = torch.empty(max(self.n, 1), dtype=torch.int32, device=self.mask.device)
         with _timed("cover"):
             check(lib().ppp_cover_open(_dev_ptr(self.mask), _dev_ptr(self.lin), _dev_ptr(self.rank_id),
                                        self.n, _dev_ptr(self.state), _dev_ptr(self.cleared),
                                        _dev_ptr(self.work), ctypes.byref(self.P), _stream()))
 
-    def step(self, what, pix_th=0):
-        with _timed("cover"):
-            check(lib().ppp_cover_step(int(what), _dev_ptr(self.bits), int(pix_th), _dev_ptr(self.state),
-                                       _dev_ptr(self.cleared), _dev_ptr(self.work), self.gz,
-                                       ctypes.byref(self.P), _stream()))
-
-    def alive(self):
-        a = ctypes.c_int32(0)
-        check(lib().ppp_cover_alive(_dev_ptr(self.work), ctypes.byref(self.P), _stream(), ctypes.byref(a)))
-        return a.value != 0
-
-    def zone(self, imp, z_lo, z_hi, own, rank=None, mask=None, clean=None):
-        with _timed("cover"):
-            check(lib().ppp_cover_zone(1 if imp else 0, _dev_ptr(self.work), int(z_lo), int(z_hi),
-                                       int(own[0]), int(own[1]), _dev_ptr(rank), _dev_ptr(mask),
-                                       _dev_ptr(clean), ctypes.byref(self.P), _stream()))
-
-    def close(self):
-        with _timed("cover"):
-            check(lib().ppp_cover_close(_dev_ptr(self.mask), _dev_ptr(self.work), ctypes.byref(self.P),
-                                        _stream()))
+    def _step_lists(self, pix_th=0):
+        return int(pix_th), _dev_ptr(self.state), _dev_ptr(self.cleared)
 
 
-class ThinShard:
+class ThinShard(_RoundShard):
     """One rank's share of the set-cover thinning rounds (ppp_thin_open / _step / _zone / _close; round 6):
     local mask uint8 (Zl, Y, X) device tensor (own slices + halo), the own selected patches (local linear
     indices, positions in the global selected list, local bit table), local params with origin_z = first
     slice.  After the rounds: state (1 = kept), count (voxels covered when kept), cleared (interior ones)."""
-    COUNT, FILTER, SELECT = 0, 1, 2
+    ENTRY, TIMER = "thin", "thin_cover"
 
     def __init__(self, mask, lin_local, index_global, bits, P, global_z):
         torch = _torch()
-        self.P, self.mask, self.bits = P, mask, bits
-        self.lin, self.index = lin_local.contiguous(), index_global.to(torch.int32).contiguous()
-        self.n = int(lin_local.numel())
-        self.gz = int(global_z)
+        super().__init__(mask, lin_local, bits, P, global_z, lib().ppp_thin_shard_workspace_bytes(ctypes.byref(P)))
+        self.index = index_global.to(torch.int32).contiguous()
         dev = mask.device
-        self.work = _workspace(lib().ppp_thin_shard_workspace_bytes(ctypes.byref(P)), dev)
         self.state = torch.empty(max(self.n, 1), dtype=torch.int32, device=dev)
         self.count = torch.empty(max(self.n, 1), dtype=torch.int32, device=dev)
         self.cleared = torch.empty(max(self.n, 1), dtype=torch.int32, device=dev)
@@ -1746,26 +1764,8 @@ class ThinShard:
                                       _dev_ptr(self.state), _dev_ptr(self.count), _dev_ptr(self.cleared),
                                       _dev_ptr(self.work), ctypes.byref(self.P), _stream()))
 
-    def step(self, what):
-        with _timed("thin_cover"):
-            check(lib().ppp_thin_step(int(what), _dev_ptr(self.bits), _dev_ptr(self.state), _dev_ptr(self.count),
-                                      _dev_ptr(self.cleared), _dev_ptr(self.work), self.gz, ctypes.byref(self.P),
-                                      _stream()))
-
-    def alive(self):
-        a = ctypes.c_int32(0)
-        check(lib().ppp_thin_alive(_dev_ptr(self.work), ctypes.byref(self.P), _stream(), ctypes.byref(a)))
-        return a.value != 0
-
-    def zone(self, imp, z_lo, z_hi, own, key=None, mask=None, clean=None):
-        with _timed("thin_cover"):
-            check(lib().ppp_thin_zone(1 if imp else 0, _dev_ptr(self.work), int(z_lo), int(z_hi), int(own[0]),
-                                      int(own[1]), _dev_ptr(key), _dev_ptr(mask), _dev_ptr(clean),
-                                      ctypes.byref(self.P), _stream()))
-
-    def close(self):
-        with _timed("thin_cover"):
-            check(lib().ppp_thin_close(_dev_ptr(self.mask), _dev_ptr(self.work), ctypes.byref(self.P), _stream()))
+    def _step_lists(self):
+        return _dev_ptr(self.state), _dev_ptr(self.count), _dev_ptr(self.cleared)
 
 
 def synth_pred(labels, P, seed=0, hi=0.95, lo=0.05, noise=0.04, f16=True, voxel_offset=0):

@@ -1236,38 +1236,55 @@ int ppp_cover_step(int32_t what, const uint32_t *d_bits, int32_t pix_th, int32_t
     if (!d_work) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
     hipError_t e;
     if (what == PPP_COVER_COUNT) e = ppp::cover_step_count(d_bits, pix_th, d_state, d_work, G, (hipStream_t)stream);
-    else if (what == PPP_COVER_FILTER) e = ppp::cover_step_filter(d_work, G, (hipStream_t)stream);
+    else if (what == PPP_COVER_FILTER) e = ppp::round_step_filter<int32_t>(d_work, G, (hipStream_t)stream);
     else if (what == PPP_COVER_SELECT) e = ppp::cover_step_select(d_bits, pix_th, d_state, d_cleared, d_work, global_z, G, (hipStream_t)stream);
     else return fail(PPP_ERR_INVALID_ARG, "unknown cover step %d", what);
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_cover_step");
 }
 
-int ppp_cover_alive(void *d_work, const ppp_params *p, void *stream, int32_t *alive) {
+/* alive, close and zone are the same steps for the cover (32-bit ranks) and the thinning (64-bit keys) */
+static int round_alive(bool thin, void *d_work, const ppp_params *p, void *stream, int32_t *alive) {
     ppp::Geo G;
     PPP_TRY(cover_geo(p, &G));
     if (!d_work || !alive) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
-    hipError_t e = ppp::cover_alive(d_work, G, alive, (hipStream_t)stream);
-    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_cover_alive");
+    hipError_t e = thin ? ppp::round_alive<long long>(d_work, G, alive, (hipStream_t)stream)
+                        : ppp::round_alive<int32_t>(d_work, G, alive, (hipStream_t)stream);
+    return e == hipSuccess ? PPP_OK : hip_fail(e, thin ? "ppp_thin_alive" : "ppp_cover_alive");
 }
 
-int ppp_cover_close(uint8_t *d_mask, void *d_work, const ppp_params *p, void *stream) {
+static int round_close(bool thin, uint8_t *d_mask, void *d_work, const ppp_params *p, void *stream) {
     ppp::Geo G;
     PPP_TRY(cover_geo(p, &G));
     if (!d_mask || !d_work) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
-    hipError_t e = ppp::cover_close(d_mask, d_work, G, (hipStream_t)stream);
-    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_cover_close");
+    hipError_t e = thin ? ppp::round_close<long long>(d_mask, d_work, G, (hipStream_t)stream)
+                        : ppp::round_close<int32_t>(d_mask, d_work, G, (hipStream_t)stream);
+    return e == hipSuccess ? PPP_OK : hip_fail(e, thin ? "ppp_thin_close" : "ppp_cover_close");
+}
+
+static int round_zone(bool thin, int32_t import, void *d_work, int32_t z_lo, int32_t z_hi, int32_t own_lo, int32_t own_hi,
+                      void *d_key, uint8_t *d_mask, uint8_t *d_clean, const ppp_params *p, void *stream) {
+    ppp::Geo G;
+    PPP_TRY(cover_geo(p, &G));
+    if (!d_work || z_lo < 0 || z_hi > G.Z || z_lo > z_hi || ((d_mask == nullptr) != (d_clean == nullptr)))
+        return fail(PPP_ERR_INVALID_ARG, "bad zone");
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = thin ? ppp::round_zone(import != 0, d_work, z_lo, z_hi, own_lo, own_hi, (long long *)d_key, d_mask, d_clean, G, s)
+                        : ppp::round_zone(import != 0, d_work, z_lo, z_hi, own_lo, own_hi, (int32_t *)d_key, d_mask, d_clean, G, s);
+    return e == hipSuccess ? PPP_OK : hip_fail(e, thin ? "ppp_thin_zone" : "ppp_cover_zone");
+}
+
+int ppp_cover_alive(void *d_work, const ppp_params *p, void *stream, int32_t *alive) {
+    return round_alive(false, d_work, p, stream, alive);
+}
+
+int ppp_cover_close(uint8_t *d_mask, void *d_work, const ppp_params *p, void *stream) {
+    return round_close(false, d_mask, d_work, p, stream);
 }
 
 int ppp_cover_zone(int32_t import, void *d_work, int32_t z_lo, int32_t z_hi, int32_t own_lo,
                    int32_t own_hi, int32_t *d_rank, uint8_t *d_mask, uint8_t *d_clean,
                    const ppp_params *p, void *stream) {
-    ppp::Geo G;
-    PPP_TRY(cover_geo(p, &G));
-    if (!d_work || z_lo < 0 || z_hi > G.Z || z_lo > z_hi || ((d_mask == nullptr) != (d_clean == nullptr)))
-        return fail(PPP_ERR_INVALID_ARG, "bad zone");
-    hipError_t e = import ? ppp::cover_zone_import(d_work, z_lo, z_hi, d_rank, d_mask, d_clean, G, (hipStream_t)stream)
-                          : ppp::cover_zone_export(d_work, z_lo, z_hi, own_lo, own_hi, d_rank, d_mask, d_clean, G, (hipStream_t)stream);
-    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_cover_zone");
+    return round_zone(false, import, d_work, z_lo, z_hi, own_lo, own_hi, d_rank, d_mask, d_clean, p, stream);
 }
 
 /* ---- sharded thinning: the rounds of ppp_thin_cover one step at a time on a rank's z-range ---- */
@@ -1295,37 +1312,23 @@ int ppp_thin_step(int32_t what, const uint32_t *d_bits, int32_t *d_state, int32_
     if (!d_work) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
     hipError_t e;
     if (what == PPP_COVER_COUNT) e = ppp::thin_step_count(d_bits, d_state, d_work, G, (hipStream_t)stream);
-    else if (what == PPP_COVER_FILTER) e = ppp::thin_step_filter(d_work, G, (hipStream_t)stream);
+    else if (what == PPP_COVER_FILTER) e = ppp::round_step_filter<long long>(d_work, G, (hipStream_t)stream);
     else if (what == PPP_COVER_SELECT) e = ppp::thin_step_select(d_bits, d_state, d_count, d_cleared, d_work, global_z, G, (hipStream_t)stream);
     else return fail(PPP_ERR_INVALID_ARG, "unknown thinning step %d", what);
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_thin_step");
 }
 
 int ppp_thin_alive(void *d_work, const ppp_params *p, void *stream, int32_t *alive) {
-    ppp::Geo G;
-    PPP_TRY(cover_geo(p, &G));
-    if (!d_work || !alive) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
-    hipError_t e = ppp::thin_alive(d_work, G, alive, (hipStream_t)stream);
-    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_thin_alive");
+    return round_alive(true, d_work, p, stream, alive);
 }
 
 int ppp_thin_close(uint8_t *d_mask, void *d_work, const ppp_params *p, void *stream) {
-    ppp::Geo G;
-    PPP_TRY(cover_geo(p, &G));
-    if (!d_mask || !d_work) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
-    hipError_t e = ppp::thin_close(d_mask, d_work, G, (hipStream_t)stream);
-    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_thin_close");
+    return round_close(true, d_mask, d_work, p, stream);
 }
 
 int ppp_thin_zone(int32_t import, void *d_work, int32_t z_lo, int32_t z_hi, int32_t own_lo, int32_t own_hi,
                   int64_t *d_key, uint8_t *d_mask, uint8_t *d_clean, const ppp_params *p, void *stream) {
-    ppp::Geo G;
-    PPP_TRY(cover_geo(p, &G));
-    if (!d_work || z_lo < 0 || z_hi > G.Z || z_lo > z_hi || ((d_mask == nullptr) != (d_clean == nullptr)))
-        return fail(PPP_ERR_INVALID_ARG, "bad zone");
-    hipError_t e = import ? ppp::thin_zone_import(d_work, z_lo, z_hi, (const long long *)d_key, d_mask, d_clean, G, (hipStream_t)stream)
-                          : ppp::thin_zone_export(d_work, z_lo, z_hi, own_lo, own_hi, (long long *)d_key, d_mask, d_clean, G, (hipStream_t)stream);
-    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_thin_zone");
+    return round_zone(true, import, d_work, z_lo, z_hi, own_lo, own_hi, d_key, d_mask, d_clean, p, stream);
 }
 
 /* ---- post-steps of the label driver (ppp_postprocess.hip) ---- */

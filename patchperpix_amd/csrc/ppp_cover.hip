@@ -51,6 +51,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <limits>
 #include <vector>
 
 #include "ppp_kernels.hpp"
@@ -60,11 +61,16 @@ namespace ppp {
 static constexpr int32_t RANK_NONE = 0x7F7F7F7F;
 static constexpr int COVER_BATCH = 8;   // rounds per host synchronisation
 
-struct CoverWork {
-    int32_t *rank_vol, *nbr_min, *tmp;   // [V] each
+// What a round works on, over the key type K: int32_t ranks in the greedy cover, long long keys in the
+// thinning.  The head of every cover / thinning workspace (round_layout): a launcher that needs nothing
+// else -- filter, alive, close, zones -- carves only this and serves both.
+template <typename K> struct RoundArrays {
+    K *key_vol, *nbr_min, *tmp;          // [V] each
     uint8_t *dirty;                      // [V]
     uint32_t *mbits;                     // [Z*Y][XW] running mask, one bit per voxel
     int32_t *counters;                   // [COVER_BATCH]
+};
+struct CoverWork : RoundArrays<int32_t> {
     int32_t *loc_vol;                    // [V] sharded cover only: index into the rank's own
                                          // state / cleared / bits tables, -1 off the own centres
     uint16_t *witness;                   // [V] pix_th == 0: ONE voxel of the window that the patch
@@ -741,15 +747,25 @@ __global__ void __launch_bounds__(256)
                             bits_vox, mark_dirty, mark_bits, G);
 }
 
-// (the same layout serves run_cover_pass and the sharded steps; n does not enter it)
-static CoverWork cover_layout(Carver &c, const Geo &G) {
-    CoverWork W;
-    W.rank_vol = c.take<int32_t>(G.V);
-    W.nbr_min = c.take<int32_t>(G.V);
-    W.tmp = c.take<int32_t>(G.V);
+template <typename K> static void round_layout(Carver &c, const Geo &G, RoundArrays<K> &W) {
+    W.key_vol = c.take<K>(G.V);
+    W.nbr_min = c.take<K>(G.V);
+    W.tmp = c.take<K>(G.V);
     W.dirty = c.take<uint8_t>(G.V);
     W.mbits = c.take<uint32_t>((size_t)G.Z * G.Y * row_words(G));
     W.counters = (int32_t *)c.take_bytes(256);
+}
+template <typename K> static RoundArrays<K> carve_round(void *work, const Geo &G) {
+    Carver c(work);
+    RoundArrays<K> W;
+    round_layout(c, G, W);
+    return W;
+}
+
+// (the same layout serves run_cover_pass and the sharded steps; n does not enter it)
+static CoverWork cover_layout(Carver &c, const Geo &G) {
+    CoverWork W;
+    round_layout(c, G, W);
     W.loc_vol = c.take<int32_t>(G.V);
     W.witness = c.take<uint16_t>(G.V);
     return W;
@@ -767,14 +783,14 @@ hipError_t run_cover_pass(uint8_t *mask, const uint32_t *bits, long long bits_vo
     if (mark_bits && (G.Y < 2 * MARK_R + 1 || G.X < 2 * MARK_R + 1)) return hipErrorNotSupported;
     CoverWork W = carve(work, G);
     hipError_t e;
-    if ((e = hipMemsetD32Async((hipDeviceptr_t)W.rank_vol, RANK_NONE, (size_t)G.V, s)) != hipSuccess) return e;
+    if ((e = hipMemsetD32Async((hipDeviceptr_t)W.key_vol, RANK_NONE, (size_t)G.V, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(W.dirty, 1, (size_t)G.V, s)) != hipSuccess) return e;   // count everything once
     if ((e = hipMemsetAsync(W.witness, 0xFF, (size_t)G.V * 2, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(cleared, 0, (size_t)n * 4, s)) != hipSuccess) return e;
     const dim3 vgrid((unsigned)((G.V + 255) / 256)), block(256);
     const long long n_words = (long long)G.Z * G.Y * row_words(G);
     cover_pack_kernel<<<dim3((unsigned)((n_words + 255) / 256)), block, 0, s>>>(mask, W.mbits, G);
-    cover_init_kernel<<<dim3((unsigned)((n + 255) / 256)), block, 0, s>>>(lin, state, (int)n, W.rank_vol);
+    cover_init_kernel<<<dim3((unsigned)((n + 255) / 256)), block, 0, s>>>(lin, state, (int)n, W.key_vol);
     int32_t n_alive = 1;
     while (n_alive > 0) {
         if ((e = hipMemsetAsync(W.counters, 0, COVER_BATCH * 4, s)) != hipSuccess) return e;
@@ -783,18 +799,18 @@ hipError_t run_cover_pass(uint8_t *mask, const uint32_t *bits, long long bits_vo
         for (int r = 0; r < COVER_BATCH; ++r) {
             if (mark_bits)
                 cover_marktest_kernel<<<dim3((unsigned)((G.V + 256 * MARKTEST_VPT - 1) / (256 * MARKTEST_VPT))), block, 0, s>>>(
-                    mark_bits, state, W.rank_vol, G);
-            cover_count_kernel<<<cgrid, cblock, 0, s>>>(W.mbits, bits, W.dirty, pix_th, state, W.rank_vol,
+                    mark_bits, state, W.key_vol, G);
+            cover_count_kernel<<<cgrid, cblock, 0, s>>>(W.mbits, bits, W.dirty, pix_th, state, W.key_vol,
                                                        W.counters + r, nullptr, witness_ok(G) ? W.witness : nullptr, bits_vox, G);
             // x, y, z; radius p-1: two windows overlap iff |dc| <= p-1 on every axis
             if (!mark_bits) {
-                minfilter_xy<int32_t>(W.rank_vol, W.tmp, W.nbr_min, G, s);
-                cover_select_kernel<<<select_grid(G), block, 0, s>>>(W.mbits, bits, W.nbr_min, state, W.rank_vol, cleared,
+                minfilter_xy<int32_t>(W.key_vol, W.tmp, W.nbr_min, G, s);
+                cover_select_kernel<<<select_grid(G), block, 0, s>>>(W.mbits, bits, W.nbr_min, state, W.key_vol, cleared,
                                                             W.dirty, nullptr, G.Z + G.oz, bits_vox, mark_dirty, G);
             } else {
                 // (with marks: y / x radius max(p - 1, 3), see mark_box_row)
-                minfilter_xy<int32_t>(W.rank_vol, W.tmp, W.nbr_min, G, mark_radius(G.px), mark_radius(G.py), s);
-                cover_select_marked_kernel<<<select_grid(G), block, 0, s>>>(W.mbits, bits, W.nbr_min, state, W.rank_vol,
+                minfilter_xy<int32_t>(W.key_vol, W.tmp, W.nbr_min, G, mark_radius(G.px), mark_radius(G.py), s);
+                cover_select_marked_kernel<<<select_grid(G), block, 0, s>>>(W.mbits, bits, W.nbr_min, state, W.key_vol,
                                                                    cleared, W.dirty, bits_vox, mark_dirty, mark_bits, G);
             }
         }
@@ -922,29 +938,13 @@ hipError_t run_mask_dilate(const uint8_t *in, uint8_t *out, int iterations, int 
 static constexpr long long THIN_NONE = FilterNone<long long>::value;
 static constexpr long long THIN_MAXC = 1ll << 20;
 
-// what the one-device thinning and its sharded form both keep per volume; the head of both workspaces
-struct ThinVolumes {
-    long long *key_vol, *nbr_min, *tmp;  // [V] each
-    uint8_t *dirty;                      // [V]
-    uint32_t *mbits;                     // [Z*Y][XW]
-    int32_t *counters;                   // [COVER_BATCH]
-};
-static void thin_volumes_layout(Carver &c, const Geo &G, ThinVolumes &W) {
-    W.key_vol = c.take<long long>(G.V);
-    W.nbr_min = c.take<long long>(G.V);
-    W.tmp = c.take<long long>(G.V);
-    W.dirty = c.take<uint8_t>(G.V);
-    W.mbits = c.take<uint32_t>((size_t)G.Z * G.Y * row_words(G));
-    W.counters = (int32_t *)c.take_bytes(256);
-}
-
-struct ThinWork : ThinVolumes {
+struct ThinWork : RoundArrays<long long> {
     unsigned long long *interior;        // [1] set interior voxels of the mask
     int32_t *state, *sel_count, *cleared;  // [n] each
 };
 static ThinWork thin_layout(Carver &c, long long n, const Geo &G) {
     ThinWork W;
-    thin_volumes_layout(c, G, W);
+    round_layout(c, G, W);
     W.interior = (unsigned long long *)c.take_bytes(256);
     const size_t per = (size_t)(n > 0 ? n : 1);
     W.state = c.take<int32_t>(per);
@@ -1269,7 +1269,7 @@ hipError_t cover_open(const uint8_t *mask, const long long *lin, const int32_t *
     PPP_GRID_CHECK((G.V + 255) / 256, 256);
     CoverWork W = carve(work, G);
     hipError_t e;
-    if ((e = hipMemsetD32Async((hipDeviceptr_t)W.rank_vol, RANK_NONE, (size_t)G.V, s)) != hipSuccess) return e;
+    if ((e = hipMemsetD32Async((hipDeviceptr_t)W.key_vol, RANK_NONE, (size_t)G.V, s)) != hipSuccess) return e;
     if ((e = hipMemsetD32Async((hipDeviceptr_t)W.loc_vol, 0xFFFFFFFF, (size_t)G.V, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(W.dirty, 1, (size_t)G.V, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(W.witness, 0xFF, (size_t)G.V * 2, s)) != hipSuccess) return e;
@@ -1280,7 +1280,7 @@ hipError_t cover_open(const uint8_t *mask, const long long *lin, const int32_t *
     cover_pack_kernel<<<dim3((unsigned)((n_words + 255) / 256)), block, 0, s>>>(mask, W.mbits, G);
     if (n)
         cover_init_local_kernel<<<dim3((unsigned)((n + 255) / 256)), block, 0, s>>>(
-            lin, rankid, state, (int)n, W.rank_vol, W.loc_vol);
+            lin, rankid, state, (int)n, W.key_vol, W.loc_vol);
     return hipGetLastError();
 }
 
@@ -1290,13 +1290,7 @@ hipError_t cover_step_count(const uint32_t *bits, int pix_th, int32_t *state, vo
     hipError_t e;
     if ((e = hipMemsetAsync(W.counters, 0, 4, s)) != hipSuccess) return e;
     cover_count_kernel<<<count_grid(G), dim3(COUNT_THREADS), 0, s>>>(
-        W.mbits, bits, W.dirty, pix_th, state, W.rank_vol, W.counters, W.loc_vol, witness_ok(G) ? W.witness : nullptr, -1ll, G);
-    return hipGetLastError();
-}
-
-hipError_t cover_step_filter(void *work, const Geo &G, hipStream_t s) {
-    CoverWork W = carve(work, G);
-    minfilter_xy<int32_t>(W.rank_vol, W.tmp, W.nbr_min, G, s);
+        W.mbits, bits, W.dirty, pix_th, state, W.key_vol, W.counters, W.loc_vol, witness_ok(G) ? W.witness : nullptr, -1ll, G);
     return hipGetLastError();
 }
 
@@ -1304,79 +1298,7 @@ hipError_t cover_step_select(const uint32_t *bits, int pix_th, int32_t *state, i
                              int gZ, const Geo &G, hipStream_t s) {
     CoverWork W = carve(work, G);
     cover_select_kernel<<<select_grid(G), dim3(256), 0, s>>>(
-        W.mbits, bits, W.nbr_min, state, W.rank_vol, cleared, W.dirty, W.loc_vol, gZ, -1ll, (pix_th != 0 || !witness_ok(G)) ? 1 : 0, G);
-    return hipGetLastError();
-}
-
-hipError_t cover_alive(void *work, const Geo &G, int32_t *alive, hipStream_t s) {
-    CoverWork W = carve(work, G);
-    hipError_t e;
-    if ((e = hipMemcpyAsync(alive, W.counters, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-    return hipStreamSynchronize(s);
-}
-
-hipError_t cover_close(uint8_t *mask, void *work, const Geo &G, hipStream_t s) {
-    CoverWork W = carve(work, G);
-    cover_unpack_kernel<<<dim3((unsigned)((G.V + 255) / 256)), dim3(256), 0, s>>>(W.mbits, mask, G);
-    return hipGetLastError();
-}
-
-// zone = local slices [z_lo, z_hi); the rank owns the local slices [own_lo, own_hi)
-__global__ void __launch_bounds__(256)
-    cover_zone_export_kernel(const int32_t *__restrict__ rank_vol, const uint32_t *__restrict__ mbits,
-                             const uint8_t *__restrict__ dirty, const int z_lo, const int z_hi,
-                             const int own_lo, const int own_hi, int32_t *__restrict__ out_rank,
-                             uint8_t *__restrict__ out_mask, uint8_t *__restrict__ out_clean,
-                             const Geo G) {
-    const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    const long long plane = (long long)G.Y * G.X;
-    if (t >= (long long)(z_hi - z_lo) * plane) return;
-    const int z = z_lo + (int)(t / plane);
-    const long long v = (long long)z * plane + t % plane;
-    const int x = (int)(v % G.X);
-    const long long row = v / G.X;
-    if (out_rank) out_rank[t] = (z >= own_lo && z < own_hi) ? rank_vol[v] : 0x7FFFFFFF;
-    if (out_mask) {
-        out_mask[t] = (mbits[row * row_words(G) + (x >> 5)] >> (x & 31)) & 1u;
-        out_clean[t] = dirty[v] ? 0 : 1;
-    }
-}
-__global__ void __launch_bounds__(256)
-    cover_zone_import_kernel(int32_t *__restrict__ rank_vol, uint32_t *__restrict__ mbits,
-                             uint8_t *__restrict__ dirty, const int z_lo, const int z_hi,
-                             const int32_t *__restrict__ in_rank, const uint8_t *__restrict__ in_mask,
-                             const uint8_t *__restrict__ in_clean, const Geo G) {
-    const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    const long long plane = (long long)G.Y * G.X;
-    if (t >= (long long)(z_hi - z_lo) * plane) return;
-    const int z = z_lo + (int)(t / plane);
-    const long long v = (long long)z * plane + t % plane;
-    const int x = (int)(v % G.X);
-    const long long row = v / G.X;
-    if (in_rank) rank_vol[v] = in_rank[t] == 0x7FFFFFFF ? RANK_NONE : in_rank[t];
-    if (in_mask) {
-        if (!in_mask[t]) atomicAnd(&mbits[row * row_words(G) + (x >> 5)], ~(1u << (x & 31)));
-        if (!in_clean[t]) dirty[v] = 1;
-    }
-}
-hipError_t cover_zone_export(void *work, int z_lo, int z_hi, int own_lo, int own_hi,
-                             int32_t *out_rank, uint8_t *out_mask, uint8_t *out_clean,
-                             const Geo &G, hipStream_t s) {
-    CoverWork W = carve(work, G);
-    const long long n = (long long)(z_hi - z_lo) * G.Y * G.X;
-    if (n <= 0) return hipSuccess;
-    cover_zone_export_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(
-        W.rank_vol, W.mbits, W.dirty, z_lo, z_hi, own_lo, own_hi, out_rank, out_mask, out_clean, G);
-    return hipGetLastError();
-}
-hipError_t cover_zone_import(void *work, int z_lo, int z_hi, const int32_t *in_rank,
-                             const uint8_t *in_mask, const uint8_t *in_clean, const Geo &G,
-                             hipStream_t s) {
-    CoverWork W = carve(work, G);
-    const long long n = (long long)(z_hi - z_lo) * G.Y * G.X;
-    if (n <= 0) return hipSuccess;
-    cover_zone_import_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(
-        W.rank_vol, W.mbits, W.dirty, z_lo, z_hi, in_rank, in_mask, in_clean, G);
+        W.mbits, bits, W.nbr_min, state, W.key_vol, cleared, W.dirty, W.loc_vol, gZ, -1ll, (pix_th != 0 || !witness_ok(G)) ? 1 : 0, G);
     return hipGetLastError();
 }
 
@@ -1390,12 +1312,12 @@ hipError_t cover_zone_import(void *work, int z_lo, int z_hi, const int32_t *in_r
 // patch's position in the GLOBAL selected list (the sequential loop's tie-break, foreground_cover.py:210);
 // loc_vol maps an own centre to its row in the rank's own lists.  The stop rule (foreground_cover.py:
 // 206-216) needs every rank's kept patches: the caller gathers (key at selection, cleared interior voxels).
-struct ThinShardWork : ThinVolumes {
+struct ThinShardWork : RoundArrays<long long> {
     int32_t *loc_vol;                    // [V]
 };
 static ThinShardWork thin_shard_layout(Carver &c, const Geo &G) {
     ThinShardWork W;
-    thin_volumes_layout(c, G, W);
+    round_layout(c, G, W);
     W.loc_vol = c.take<int32_t>(G.V);
     return W;
 }
@@ -1438,11 +1360,6 @@ hipError_t thin_step_count(const uint32_t *bits, int32_t *state, void *work, con
         W.mbits, bits, W.dirty, state, W.key_vol, W.counters, W.loc_vol, G);
     return hipGetLastError();
 }
-hipError_t thin_step_filter(void *work, const Geo &G, hipStream_t s) {
-    ThinShardWork W = carve_thin_shard(work, G);
-    minfilter_xy<long long>(W.key_vol, W.tmp, W.nbr_min, G, s);
-    return hipGetLastError();
-}
 hipError_t thin_step_select(const uint32_t *bits, int32_t *state, int32_t *sel_count, int32_t *cleared, void *work,
                             int gZ, const Geo &G, hipStream_t s) {
     ThinShardWork W = carve_thin_shard(work, G);
@@ -1450,23 +1367,35 @@ hipError_t thin_step_select(const uint32_t *bits, int32_t *state, int32_t *sel_c
         W.mbits, bits, W.nbr_min, state, W.key_vol, sel_count, cleared, W.dirty, W.loc_vol, G.oz, gZ, G);
     return hipGetLastError();
 }
-hipError_t thin_alive(void *work, const Geo &G, int32_t *alive, hipStream_t s) {
-    ThinShardWork W = carve_thin_shard(work, G);
+
+// ---- the steps that the sharded cover (K = int32_t) and the sharded thinning (K = long long) share: they
+// touch the arrays of a round only, which both workspaces begin with -----------------------------------
+template <typename K> hipError_t round_step_filter(void *work, const Geo &G, hipStream_t s) {
+    RoundArrays<K> W = carve_round<K>(work, G);
+    minfilter_xy<K>(W.key_vol, W.tmp, W.nbr_min, G, s);
+    return hipGetLastError();
+}
+template <typename K> hipError_t round_alive(void *work, const Geo &G, int32_t *alive, hipStream_t s) {
+    RoundArrays<K> W = carve_round<K>(work, G);
     hipError_t e;
     if ((e = hipMemcpyAsync(alive, W.counters, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
     return hipStreamSynchronize(s);
 }
-hipError_t thin_close(uint8_t *mask, void *work, const Geo &G, hipStream_t s) {
-    ThinShardWork W = carve_thin_shard(work, G);
+template <typename K> hipError_t round_close(uint8_t *mask, void *work, const Geo &G, hipStream_t s) {
+    RoundArrays<K> W = carve_round<K>(work, G);
     cover_unpack_kernel<<<dim3((unsigned)((G.V + 255) / 256)), dim3(256), 0, s>>>(W.mbits, mask, G);
     return hipGetLastError();
 }
-static constexpr long long THIN_ZONE_NONE = 0x7FFFFFFFFFFFFFFFll;      // "not my slice" in an exported zone of keys
+
+// zone = local slices [z_lo, z_hi); the rank owns the local slices [own_lo, own_hi).  In an exported zone
+// "not my slice" is the largest K (what MIN leaves alone); in the volume "none" is FilterNone<K>::value.
+template <typename K> static constexpr K ZONE_NONE = std::numeric_limits<K>::max();
+template <typename K>
 __global__ void __launch_bounds__(256)
-    thin_zone_export_kernel(const long long *__restrict__ key_vol, const uint32_t *__restrict__ mbits,
-                            const uint8_t *__restrict__ dirty, const int z_lo, const int z_hi, const int own_lo,
-                            const int own_hi, long long *__restrict__ out_key, uint8_t *__restrict__ out_mask,
-                            uint8_t *__restrict__ out_clean, const Geo G) {
+    zone_export_kernel(const K *__restrict__ key_vol, const uint32_t *__restrict__ mbits,
+                       const uint8_t *__restrict__ dirty, const int z_lo, const int z_hi, const int own_lo,
+                       const int own_hi, K *__restrict__ out_key, uint8_t *__restrict__ out_mask,
+                       uint8_t *__restrict__ out_clean, const Geo G) {
     const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     const long long plane = (long long)G.Y * G.X;
     if (t >= (long long)(z_hi - z_lo) * plane) return;
@@ -1474,16 +1403,17 @@ __global__ void __launch_bounds__(256)
     const long long v = (long long)z * plane + t % plane;
     const int x = (int)(v % G.X);
     const long long row = v / G.X;
-    if (out_key) out_key[t] = (z >= own_lo && z < own_hi) ? key_vol[v] : THIN_ZONE_NONE;
+    if (out_key) out_key[t] = (z >= own_lo && z < own_hi) ? key_vol[v] : ZONE_NONE<K>;
     if (out_mask) {
         out_mask[t] = (mbits[row * row_words(G) + (x >> 5)] >> (x & 31)) & 1u;
         out_clean[t] = dirty[v] ? 0 : 1;
     }
 }
+template <typename K>
 __global__ void __launch_bounds__(256)
-    thin_zone_import_kernel(long long *__restrict__ key_vol, uint32_t *__restrict__ mbits, uint8_t *__restrict__ dirty,
-                            const int z_lo, const int z_hi, const long long *__restrict__ in_key,
-                            const uint8_t *__restrict__ in_mask, const uint8_t *__restrict__ in_clean, const Geo G) {
+    zone_import_kernel(K *__restrict__ key_vol, uint32_t *__restrict__ mbits, uint8_t *__restrict__ dirty,
+                       const int z_lo, const int z_hi, const K *__restrict__ in_key,
+                       const uint8_t *__restrict__ in_mask, const uint8_t *__restrict__ in_clean, const Geo G) {
     const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     const long long plane = (long long)G.Y * G.X;
     if (t >= (long long)(z_hi - z_lo) * plane) return;
@@ -1491,29 +1421,34 @@ __global__ void __launch_bounds__(256)
     const long long v = (long long)z * plane + t % plane;
     const int x = (int)(v % G.X);
     const long long row = v / G.X;
-    if (in_key) key_vol[v] = in_key[t] == THIN_ZONE_NONE ? THIN_NONE : in_key[t];
+    if (in_key) key_vol[v] = in_key[t] == ZONE_NONE<K> ? FilterNone<K>::value : in_key[t];
     if (in_mask) {
         if (!in_mask[t]) atomicAnd(&mbits[row * row_words(G) + (x >> 5)], ~(1u << (x & 31)));
         if (!in_clean[t]) dirty[v] = 1;
     }
 }
-hipError_t thin_zone_export(void *work, int z_lo, int z_hi, int own_lo, int own_hi, long long *out_key,
-                            uint8_t *out_mask, uint8_t *out_clean, const Geo &G, hipStream_t s) {
-    ThinShardWork W = carve_thin_shard(work, G);
+// import: keys / mask / clean are read into the zone; else they are written from it
+template <typename K>
+hipError_t round_zone(bool import, void *work, int z_lo, int z_hi, int own_lo, int own_hi, K *keys, uint8_t *mask,
+                      uint8_t *clean, const Geo &G, hipStream_t s) {
+    RoundArrays<K> W = carve_round<K>(work, G);
     const long long n = (long long)(z_hi - z_lo) * G.Y * G.X;
     if (n <= 0) return hipSuccess;
-    thin_zone_export_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(
-        W.key_vol, W.mbits, W.dirty, z_lo, z_hi, own_lo, own_hi, out_key, out_mask, out_clean, G);
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (import)
+        zone_import_kernel<K><<<grid, block, 0, s>>>(W.key_vol, W.mbits, W.dirty, z_lo, z_hi, keys, mask, clean, G);
+    else
+        zone_export_kernel<K><<<grid, block, 0, s>>>(W.key_vol, W.mbits, W.dirty, z_lo, z_hi, own_lo, own_hi, keys, mask,
+                                                     clean, G);
     return hipGetLastError();
 }
-hipError_t thin_zone_import(void *work, int z_lo, int z_hi, const long long *in_key, const uint8_t *in_mask,
-                            const uint8_t *in_clean, const Geo &G, hipStream_t s) {
-    ThinShardWork W = carve_thin_shard(work, G);
-    const long long n = (long long)(z_hi - z_lo) * G.Y * G.X;
-    if (n <= 0) return hipSuccess;
-    thin_zone_import_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(
-        W.key_vol, W.mbits, W.dirty, z_lo, z_hi, in_key, in_mask, in_clean, G);
-    return hipGetLastError();
-}
+#define PPP_ROUND_STEPS(K)                                                                                      \
+    template hipError_t round_step_filter<K>(void *, const Geo &, hipStream_t);                                  \
+    template hipError_t round_alive<K>(void *, const Geo &, int32_t *, hipStream_t);                             \
+    template hipError_t round_close<K>(uint8_t *, void *, const Geo &, hipStream_t);                             \
+    template hipError_t round_zone<K>(bool, void *, int, int, int, int, K *, uint8_t *, uint8_t *, const Geo &, hipStream_t);
+PPP_ROUND_STEPS(int32_t)
+PPP_ROUND_STEPS(long long)
+#undef PPP_ROUND_STEPS
 
 }  // namespace ppp

@@ -31,6 +31,7 @@ so a rank holds its slabs grown by H = 2 pz + rz slices (clipped to the volume).
 use local coordinates; ``ppp_params.origin_z`` carries the global offset (the per-pair LCG seed
 of the patch-graph kernel is the only thing that depends on absolute coordinates).
 """
+import collections
 import logging
 import ctypes
 import os
@@ -730,14 +731,113 @@ def sharded_cover(ops, comm, shape, ps, my_range, ranges, mask_to_cover, lin_t, 
     return selected
 
 
+ZoneGeometry = collections.namedtuple("ZoneGeometry", "a b bounds zones mine own_loc zslices pairwise")
+
+
+def zone_geometry(ranges, my_range, h, Z):
+    """Where a rank of a volume split by z keeps its rounds and what it exchanges.  ranges: every rank's
+    (z0, z1) in rank order (contiguous, ascending), my_range: this rank's, h = pz - 1, Z: slices of the volume.
+    a, b      the rank's local buffer holds the global slices [a, b) = own +- h, clipped;
+    bounds    the internal slab boundaries; zones[i]: the global slices [lo, hi) within h of bounds[i];
+    mine      the indices of the zones at this rank's own two boundaries -- those it takes part in;
+    own_loc   the own slices as local ones; zslices = 2 h: the slices a zone buffer has room for;
+    pairwise  a zone reaches the two ranks next to its boundary only (no slab is thinner than a zone)."""
+    z0, z1 = int(my_range[0]), int(my_range[1])
+    a, b = max(0, z0 - h), min(Z, z1 + h)
+    bounds = [int(r[1]) for r in ranges[:-1]]
+    zones = [(max(0, zb - h), min(Z, zb + h)) for zb in bounds]
+    mine = [i for i, zb in enumerate(bounds) if zb == z0 or zb == z1]
+    return ZoneGeometry(a, b, bounds, zones, mine, (z0 - a, z1 - a), 2 * h, all(r[1] - r[0] >= 2 * h for r in ranges))
+
+
+class _ShardedRounds:
+    """The rounds of the greedy cover or of the thinning on one rank of a volume split by z: COUNT, exchange
+    of the ranks / keys, FILTER, SELECT, exchange of mask and clean bytes, with the 2(pz - 1) slices around
+    every slab boundary made consistent in each exchange -- point to point between the two neighbours, or by
+    a MIN all-reduce when slabs are thinner than the zones -- and every COVER_BATCH rounds a MAX all-reduce
+    of "somebody is still undecided".  Every rank issues the same collectives in the same order.
+
+    shard: ops.cover_shard(...) / ops.thin_shard(...) on the local buffer, which starts at global slice a;
+    key_dtype, key_none: what the shard's zones carry (int32 ranks / int64 keys) and their "not mine"."""
+
+    def __init__(self, shard, comm, dev, shape, ps, my_range, ranges, a, key_dtype, key_none):
+        import torch
+        Z, Y, X = [int(v) for v in shape]
+        self.shard, self.comm, self.dev, self.key_none = shard, comm, dev, key_none
+        self.geo = g = zone_geometry(ranges, my_range, int(ps[0]) - 1, Z)
+        assert g.a == a, "the local buffer starts %d slices below the own range, clipped" % (int(ps[0]) - 1)
+        self.z1 = int(my_range[1])
+        self.key_buf = torch.empty((max(len(g.zones), 1), g.zslices * Y * X), dtype=key_dtype, device=dev)
+        self.mask_buf = torch.empty((max(len(g.zones), 1), 2, g.zslices * Y * X), dtype=torch.uint8, device=dev)
+        # a boundary zone concerns the two ranks next to it -- unless slabs are thinner than the zones
+        # (then a zone reaches a third rank and everybody takes part in an all-reduce)
+        self.pairwise = hasattr(comm, "neighbour_min") and os.environ.get("PPP_COVER_P2P", "1") != "0" and g.pairwise
+
+    def zone_io(self, imp, i, with_key):
+        g = self.geo
+        lo_z, hi_z = g.zones[i][0] - g.a, g.zones[i][1] - g.a
+        if with_key:
+            self.shard.zone(imp, lo_z, hi_z, g.own_loc, self.key_buf[i])          # (the key buffer, by position)
+        else:
+            self.shard.zone(imp, lo_z, hi_z, g.own_loc, mask=self.mask_buf[i, 0], clean=self.mask_buf[i, 1])
+
+    def exchange(self, with_key):
+        g, comm = self.geo, self.comm
+        if not g.zones:
+            return
+        buf = self.key_buf if with_key else self.mask_buf
+        if self.pairwise:
+            for i in g.mine:
+                self.zone_io(False, i, with_key)
+            comm.neighbour_min([(comm.rank + 1 if g.bounds[i] == self.z1 else comm.rank - 1, buf[i]) for i in g.mine])
+        else:
+            buf.fill_(self.key_none if with_key else 1)
+            for i in g.mine:
+                self.zone_io(False, i, with_key)
+            comm.all_reduce_min(buf)
+        for i in g.mine:
+            self.zone_io(True, i, with_key)
+
+    def run(self, *step_args):
+        """rounds until no rank has an undecided patch; step_args: what COUNT and SELECT take.  Returns
+        the number of rounds."""
+        import torch
+        shard, rounds, alive = self.shard, 0, True
+        while alive:
+            for _ in range(COVER_BATCH):
+                shard.step(shard.COUNT, *step_args)
+                self.exchange(True)
+                shard.step(shard.FILTER)
+                shard.step(shard.SELECT, *step_args)
+                self.exchange(False)
+            rounds += COVER_BATCH
+            flag = torch.tensor([1 if shard.alive() else 0], dtype=torch.int32, device=self.dev)
+            alive = int(self.comm.all_reduce_max(flag).item()) > 0
+        return rounds
+
+
+def _picks_reached(comm, key, cleared, remaining):
+    """The sequential loop's stop rule over ALL ranks' picks: it takes them in the order of their keys
+    and ends right after the one that leaves no interior voxel.  key, cleared: int64 [k], the own picks
+    and the interior voxels each cleared (gathered: lists as long as the selection); remaining: interior
+    voxels before them.  Returns (the keys of the picks the loop reaches, in its order; what is left)."""
+    import torch
+    pairs = torch.cat(gather_lists(comm, torch.stack([key, cleared], 1)), 0)
+    if not pairs.shape[0]:
+        return pairs[:, 0], remaining
+    order = torch.argsort(pairs[:, 0])
+    left = remaining - torch.cumsum(pairs[order, 1], 0)
+    done = torch.nonzero(left <= 0).reshape(-1)
+    n_keep = int(done[0].item()) + 1 if done.numel() else int(order.numel())
+    return pairs[order[:n_keep], 0], int(left[n_keep - 1].item())
+
+
 def sharded_cover_own(ops, comm, shape, ps, my_range, ranges, mask_ab, a, remaining, lin_own,
                       rank_id, never_own, bits_own, pix_ths, make_local_params):
     """The priority-parallel greedy cover (csrc/ppp_cover.hip) with the volume split by z: every
     rank runs the rounds on its own slices + a halo of pz-1 slices and decides its OWN patches;
-    twice per round the 2(pz-1) slices around every slab boundary are made consistent (rank
-    volume after the count step; mask and dirty marks after the select step) -- point to point
-    between the two neighbours, or by a MIN all-reduce when slabs are thinner than the zones.
-    Same result as the sequential cover.
+    twice per round the slab-boundary zones are made consistent (_ShardedRounds: rank volume after
+    the count step; mask and dirty marks after the select step).  Same result as the sequential cover.
 
     my_range (z0, z1), ranges: every rank's (z0, z1) in rank order (contiguous, ascending);
     mask_ab   uint8 0 / 1 device tensor, the mask on the global slices [a, b) = own +- (pz - 1)
@@ -751,50 +851,11 @@ def sharded_cover_own(ops, comm, shape, ps, my_range, ranges, mask_ab, a, remain
     import torch
     dev = ops.device
     Z, Y, X = [int(v) for v in shape]
-    h = int(ps[0]) - 1
-    z0, z1 = my_range
     b = a + int(mask_ab.shape[0])
-    plane = Y * X
     m_own = int(lin_own.numel())
-    shard = ops.cover_shard(mask_ab, (lin_own - a * plane).contiguous(), rank_id.contiguous(), bits_own,
+    shard = ops.cover_shard(mask_ab, (lin_own - a * Y * X).contiguous(), rank_id.contiguous(), bits_own,
                             make_local_params(a, b), Z)
-    # zones around the internal slab boundaries (global slices), and which of them touch me
-    bounds = [int(r[1]) for r in ranges[:-1]]
-    zones = [(max(0, zb - h), min(Z, zb + h)) for zb in bounds]
-    mine = [i for i, zb in enumerate(bounds) if zb == z0 or zb == z1]
-    zlen = 2 * h * plane
-    rank_buf = torch.empty((max(len(zones), 1), zlen), dtype=torch.int32, device=dev)
-    mask_buf = torch.empty((max(len(zones), 1), 2, zlen), dtype=torch.uint8, device=dev)
-    own_loc = (z0 - a, z1 - a)
-
-    # a boundary zone concerns the two ranks next to it -- unless slabs are thinner than the zones
-    # (then a zone reaches a third rank and everybody takes part in an all-reduce)
-    pairwise = hasattr(comm, "neighbour_min") and os.environ.get("PPP_COVER_P2P", "1") != "0" and \
-        all(r[1] - r[0] >= 2 * h for r in ranges)
-
-    def zone_io(imp, i, with_rank):
-        lo_z, hi_z = zones[i][0] - a, zones[i][1] - a
-        if with_rank:
-            shard.zone(imp, lo_z, hi_z, own_loc, rank=rank_buf[i])
-        else:
-            shard.zone(imp, lo_z, hi_z, own_loc, mask=mask_buf[i, 0], clean=mask_buf[i, 1])
-
-    def exchange(with_rank):
-        if not zones:
-            return
-        buf = rank_buf if with_rank else mask_buf
-        if pairwise:
-            for i in mine:
-                zone_io(False, i, with_rank)
-            comm.neighbour_min([(comm.rank + 1 if bounds[i] == z1 else comm.rank - 1, buf[i]) for i in mine])
-        else:
-            buf.fill_(INT32_MAX if with_rank else 1)
-            for i in mine:
-                zone_io(False, i, with_rank)
-            comm.all_reduce_min(buf)
-        for i in mine:
-            zone_io(True, i, with_rank)
-
+    rounds = _ShardedRounds(shard, comm, dev, shape, ps, my_range, ranges, a, torch.int32, INT32_MAX)
     selected = torch.zeros(m_own, dtype=torch.bool, device=dev)
     total_rounds = 0
     for pix_th in pix_ths:
@@ -802,45 +863,19 @@ def sharded_cover_own(ops, comm, shape, ps, my_range, ranges, mask_ab, a, remain
             break
         # every pass restarts at rank 0 (the reference passes rpidx by value)
         shard.open(torch.where(selected, 1, torch.where(never_own, 2, 0)).to(torch.int32))
-        alive = True
-        while alive:
-            for _ in range(COVER_BATCH):
-                shard.step(shard.COUNT, pix_th)
-                exchange(True)
-                shard.step(shard.FILTER)
-                shard.step(shard.SELECT, pix_th)
-                exchange(False)
-            total_rounds += COVER_BATCH
-            flag = torch.tensor([1 if shard.alive() else 0], dtype=torch.int32, device=dev)
-            alive = int(comm.all_reduce_max(flag).item()) > 0
+        total_rounds += rounds.run(pix_th)
         shard.close()
-        # The loop's stop rule: it ends right after the patch that empties the interior.  The
-        # patches selected in this pass, in rank order over ALL ranks, with the interior voxels
-        # each cleared: (rank id, cleared) of the own ones are gathered -- a list as long as the
-        # selection, not as the ranked list.
+        # The patches selected in this pass, in rank order over ALL ranks, up to the one that empties
+        # the interior
         new_own = torch.nonzero((shard.state[:m_own] == 1) & ~selected).reshape(-1) if m_own else \
             torch.zeros((0,), dtype=torch.int64, device=dev)
-        mine_rc = torch.stack([rank_id[new_own].to(torch.int64), shard.cleared[:m_own][new_own].to(torch.int64)], 1) \
-            if m_own else torch.zeros((0, 2), dtype=torch.int64, device=dev)
-        allrc = torch.cat(gather_lists(comm, mine_rc), 0)
-        cut = None
-        if allrc.shape[0]:
-            order = torch.argsort(allrc[:, 0])
-            left = remaining - torch.cumsum(allrc[order, 1], 0)
-            done = torch.nonzero(left <= 0).reshape(-1)
-            if done.numel():
-                cut = int(allrc[order[int(done[0].item())], 0].item())     # last rank id the loop reaches
-                remaining = 0
-            else:
-                remaining = int(left[-1].item())
-        if m_own:
-            keep = new_own if cut is None else new_own[rank_id[new_own].to(torch.int64) <= cut]
-            selected[keep] = True
-        if remaining < 1:
-            break
+        new_id = rank_id[new_own].to(torch.int64)
+        reached, remaining = _picks_reached(comm, new_id, shard.cleared[:m_own][new_own].to(torch.int64), remaining)
+        if reached.numel():
+            selected[new_own[new_id <= reached[-1]]] = True           # (the last rank id the loop reaches)
     backend.note("cover_rounds", total_rounds)
     backend.note("cover_sharded", comm.world)
-    backend.note("cover_p2p", 1 if pairwise else 0)
+    backend.note("cover_p2p", 1 if rounds.pairwise else 0)
     return selected
 
 
@@ -850,11 +885,10 @@ THIN_MAXC = 1 << 20          # csrc/ppp_cover.hip: key = (THIN_MAXC - count) << 
 def sharded_thin_own(ops, comm, shape, ps, my_range, ranges, mask_ab, a, interior_total, lin_own, index_own,
                      bits_own, make_local_params):
     """The set-cover thinning (foreground_cover.py:183-256; priority-parallel rounds, csrc/ppp_cover.hip) with
-    the volume split by z, after the pattern of sharded_cover_own: every rank runs the rounds on its own
-    slices + pz - 1 halo slices and decides its OWN selected patches; twice per round the 2(pz - 1) slices
-    around every slab boundary are made consistent -- the 64-bit keys (count, position in the global list)
-    after the count step, mask and dirty marks after the select step -- point to point between the two
-    neighbours (or by MIN all-reduces when slabs are thinner than the zones).
+    the volume split by z: every rank runs the rounds on its own slices + pz - 1 halo slices and decides its
+    OWN selected patches; twice per round the slab-boundary zones are made consistent (_ShardedRounds: the
+    64-bit keys (count, position in the global list) after the count step, mask and dirty marks after the
+    select step).
 
     mask_ab  uint8 device tensor, the mask on the global slices [a, b) = own +- (pz - 1) (clipped; cleared in
              place); interior_total: interior mask voxels of the WHOLE volume before the thinning (the loop
@@ -865,74 +899,17 @@ def sharded_thin_own(ops, comm, shape, ps, my_range, ranges, mask_ab, a, interio
     import torch
     dev = ops.device
     Z, Y, X = [int(v) for v in shape]
-    h = int(ps[0]) - 1
-    z0, z1 = my_range
     b = a + int(mask_ab.shape[0])
-    plane = Y * X
     m_own = int(lin_own.numel())
-    shard = ops.thin_shard(mask_ab, (lin_own - a * plane).contiguous(), index_own, bits_own, make_local_params(a, b), Z)
-    bounds = [int(r[1]) for r in ranges[:-1]]
-    zones = [(max(0, zb - h), min(Z, zb + h)) for zb in bounds]
-    mine = [i for i, zb in enumerate(bounds) if zb == z0 or zb == z1]
-    zlen = 2 * h * plane
-    key_buf = torch.empty((max(len(zones), 1), zlen), dtype=torch.int64, device=dev)
-    mask_buf = torch.empty((max(len(zones), 1), 2, zlen), dtype=torch.uint8, device=dev)
-    own_loc = (z0 - a, z1 - a)
-    pairwise = hasattr(comm, "neighbour_min") and os.environ.get("PPP_COVER_P2P", "1") != "0" and \
-        all(r[1] - r[0] >= 2 * h for r in ranges)
-
-    def zone_io(imp, i, with_key):
-        lo_z, hi_z = zones[i][0] - a, zones[i][1] - a
-        if with_key:
-            shard.zone(imp, lo_z, hi_z, own_loc, key=key_buf[i])
-        else:
-            shard.zone(imp, lo_z, hi_z, own_loc, mask=mask_buf[i, 0], clean=mask_buf[i, 1])
-
-    def exchange(with_key):
-        if not zones:
-            return
-        buf = key_buf if with_key else mask_buf
-        if pairwise:
-            for i in mine:
-                zone_io(False, i, with_key)
-            comm.neighbour_min([(comm.rank + 1 if bounds[i] == z1 else comm.rank - 1, buf[i]) for i in mine])
-        else:
-            buf.fill_(INT64_MAX if with_key else 1)
-            for i in mine:
-                zone_io(False, i, with_key)
-            comm.all_reduce_min(buf)
-        for i in mine:
-            zone_io(True, i, with_key)
-
-    rounds, alive = 0, True
-    while alive:
-        for _ in range(COVER_BATCH):
-            shard.step(shard.COUNT)
-            exchange(True)
-            shard.step(shard.FILTER)
-            shard.step(shard.SELECT)
-            exchange(False)
-        rounds += COVER_BATCH
-        flag = torch.tensor([1 if shard.alive() else 0], dtype=torch.int32, device=dev)
-        alive = int(comm.all_reduce_max(flag).item()) > 0
+    shard = ops.thin_shard(mask_ab, (lin_own - a * Y * X).contiguous(), index_own, bits_own, make_local_params(a, b), Z)
+    rounds = _ShardedRounds(shard, comm, dev, shape, ps, my_range, ranges, a, torch.int64, INT64_MAX).run()
     shard.close()
     # ---- the stop rule over ALL ranks' kept patches: the order the sequential loop picks them in is the
-    # order of their keys when they were kept (count descending, index ascending); it stops at the first
-    # pick that leaves no interior voxel uncovered
+    # order of their keys when they were kept (count descending, index ascending)
     kept = torch.nonzero(shard.state[:m_own] == 1).reshape(-1) if m_own else torch.zeros((0,), dtype=torch.int64, device=dev)
     key = ((THIN_MAXC - shard.count[:m_own][kept].to(torch.int64)) << 32) | index_own[kept].to(torch.int64)
-    mine_kc = torch.stack([key, shard.cleared[:m_own][kept].to(torch.int64)], 1) if m_own else \
-        torch.zeros((0, 2), dtype=torch.int64, device=dev)
-    allkc = torch.cat(gather_lists(comm, mine_kc), 0)
-    keep_idx = torch.zeros((0,), dtype=torch.int64, device=dev)
-    remaining = int(interior_total)
-    if allkc.shape[0]:
-        order = torch.argsort(allkc[:, 0])
-        left = remaining - torch.cumsum(allkc[order, 1], 0)
-        done = torch.nonzero(left <= 0).reshape(-1)
-        n_keep = int(done[0].item()) + 1 if done.numel() else int(order.numel())
-        remaining = int(left[n_keep - 1].item())
-        keep_idx = allkc[order[:n_keep], 0] & 0xFFFFFFFF
+    reached, remaining = _picks_reached(comm, key, shard.cleared[:m_own][kept].to(torch.int64), int(interior_total))
+    keep_idx = reached & 0xFFFFFFFF
     if remaining > 0:
         # every count is 0 with voxels left: np.argmax picks patch 0 once more (foreground_cover.py:210-216)
         keep_idx = torch.cat([keep_idx, torch.zeros((1,), dtype=torch.int64, device=dev)])
@@ -1030,6 +1007,10 @@ class _Assembly:
             # the helper closures hold `self` and `self` holds them: without this the tensors among the
             # attributes (fields, node lists, an exchanged slab) would wait for the cycle collector
             self.__dict__.clear()
+
+    def local_params(self, a, b):
+        """ppp_params of a rank's buffer of the global slices [a, b) (sharded cover and thinning)"""
+        return backend.make_params((b - a, self.Y, self.X), self.ps, origin=(a, 0, 0), **self.flags)
 
     def setup(self):
         """arguments checked, the per-voxel fields on the device, the halo exchange, the early-outs"""
@@ -1603,9 +1584,6 @@ class _Assembly:
         def coords_of(lin_g):
             return torch.stack([lin_g // self.plane, (lin_g // self.X) % self.Y, lin_g % self.X], dim=1).to(torch.int32)
 
-        def local_params(a, b):
-            return backend.make_params((b - a, self.Y, self.X), self.ps, origin=(a, 0, 0), **self.flags)
-
         from .vote_instances import foreground_cover as fc
         pix_ths = fc._pix_thresholds(self.ps, self.kw)
         thr = self.kw.get("score_threshold", False)
@@ -1652,7 +1630,7 @@ class _Assembly:
                                                 self.mask_d[self.own_z(a, b)].clone(), a, self.interior_count(self.mask_d),
                                                 lin_own, rank_id.to(torch.int32), never,
                                                 self.bits_of_own(coords_of(lin_own), self.kw["fc_threshold"], True),
-                                                pix_ths, local_params)
+                                                pix_ths, self.local_params)
                     del never
                 mine_sel = torch.stack([rank_id[sel_own], lin_own[sel_own]], 1)
                 allsel = torch.cat(gather_lists(self.comm, mine_sel), 0)
@@ -1732,7 +1710,7 @@ class _Assembly:
                         selected = sharded_cover(self.ops, self.comm, self.shape, self.ps, self.rank_ranges[self.comm.rank], self.rank_ranges,
                                                  self.mask_d, lin_t, never, pix_ths, radslice,
                                                  lambda idx: self.bits_of_own(self.coords_t[idx], self.kw["fc_threshold"]),
-                                                 local_params)
+                                                 self.local_params)
                     elif self.provider and self.comm.world == 1 and hasattr(self.ops, "voxel_major_pool"):
                         # the per-voxel bit table of stage A serves the cover as it is (a copy in rank
                         # order would double its 92 bytes per voxel)
@@ -1777,7 +1755,7 @@ class _Assembly:
                         self.ops, self.comm, self.shape, self.ps, (self.oz0, self.oz1), self.rank_ranges,
                         self.mask_d[self.own_z(a_t, b_t)].clone(), a_t, self.interior_count(self.mask_d),
                         lin_own, torch.from_numpy(idx_own.astype(np.int64)).to(self.dev), bits,
-                        lambda a, b: backend.make_params((b - a, self.Y, self.X), self.ps, origin=(a, 0, 0), **self.flags))
+                        self.local_params)
                     self.sel_coords = self.sel_coords[keep_idx.cpu().numpy()]
                     del bits, c_own, lin_own, keep_idx
             else:

@@ -375,23 +375,23 @@ class OracleCoverShard:
     def alive(self):
         return bool(self._alive)
 
-    def zone(self, imp, z_lo, z_hi, own, rank=None, mask=None, clean=None):
+    def zone(self, imp, z_lo, z_hi, own, key=None, mask=None, clean=None):
         n = (z_hi - z_lo) * self.shape[1] * self.shape[2]
         if n <= 0:
             return
         if not imp:
-            if rank is not None:
+            if key is not None:
                 r = np.full((z_hi - z_lo,) + self.shape[1:], self.IMAX, dtype=np.int64)
                 for z in range(z_lo, z_hi):
                     if own[0] <= z < own[1]:
                         r[z - z_lo] = self.rank_vol[z]
-                rank.numpy()[:n] = r.reshape(-1)
+                key.numpy()[:n] = r.reshape(-1)
             if mask is not None:
                 mask.numpy()[:n] = self.run[z_lo:z_hi].reshape(-1)
                 clean.numpy()[:n] = ~self.dirty[z_lo:z_hi].reshape(-1)
         else:
-            if rank is not None:
-                r = rank.numpy()[:n].astype(np.int64).reshape((z_hi - z_lo,) + self.shape[1:])
+            if key is not None:
+                r = key.numpy()[:n].astype(np.int64).reshape((z_hi - z_lo,) + self.shape[1:])
                 self.rank_vol[z_lo:z_hi] = np.where(r == self.IMAX, self.NONE, r)
             if mask is not None:
                 m = mask.numpy()[:n].reshape((z_hi - z_lo,) + self.shape[1:]) != 0

@@ -80,7 +80,8 @@ class DeviceSide:
 
 
 class Geometry:
-    """Slabs, local buffers, zones and who takes part in which -- as tiling.sharded_cover_own has them."""
+    """Slabs, local buffers, zones and who takes part in which -- restated here, held to tiling.zone_geometry
+    by test_shard_zones_match_the_lockstep_geometry."""
 
     def __init__(self, case, cuts):
         self.case = case
@@ -165,7 +166,7 @@ class Shards:
         dev = self.side.device
         if with_key:
             buf = torch.empty(n, dtype=self.key_dtype, device=dev)
-            self.shards[s].zone(False, 0, Zl, (0, Zl), **{"key" if self.thin else "rank": buf})
+            self.shards[s].zone(False, 0, Zl, (0, Zl), key=buf)
             return buf.cpu().numpy()
         m, c = torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.uint8, device=dev)
         self.shards[s].zone(False, 0, Zl, (0, Zl), mask=m, clean=c)
@@ -175,7 +176,7 @@ class Shards:
         lo, hi = self.geo.zone_loc(s, i)
         if with_key:
             buf = self.key_buf[s] if buf is None else buf
-            self.shards[s].zone(imp, lo, hi, self.geo.own_loc(s), **{"key" if self.thin else "rank": buf[i]})
+            self.shards[s].zone(imp, lo, hi, self.geo.own_loc(s), key=buf[i])
         else:
             buf = self.mask_buf[s] if buf is None else buf
             self.shards[s].zone(imp, lo, hi, self.geo.own_loc(s), mask=buf[i, 0], clean=buf[i, 1])

@@ -80,6 +80,34 @@ def test_model_shards_equal_one_model_shard(name, what):
         assert (a["state"] == 1).any()
 
 
+# ---- the product's zone geometry against the driver's -----------------------------------------------------
+# all(z1 - z0 >= 2 (pz - 1)) from the cuts above: slabs of 10, 10 against 8; 13, 13 against 12; 6, 6 against 4 --
+# and 5, 4, 13 against 8; 7, 7, 7 against 8; 14, 14 against 16
+PAIRWISE = {"base": True, "p7": True, "aniso": True, "thin_slabs": False, "three": False, "p9": False}
+
+
+def test_shard_zones_match_the_lockstep_geometry():
+    """tiling.zone_geometry -- what the product's round loop exchanges -- gives every shard of every volume the
+    buffer [a, b), zones, membership, own slices and zone length of shard_lockstep.Geometry, the independent
+    restatement that the step tests run on; and "a zone concerns two neighbours only" where no slab is thinner
+    than a zone."""
+    from types import SimpleNamespace
+    from patchperpix_amd import tiling
+    assert set(PAIRWISE) == set(VOLUMES)
+    for name, (shape, ps, cuts) in VOLUMES.items():
+        geo = ls.Geometry(SimpleNamespace(shape=shape, ps=ps, centres=np.zeros((0, 3), dtype=np.int64), n=0), cuts)
+        assert geo.k == len(cuts) - 1 >= 2
+        for s in range(geo.k):
+            g = tiling.zone_geometry(geo.ranges, geo.ranges[s], ps[0] - 1, shape[0])
+            what = "%s, shard %d" % (name, s)
+            assert (g.a, g.b) == geo.ab[s], what
+            assert list(g.bounds) == geo.bounds and list(g.zones) == geo.zones, what
+            assert list(g.mine) == geo.mine[s] and len(g.mine) == (1 if s in (0, geo.k - 1) else 2), what
+            assert tuple(g.own_loc) == geo.own_loc(s), what
+            assert g.zslices * shape[1] * shape[2] == geo.zlen, what
+            assert g.pairwise is PAIRWISE[name], what
+
+
 # ---- device against model, step by step -------------------------------------------------------------------
 def _fail(tag, thin, s, what, where, dev, mod):
     p, pix_th, rnd, step, phase = tag
