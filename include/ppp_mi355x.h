@@ -915,6 +915,38 @@ int ppp_synth_pred_box(const int32_t *d_labels, const int32_t *label_box, void *
 int ppp_decode_tail(const float *d_x, int64_t n, int32_t fmaps, int32_t side, const float *d_w1, float b1,
                     const float *d_w2, float b2, const float *d_w3, float b3, const int64_t *d_dst,
                     void *d_pred, int pred_dtype, const ppp_params *p, void *stream);
+/* The same tail, arithmetic and float16 rounding included, with patch b stored as the ROW
+ * d_rows[d_dst[b]][0 .. C) of a rows table (below) instead of a column of a block: d_dst holds row
+ * numbers, C must be 343.  PPP_F32 / PPP_F16, as ppp_decode_tail. */
+int ppp_decode_tail_rows(const float *d_x, int64_t n, int32_t fmaps, int32_t side, const float *d_w1, float b1,
+                         const float *d_w2, float b2, const float *d_w3, float b3, const int64_t *d_dst,
+                         void *d_rows, int rows_dtype, int32_t C, void *stream);
+
+/* --- a prediction kept as ROWS for the voxels of a mask only (no counterpart in the reference, whose
+ * decode writes the dense array, zero outside the foreground: decode.py:43-65) ---------------------
+ * d_mask  uint8 (Z, Y, X), non-zero = the voxel has a row; row k belongs to the k-th such voxel in
+ *         raster order (x fastest).
+ * d_rows  [n_rows][C], C contiguous, elements of PPP_F32 / PPP_F16 / PPP_BF16: moved as bits, never
+ *         converted.  Row numbers and n_rows * C are 64-bit.
+ * d_index ppp_rows_index_bytes(Z, Y, X) bytes (8-byte aligned), filled by ppp_rows_index_build: the
+ *         mask as 64-bit words over the linear voxel index and an int64 count of the mask voxels
+ *         before each word -- any voxel's row number in O(1), 0.25 bytes per voxel (plus under 1 KiB).
+ *         ppp_rows_index_build runs on the device, writes *n_rows and synchronises the stream.
+ * ppp_rows_expand   writes the WHOLE (C, bz, by, bx) box at d_pred_box: a voxel with a row gets the
+ *         row's C values, every other voxel zeros in all C channels (the kernel stores them itself).
+ * ppp_rows_compact  the inverse on a box: the rows of the box's mask voxels are written from the dense
+ *         box, every other row stays untouched.
+ * d_rows and d_pred_box must be 4-byte aligned.  PPP_ERR_UNSUPPORTED for 2^31 voxels or more (the size
+ * query returns that code too). */
+int64_t ppp_rows_index_bytes(int32_t Z, int32_t Y, int32_t X);
+int ppp_rows_index_build(const uint8_t *d_mask, int32_t Z, int32_t Y, int32_t X,
+                         void *d_index, int64_t *n_rows, void *stream);
+int ppp_rows_expand(const void *d_rows, int dtype, int32_t C, const void *d_index,
+                    int32_t Z, int32_t Y, int32_t X, const ppp_box *box,
+                    void *d_pred_box, void *stream);
+int ppp_rows_compact(const void *d_pred_box, int dtype, int32_t C, const ppp_box *box,
+                     const void *d_index, int32_t Z, int32_t Y, int32_t X,
+                     void *d_rows, void *stream);
 
 #ifdef __cplusplus
 }

@@ -141,6 +141,33 @@ def computePatchGraph_cuda(pred_affs, consensus_vote_array, selected_patch_pairs
     return aff
 
 
+# ---- a prediction kept as rows of the foreground voxels (no counterpart in the reference) ----------
+def rows_index_build(mask):
+    """(index, n_rows) for a (Z, Y, X) mask: what ppp_rows_expand needs to find a voxel's row"""
+    Z, Y, X = [int(s) for s in mask.shape]
+    _lib.ppp_rows_index_bytes.restype = ctypes.c_int64
+    nbytes = int(_lib.ppp_rows_index_bytes(Z, Y, X))
+    _check(min(nbytes, 0))
+    m = torch.as_tensor(np.ascontiguousarray(np.asarray(mask) != 0).astype(np.uint8), device="cuda")
+    index = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    n = ctypes.c_int64(0)
+    _check(_lib.ppp_rows_index_build(_ptr(m), Z, Y, X, _ptr(index), ctypes.byref(n), None))
+    return index, int(n.value)
+
+
+def rows_expand(rows, index, shape, box):
+    """dense (C, bz, by, bx) prediction of box = Box(z0, y0, x0, z1, y1, x1) from the rows [n, C] of the
+    mask voxels (raster order): decoded patches never have to be scattered into a (C, Z, Y, X) array"""
+    code = {torch.float32: PPP_F32, torch.float16: PPP_F16, torch.bfloat16: PPP_BF16}[rows.dtype]
+    C = int(rows.shape[1])
+    out = torch.empty((C, box.z1 - box.z0, box.y1 - box.y0, box.x1 - box.x0), dtype=rows.dtype, device="cuda")
+    _lib.ppp_rows_expand.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                     ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(Box), ctypes.c_void_p, ctypes.c_void_p]
+    _check(_lib.ppp_rows_expand(_ptr(rows.contiguous()), code, C, _ptr(index), int(shape[0]), int(shape[1]), int(shape[2]),
+                                ctypes.byref(box), _ptr(out), None))
+    return out
+
+
 # ---- the cuda=False stages (int16 votes, integer ranks, all-pairs graph weights) ------------------
 # The reference's signatures take Python sets / the lookup table; a maintainer keeps the call sites
 # and passes the arrays the sets were made from (pred_affs, foreground): the device kernels form the

@@ -282,7 +282,20 @@ _SIGNATURES = {
                                        ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_float,
                                        ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_int, ctypes.POINTER(Params), ctypes.c_void_p]),
-    "ppp_host_mws": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+    "ppp_decode_tail_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                            ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_float,
+                                            ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_int, ctypes.c_int32, ctypes.c_void_p]),
+    "ppp_rows_index_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "ppp_rows_index_build": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                            ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]),
+    "ppp_rows_expand": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p,
+                                       ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(Box),
+                                       ctypes.c_void_p, ctypes.c_void_p]),
+    "ppp_rows_compact": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.POINTER(Box),
+                                        ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                        ctypes.c_void_p, ctypes.c_void_p]),
+    "ppp_host_mws":(ctypes.c_int64, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
     "ppp_host_rank_order": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -1831,6 +1844,90 @@ def decode_tail(x, w1, b1, w2, b2, w3, b3, dst, pred, patchshape):
                                 _dev_ptr(dst.to(torch.int64).contiguous()), _dev_ptr(pred),
                                 pred_dtype_code(pred), ctypes.byref(P), _stream()))
     return pred
+
+
+def decode_tail_rows(x, w1, b1, w2, b2, w3, b3, dst, rows):
+    """ppp_decode_tail_rows: decode_tail with patch k written as the row rows[dst[k]] of a
+    contiguous [n_rows, 343] float16 / float32 table (the VALUES of dst, each in [0, n_rows), stay
+    the caller's promise)."""
+    torch = _torch()
+    n = int(x.shape[0])
+    if tuple(x.shape[1:]) != (64, 4, 4, 4):
+        raise ValueError("decode_tail_rows: features must be (n, 64, 4, 4, 4), got %s" % (tuple(x.shape),))
+    if int(dst.numel()) != n or dst.dtype != torch.int64:
+        raise ValueError("decode_tail_rows: dst must hold %d int64 row numbers" % n)
+    if rows.dim() != 2 or int(rows.shape[1]) != 343 or not rows.is_contiguous() or \
+            rows.dtype not in (torch.float16, torch.float32):
+        raise ValueError("decode_tail_rows: rows must be a contiguous [n_rows, 343] float16 / float32 table")
+    for name, w, count in (("w1", w1, 64 * 27), ("w2", w2, 27), ("w3", w3, 27)):
+        if int(w.numel()) != count:
+            raise ValueError("decode_tail_rows: %s has %d elements, expected %d" % (name, int(w.numel()), count))
+    if len({t.device for t in (x, dst, rows, w1, w2, w3)}) != 1:
+        raise ValueError("decode_tail_rows: x, dst, rows and the weights must be on one device")
+    if n == 0:
+        return rows
+    f32 = lambda t: t.detach().to(torch.float32).contiguous()
+    x, w1, w2, w3 = f32(x), f32(w1).reshape(-1), f32(w2).reshape(-1), f32(w3).reshape(-1)
+    check(lib().ppp_decode_tail_rows(_dev_ptr(x), n, 64, 4, _dev_ptr(w1), float(b1), _dev_ptr(w2), float(b2),
+                                     _dev_ptr(w3), float(b3), _dev_ptr(dst.contiguous()), _dev_ptr(rows),
+                                     pred_dtype_code(rows), 343, _stream()))
+    return rows
+
+
+def rows_index_build(mask):
+    """ppp_rows_index_build: mask (Z, Y, X) device tensor, non-zero = has a row.  Returns (index,
+    n_rows): the device index (uint8 tensor, layout private to the library) that gives any voxel's
+    row number in O(1), and the number of rows.  Synchronises."""
+    torch = _torch()
+    if mask.dim() != 3 or not mask.is_cuda:
+        raise ValueError("rows_index_build: mask must be a (Z, Y, X) device tensor")
+    Z, Y, X = [int(v) for v in mask.shape]
+    index = _workspace(lib().ppp_rows_index_bytes(Z, Y, X), mask.device)
+    m = (mask != 0).to(torch.uint8).contiguous() if mask.dtype != torch.uint8 else mask.contiguous()
+    n = ctypes.c_int64(0)
+    check(lib().ppp_rows_index_build(_dev_ptr(m), Z, Y, X, _dev_ptr(index), ctypes.byref(n), _stream()))
+    return index, int(n.value)
+
+
+def _rows_args(who, rows, index, shape, box, pred_box):
+    Z, Y, X = [int(v) for v in shape]
+    z0, z1, y0, y1, x0, x1 = [int(v) for v in box]
+    if rows.dim() != 2 or not rows.is_contiguous() or not pred_box.is_contiguous():
+        raise ValueError("%s: rows must be a contiguous [n_rows, C] table, the box contiguous" % who)
+    C = int(rows.shape[1])
+    if tuple(int(v) for v in pred_box.shape) != (C, z1 - z0, y1 - y0, x1 - x0) or pred_box.dtype != rows.dtype:
+        raise ValueError("%s: the box tensor must be (%d, %d, %d, %d) of %s, got %s of %s" %
+                         (who, C, z1 - z0, y1 - y0, x1 - x0, rows.dtype, tuple(pred_box.shape), pred_box.dtype))
+    if int(index.numel()) != int(lib().ppp_rows_index_bytes(Z, Y, X)):
+        raise ValueError("%s: the index was not built for a volume of %s" % (who, (Z, Y, X)))
+    if len({rows.device, index.device, pred_box.device}) != 1:
+        raise ValueError("%s: rows, index and box must be on one device" % who)
+    return C, (Z, Y, X), Box(z0, y0, x0, z1, y1, x1)
+
+
+def rows_expand(rows, index, shape, box, out=None):
+    """ppp_rows_expand: the dense (C, bz, by, bx) prediction of `box` = (z0, z1, y0, y1, x0, x1) from the
+    rows table [n_rows, C] (float32 / float16 / bfloat16, moved as bits) of the mask `index` was built
+    from: a mask voxel gets its row, every other voxel zeros -- all written by the kernel.  The
+    number of rows must be the index's (the caller's promise, as CompactPrediction keeps it)."""
+    torch = _torch()
+    z0, z1, y0, y1, x0, x1 = [int(v) for v in box]
+    if out is None:
+        out = torch.empty((int(rows.shape[1]), z1 - z0, y1 - y0, x1 - x0), dtype=rows.dtype, device=rows.device)
+    C, (Z, Y, X), b = _rows_args("rows_expand", rows, index, shape, box, out)
+    with _timed("rows_expand"):
+        check(lib().ppp_rows_expand(_dev_ptr(rows), pred_dtype_code(rows), C, _dev_ptr(index), Z, Y, X, ctypes.byref(b),
+                                    _dev_ptr(out), _stream()))
+    return out
+
+
+def rows_compact(pred_box, box, index, shape, rows):
+    """ppp_rows_compact: the rows of the mask voxels of `box` written from its dense prediction
+    (C, bz, by, bx); every other row of `rows` stays as it is."""
+    C, (Z, Y, X), b = _rows_args("rows_compact", rows, index, shape, box, pred_box)
+    check(lib().ppp_rows_compact(_dev_ptr(pred_box), pred_dtype_code(rows), C, ctypes.byref(b), _dev_ptr(index), Z, Y, X,
+                                 _dev_ptr(rows), _stream()))
+    return rows
 
 
 def synth_pred_box(labels, label_box, box, gshape, patchshape, flags, seed=0, hi=0.95, lo=0.05,

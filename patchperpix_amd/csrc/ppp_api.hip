@@ -1016,6 +1016,79 @@ int ppp_decode_tail(const float *d_x, int64_t n, int32_t fmaps, int32_t side, co
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_decode_tail");
 }
 
+int ppp_decode_tail_rows(const float *d_x, int64_t n, int32_t fmaps, int32_t side, const float *d_w1, float b1,
+                         const float *d_w2, float b2, const float *d_w3, float b3, const int64_t *d_dst,
+                         void *d_rows, int rows_dtype, int32_t C, void *stream) {
+    PPP_TRY(check_dtype_f32_f16(rows_dtype, "ppp_decode_tail_rows"));
+    if (n <= 0) return PPP_OK;
+    if (!d_x || !d_w1 || !d_w2 || !d_w3 || !d_dst || !d_rows) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    PPP_TRY(need_device());
+    hipError_t e = C != 343 ? hipErrorNotSupported
+                            : ppp::launch_decode_tail_rows(d_x, n, fmaps, side, d_w1, b1, d_w2, b2, d_w3, b3,
+                                                           (const long long *)d_dst, d_rows, rows_dtype, (hipStream_t)stream);
+    if (e == hipErrorNotSupported)
+        return fail(PPP_ERR_UNSUPPORTED, "ppp_decode_tail_rows serves the shipped decoder tail only: 64 feature maps "
+                                         "at 4^3, 3^3 kernels, rows of 7^3 = 343 values");
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_decode_tail_rows");
+}
+
+/* ---- a prediction kept as rows of the mask voxels (ppp_rows.hip) ---- */
+static int rows_volume(int32_t Z, int32_t Y, int32_t X, long long *V) {
+    if (Z <= 0 || Y <= 0 || X <= 0) return fail(PPP_ERR_INVALID_ARG, "bad volume %d x %d x %d", Z, Y, X);
+    *V = (long long)Z * Y * X;
+    if (*V >= (1ll << 31)) return fail(PPP_ERR_UNSUPPORTED, "volumes of 2^31 voxels or more are not supported");
+    return PPP_OK;
+}
+
+int64_t ppp_rows_index_bytes(int32_t Z, int32_t Y, int32_t X) {
+    long long V;
+    int rc = rows_volume(Z, Y, X, &V);
+    return rc != PPP_OK ? rc : (int64_t)ppp::rows_index_bytes(V);
+}
+
+int ppp_rows_index_build(const uint8_t *d_mask, int32_t Z, int32_t Y, int32_t X, void *d_index, int64_t *n_rows,
+                         void *stream) {
+    long long V;
+    PPP_TRY(rows_volume(Z, Y, X, &V));
+    if (!d_mask || !d_index || !n_rows) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    if ((uintptr_t)d_index & 7) return fail(PPP_ERR_INVALID_ARG, "ppp_rows_index_build: the index must be 8-byte aligned");
+    PPP_TRY(need_device());
+    long long n = 0;
+    hipError_t e = ppp::run_rows_index_build(d_mask, V, d_index, &n, (hipStream_t)stream);
+    *n_rows = n;
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_rows_index_build");
+}
+
+static int rows_move(bool expand, const char *who, void *d_rows, int dtype, int32_t C, const void *d_index, int32_t Z,
+                     int32_t Y, int32_t X, const ppp_box *box, void *d_pred_box, void *stream) {
+    long long V;
+    PPP_TRY(rows_volume(Z, Y, X, &V));
+    PPP_TRY(check_dtype(dtype));
+    if (C <= 0) return fail(PPP_ERR_INVALID_ARG, "%s: rows of %d values", who, C);
+    if (!d_index || !box || !d_pred_box) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    if (box->z0 < 0 || box->y0 < 0 || box->x0 < 0 || box->z1 > Z || box->y1 > Y || box->x1 > X || box->z1 <= box->z0 ||
+        box->y1 <= box->y0 || box->x1 <= box->x0)
+        return fail(PPP_ERR_INVALID_ARG, "%s: box outside the volume or empty", who);
+    // (the 2-byte forms move aligned dwords where they can: both buffers must start on one)
+    if (((uintptr_t)d_rows & 3) || ((uintptr_t)d_pred_box & 3) || ((uintptr_t)d_index & 7))
+        return fail(PPP_ERR_INVALID_ARG, "%s: rows and box must be 4-byte aligned, the index 8-byte aligned", who);
+    PPP_TRY(need_device());
+    hipError_t e = ppp::launch_rows_move(expand, d_rows, dtype == PPP_F32 ? 4 : 2, C, d_index, Z, Y, X, *box, d_pred_box,
+                                         (hipStream_t)stream);
+    return e == hipSuccess ? PPP_OK : hip_fail(e, who);
+}
+
+int ppp_rows_expand(const void *d_rows, int dtype, int32_t C, const void *d_index, int32_t Z, int32_t Y, int32_t X,
+                    const ppp_box *box, void *d_pred_box, void *stream) {
+    return rows_move(true, "ppp_rows_expand", const_cast<void *>(d_rows), dtype, C, d_index, Z, Y, X, box, d_pred_box, stream);
+}
+
+int ppp_rows_compact(const void *d_pred_box, int dtype, int32_t C, const ppp_box *box, const void *d_index, int32_t Z,
+                     int32_t Y, int32_t X, void *d_rows, void *stream) {
+    return rows_move(false, "ppp_rows_compact", d_rows, dtype, C, d_index, Z, Y, X, box, const_cast<void *>(d_pred_box),
+                     stream);
+}
+
 int64_t ppp_cover_workspace_bytes(int64_t n, const ppp_params *p) {
     ppp::Geo G;
     if (make_geo(p, &G) != PPP_OK) return -1;

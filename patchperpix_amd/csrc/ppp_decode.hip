@@ -46,7 +46,10 @@ static constexpr int DT_NO = DT_O * DT_O * DT_O;                                
 static constexpr int DT_WAVES = 4, DT_GROUP = 64;       // patches per workgroup (one output tile)
 static constexpr int DT_ZS = 33;                        // padded tap stride of Z in LDS
 
-template <typename T, int P>
+// ROWS: patch b becomes the row pred[dst[b] * C + r] of a rows table (ppp_rows.hip) instead of the column
+// pred[r * V + dst[b]] of a block: the same arithmetic, the LDS tile kept [patch][value] and stored with
+// the lanes along r.
+template <typename T, int P, bool ROWS = false>
 __global__ void __launch_bounds__(64 * DT_WAVES)
     decode_tail_kernel(const float *__restrict__ X, const long long B, const float *__restrict__ W1,
                        const float b1, const float *__restrict__ W2, const float b2,
@@ -128,8 +131,10 @@ __global__ void __launch_bounds__(64 * DT_WAVES)
                 else {
                     // centre crop and the float16 the prediction is stored in (decode.py:104-109)
                     const int pz = oz - OFF, py = oy - OFF, px = ox - OFF;
-                    if (pz >= 0 && pz < P && py >= 0 && py < P && px >= 0 && px < P)
-                        tile[(pz * P + py) * P + px][pi] = __float2half_rn(s);
+                    if (pz >= 0 && pz < P && py >= 0 && py < P && px >= 0 && px < P) {
+                        if constexpr (ROWS) (&tile[0][0])[pi * C + (pz * P + py) * P + px] = __float2half_rn(s);
+                        else tile[(pz * P + py) * P + px][pi] = __float2half_rn(s);
+                    }
                 }
             }
         };
@@ -141,6 +146,21 @@ __global__ void __launch_bounds__(64 * DT_WAVES)
         __builtin_amdgcn_wave_barrier();
     }
     __syncthreads();
+    if constexpr (ROWS) {
+        // ---- a patch per wave and step, the lanes along its C values: one contiguous row of the table
+        const __half *flat = &tile[0][0];
+        for (int pi = wave; pi < DT_GROUP; pi += DT_WAVES) {
+            const long long b = g0 + pi;
+            if (b >= B) break;
+            T *row = pred + dst[b] * (long long)C;
+            for (int r = lane; r < C; r += 64) {
+                const __half hv = flat[pi * C + r];
+                if constexpr (std::is_same<T, __half>::value) row[r] = hv;
+                else row[r] = __half2float(hv);
+            }
+        }
+        return;
+    }
     // ---- the group's patches into pred[r][dst]: lanes = patches (consecutive foreground voxels
     // are consecutive addresses), one patch value r per wave and step
     const long long b = g0 + lane;
@@ -155,24 +175,38 @@ __global__ void __launch_bounds__(64 * DT_WAVES)
     }
 }
 
-hipError_t launch_decode_tail(const float *X, long long B, int F, int S, const float *W1, float b1,
-                              const float *W2, float b2, const float *W3, float b3, const long long *dst,
-                              void *pred, int dtype, const Geo &G, hipStream_t s) {
+template <bool ROWS>
+static hipError_t launch_decode_tail_as(const float *X, long long B, int F, int S, const float *W1, float b1,
+                                        const float *W2, float b2, const float *W3, float b3, const long long *dst,
+                                        void *pred, int dtype, long long V, hipStream_t s) {
     if (B <= 0) return hipSuccess;
-    if (F != DT_F || S != DT_S || G.pz != 7 || G.py != 7 || G.px != 7) return hipErrorNotSupported;
+    if (F != DT_F || S != DT_S) return hipErrorNotSupported;
     const long long groups = (B + DT_GROUP - 1) / DT_GROUP;
     PPP_GRID_CHECK(groups, 64 * DT_WAVES);
     const size_t lds = (size_t)(DT_F * 32 + DT_WAVES * DT_NV * DT_ZS + 2 * DT_WAVES * DT_NO + 2 * 27 + 2) * 4 +
                        (size_t)343 * DT_GROUP * 2;
     return with_f32_f16_type(dtype, [&](auto tag) {
         using T = PPP_PRED_T(tag);
-        const hipError_t e = hipFuncSetAttribute((const void *)decode_tail_kernel<T, 7>,
+        const hipError_t e = hipFuncSetAttribute((const void *)decode_tail_kernel<T, 7, ROWS>,
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
-        decode_tail_kernel<T, 7><<<dim3((unsigned)groups), dim3(64 * DT_WAVES), lds, s>>>(
-            X, B, W1, b1, W2, b2, W3, b3, dst, (T *)pred, G.V);
+        decode_tail_kernel<T, 7, ROWS><<<dim3((unsigned)groups), dim3(64 * DT_WAVES), lds, s>>>(
+            X, B, W1, b1, W2, b2, W3, b3, dst, (T *)pred, V);
         return hipGetLastError();
     });
+}
+
+hipError_t launch_decode_tail(const float *X, long long B, int F, int S, const float *W1, float b1,
+                              const float *W2, float b2, const float *W3, float b3, const long long *dst,
+                              void *pred, int dtype, const Geo &G, hipStream_t s) {
+    if (G.pz != 7 || G.py != 7 || G.px != 7) return hipErrorNotSupported;
+    return launch_decode_tail_as<false>(X, B, F, S, W1, b1, W2, b2, W3, b3, dst, pred, dtype, G.V, s);
+}
+
+hipError_t launch_decode_tail_rows(const float *X, long long B, int F, int S, const float *W1, float b1,
+                                   const float *W2, float b2, const float *W3, float b3, const long long *dst,
+                                   void *rows, int dtype, hipStream_t s) {
+    return launch_decode_tail_as<true>(X, B, F, S, W1, b1, W2, b2, W3, b3, dst, rows, dtype, 0, s);
 }
 
 }  // namespace ppp

@@ -170,6 +170,17 @@ hipError_t launch_decode_tail(const float *X, long long B, int F, int S, const f
                               const float *W2, float b2, const float *W3, float b3, const long long *dst,
                               void *pred, int dtype, const Geo &G, hipStream_t s);
 
+// the same tail with patch b stored as a row, rows[dst[b]][0 .. C), instead of a column of the block
+hipError_t launch_decode_tail_rows(const float *X, long long B, int F, int S, const float *W1, float b1,
+                                   const float *W2, float b2, const float *W3, float b3, const long long *dst,
+                                   void *rows, int dtype, hipStream_t s);
+
+// a prediction kept as rows of the mask voxels (ppp_rows.hip): index, expand into a box, compact from a box
+size_t rows_index_bytes(long long V);
+hipError_t run_rows_index_build(const uint8_t *mask, long long V, void *index, long long *n_rows, hipStream_t s);
+hipError_t launch_rows_move(bool expand, void *rows, int elem_bytes, int C, const void *index, int Z, int Y, int X,
+                            const ppp_box &bx, void *box, hipStream_t s);
+
 size_t cover_workspace_bytes(long long n, const Geo &G);
 hipError_t run_cover_pass(uint8_t *mask, const uint32_t *bits, long long bits_vox, const long long *lin,
                           long long n, int pix_th, int32_t *state, int32_t *cleared, void *work,

@@ -321,6 +321,61 @@ def decode_volume(decoder, pred_code, pred_fg, batch_size=1024, device="cuda", o
     return out
 
 
+def decode_rows(decoder, code, fg, batch_size=1024, device="cuda", out_dtype=None, fused=None, expit=False):
+    """decode_volume without the dense block: every foreground voxel is decoded exactly once, patch k
+    of the raster order straight into row k of a ``compact.CompactPrediction`` (rows [n, C] of
+    `out_dtype`, float32 unless given).  Same decoder head, same batches, same tail arithmetic as
+    decode_volume -- the fused tail (ppp_decode_tail_rows) where ``fused_tail_params()`` exists, else
+    the torch tail -- so ``rows`` equals ``decode_volume(...)[:, fg].T`` bit for bit.  The number of
+    voxels decoded is kept in ``voxels_decoded`` of the result.  expit: see CompactPrediction."""
+    torch = _torch()
+    from . import backend
+    from .compact import CompactPrediction
+    out_dtype = out_dtype or torch.float32
+    code = torch.as_tensor(np.asarray(code) if not torch.is_tensor(code) else code, device=device)
+    fg = torch.as_tensor(np.asarray(fg) != 0 if not torch.is_tensor(fg) else fg != 0, device=device)
+    units = code.shape[0]
+    C = int(np.prod(decoder.patchshape))
+    flat_code = code.reshape(units, -1)
+    idx = torch.nonzero(fg.reshape(-1)).reshape(-1)
+    spatial = tuple(int(v) for v in fg.shape)
+    cp = CompactPrediction.empty(fg.reshape((1,) * (3 - len(spatial)) + spatial), C, out_dtype, device,
+                                 patchshape=(1,) * (3 - len(decoder.patchshape)) + tuple(decoder.patchshape), expit=expit)
+    rows = cp.rows
+    decoder = decoder.to(device).eval()
+    tp = decoder.fused_tail_params() if fused is not False else None
+    if fused and tp is None:
+        raise RuntimeError("this decoder's tail has no fused kernel")
+    if getattr(decoder, "_dense", None) is None and rows.is_cuda and \
+            os.environ.get("PPP_DECODE_HEAD", "dense") != "conv" and not getattr(decoder, "_dense_tried", False):
+        decoder._dense_tried = True
+        decoder.enable_dense_head()
+    # (a ragged last batch is padded whenever a convolution sees it: decode_into says why)
+    convs_run = tp is None or getattr(decoder, "_dense", None) is None or \
+        decoder._dense["n_stages"] < len(decoder.up) - 1
+    cp.voxels_decoded = 0
+    chunk = max(int(batch_size), 1 << 18)
+    with torch.no_grad():
+        for c0 in range(0, int(idx.numel()), chunk):
+            sel = idx[c0:c0 + chunk]
+            codes = flat_code[:, sel].t().float().contiguous()
+            for s in range(0, int(sel.numel()), int(batch_size)):
+                cb = codes[s:s + batch_size]
+                n = int(cb.shape[0])
+                if convs_run and n < int(batch_size) and rows.is_cuda:
+                    cb = torch.cat([cb, cb.new_zeros((int(batch_size) - n,) + tuple(cb.shape[1:]))], 0)
+                feats = decoder.head(cb)
+                r0 = c0 + s
+                if tp is not None:
+                    backend.decode_tail_rows(feats[:n].contiguous() if feats.shape[0] != n else feats,
+                                             tp[0], tp[1], tp[2], tp[3], tp[4], tp[5],
+                                             torch.arange(r0, r0 + n, dtype=torch.int64, device=rows.device), rows)
+                else:
+                    rows[r0:r0 + n] = decoder.tail(feats)[:n].reshape(n, C).to(rows.dtype)
+                cp.voxels_decoded += n
+    return cp
+
+
 class DecodeProvider:
     """Prediction provider for patchperpix_amd.tiling.assemble in ppp+dec mode: pred_box() DECODES
     the float16 prediction of a box on demand from the per-voxel code (code_units, Z, Y, X) -- a
@@ -415,14 +470,11 @@ def map_decoder_state(state, decoder):
     return out
 
 
-def decode(**config):
-    """decode(**cfg) of the reference (decode.py:69-130): load the decoder weights, decode every
-    sample, write ``aff_key`` as float16."""
+def load_decoder(config, device):
+    """The decoder of a decode configuration (decode.py:69-101): built from its ``autoencoder`` table,
+    weights from ``checkpoint_file`` (``use_swa``: the averaged model's), mapped completely or not at
+    all (map_decoder_state)."""
     torch = _torch()
-    from .vote_instances import io_hdflike
-    if not torch.cuda.is_available():
-        raise RuntimeError("patchperpix_amd.decode needs a GPU (there is no CPU fallback)")
-    device = torch.device("cuda")
     ae = dict(config.get("autoencoder") or config.get("included_ae_config") or {})
     ae.setdefault("code_units", config["code_units"])
     ae.setdefault("input_shape_squeezed",
@@ -435,6 +487,18 @@ def decode(**config):
     if config.get("use_swa"):    # AveragedModel prefixes every key with `module.` and adds n_averaged
         state = {k.split("module.", 1)[1]: v for k, v in state.items() if k.startswith("module.")}
     decoder.load_state_dict(map_decoder_state(state, decoder), strict=True)
+    return decoder
+
+
+def decode(**config):
+    """decode(**cfg) of the reference (decode.py:69-130): load the decoder weights, decode every
+    sample, write ``aff_key`` as float16."""
+    torch = _torch()
+    from .vote_instances import io_hdflike
+    if not torch.cuda.is_available():
+        raise RuntimeError("patchperpix_amd.decode needs a GPU (there is no CPU fallback)")
+    device = torch.device("cuda")
+    decoder = load_decoder(config, device)
     for sample in config["samples"]:
         with io_hdflike.open_container(sample, "r") as f:
             code = np.array(f[config["code_key"]])

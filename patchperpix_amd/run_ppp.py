@@ -56,9 +56,21 @@ def vote_instances_sample(config, pred_folder, output_folder, sample):
     pred_fmt = config["prediction"]["output_format"]
     pred_file = os.path.join(pred_folder, sample + "." + pred_fmt)
     pred = config["prediction"]
+    if cfg.get("vote_from_code", False) and not cfg.get("blockwise", False):
+        raise NotImplementedError("[vote_instances] vote_from_code = true needs blockwise = true")
     if cfg.get("blockwise", False):
+        extra = {}
+        if cfg.get("vote_from_code", False):
+            # project-own option: a sample that holds the code is decoded into rows
+            # for its foreground voxels and voted from them; what the `decode` task is given
+            extra = dict(code_key=pred.get("code_key"), checkpoint_file=config.get("_checkpoint"))
+            if "autoencoder" not in config["model"] and config.get("autoencoder"):
+                extra["included_ae_config"] = config["autoencoder"]
+            for k in ("use_swa", "decode_batch_size"):
+                if k in pred and k not in cfg and k not in config["model"]:
+                    extra[k] = pred[k]
         vi.stitch_patch_graph.main(
-            pred_file, **cfg, **config["model"], **config.get("visualize", {}),
+            pred_file, **cfg, **config["model"], **config.get("visualize", {}), **extra,
             aff_key=pred.get("aff_key"), numinst_key=pred.get("numinst_key"),
             fg_key=pred.get("fg_key"), fg_folder=pred.get("fg_folder"),
             fg_thresh=pred.get("fg_thresh"))
@@ -96,6 +108,9 @@ def label(args, config):
                                args.sample)
     os.makedirs(args.output_folder, exist_ok=True)
     cfg = config["vote_instances"]
+    if cfg.get("vote_from_code", False) and not cfg.get("blockwise", False):
+        raise NotImplementedError("[vote_instances] vote_from_code = true needs blockwise = true")
+    config["_checkpoint"] = args.checkpoint
     if int(cfg.get("batch_2d") or 0) > 1 and not cfg.get("blockwise", False):
         t0 = time.time()
         label_batched(config, args.pred_folder, args.output_folder, samples)

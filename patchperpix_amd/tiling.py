@@ -1042,6 +1042,10 @@ class _Assembly:
         if not self.my_slabs:
             raise ValueError("this rank owns no z-slab (more ranks than slabs)")
         self.comm = self.comm or LocalComm()
+        if self.comm.world > 1:
+            from .compact import CompactPrediction
+            if isinstance(self.pred_local, CompactPrediction):
+                raise NotImplementedError("compact prediction: one rank only")
         if self.seq_cover and self.comm.world > 1:
             raise NotImplementedError("mark_close_neighboorhood / select_patches_overlap_neighborhood walk the ranked "
                                       "list sequentially: one rank only")
@@ -2438,8 +2442,54 @@ def _logits_in(arr, patchshape):
     return False
 
 
+def _holds_code(pred_file, kw):
+    """does the sample's container hold the per-voxel code (``code_key``)?"""
+    if not pred_file.rstrip("/").endswith((".zarr", ".hdf")):
+        return False
+    from .vote_instances import io_hdflike
+    with io_hdflike.open_container(pred_file, "r") as f:
+        return (kw.get("code_key") or "volumes/pred_code") in f
+
+
+def _compact_from_code(stack, pred_file, patchshape, kw):
+    """``vote_from_code``: (CompactPrediction, numinst, foreground) of a sample that holds the code.
+    The decoder and its foreground are those of the `decode` task (decode.load_decoder,
+    foreground_from_numinst, float16, ``decode_batch_size``): the rows are, bit for bit, the foreground
+    columns of the array that task writes, and the fields are read as the `label` task reads them.
+    Logits by loadAffinities' rule (utilVoteInstances.py:249-250) over that array -- the rows and,
+    where there is background, its zeros; `logits = true / false` in the configuration decides instead."""
+    import torch
+    from . import decode as dec
+    from .vote_instances import io_hdflike, utilVoteInstances as util
+    if not torch.cuda.is_available():
+        raise RuntimeError("vote_from_code needs a GPU (there is no CPU fallback)")
+    if not kw.get("checkpoint_file"):
+        raise ValueError("vote_from_code needs the decoder's checkpoint (--checkpoint)")
+    for a in "zyx":
+        if kw.get("crop_%s_s" % a, 0) or kw.get("crop_%s_e" % a) is not None:
+            raise NotImplementedError("crops are not supported with vote_from_code")
+    device = torch.device("cuda")
+    decoder = dec.load_decoder(dict(kw, patchshape=[int(p) for p in patchshape]), device)
+    with io_hdflike.open_container(pred_file, "r") as f:
+        code = np.array(f[kw.get("code_key") or "volumes/pred_code"])
+        numinstfg = np.array(f[kw.get("numinst_key") if kw.get("numinst_key") is not None else kw.get("fg_key")])
+        numinst = util.maybeLoadNuminst(f, **kw)
+        foreground, _ = util.loadFg(f, **dict(kw, patchshape=patchshape))
+    fg_dec = dec.foreground_from_numinst(numinstfg, kw.get("fg_thresh") if kw.get("fg_thresh") is not None else 0.5)
+    cp = dec.decode_rows(decoder, code, fg_dec, kw.get("decode_batch_size", 1024), device, out_dtype=torch.float16)
+    logits = kw.get("logits")
+    if logits is None:
+        logits = cp.n_rows > 0 and bool(cp.rows.min() < 0) and bool(cp.rows.max() > 1)
+    if logits:
+        cp.expit = True
+    logger.info("vote_from_code: %d rows of %d values (%.2f GB) for %d voxels (dense float16: %.2f GB)", cp.n_rows, cp.C,
+                cp.nbytes / 1e9, int(np.prod(cp.shape)), 2e-9 * cp.C * float(np.prod(cp.shape)))
+    return cp, numinst, foreground
+
+
 def _stitch_main(stack, pred_file, result_folder=".", **kwargs):
     import os
+    from .compact import CompactPrediction
     from scipy import ndimage
     from .vote_instances import utilVoteInstances as util
     from .vote_instances.stitch_patch_graph import clean_mask
@@ -2447,7 +2497,14 @@ def _stitch_main(stack, pred_file, result_folder=".", **kwargs):
     patchshape = np.array(kwargs["patchshape"])
     kw = dict(kwargs)
     kw.pop("patchshape")
-    if pred_file.endswith(".npy"):
+    from_code = bool(kw.pop("vote_from_code", False))
+    if from_code and not kwargs.get("blockwise", False):
+        raise NotImplementedError("vote_from_code needs blockwise = true (the tiled assembly votes the rows)")
+    if from_code and _holds_code(pred_file, kw):
+        # ppp+dec without the decoded array: the code is decoded ONCE into rows for the foreground
+        # voxels (decode.decode_rows), which stay in HBM and are expanded tile by tile
+        affinities, numinst, foreground = _compact_from_code(stack, pred_file, patchshape, kw)
+    elif pred_file.endswith(".npy"):
         # (C, Z, Y, X) array; foreground from the centre channel (utilVoteInstances.py:233-242,
         # whose own .npy branch only handles 2-d data)
         affinities = np.load(pred_file)
@@ -2513,7 +2570,7 @@ def _stitch_main(stack, pred_file, result_folder=".", **kwargs):
     # (default.toml:159, stitch_patch_graph.py:131-133); here the boxed volume is assembled as a
     # whole and the driver wants the instance map
     kw["return_intermediates"] = False
-    if isinstance(affinities, ZarrProvider):
+    if isinstance(affinities, (ZarrProvider, CompactPrediction)):
         return _stitch_streamed(affinities, foreground, numinst, bb, shape, patchshape, pred_file,
                                 result_folder, kw)
     fg_bb = np.ascontiguousarray(foreground[bb])

@@ -151,6 +151,11 @@ def _to_instance_seg(pred_affs, foreground, mask_to_cover, numinst, patchshape, 
     alone returns (batch2d.py).  With ``return_intermediates`` a list of N per-slice (pairs, aff).
     """
     import torch
+    from .. import compact
+    if isinstance(pred_affs, compact.CompactPrediction):
+        # rows for the foreground voxels only: expanded once when the dense block fits, else voted
+        # tile by tile through the provider protocol (compact.vote)
+        return compact.vote(pred_affs, foreground, mask_to_cover, numinst, patchshape, **kwargs)
     if kwargs.pop("independent_slices", False):
         from . import batch2d
         return batch2d.to_instance_seg_slices(pred_affs, foreground, mask_to_cover, numinst, patchshape,
