@@ -827,6 +827,40 @@ int64_t ppp_post_clean_mask_workspace_bytes(int32_t Z, int32_t Y, int32_t X);
 int ppp_post_clean_mask(const uint8_t *d_mask, uint8_t *d_out, int32_t Z, int32_t Y, int32_t X, uint32_t structure,
                         int64_t size, int64_t *n_found, int64_t *n_kept, void *d_work, void *stream);
 
+/* --- postprocess_fg on the device (csrc/ppp_edt.hip, csrc/ppp_postprocess.hip) ------------------
+ * The reference's `process_fg_prediction` branch (PatchPerPix/util/postprocess.py:122-199): the
+ * thresholded foreground is labelled with the 3 x 3 x 3 structure, and a component of at most
+ * `remove_small_comps` voxels is removed when all its voxels lie at a distance >= max_distance_to_fg
+ * from the larger components (scipy.ndimage.distance_transform_edt).  Both calls work in integers only:
+ * the distance is the exact SQUARED Euclidean distance, and the caller turns the reference's float
+ * comparison into one integer bound (patchperpix_amd.postprocess.min_sq_distance).  Volumes of 2^31
+ * voxels or more, or with Z^2 + Y^2 + X^2 >= 2^32 - 1 (a squared distance could reach the 32-bit
+ * infinity), return PPP_ERR_UNSUPPORTED; the size queries return it as a negative value.
+ *
+ * ppp_post_edt_sq: d_out u32 [Z][Y][X], d_out[v] = min(min over voxels w with d_feature[w] != 0 of
+ *   |v - w|^2, cap); cap = 0 means no cap, and then 0xFFFFFFFF is written where the volume holds no
+ *   feature.  Three separable passes x -> y -> z between d_out and the workspace (one u32 volume),
+ *   each an expanding window that stops at k^2 >= the best value so far: exact, and bounded by
+ *   ceil(sqrt(cap)) steps per pass under a cap; without one the cost is the sum of the distances.
+ *   Does not synchronise the stream.
+ * ppp_post_fg_filter: the whole step.  d_mask u8 [Z][Y][X], 0 / non-zero.  Components are 26-connected;
+ *   BIG: more than `compsize` voxels, SMALL: the others.  d_fg u8 (may be d_mask) = 1 on the voxels of
+ *   big components and of small components with a voxel at a squared distance < min_d2 from a voxel of
+ *   a big one, else 0.  min_d2 = 0: every small component is removed and no transform runs (the
+ *   reference's else branch, remove_small_components).  No big component: every small component is
+ *   removed (the minimum over an empty set; the reference's result is an artefact of scipy there).
+ *   d_inst u32 (or NULL): the surviving components numbered 1, 2, ... in ascending order of their
+ *   smallest raster index -- scipy.ndimage.label of d_fg.  stats[4] = components found, small ones,
+ *   small ones removed, components kept.  Synchronises the stream once.  The workspace holds the
+ *   union-find, label, count, distance and scan volumes: about 29 bytes per voxel.              */
+int64_t ppp_post_edt_sq_workspace_bytes(int32_t Z, int32_t Y, int32_t X);
+int ppp_post_edt_sq(const uint8_t *d_feature, uint32_t *d_out, int32_t Z, int32_t Y, int32_t X, uint32_t cap,
+                    void *d_work, void *stream);
+int64_t ppp_post_fg_filter_workspace_bytes(int32_t Z, int32_t Y, int32_t X);
+int ppp_post_fg_filter(const uint8_t *d_mask, uint8_t *d_fg /* may be d_mask */, uint32_t *d_inst /* or NULL */,
+                       int32_t Z, int32_t Y, int32_t X, int64_t compsize, uint32_t min_d2,
+                       int64_t *stats /* [4]: found, small, removed, kept */, void *d_work, void *stream);
+
 /* --- 3-d thinning of the foreground on the device (csrc/ppp_skeleton.hip) ----------------------
  * `skeletonize_foreground` (vote_instances.py:219-224, stitch_patch_graph.py:756-759: the cover mask, or
  * the bounding box in blockwise mode, is the 3-d skeleton of the foreground).  The result is DEFINED as

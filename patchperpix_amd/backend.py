@@ -363,6 +363,14 @@ _SIGNATURES = {
                                            ctypes.c_int32, ctypes.c_uint32, ctypes.c_int64,
                                            ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
                                            ctypes.c_void_p, ctypes.c_void_p]),
+    # postprocess_fg: exact squared distance transform and the component filter (ppp_edt.hip, ppp_postprocess.hip)
+    "ppp_post_edt_sq_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "ppp_post_edt_sq": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                       ctypes.c_int32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
+    "ppp_post_fg_filter_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "ppp_post_fg_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                          ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32,
+                                          ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p, ctypes.c_void_p]),
     # 3-d thinning of the foreground on the device (ppp_skeleton.hip)
     "ppp_skeletonize_3d_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "ppp_skeletonize_3d": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
@@ -2122,6 +2130,41 @@ def post_clean_mask(mask, structure_bits, size):
         check(lib().ppp_post_clean_mask(_dev_ptr(mask), _dev_ptr(out), Z, Y, X, int(structure_bits), int(size),
                                         ctypes.byref(found), ctypes.byref(kept), _dev_ptr(work), _stream()))
     return out, int(found.value), int(kept.value)
+
+
+def post_edt_sq(feature, cap=0):
+    """ppp_post_edt_sq on a contiguous (Z, Y, X) uint8 device tensor: the exact squared Euclidean distance
+    of every voxel to the nearest voxel with feature != 0, cut at `cap` (0: no cap; 0xFFFFFFFF where
+    the volume holds no feature then).  Returns an int32 tensor whose bits are the uint32 values."""
+    torch = _torch()
+    assert feature.dtype == torch.uint8 and feature.dim() == 3, "post_edt_sq needs a uint8 (Z, Y, X) volume"
+    assert 0 <= int(cap) <= 0xFFFFFFFF, "cap is an unsigned 32-bit value"
+    Z, Y, X = [int(v) for v in feature.shape]
+    work = _workspace(lib().ppp_post_edt_sq_workspace_bytes(Z, Y, X), feature.device)
+    out = torch.empty((Z, Y, X), dtype=torch.int32, device=feature.device)
+    with _timed("post_edt_sq"):
+        check(lib().ppp_post_edt_sq(_dev_ptr(feature), _dev_ptr(out), Z, Y, X, int(cap), _dev_ptr(work), _stream()))
+    return out
+
+
+def post_fg_filter(mask, compsize, min_d2, want_instances=False):
+    """ppp_post_fg_filter on a contiguous (Z, Y, X) uint8 device tensor: the mask without its 26-connected
+    components of at most `compsize` voxels that have no voxel at a squared distance < `min_d2` from a
+    larger component (min_d2 = 0: all of them go).  Returns (uint8 tensor, int32 tensor with the bits of the
+    uint32 component numbers -- scipy.ndimage.label's of the result -- or None, (found, small, removed,
+    kept))."""
+    torch = _torch()
+    assert mask.dtype == torch.uint8 and mask.dim() == 3, "post_fg_filter needs a uint8 (Z, Y, X) mask"
+    assert 0 <= int(min_d2) <= 0xFFFFFFFF, "min_d2 is an unsigned 32-bit value"
+    Z, Y, X = [int(v) for v in mask.shape]
+    work = _workspace(lib().ppp_post_fg_filter_workspace_bytes(Z, Y, X), mask.device)
+    fg = torch.empty_like(mask)
+    inst = torch.empty((Z, Y, X), dtype=torch.int32, device=mask.device) if want_instances else None
+    stats = (ctypes.c_int64 * 4)()
+    with _timed("post_fg_filter"):
+        check(lib().ppp_post_fg_filter(_dev_ptr(mask), _dev_ptr(fg), None if inst is None else _dev_ptr(inst), Z, Y, X,
+                                       int(compsize), int(min_d2), stats, _dev_ptr(work), _stream()))
+    return fg, inst, tuple(int(v) for v in stats)
 
 
 def host_cover_pass(mask_running, overlap, patchshape, ranked_lin, ranked_score, bits, pix_th,

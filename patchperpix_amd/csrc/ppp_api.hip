@@ -1475,6 +1475,50 @@ int ppp_post_clean_mask(const uint8_t *d_mask, uint8_t *d_out, int32_t Z, int32_
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_post_clean_mask");
 }
 
+/* ---- exact squared distance transform (ppp_edt.hip) and postprocess_fg (ppp_postprocess.hip) ---- */
+static int edt_volume(int32_t Z, int32_t Y, int32_t X, long long *V) {
+    PPP_TRY(post_volume(Z, Y, X, V));
+    // the largest squared distance of the volume must stay below the 32-bit infinity
+    if ((long long)Z * Z + (long long)Y * Y + (long long)X * X >= 0xFFFFFFFFll)
+        return fail(PPP_ERR_UNSUPPORTED, "squared distances of a %d x %d x %d volume do not fit 32 bits", Z, Y, X);
+    return PPP_OK;
+}
+
+int64_t ppp_post_edt_sq_workspace_bytes(int32_t Z, int32_t Y, int32_t X) {
+    long long V;
+    int rc = edt_volume(Z, Y, X, &V);
+    return rc != PPP_OK ? rc : (int64_t)ppp::post_edt_workspace_bytes(V);
+}
+
+int ppp_post_edt_sq(const uint8_t *d_feature, uint32_t *d_out, int32_t Z, int32_t Y, int32_t X, uint32_t cap,
+                    void *d_work, void *stream) {
+    long long V;
+    PPP_TRY(edt_volume(Z, Y, X, &V));
+    if (!d_feature || !d_out || !d_work || ((uintptr_t)d_out & 3)) return fail(PPP_ERR_INVALID_ARG, "NULL or misaligned pointer argument");
+    PPP_TRY(need_device());
+    hipError_t e = ppp::run_post_edt_sq(d_feature, d_out, Z, Y, X, cap, d_work, (hipStream_t)stream);
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_post_edt_sq");
+}
+
+int64_t ppp_post_fg_filter_workspace_bytes(int32_t Z, int32_t Y, int32_t X) {
+    long long V;
+    int rc = edt_volume(Z, Y, X, &V);
+    return rc != PPP_OK ? rc : (int64_t)ppp::post_fg_filter_workspace_bytes(V);
+}
+
+int ppp_post_fg_filter(const uint8_t *d_mask, uint8_t *d_fg, uint32_t *d_inst, int32_t Z, int32_t Y, int32_t X,
+                       int64_t compsize, uint32_t min_d2, int64_t *stats, void *d_work, void *stream) {
+    long long V;
+    PPP_TRY(edt_volume(Z, Y, X, &V));
+    if (!d_mask || !d_fg || !d_work || !stats || ((uintptr_t)d_inst & 3))
+        return fail(PPP_ERR_INVALID_ARG, "NULL or misaligned pointer argument");
+    PPP_TRY(need_device());
+    long long st[4] = {0, 0, 0, 0};
+    hipError_t e = ppp::run_post_fg_filter(d_mask, d_fg, d_inst, Z, Y, X, compsize, min_d2, st, d_work, (hipStream_t)stream);
+    for (int i = 0; i < 4; ++i) stats[i] = st[i];
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_post_fg_filter");
+}
+
 /* ---- 3-d thinning of the foreground (ppp_skeleton.hip) ---- */
 static int skeleton_volume(int32_t Z, int32_t Y, int32_t X) {
     long long V;

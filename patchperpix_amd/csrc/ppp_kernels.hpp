@@ -244,6 +244,22 @@ size_t post_clean_mask_workspace_bytes(long long V);
 hipError_t run_post_clean_mask(const uint8_t *mask, uint8_t *out, int Z, int Y, int X, uint32_t structure,
                                long long size, long long *n_found, long long *n_kept, void *work, hipStream_t s);
 
+// exact squared Euclidean distance transform (ppp_edt.hip): out[v] = min(min over feature voxels w of
+// |v - w|^2, cap), cap = 0: no cap, 0xFFFFFFFF where there is neither feature nor cap
+struct EdtWork {
+    uint32_t *tmp;       // [V]: the volume between the y and the z pass
+};
+EdtWork edt_layout(Carver &c, long long V);
+size_t post_edt_workspace_bytes(long long V);
+hipError_t launch_edt_sq(const uint8_t *feature, uint32_t *out, int Z, int Y, int X, uint32_t cap, const EdtWork &W,
+                         hipStream_t s);
+hipError_t run_post_edt_sq(const uint8_t *feature, uint32_t *out, int Z, int Y, int X, uint32_t cap, void *work,
+                           hipStream_t s);
+// postprocess_fg (util/postprocess.py:122-199) in one call (ppp_postprocess.hip); stats[4]: found, small, removed, kept
+size_t post_fg_filter_workspace_bytes(long long V);
+hipError_t run_post_fg_filter(const uint8_t *mask, uint8_t *fg, uint32_t *inst, int Z, int Y, int X, long long compsize,
+                              uint32_t min_d2, long long *stats, void *work, hipStream_t s);
+
 // 3-d thinning of the foreground (ppp_skeleton.hip)
 size_t skeleton_workspace_bytes(int Z, int Y, int X);
 hipError_t run_skeletonize_3d(const uint8_t *mask, uint8_t *out, int Z, int Y, int X, long long *n_kept, int *stats,

@@ -7,6 +7,9 @@
 //                without the loop over instances (see "dilation" below).
 //   clean_mask   stitch_patch_graph.py:46-57: connected components of a mask (union-find over linear
 //                voxel indices), components of at most `size` voxels dropped.
+//   fg_filter    postprocess_fg (PatchPerPix/util/postprocess.py:122-199): the same components, the small
+//                ones dropped unless they lie near a big one (the distance transform of ppp_edt.hip),
+//                the survivors numbered like scipy's labels of the cleaned mask.
 //
 // Ids are UNSIGNED 32-bit everywhere: they index tables as size_t and compare as uint32_t.
 #include <cstring>
@@ -454,6 +457,134 @@ hipError_t run_post_clean_mask(const uint8_t *mask, uint8_t *out, int Z, int Y, 
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
     *n_found = h[0];
     *n_kept = h[1];
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// fg_filter: postprocess_fg (PatchPerPix/util/postprocess.py:122-199)
+// ---------------------------------------------------------------------------------------------
+// 26-connected components of the mask; a component of more than `compsize` voxels is BIG, the others are
+// SMALL.  A small component stays iff one of its voxels lies at a squared distance < min_d2 from a voxel
+// of a big one (min_d2 = 0: no small component stays, and no distance transform runs).  Integers only:
+// the host turns the reference's `dist >= max_distance_to_fg` into min_d2 once.  Labels are root + 1 with
+// the root the smallest raster index of the component, so ascending label order is scipy's numbering,
+// and the surviving components numbered 1, 2, ... in that order are scipy's labels of the cleaned mask.
+__global__ void __launch_bounds__(256)
+    fg_feature_kernel(const uint32_t *__restrict__ lab, const uint32_t *__restrict__ counts, const long long compsize,
+                      uint8_t *__restrict__ feature, const long long V, uint32_t *__restrict__ counters) {
+    const long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    bool small_root = false;
+    if (v < V) {
+        const uint32_t l = lab[v];
+        const bool big = l != 0u && (long long)counts[l] > compsize;
+        feature[v] = big ? 1 : 0;
+        small_root = l == (uint32_t)v + 1u && !big;
+    }
+    const unsigned long long m = __ballot(small_root);
+    if (m && (threadIdx.x & 63) == 0) atomicAdd(&counters[1], (uint32_t)__popcll(m));
+}
+// one atomicMin per voxel of a small component: at most `compsize` of them share an address
+__global__ void __launch_bounds__(256)
+    fg_min_d2_kernel(const uint32_t *__restrict__ lab, const uint32_t *__restrict__ counts, const long long compsize,
+                     const uint32_t *__restrict__ d2, uint32_t *__restrict__ mind2, const long long V) {
+    const long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (v >= V) return;
+    const uint32_t l = lab[v];
+    if (l != 0u && (long long)counts[l] <= compsize) atomicMin(&mind2[l], d2[v]);
+}
+// in place: table[i] = voxels of label i  ->  1 when label i stays; counters[2] += small components removed
+__global__ void __launch_bounds__(256)
+    fg_keep_kernel(uint32_t *__restrict__ table, const uint32_t *__restrict__ mind2, const size_t slots,
+                   const long long compsize, const uint32_t min_d2, uint32_t *__restrict__ counters) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    bool removed = false;
+    if (i < slots) {
+        const uint32_t c = table[i];
+        const bool present = i != 0 && c != 0u;
+        const bool keep = present && ((long long)c > compsize || (min_d2 != 0u && mind2[i] < min_d2));
+        removed = present && !keep;
+        table[i] = keep ? 1u : 0u;
+    }
+    const unsigned long long m = __ballot(removed);
+    if (m && (threadIdx.x & 63) == 0) atomicAdd(&counters[2], (uint32_t)__popcll(m));
+}
+__global__ void __launch_bounds__(256)
+    fg_out_kernel(const uint32_t *__restrict__ lab, const uint32_t *__restrict__ keep, const uint32_t *__restrict__ rank,
+                  uint8_t *__restrict__ fg, uint32_t *__restrict__ inst, const long long V) {
+    const long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (v >= V) return;
+    const uint32_t l = lab[v];
+    const bool k = l != 0u && keep[l] != 0u;
+    fg[v] = k ? 1 : 0;
+    if (inst) inst[v] = k ? rank[l] + 1u : 0u;
+}
+
+struct FgWork {
+    CleanWork cc;        // parent, labels, counts (then keep flags), counters: [0] found, [1] small, [2] removed, [3] bad id
+    uint8_t *feature;    // [V]: voxels of big components
+    uint32_t *d2;        // [V]: min(squared distance to a feature, min_d2)
+    EdtWork edt;
+    uint32_t *mind2;     // [V + 2]: per label, the minimum of d2 over its voxels
+    uint32_t *rank;      // [V + 2]: exclusive scan of the keep flags
+    void *temp;
+    size_t temp_bytes, slots;
+};
+static FgWork fg_layout(Carver &c, long long V) {
+    FgWork W;
+    W.cc = clean_layout(c, V);
+    W.slots = (size_t)V + 2;
+    W.feature = c.take<uint8_t>((size_t)V);
+    W.d2 = c.take<uint32_t>((size_t)V);
+    W.edt = edt_layout(c, V);
+    W.mind2 = c.take<uint32_t>(W.slots);
+    W.rank = c.take<uint32_t>(W.slots);
+    size_t tb = 0;
+    (void)rocprim::exclusive_scan(nullptr, tb, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, W.slots,
+                                  rocprim::plus<uint32_t>(), (hipStream_t)0);
+    W.temp_bytes = up256(tb);
+    W.temp = c.take_bytes(W.temp_bytes);
+    return W;
+}
+size_t post_fg_filter_workspace_bytes(long long V) { Carver c(nullptr); fg_layout(c, V); return c.used; }
+
+// fg may be mask; inst may be NULL.  Synchronises once (stats go to the host).  Without a big component
+// the transform still runs and fills d2 with min_d2: no small component is below it, all are removed --
+// the minimum over an empty set -- and the stream is not synchronised a second time to find that out.
+hipError_t run_post_fg_filter(const uint8_t *mask, uint8_t *fg, uint32_t *inst, int Z, int Y, int X, long long compsize,
+                              uint32_t min_d2, long long *stats, void *work, hipStream_t s) {
+    Vol G;
+    G.Z = Z; G.Y = Y; G.X = X;
+    G.YX = (long long)Y * X;
+    G.V = G.YX * Z;
+    PPP_GRID_CHECK((G.V + 255) / 256, 256);
+    Carver carver(work);
+    const FgWork W = fg_layout(carver, G.V);
+    const dim3 block(256), vgrid((unsigned)((G.V + 255) / 256)), sgrid((unsigned)((W.slots + 255) / 256));
+    hipError_t e;
+    if ((e = hipMemsetAsync(W.cc.counts, 0, W.slots * 4, s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(W.cc.counters, 0, 16, s)) != hipSuccess) return e;
+    cc_init_kernel<<<vgrid, block, 0, s>>>(mask, W.cc.parent, G.V);
+    cc_union_kernel<<<vgrid, block, 0, s>>>(mask, W.cc.parent, G, 0x7FFFFFFu);
+    cc_label_kernel<<<vgrid, block, 0, s>>>(W.cc.parent, W.cc.lab, G.V, W.cc.counters);
+    if ((e = launch_count_ids(W.cc.lab, G.V, (uint32_t)G.V, W.cc.counts, W.cc.counters + 3, s)) != hipSuccess) return e;
+    fg_feature_kernel<<<vgrid, block, 0, s>>>(W.cc.lab, W.cc.counts, compsize, W.feature, G.V, W.cc.counters);
+    if (min_d2 != 0u) {
+        if ((e = hipMemsetAsync(W.mind2, 0xFF, W.slots * 4, s)) != hipSuccess) return e;
+        if ((e = launch_edt_sq(W.feature, W.d2, Z, Y, X, min_d2, W.edt, s)) != hipSuccess) return e;
+        fg_min_d2_kernel<<<vgrid, block, 0, s>>>(W.cc.lab, W.cc.counts, compsize, W.d2, W.mind2, G.V);
+    }
+    fg_keep_kernel<<<sgrid, block, 0, s>>>(W.cc.counts, W.mind2, W.slots, compsize, min_d2, W.cc.counters);
+    size_t tb = W.temp_bytes;
+    if ((e = rocprim::exclusive_scan(W.temp, tb, W.cc.counts, W.rank, 0u, W.slots, rocprim::plus<uint32_t>(), s)) != hipSuccess)
+        return e;
+    fg_out_kernel<<<vgrid, block, 0, s>>>(W.cc.lab, W.cc.counts, W.rank, fg, inst, G.V);
+    uint32_t h[3] = {0, 0, 0};
+    if ((e = hipMemcpyAsync(h, W.cc.counters, 12, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+    stats[0] = h[0];
+    stats[1] = h[1];
+    stats[2] = h[2];
+    stats[3] = (long long)h[0] - (long long)h[2];
     return hipGetLastError();
 }
 

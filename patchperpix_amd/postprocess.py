@@ -8,7 +8,12 @@ is the block the drivers run after the assembly and picks between the two (`use_
 
 `postprocess_instances` is the reference driver's `postprocess` task (postprocess.py:77-119): the instance
 map cleaned again and one 3-d skeleton per instance -- `skeletonize_instances` (host loop, the definition)
-or `skeletonize_instances_device` (all instances in one pass, csrc/ppp_skeleton.hip)."""
+or `skeletonize_instances_device` (all instances in one pass, csrc/ppp_skeleton.hip).
+
+`postprocess_fg` is the task's other branch, `process_fg_prediction` (postprocess.py:122-199): the thresholded
+foreground without its small components that lie far from the large ones -- `fg_filter` (scipy, the
+definition) or `fg_filter_device` (csrc/ppp_edt.hip and the fg_filter kernels of csrc/ppp_postprocess.hip),
+both comparing the exact integer squared distance with `min_sq_distance`."""
 import logging
 import math
 import os
@@ -295,6 +300,150 @@ def postprocess_instances(samples, output_folder, **kwargs):
                 for lbl in np.unique(cleaned):
                     if lbl > 0:
                         mininrrd.write(os.path.join(output_folder, sample_name + ("_%i.nrrd" % lbl)), vol == lbl)
+
+
+# ----------------------------------------------------------------------------------------
+# the `postprocess_fg` task: small foreground components far from the large ones removed
+# (postprocess.py:122-199)
+# ----------------------------------------------------------------------------------------
+def min_sq_distance(max_distance):
+    """The reference removes a small component when ``dist >= max_distance_to_fg`` holds on all its voxels,
+    with ``dist = sqrt(float64(d2))`` of the exact integer squared distance d2 (scipy's
+    distance_transform_edt).  sqrt is monotone, so that is ``min d2 >= T`` with T the smallest integer
+    t >= 0 such that ``np.sqrt(np.float64(t)) >= np.float64(max_distance)``; this returns T, found by
+    searching around ceil(max_distance ** 2).  0 for a value that is not positive (the reference's else
+    branch: every small component goes).  From 2 ** 31 on, beyond the diagonal of any volume a call
+    accepts, the answer is 2 ** 62: above every squared distance."""
+    m = np.float64(max_distance)
+    if not m > 0:
+        return 0
+    if m >= 2.0 ** 31:
+        return 1 << 62
+    t = int(math.ceil(float(m) * float(m)))
+    while t > 0 and np.sqrt(np.float64(t - 1)) >= m:
+        t -= 1
+    while np.sqrt(np.float64(t)) < m:
+        t += 1
+    return t
+
+
+def fg_filter(mask, compsize, max_distance, want_instances=False):
+    """postprocess.py:134-174 and :185 on a (Z, Y, X) mask, the host DEFINITION of `fg_filter_device`.
+    Components are those of ``ndimage.label(mask, np.ones((3, 3, 3)))``; SMALL: ``count <= compsize``, BIG:
+    the others.  With ``T = min_sq_distance(max_distance)``:
+
+    - fg = the voxels of big components and of the small ones whose minimum squared distance to a voxel
+      of a big component is < T (T = 0, the reference's else branch: no small one stays);
+    - instances = the surviving components numbered in ascending order of their smallest raster
+      index, which is ``ndimage.label`` of fg.
+
+    Two inputs on which the reference has no defined result are defined here:
+
+    - no big component while max_distance > 0 (scipy's transform of an all-ones array returns an
+      artefact): the minimum over an empty set is infinite, every small component is removed;
+    - nothing to remove (the reference raises IndexError: it indexes with an empty float array):
+      nothing is removed.
+
+    Returns (uint8 fg, uint32 instances or None, (found, small, removed, kept))."""
+    m = np.asarray(mask) != 0
+    if m.ndim != 3:
+        raise ValueError("fg_filter needs a (Z, Y, X) mask, not %d axes" % m.ndim)
+    T = min_sq_distance(max_distance)
+    labels, found = ndimage.label(m, np.ones((3, 3, 3)))
+    counts = np.bincount(labels.ravel(), minlength=found + 1)
+    big = counts > compsize
+    big[0] = False
+    small = counts <= compsize
+    small[0] = False
+    remove = small.copy()
+    if T > 0 and big.any() and small.any():
+        dist = ndimage.distance_transform_edt(np.logical_not(big[labels]))
+        d2 = np.rint(dist * dist).astype(np.int64)
+        mind2 = np.full(found + 1, np.iinfo(np.int64).max, dtype=np.int64)
+        sel = small[labels]
+        np.minimum.at(mind2, labels[sel], d2[sel])
+        remove &= mind2 >= T
+    keep = (big | small) & ~remove
+    fg = keep[labels].astype(np.uint8)
+    inst = None
+    if want_instances:
+        inst = np.where(keep, np.cumsum(keep), 0).astype(np.uint32)[labels]
+    n_small, n_removed = int(small.sum()), int(remove.sum())
+    return fg, inst, (int(found), n_small, n_removed, int(found) - n_removed)
+
+
+def fg_filter_device(mask, compsize, max_distance, want_instances=False):
+    """`fg_filter` from the device (backend.post_fg_filter = ppp_post_fg_filter: union-find components, the
+    exact squared distance transform of csrc/ppp_edt.hip, integers only): the same three results.  Masks
+    that are empty or hold 2^31 voxels or more are the host's."""
+    from . import backend
+    import torch
+    m = np.asarray(mask)
+    if m.ndim != 3 or m.size == 0 or m.size >= 1 << 31 or sum(int(n) ** 2 for n in m.shape) >= (1 << 32) - 1:
+        logger.debug("postprocess_fg: component filter on the host (shape %s)", m.shape)
+        return fg_filter(m, compsize, max_distance, want_instances)
+    T = min(min_sq_distance(max_distance), 0xFFFFFFFF)      # (no squared distance of the volume reaches it)
+    size = min(max(int(math.floor(compsize)), -1), m.size)
+    t = torch.from_numpy(np.ascontiguousarray(m != 0).astype(np.uint8)).cuda()
+    fg, inst, stats = backend.post_fg_filter(t, size, T, want_instances)
+    return (fg.cpu().numpy(), None if inst is None else inst.cpu().numpy().view(np.uint32), stats)
+
+
+def postprocess_fg(samples, output_folder, **kwargs):
+    """The `process_fg_prediction` branch of the reference's `postprocess` task (postprocess.py:122-199,
+    called from run_ppp.py:2234-2245), under its name and kwargs: fg_key, fg_threshold, remove_small_comps,
+    max_distance_to_fg, cc_instances, export_skeleton_nrrds.  For every prediction file ``sample`` (zarr
+    through minizarr, ``.hdf`` through minihdf5):
+
+    - ``mask = np.asarray(sample[fg_key]) > fg_threshold`` on the host, the reference's own expression; a
+      dataset that is not 3-d raises ValueError (scipy's label refuses it with the 3 x 3 x 3 structure);
+    - `fg_filter` / `fg_filter_device` by the dispatch rule (`use_device`), see there for the result and for
+      the two inputs the reference leaves undefined;
+    - the output file is ``<output_folder>/<basename with .zarr -> .hdf>``, opened "w" (ValueError when
+      that is the sample itself): ``volumes/fg`` (uint8, gzip) and, with ``cc_instances``,
+      ``volumes/instances`` (``astype(np.uint16)``, gzip: ids above 65535 wrap as in the reference);
+    - ``export_skeleton_nrrds``: the 3-d thinning of the foreground (backend.skeletonize_3d on the device,
+      else backend.host_skeletonize_3d), written to the output name with ``.nrrd`` (mininrrd: the payload
+      of the reference's ``nrrd.write(mask.transpose(2, 1, 0))``).  The thinning is the library's own (Lee /
+      Kashyap / Chu 1994): parity with scikit-image's skeletonize_3d stays UNPINNED.
+
+    ``volumes/fg`` carries the attribute ``fg_filter`` naming the implementation used and, with a
+    skeleton, ``skeletonize_foreground`` naming the thinning."""
+    from . import backend, minihdf5, mininrrd, minizarr
+    comp_thresh = kwargs["remove_small_comps"]
+    max_distance = kwargs.get("max_distance_to_fg", 0)
+    want_inst = bool(kwargs.get("cc_instances", False))
+    os.makedirs(output_folder, exist_ok=True)
+    for sample in samples:
+        outfn = os.path.join(output_folder, os.path.basename(os.path.normpath(sample)).replace(".zarr", ".hdf"))
+        if os.path.abspath(outfn) == os.path.abspath(sample):
+            raise ValueError("postprocess_fg: the output file %s is the sample itself" % outfn)
+        if str(sample).rstrip("/").endswith(".hdf"):
+            with minihdf5.File(sample, "r") as inf:
+                pred = np.asarray(inf[kwargs["fg_key"]])
+        else:
+            pred = np.asarray(minizarr.open(sample, "r")[kwargs["fg_key"]])
+        if pred.ndim != 3:
+            raise ValueError("postprocess_fg: %s[%s] has %d axes, the 3 x 3 x 3 structure needs 3"
+                             % (sample, kwargs["fg_key"], pred.ndim))
+        mask = pred > kwargs["fg_threshold"]
+        device = use_device()
+        fg, inst, stats = (fg_filter_device if device else fg_filter)(mask, comp_thresh, max_distance, want_inst)
+        logger.info("postprocess_fg %s: %d components, %d small, %d removed, %d kept", os.path.basename(outfn), *stats)
+        with minihdf5.File(outfn, "w") as hout:
+            ds = hout.create_dataset("volumes/fg", data=fg.astype(np.uint8), dtype=np.uint8, compression="gzip")
+            ds.attrs["fg_filter"] = "ppp_post_fg_filter" if device else "scipy"
+            if want_inst:
+                hout.create_dataset("volumes/instances", data=inst.astype(np.uint16), dtype=np.uint16,
+                                    compression="gzip")
+            if kwargs.get("export_skeleton_nrrds", False):
+                skel = backend.skeletonize_3d(fg) if device else backend.host_skeletonize_3d(fg)
+                served_by = "ppp_skeletonize_3d" if device else "ppp_host_skeletonize_3d"
+                logger.warning("postprocess_fg: foreground skeleton by %s; not pinned to scikit-image's "
+                               "skeletonize_3d", served_by)
+                ds.attrs["skeletonize_foreground"] = served_by
+                stem = outfn[:-len(".hdf")] if outfn.endswith(".hdf") else outfn
+                mininrrd.write(stem + ".nrrd", np.asarray(skel))
 
 
 def post_steps(instances, foreground, res_key, **kw):

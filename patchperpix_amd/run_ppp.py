@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""`label`, `decode` and `postprocess` tasks with the reference driver's interface
+"""`label`, `decode`, `postprocess` and `postprocess_fg` tasks with the reference driver's interface
 (reference: experiments/run_ppp.py -- argument names :157-267, task dispatch :1974-2293,
 ``decode`` :682-746, ``vote_instances`` / ``vote_instances_sample`` :1054-1190, ``postprocess``
-:2230-2259 -- its ``process_instances`` branch; ``process_fg_prediction`` is refused).
+:2230-2259).  The reference's ``postprocess`` has two branches: ``process_instances`` is this driver's
+``--do postprocess``; ``process_fg_prediction`` (:2234-2245) is a task of its own here,
+``--do postprocess_fg``, and stays refused under ``--do postprocess``.
 
 Only the tasks on this repository's path are provided; training, prediction and evaluation
 stay with the reference.  Usage, as in the reference README:
@@ -141,10 +143,8 @@ def postprocess(args, config):
     from . import postprocess as post
     cfg = config.get("postprocessing", {})
     if cfg.get("process_fg_prediction", False):
-        # its max_distance_to_fg branch needs an exact Euclidean distance transform: not provided
-        raise NotImplementedError("[postprocessing] process_fg_prediction = true is not provided by this "
-                                  "repository (postprocess_fg stays with the reference); unset it to run "
-                                  "process_instances")
+        raise NotImplementedError("[postprocessing] process_fg_prediction = true is not served by --do postprocess: "
+                                  "run that branch as --do postprocess_fg; unset it to run process_instances")
     if cfg.get("process_instances", False):
         fmt = config["vote_instances"].get("output_format", "hdf")
         samples = [os.path.join(args.output_folder, s + "." + fmt)
@@ -154,6 +154,21 @@ def postprocess(args, config):
         logger.info("time postprocess_instances (%d samples): %.2fs", len(samples), time.time() - t0)
 
 
+def postprocess_fg(args, config):
+    """run_ppp.py:2234-2245, the ``process_fg_prediction`` branch as a task of its own: the prediction
+    files ``*.<prediction.output_format>`` of --pred-folder, ``fg_key`` from [prediction], everything else
+    from [postprocessing]; one ``<sample>.hdf`` per file in --output-folder."""
+    from . import postprocess as post
+    fmt = config["prediction"]["output_format"]
+    samples = [os.path.join(args.pred_folder, s + "." + fmt)
+               for s in get_list_samples(args.pred_folder, fmt, args.sample)]
+    os.makedirs(args.output_folder, exist_ok=True)
+    t0 = time.time()
+    post.postprocess_fg(samples, args.output_folder, fg_key=config["prediction"]["fg_key"],
+                        **config.get("postprocessing", {}))
+    logger.info("time postprocess_fg (%d samples): %.2fs", len(samples), time.time() - t0)
+
+
 def main(argv=None):
     from patchperpix_amd import backend as _backend
     _backend.tune_host_allocator(cli=True)     # (main(argv) IS the program, also behind a console script)
@@ -161,7 +176,7 @@ def main(argv=None):
     ap.add_argument("-c", "--config", action="append", required=True)
     ap.add_argument("-a", "--app", default="flylight")
     ap.add_argument("-s", "--setup", default="setup01")
-    ap.add_argument("-d", "--do", nargs="+", default=["label"], choices=["label", "decode", "postprocess"])
+    ap.add_argument("-d", "--do", nargs="+", default=["label"], choices=["label", "decode", "postprocess", "postprocess_fg"])
     ap.add_argument("--pred-folder", required=True)
     ap.add_argument("--output-folder", required=True)
     ap.add_argument("--checkpoint", default=None)
@@ -170,7 +185,7 @@ def main(argv=None):
     logging.basicConfig(level=logging.INFO)
     config = load_config(args.config)
     for task in args.do:
-        {"label": label, "decode": decode, "postprocess": postprocess}[task](args, config)
+        {"label": label, "decode": decode, "postprocess": postprocess, "postprocess_fg": postprocess_fg}[task](args, config)
 
 
 if __name__ == "__main__":
