@@ -861,6 +861,40 @@ int ppp_post_fg_filter(const uint8_t *d_mask, uint8_t *d_fg /* may be d_mask */,
                        int32_t Z, int32_t Y, int32_t X, int64_t compsize, uint32_t min_d2,
                        int64_t *stats /* [4]: found, small, removed, kept */, void *d_work, void *stream);
 
+/* --- evaluate_patch on the device (csrc/ppp_eval.hip) --------------------------------------------
+ * The reference's `evaluate_patch` (PatchPerPix/evaluate/evaluate_prediction.py:38-150) scores the dense
+ * patch prediction against the ground-truth affinities of the label volume, per threshold.  Here it is
+ * one streaming reduction: every prediction element is read once per pass of
+ * ppp_eval_patch_thresholds_per_pass() thresholds, the ground-truth affinity is computed from the labels
+ * on the fly and never stored.
+ *   d_pred   [C][tz][Y][X], elements of PPP_F32 / PPP_F16 / PPP_BF16: the slices z0 .. z0 + tz of the
+ *            prediction of the volume vol = (Z, Y, X); C = pz * py * px, patch = (pz, py, px), all odd;
+ *            channel e = ((dz + rz) py + (dy + ry)) px + (dx + rx), r = patch / 2.  No halo.
+ *   d_labels int32 [L][Z][Y][X], the WHOLE volume, values >= 0 (the caller checks; a negative value counts
+ *            as background here).
+ *   numinst[v] = #{c : labels[c][v] > 0}, ov[v] = numinst[v] > 1.
+ *   G'[e][v] = 1 iff !ov[v], v + off(e) lies inside the volume and some channel c has labels[c][v] != 0 and
+ *            labels[c][v] == labels[c][v + off(e)]  (gunpowder's seg_to_affgraph* as restated by the
+ *            reference's util/train_util.py:523-695, with the centre's overlap zeroed as evaluate_patch does).
+ *   P_t[e][v] = (ov[v] ? 0 : pred[e][v]) > thresholds[t]: the element widened exactly to float, a float
+ *            compare, NaN false.  `thresholds` is a HOST array the caller has already rounded to the
+ *            element type (float32 rounding for PPP_F32 and PPP_BF16, float16 rounding for PPP_F16: NumPy's
+ *            compare of an array with a Python float); a value that is not finite: PPP_ERR_INVALID_ARG.
+ *   d_counts int64 [1 + 2T], ADDED to (zero it before the first tile): num_gt = sum G', then per threshold
+ *            num_pred_t = sum P_t and tp_t = sum P_t & G'.  Integer atomics: independent of the order.
+ *   d_inter, d_union int32 [T][tz][Y][X], both or neither (NULL): per voxel sum_e P_t & G' and sum_e P_t | G'.
+ * PPP_ERR_INVALID_ARG: C != pz py px, an even patch side, T < 1 or T > ppp_eval_patch_max_thresholds() (32),
+ * z0 + tz > Z, tz < 1, L < 1.  PPP_ERR_UNSUPPORTED: volumes of 2^31 voxels or more, patches of more than
+ * 65535 elements (the size query returns it as a negative value).  Does not synchronise the stream.
+ * The workspace holds two int32 per voxel of the tile.                                              */
+int32_t ppp_eval_patch_thresholds_per_pass(void);
+int32_t ppp_eval_patch_max_thresholds(void);
+int64_t ppp_eval_patch_workspace_bytes(const int32_t *vol /* [3] */, int32_t tz);
+int ppp_eval_patch(const void *d_pred, int pred_dtype, int32_t C, const int32_t *d_labels, int32_t L,
+                   const int32_t *vol /* [3] */, const int32_t *patch /* [3] */, int32_t z0, int32_t tz,
+                   const float *thresholds /* host [T] */, int32_t T, int64_t *d_counts /* [1 + 2T] */,
+                   int32_t *d_inter, int32_t *d_union /* [T][tz][Y][X] or NULL */, void *d_work, void *stream);
+
 /* --- 3-d thinning of the foreground on the device (csrc/ppp_skeleton.hip) ----------------------
  * `skeletonize_foreground` (vote_instances.py:219-224, stitch_patch_graph.py:756-759: the cover mask, or
  * the bounding box in blockwise mode, is the 3-d skeleton of the foreground).  The result is DEFINED as

@@ -371,6 +371,14 @@ _SIGNATURES = {
     "ppp_post_fg_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32,
                                           ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p, ctypes.c_void_p]),
+    # evaluate_patch as one streaming reduction (ppp_eval.hip)
+    "ppp_eval_patch_thresholds_per_pass": (ctypes.c_int32, []),
+    "ppp_eval_patch_max_thresholds": (ctypes.c_int32, []),
+    "ppp_eval_patch_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
+    "ppp_eval_patch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
+                                      ctypes.c_int32, ctypes.POINTER(ctypes.c_float), ctypes.c_int32, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     # 3-d thinning of the foreground on the device (ppp_skeleton.hip)
     "ppp_skeletonize_3d_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "ppp_skeletonize_3d": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
@@ -2165,6 +2173,35 @@ def post_fg_filter(mask, compsize, min_d2, want_instances=False):
         check(lib().ppp_post_fg_filter(_dev_ptr(mask), _dev_ptr(fg), None if inst is None else _dev_ptr(inst), Z, Y, X,
                                        int(compsize), int(min_d2), stats, _dev_ptr(work), _stream()))
     return fg, inst, tuple(int(v) for v in stats)
+
+
+def eval_patch(pred_tile, labels, patchshape, z0, thresholds, counts, want_maps=False):
+    """ppp_eval_patch on the slices z0 .. z0 + tz of a prediction: `pred_tile` a contiguous (C, tz, Y, X) device
+    tensor (float32 / float16 / bfloat16), `labels` the contiguous int32 (L, Z, Y, X) device tensor of the WHOLE
+    volume (values >= 0), `thresholds` floats already rounded to the element type, `counts` an int64 device
+    tensor of 1 + 2 T entries that is ADDED to (num_gt, then num_pred and tp per threshold).  Returns
+    (inter, union), int32 (T, tz, Y, X) device tensors, or (None, None) without `want_maps`.  Does not
+    synchronise."""
+    torch = _torch()
+    assert pred_tile.dim() == 4 and labels.dim() == 4 and labels.dtype == torch.int32, \
+        "eval_patch needs a (C, tz, Y, X) prediction and int32 (L, Z, Y, X) labels"
+    C, tz, Y, X = [int(v) for v in pred_tile.shape]
+    L, Z = int(labels.shape[0]), int(labels.shape[1])
+    assert tuple(labels.shape[2:]) == (Y, X), "prediction and labels differ in (Y, X)"
+    T = len(thresholds)
+    assert counts.dtype == torch.int64 and counts.numel() == 1 + 2 * T, "counts holds 1 + 2 T int64 entries"
+    vol, patch = (ctypes.c_int32 * 3)(Z, Y, X), (ctypes.c_int32 * 3)(*[int(p) for p in patchshape])
+    th = (ctypes.c_float * max(T, 1))(*[float(t) for t in thresholds])
+    work = _workspace(lib().ppp_eval_patch_workspace_bytes(vol, tz), pred_tile.device)
+    inter = union = None
+    if want_maps:
+        inter = torch.empty((T, tz, Y, X), dtype=torch.int32, device=pred_tile.device)
+        union = torch.empty_like(inter)
+    with _timed("eval_patch"):
+        check(lib().ppp_eval_patch(_dev_ptr(pred_tile), pred_dtype_code(pred_tile), C, _dev_ptr(labels), L, vol, patch,
+                                   int(z0), tz, th, T, _dev_ptr(counts), _dev_ptr(inter), _dev_ptr(union),
+                                   _dev_ptr(work), _stream()))
+    return inter, union
 
 
 def host_cover_pass(mask_running, overlap, patchshape, ranked_lin, ranked_score, bits, pix_th,

@@ -1519,6 +1519,55 @@ int ppp_post_fg_filter(const uint8_t *d_mask, uint8_t *d_fg, uint32_t *d_inst, i
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_post_fg_filter");
 }
 
+/* ---- evaluate_patch (ppp_eval.hip) ---- */
+static int eval_args(int32_t L, const int32_t *vol, const int32_t *patch, int32_t z0, int32_t tz, long long *n) {
+    if (!vol || !patch) return fail(PPP_ERR_INVALID_ARG, "NULL vol / patch");
+    long long V;
+    PPP_TRY(post_volume(vol[0], vol[1], vol[2], &V));
+    if (L < 1) return fail(PPP_ERR_INVALID_ARG, "labels need at least one channel (L = %d)", L);
+    for (int a = 0; a < 3; ++a)
+        if (patch[a] < 1 || patch[a] % 2 == 0) return fail(PPP_ERR_INVALID_ARG, "patch side %d must be odd and positive", patch[a]);
+    if ((long long)patch[0] * patch[1] * patch[2] > 65535)
+        return fail(PPP_ERR_UNSUPPORTED, "patches of more than 65535 elements are not supported");
+    if (z0 < 0 || tz < 1 || (long long)z0 + tz > vol[0])
+        return fail(PPP_ERR_INVALID_ARG, "z-tile [%d, %d + %d) outside the volume of %d slices", z0, z0, tz, vol[0]);
+    *n = (long long)tz * vol[1] * vol[2];
+    return PPP_OK;
+}
+
+int32_t ppp_eval_patch_thresholds_per_pass(void) { return ppp::kEvalT; }
+int32_t ppp_eval_patch_max_thresholds(void) { return ppp::kEvalMaxT; }
+
+int64_t ppp_eval_patch_workspace_bytes(const int32_t *vol, int32_t tz) {
+    const int32_t unit[3] = {1, 1, 1};
+    long long n;
+    int rc = eval_args(1, vol, unit, 0, tz, &n);
+    return rc != PPP_OK ? rc : (int64_t)ppp::eval_patch_workspace_bytes(n);
+}
+
+int ppp_eval_patch(const void *d_pred, int pred_dtype, int32_t C, const int32_t *d_labels, int32_t L, const int32_t *vol,
+                   const int32_t *patch, int32_t z0, int32_t tz, const float *thresholds, int32_t T, int64_t *d_counts,
+                   int32_t *d_inter, int32_t *d_union, void *d_work, void *stream) {
+    long long n;
+    PPP_TRY(eval_args(L, vol, patch, z0, tz, &n));
+    PPP_TRY(check_dtype(pred_dtype));
+    if (C != patch[0] * patch[1] * patch[2])
+        return fail(PPP_ERR_INVALID_ARG, "%d channels, but the patch %d x %d x %d has %d elements", C, patch[0], patch[1],
+                    patch[2], patch[0] * patch[1] * patch[2]);
+    if (!thresholds || T < 1 || T > ppp::kEvalMaxT) return fail(PPP_ERR_INVALID_ARG, "T = %d thresholds: 1 .. %d", T, ppp::kEvalMaxT);
+    for (int t = 0; t < T; ++t)
+        if (!(thresholds[t] - thresholds[t] == 0.0f)) return fail(PPP_ERR_INVALID_ARG, "threshold %d is not finite", t);
+    if ((d_inter == nullptr) != (d_union == nullptr)) return fail(PPP_ERR_INVALID_ARG, "d_inter and d_union: both or neither");
+    if (!d_pred || !d_labels || !d_counts || !d_work || ((uintptr_t)d_counts & 7) || ((uintptr_t)d_labels & 3) ||
+        ((uintptr_t)d_inter & 3) || ((uintptr_t)d_union & 3) || ((uintptr_t)d_pred & (pred_dtype == PPP_F32 ? 3 : 1)))
+        return fail(PPP_ERR_INVALID_ARG, "NULL or misaligned pointer argument");
+    PPP_TRY(need_device());
+    hipError_t e = ppp::run_eval_patch(d_pred, pred_dtype, d_labels, L, vol[0], vol[1], vol[2], patch[0], patch[1], patch[2],
+                                       z0, tz, thresholds, T, (long long *)d_counts, d_inter, d_union, d_work,
+                                       (hipStream_t)stream);
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_eval_patch");
+}
+
 /* ---- 3-d thinning of the foreground (ppp_skeleton.hip) ---- */
 static int skeleton_volume(int32_t Z, int32_t Y, int32_t X) {
     long long V;

@@ -260,6 +260,14 @@ size_t post_fg_filter_workspace_bytes(long long V);
 hipError_t run_post_fg_filter(const uint8_t *mask, uint8_t *fg, uint32_t *inst, int Z, int Y, int X, long long compsize,
                               uint32_t min_d2, long long *stats, void *work, hipStream_t s);
 
+// evaluate_patch as one streaming reduction (ppp_eval.hip): counts [1 + 2T] are ADDED to, maps [T][tz][Y][X] or null
+constexpr int kEvalT = 4;        // thresholds served by one pass over the prediction
+constexpr int kEvalMaxT = 32;    // thresholds per call
+size_t eval_patch_workspace_bytes(long long n_tile_voxels);
+hipError_t run_eval_patch(const void *pred, int dtype, const int32_t *labels, int L, int Z, int Y, int X, int pz, int py,
+                          int px, int z0, int tz, const float *th, int T, long long *counts, int32_t *inter, int32_t *uni,
+                          void *work, hipStream_t s);
+
 // 3-d thinning of the foreground (ppp_skeleton.hip)
 size_t skeleton_workspace_bytes(int Z, int Y, int X);
 hipError_t run_skeletonize_3d(const uint8_t *mask, uint8_t *out, int Z, int Y, int X, long long *n_kept, int *stats,

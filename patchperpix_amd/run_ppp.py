@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
-"""`label`, `decode`, `postprocess` and `postprocess_fg` tasks with the reference driver's interface
+"""`label`, `decode`, `postprocess`, `postprocess_fg` and `evaluate_prediction` tasks with the reference driver's interface
 (reference: experiments/run_ppp.py -- argument names :157-267, task dispatch :1974-2293,
 ``decode`` :682-746, ``vote_instances`` / ``vote_instances_sample`` :1054-1190, ``postprocess``
 :2230-2259).  The reference's ``postprocess`` has two branches: ``process_instances`` is this driver's
 ``--do postprocess``; ``process_fg_prediction`` (:2234-2245) is a task of its own here,
 ``--do postprocess_fg``, and stays refused under ``--do postprocess``.
 
-Only the tasks on this repository's path are provided; training, prediction and evaluation
-stay with the reference.  Usage, as in the reference README:
+``evaluate_prediction`` (:1300-1443, the reference's ``[evaluation] prediction_only_test`` branch
+:2207-2211) scores the dense prediction against ``[data] test_data`` before any instance is voted.
+
+Only the tasks on this repository's path are provided; training, prediction and the evaluation of
+instance segmentations stay with the reference.  Usage, as in the reference README:
 
     python -m patchperpix_amd.run_ppp --setup setup01 --config default.toml --do label \
         --pred-folder <dir with *.zarr|*.hdf|*.npy> --output-folder <dir> [--sample NAME]
@@ -169,6 +172,29 @@ def postprocess_fg(args, config):
     logger.info("time postprocess_fg (%d samples): %.2fs", len(samples), time.time() - t0)
 
 
+def evaluate_prediction(args, config):
+    """run_ppp.py:1370-1443: every ``*.<prediction.output_format>`` of --pred-folder against the ground truth
+    of ``[data] test_data`` -- a ``.zarr`` / ``.hdf`` file with ``<sample>/<gt_key>``, or a folder of
+    ``<sample>.<input_format>`` files with ``gt_key`` -- by ``[evaluation.prediction]``'s switches
+    (``eval_numinst_prediction``, ``eval_fg_prediction``, ``eval_patch_prediction``).  The per-sample dicts
+    go to ``prediction_metrics.json`` in --output-folder (this project's file, in place of the reference's
+    ``summarize_metric_dict``); returns (metrics, ths) as the reference does."""
+    import json
+    from . import evaluate_prediction as ev
+    fmt = config["prediction"]["output_format"]
+    data = config["data"]["test_data"]
+    samples = get_list_samples(args.pred_folder, fmt, args.sample)
+    os.makedirs(args.output_folder, exist_ok=True)
+    t0 = time.time()
+    metric_dicts = [ev.evaluate_prediction_sample(config, s, data, args.pred_folder, fmt, args.output_folder)
+                    for s in samples]
+    with open(os.path.join(args.output_folder, "prediction_metrics.json"), "w") as f:
+        json.dump({s: ev.jsonable(m) for s, m in zip(samples, metric_dicts)}, f, indent=1, sort_keys=True)
+    result = ev.summarize(metric_dicts, samples, config["evaluation"]["metric"])
+    logger.info("time evaluate_prediction (%d samples): %.2fs", len(samples), time.time() - t0)
+    return result
+
+
 def main(argv=None):
     from patchperpix_amd import backend as _backend
     _backend.tune_host_allocator(cli=True)     # (main(argv) IS the program, also behind a console script)
@@ -176,7 +202,7 @@ def main(argv=None):
     ap.add_argument("-c", "--config", action="append", required=True)
     ap.add_argument("-a", "--app", default="flylight")
     ap.add_argument("-s", "--setup", default="setup01")
-    ap.add_argument("-d", "--do", nargs="+", default=["label"], choices=["label", "decode", "postprocess", "postprocess_fg"])
+    ap.add_argument("-d", "--do", nargs="+", default=["label"], choices=["label", "decode", "postprocess", "postprocess_fg", "evaluate_prediction"])
     ap.add_argument("--pred-folder", required=True)
     ap.add_argument("--output-folder", required=True)
     ap.add_argument("--checkpoint", default=None)
@@ -185,7 +211,8 @@ def main(argv=None):
     logging.basicConfig(level=logging.INFO)
     config = load_config(args.config)
     for task in args.do:
-        {"label": label, "decode": decode, "postprocess": postprocess, "postprocess_fg": postprocess_fg}[task](args, config)
+        {"label": label, "decode": decode, "postprocess": postprocess, "postprocess_fg": postprocess_fg,
+         "evaluate_prediction": evaluate_prediction}[task](args, config)
 
 
 if __name__ == "__main__":
