@@ -33,11 +33,15 @@
 //   xy minimum  a staging loop of 14 serial load -> wait -> LDS write trips, 2 r + 1 LDS reads per output
 //               and pass, 36 % of the lanes on padding -> cover_minfilter_xy_cubic_kernel (see there);
 //   count       670 workgroups of 1024 threads, 512 resident -> 512 threads x 8 voxels, all resident, eight
-//               loads in flight per pass; the thinning's count had one voxel per thread (2 680 workgroups)
-//               and now shares the form;
+//               loads in flight per pass.  ONE sweep, two instantiations: cover_count_kernel and
+//               thin_count_kernel load and classify their voxels (ranks and witnesses / keys), then share the
+//               compaction (compact_marked) and the window recount (window_hits: the cover's stops early,
+//               records a witness and preloads a plane of rows; the thinning's counts in full);
 //   select      one voxel per thread, 10 719 workgroups, each the chain own value -> own slice of the
 //               filtered volume -> eight voxels per thread, both loads of all eight issued together, the
 //               other slices asked nearest first for all of a thread's candidates at once (ready_voxels).
+//               ONE body (select_body) over what the algorithm makes of a key (CoverPick, ThinPick):
+//               cover_select_kernel, cover_select_marked_kernel and thin_select_kernel instantiate it.
 // The round keeps its three launches and every step leaves the state it left before (tests/test_shard_steps.py
 // compares it step by step, tests/test_cover_sweeps.py the filter alone and the number of rounds):
 //   * the xy minimum is NOT fused into select -- a workgroup would read a neighbour's rank that another
@@ -58,7 +62,11 @@
 
 namespace ppp {
 
-static constexpr int32_t RANK_NONE = 0x7F7F7F7F;
+// "no patch here" of a key / filter volume: the largest value of the element type's byte pattern 0x7F..
+template <typename T> struct FilterNone;
+template <> struct FilterNone<int32_t> { static constexpr int32_t value = 0x7F7F7F7F; };
+template <> struct FilterNone<long long> { static constexpr long long value = 0x7F7F7F7F7F7F7F7Fll; };
+static constexpr int32_t RANK_NONE = FilterNone<int32_t>::value;
 static constexpr int COVER_BATCH = 8;   // rounds per host synchronisation
 
 // What a round works on, over the key type K: int32_t ranks in the greedy cover, long long keys in the
@@ -150,6 +158,95 @@ static constexpr int COUNT_VPT = 8;     // voxels per thread of the count sweeps
 static inline dim3 count_grid(const Geo &G) {
     return dim3((unsigned)((G.V + COUNT_THREADS * COUNT_VPT - 1) / (COUNT_THREADS * COUNT_VPT)));
 }
+
+// First phase of a count sweep, after a kernel has loaded and classified its voxels (alive: an undecided
+// patch of the rank's own; marked: its neighbourhood changed): the workgroup's voxels that are both are
+// compacted into s_list (offsets from the block's first voxel; *s_n was zeroed before a barrier).  Returns
+// their number, after a barrier.
+__device__ __forceinline__ int compact_marked(const bool (&alive)[COUNT_VPT], const bool (&marked)[COUNT_VPT],
+                                              uint16_t *s_list, int *s_n, int32_t *__restrict__ n_alive) {
+    bool rest = false;
+#pragma unroll
+    for (int j = 0; j < COUNT_VPT; ++j) {
+        const unsigned long long m = __ballot(alive[j] && marked[j]);
+        if (m != 0ull) {
+            const int lane = threadIdx.x & 63;
+            int base = 0;
+            if (lane == 0) base = atomicAdd(s_n, __popcll(m));
+            base = __shfl(base, 0);
+            if (alive[j] && marked[j])
+                s_list[base + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)(j * COUNT_THREADS + threadIdx.x);
+        }
+        rest = rest || (alive[j] && !marked[j]);
+    }
+    // "is any patch still undecided" AFTER this step: a plain store of the same value from
+    // every wave that has one that is not recounted now (same-address atomics from ~V/64
+    // waves would dominate the kernel); the recounted ones report after their recount if they survive
+    if (__ballot(rest) != 0 && (threadIdx.x & 63) == 0) *n_alive = 1;
+    __syncthreads();
+    return *s_n;
+}
+
+// Second phase: |mask bits & patch bits| over the pz * py rows of the window of the patch centred at voxel v
+// (b: its bit string, px bits per row), with a sliding 64-bit window over the bit string and the mask row
+// read as two words where the window straddles one.  What the cover needs on top, at compile time:
+//   STOP_EARLY  only "more than pix_th" matters: stop after the first plane of rows that settles it (with
+//               pix_th = 0 a surviving patch is usually done after the first plane);
+//   WITNESS     wit = the first covered voxel found, window row << 5 | x offset (WIT_NONE: none);
+//   PRELOAD     py <= 9: the mask words of a whole plane are loaded before any of them is used.
+template <bool STOP_EARLY, bool WITNESS, bool PRELOAD>
+__device__ __forceinline__ int window_hits(const uint32_t *__restrict__ mbits, const uint32_t *__restrict__ b,
+                                           const long long v, const int pix_th, unsigned &wit, const Geo &G) {
+    const int words = (G.C + 31) / 32, XW = row_words(G);
+    int cz, cy, cx;
+    centre_of(G, v, cz, cy, cx);
+    const int start = cx - G.rx, wi = start >> 5, sh = start & 31;
+    const bool two = sh + G.px > 32;
+    const uint32_t pmask = G.px >= 32 ? 0xFFFFFFFFu : ((1u << G.px) - 1u);
+    unsigned long long win = b[0] | ((unsigned long long)(words > 1 ? b[1] : 0u) << 32);
+    int have = 64, next = 2, hits = 0;
+    // (the witness stays a local until the end: carried through the rows in the caller's variable, the unrolled
+    // plane of the cover's count takes 81 registers instead of 71)
+    unsigned wloc = WIT_NONE;
+    auto add_row = [&](const unsigned long long mw, const int r) {
+        const uint32_t hm = (uint32_t)(mw >> sh) & (uint32_t)win & pmask;
+        const int rh = __popc(hm);
+        if (WITNESS && rh && wloc == WIT_NONE) wloc = ((unsigned)r << 5) | (unsigned)__builtin_ctz(hm);
+        hits += rh;
+        win >>= G.px;
+        have -= G.px;
+        if (have <= 32) {
+            win |= (unsigned long long)(next < words ? b[next] : 0u) << have;
+            ++next;
+            have += 32;
+        }
+    };
+    constexpr int MAXPY = 9;
+    for (int dz = 0; dz < G.pz && !(STOP_EARLY && hits > pix_th); ++dz) {
+        const uint32_t *row = mbits + ((long long)(cz + dz - G.rz) * G.Y + (cy - G.ry)) * XW + wi;
+        if (PRELOAD && G.py <= MAXPY) {
+            uint32_t lo[MAXPY], hi[MAXPY];
+#pragma unroll
+            for (int dy = 0; dy < MAXPY; ++dy) {
+                const bool in_p = dy < G.py;
+                lo[dy] = in_p ? row[(long long)dy * XW] : 0u;
+                hi[dy] = (in_p && two) ? row[(long long)dy * XW + 1] : 0u;
+            }
+#pragma unroll
+            for (int dy = 0; dy < MAXPY; ++dy)
+                if (dy < G.py) add_row(lo[dy] | ((unsigned long long)hi[dy] << 32), dz * G.py + dy);
+        } else {
+            for (int dy = 0; dy < G.py; ++dy, row += XW) {
+                unsigned long long mw = row[0];
+                if (two) mw |= (unsigned long long)row[1] << 32;
+                add_row(mw, dz * G.py + dy);
+            }
+        }
+    }
+    wit = wloc;
+    return hits;
+}
+
 __global__ void __launch_bounds__(COUNT_THREADS)
     cover_count_kernel(const uint32_t *__restrict__ mbits, const uint32_t *__restrict__ bits,
                        uint8_t *__restrict__ dirty, const int pix_th, int32_t *__restrict__ state,
@@ -165,6 +262,7 @@ __global__ void __launch_bounds__(COUNT_THREADS)
     if (threadIdx.x == 0) s_n = 0;
     __syncthreads();
     const long long v0 = blockIdx.x * (long long)(COUNT_THREADS * COUNT_VPT);
+    int n;
     {
         const bool use_wit = pix_th == 0 && witness != nullptr;
         long long vv[COUNT_VPT];
@@ -212,107 +310,25 @@ __global__ void __launch_bounds__(COUNT_THREADS)
 #pragma unroll
             for (int j = 0; j < COUNT_VPT; ++j) marked[j] = alive[j] && ((mw[j] >> xb[j]) & 1u) == 0u;
         }
-        bool rest = false;
-#pragma unroll
-        for (int j = 0; j < COUNT_VPT; ++j) {
-            const unsigned long long m = __ballot(alive[j] && marked[j]);
-            if (m != 0ull) {
-                const int lane = threadIdx.x & 63;
-                int base = 0;
-                if (lane == 0) base = atomicAdd(&s_n, __popcll(m));
-                base = __shfl(base, 0);
-                if (alive[j] && marked[j])
-                    s_list[base + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)(j * COUNT_THREADS + threadIdx.x);
-            }
-            rest = rest || (alive[j] && !marked[j]);
-        }
-        // "is any patch still undecided" AFTER this step: a plain store of the same value from
-        // every wave that has one that is not recounted now (same-address atomics from ~V/64
-        // waves would dominate the kernel); the recounted ones report below if they survive
-        if (__ballot(rest) != 0 && (threadIdx.x & 63) == 0) *n_alive = 1;
+        n = compact_marked(alive, marked, s_list, &s_n, n_alive);
     }
-    __syncthreads();
-    const int n = s_n;
     for (int t = threadIdx.x; t < n; t += blockDim.x) {
         const long long v = v0 + s_list[t];
         int k = rank_vol[v];
         if (loc_vol) k = loc_vol[v];
-        const int words = (G.C + 31) / 32, XW = row_words(G);
-        int cz, cy, cx;
-        centre_of(G, v, cz, cy, cx);
         // (bits_vox >= 0: the table has a row per VOXEL, its first row belongs to voxel bits_vox)
-        const uint32_t *b = bits + (bits_vox >= 0 ? v - bits_vox : (long long)k) * words;
-        const int start = cx - G.rx, wi = start >> 5, sh = start & 31;
-        const bool two = sh + G.px > 32;
-        const uint32_t pmask = G.px >= 32 ? 0xFFFFFFFFu : ((1u << G.px) - 1u);
-        const bool use_wit = pix_th == 0 && witness != nullptr;
-        unsigned wit_new = WIT_NONE;      // first covered voxel found: row << 5 | x offset
-        // sliding 64-bit window over the patch's bit string
-        unsigned long long win = b[0] | ((unsigned long long)(words > 1 ? b[1] : 0u) << 32);
-        int have = 64, next = 2, hits = 0;
-        // only "more than pix_th" matters: stop at the first plane of rows that settles it
-        // (with pix_th = 0 a surviving patch is usually done after the first plane).  The mask
-        // words of a whole plane are loaded before any of them is used.
-        constexpr int MAXPY = 9;
-        for (int dz = 0; dz < G.pz && hits <= pix_th; ++dz) {
-            const uint32_t *row = mbits + ((long long)(cz + dz - G.rz) * G.Y + (cy - G.ry)) * XW + wi;
-            if (G.py <= MAXPY) {
-                uint32_t lo[MAXPY], hi[MAXPY];
-#pragma unroll
-                for (int dy = 0; dy < MAXPY; ++dy) {
-                    const bool in_p = dy < G.py;
-                    lo[dy] = in_p ? row[(long long)dy * XW] : 0u;
-                    hi[dy] = (in_p && two) ? row[(long long)dy * XW + 1] : 0u;
-                }
-#pragma unroll
-                for (int dy = 0; dy < MAXPY; ++dy) {
-                    if (dy < G.py) {
-                        const unsigned long long mw = lo[dy] | ((unsigned long long)hi[dy] << 32);
-                        const uint32_t hm = (uint32_t)(mw >> sh) & (uint32_t)win & pmask;
-                        const int rh = __popc(hm);
-                        if (rh && wit_new == WIT_NONE) wit_new = ((unsigned)(dz * G.py + dy) << 5) | (unsigned)__builtin_ctz(hm);
-                        hits += rh;
-                        win >>= G.px;
-                        have -= G.px;
-                        if (have <= 32) {
-                            win |= (unsigned long long)(next < words ? b[next] : 0u) << have;
-                            ++next;
-                            have += 32;
-                        }
-                    }
-                }
-            } else {
-                for (int dy = 0; dy < G.py; ++dy, row += XW) {
-                    unsigned long long mw = row[0];
-                    if (two) mw |= (unsigned long long)row[1] << 32;
-                    const uint32_t hm = (uint32_t)(mw >> sh) & (uint32_t)win & pmask;
-                    const int rh = __popc(hm);
-                    if (rh && wit_new == WIT_NONE) wit_new = ((unsigned)(dz * G.py + dy) << 5) | (unsigned)__builtin_ctz(hm);
-                    hits += rh;
-                    win >>= G.px;
-                    have -= G.px;
-                    if (have <= 32) {
-                        win |= (unsigned long long)(next < words ? b[next] : 0u) << have;
-                        ++next;
-                        have += 32;
-                    }
-                }
-            }
-        }
+        const uint32_t *b = bits + (bits_vox >= 0 ? v - bits_vox : (long long)k) * ((G.C + 31) / 32);
+        unsigned wit_new;
+        const int hits = window_hits<true, true, true>(mbits, b, v, pix_th, wit_new, G);
         if (hits <= pix_th) {
             state[k] = 2;
             rank_vol[v] = RANK_NONE;
         } else {
-            if (use_wit) witness[v] = (uint16_t)wit_new;
+            if (pix_th == 0 && witness != nullptr) witness[v] = (uint16_t)wit_new;
             *n_alive = 1;
         }
     }
 }
-
-// "no patch here" of a filter volume: the largest value of the element type's byte pattern 0x7F..
-template <typename T> struct FilterNone;
-template <> struct FilterNone<int32_t> { static constexpr int32_t value = 0x7F7F7F7F; };
-template <> struct FilterNone<long long> { static constexpr long long value = 0x7F7F7F7F7F7F7F7Fll; };
 
 // 1-d running minimum of width 2*radius+1 along one axis (stride in elements, n along axis)
 template <typename T>
@@ -655,23 +671,25 @@ __global__ void __launch_bounds__(256)
     mark_box_row(mark_bits, cz, cy, cx, (int)(t % 7), G);
 }
 
-// SELECT_VPT voxels per thread: the best ranked undecided patch of its neighbourhood selects itself;
-// its wave clears the voxels (lane per window row) and marks the centres whose counts may have
-// changed.  Selected patches never share a voxel, but they may share a mask word.
+// The select sweep of a round, SELECT_VPT voxels per thread: the undecided patch with the best key of its
+// neighbourhood selects itself; its wave clears the voxels (lane per window row) and marks the centres whose
+// counts may have changed.  Selected patches never share a voxel, but they may share a mask word.
+// The buffer starts at slice oz of a volume of gZ slices (the interior that `cleared` counts is the volume's).
 // (MARKS: `mark_close_neighboorhood` -- a selected patch also sets the (0, +-3, +-3) box around its centre
 // in the mark bits, see mark_box_row)
-template <bool MARKS>
+// P says what the algorithm makes of a key: K, index(key) = the winner's row of the tables where loc_vol does
+// not give it, bits_row, marks_dirty and what the winner records.
+template <bool MARKS, typename P>
 __device__ __forceinline__ void
-    cover_select_body(uint32_t *__restrict__ mbits, const uint32_t *__restrict__ bits,
-                      const int32_t *__restrict__ nbr_min, int32_t *__restrict__ state,
-                      int32_t *__restrict__ rank_vol, int32_t *__restrict__ cleared_interior,
-                      uint8_t *__restrict__ dirty, const int32_t *__restrict__ loc_vol,
-                      const int gZ, const long long bits_vox, const int mark_dirty,
-                      uint32_t *__restrict__ mark_bits, const Geo &G) {
+    select_body(uint32_t *__restrict__ mbits, const uint32_t *__restrict__ bits,
+                const typename P::K *__restrict__ nbr_min, typename P::K *__restrict__ key_vol,
+                uint8_t *__restrict__ dirty, const int32_t *__restrict__ loc_vol, const int oz, const int gZ,
+                uint32_t *__restrict__ mark_bits, const P pick, const Geo &G) {
+    using K = typename P::K;
     const long long first = blockIdx.x * (long long)(256 * SELECT_VPT) + threadIdx.x;
     const int lane = threadIdx.x & 63;
-    int32_t mine[SELECT_VPT];
-    unsigned ready_bits = ready_voxels<int32_t>(rank_vol, nbr_min, first, mine, G);   // nbr_min: xy-filtered ranks
+    K mine[SELECT_VPT];
+    unsigned ready_bits = ready_voxels<K>(key_vol, nbr_min, first, mine, G);   // nbr_min: xy-filtered keys
     if (__ballot(ready_bits != 0u) == 0ull) return;
     if (loc_vol) {                                              // own centres only
 #pragma unroll
@@ -685,10 +703,11 @@ __device__ __forceinline__ void
             const int src = __builtin_ctzll(todo);
             todo &= todo - 1;
             const long long cc = first + j * 256 - lane + src;
-            const int kk = loc_vol ? loc_vol[cc] : rank_vol[cc];      // (local index; every lane the same word)
+            const K key = key_vol[cc];                                // (every lane the same word)
+            const int kk = loc_vol ? loc_vol[cc] : P::index(key);     // local index
             int cz, cy, cx;
             centre_of(G, cc, cz, cy, cx);
-            const uint32_t *b = bits + (bits_vox >= 0 ? cc - bits_vox : (long long)kk) * words;
+            const uint32_t *b = bits + pick.bits_row(cc, kk) * words;
             const int start = cx - G.rx, sh = start & 31;
             // window bits whose voxel is an interior x position
             uint32_t xin = 0;
@@ -702,8 +721,7 @@ __device__ __forceinline__ void
                 if (cl) {
                     atomicAnd(row + (start >> 5), ~(cl << sh));
                     if (sh && (cl >> (32 - sh))) atomicAnd(row + (start >> 5) + 1, ~(cl >> (32 - sh)));
-                    // (interior of the WHOLE volume: gZ slices, this buffer starts at slice G.oz)
-                    if (z + G.oz >= G.rz && z + G.oz < gZ - G.rz && y >= G.ry && y < G.Y - G.ry)
+                    if (z + oz >= G.rz && z + oz < gZ - G.rz && y >= G.ry && y < G.Y - G.ry)
                         cleared += __popc(cl & xin);
                 }
             }
@@ -713,38 +731,48 @@ __device__ __forceinline__ void
             const int y0 = max(cy - (G.py - 1), 0), y1 = min(cy + G.py - 1, G.Y - 1);
             const int x0 = max(cx - (G.px - 1), 0), x1 = min(cx + G.px - 1, G.X - 1);
             const int ny = y1 - y0 + 1, nx = x1 - x0 + 1;
-            // (pix_th == 0: the count step asks every undecided patch's witness voxel instead)
-            const int rows = mark_dirty ? (z1 - z0 + 1) * ny : 0;
+            const int rows = pick.marks_dirty() ? (z1 - z0 + 1) * ny : 0;
             for (int row = lane; row < rows; row += 64) {
                 uint8_t *d = dirty + vox(G, z0 + row / ny, y0 + row % ny, x0);
                 for (int x = 0; x < nx; ++x) d[x] = 1;
             }
             if (MARKS && lane < 7) mark_box_row(mark_bits, cz, cy, cx, lane, G);
             if (lane == src) {
-                state[kk] = 1;
-                rank_vol[cc] = RANK_NONE;
-                cleared_interior[kk] = cleared;
+                key_vol[cc] = FilterNone<K>::value;
+                pick.record(kk, key, cleared);
             }
         }
     }
 }
+
+// the greedy cover's: the key is the rank, which is the row of state / cleared / bits on one device
+struct CoverPick {
+    using K = int32_t;
+    int32_t *__restrict__ state, *__restrict__ cleared;
+    long long bits_vox;                  // >= 0: the bit table has a row per VOXEL, its first row belongs to this voxel
+    int mark_dirty;                      // 0 at pix_th == 0: the count step asks every undecided patch's witness instead
+    __device__ static int index(K key) { return key; }
+    __device__ long long bits_row(long long cc, int kk) const { return bits_vox >= 0 ? cc - bits_vox : (long long)kk; }
+    __device__ bool marks_dirty() const { return mark_dirty != 0; }
+    __device__ void record(int kk, K, int n_cleared) const { state[kk] = 1; cleared[kk] = n_cleared; }
+};
 __global__ void __launch_bounds__(256)
     cover_select_kernel(uint32_t *__restrict__ mbits, const uint32_t *__restrict__ bits,
                         const int32_t *__restrict__ nbr_min, int32_t *__restrict__ state,
                         int32_t *__restrict__ rank_vol, int32_t *__restrict__ cleared_interior,
-                        uint8_t *__restrict__ dirty, const int32_t *__restrict__ loc_vol,
+                        uint8_t *__restrict__ dirty, const int32_t *__restrict__ loc_vol, const int oz,
                         const int gZ, const long long bits_vox, const int mark_dirty, const Geo G) {
-    cover_select_body<false>(mbits, bits, nbr_min, state, rank_vol, cleared_interior, dirty, loc_vol, gZ, bits_vox,
-                             mark_dirty, nullptr, G);
+    select_body<false>(mbits, bits, nbr_min, rank_vol, dirty, loc_vol, oz, gZ, nullptr,
+                       CoverPick{state, cleared_interior, bits_vox, mark_dirty}, G);
 }
 __global__ void __launch_bounds__(256)
     cover_select_marked_kernel(uint32_t *__restrict__ mbits, const uint32_t *__restrict__ bits,
                                const int32_t *__restrict__ nbr_min, int32_t *__restrict__ state,
                                int32_t *__restrict__ rank_vol, int32_t *__restrict__ cleared_interior,
-                               uint8_t *__restrict__ dirty, const long long bits_vox, const int mark_dirty,
-                               uint32_t *__restrict__ mark_bits, const Geo G) {
-    cover_select_body<true>(mbits, bits, nbr_min, state, rank_vol, cleared_interior, dirty, nullptr, G.Z + G.oz,
-                            bits_vox, mark_dirty, mark_bits, G);
+                               uint8_t *__restrict__ dirty, const int oz, const int gZ, const long long bits_vox,
+                               const int mark_dirty, uint32_t *__restrict__ mark_bits, const Geo G) {
+    select_body<true>(mbits, bits, nbr_min, rank_vol, dirty, nullptr, oz, gZ, mark_bits,
+                      CoverPick{state, cleared_interior, bits_vox, mark_dirty}, G);
 }
 
 template <typename K> static void round_layout(Carver &c, const Geo &G, RoundArrays<K> &W) {
@@ -760,6 +788,41 @@ template <typename K> static RoundArrays<K> carve_round(void *work, const Geo &G
     RoundArrays<K> W;
     round_layout(c, G, W);
     return W;
+}
+
+// What every start of a cover or a thinning does to the arrays of a round: no patch anywhere, every centre marked
+// (count everything once), the mask as bits.
+template <typename K>
+static hipError_t round_reset(const RoundArrays<K> &W, const uint8_t *mask, const Geo &G, hipStream_t s) {
+    hipError_t e;
+    if ((e = hipMemsetD32Async((hipDeviceptr_t)W.key_vol, (int)(FilterNone<K>::value & 0xFFFFFFFF),
+                               (size_t)G.V * (sizeof(K) / 4), s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(W.dirty, 1, (size_t)G.V, s)) != hipSuccess) return e;
+    const long long n_words = (long long)G.Z * G.Y * row_words(G);
+    cover_pack_kernel<<<dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, s>>>(mask, W.mbits, G);
+    return hipSuccess;
+}
+
+// Rounds in batches of COVER_BATCH with one host synchronisation each, until the counter of a batch's last
+// round reads zero: no patch was undecided at its start, so that round was a no-op and nothing is left.
+// round(counter) launches one round, whose count step raises *counter; *rounds = the rounds run so far (what
+// after_batch, called after every batch's synchronisation, may report).
+template <typename Round, typename AfterBatch>
+static hipError_t run_rounds(int32_t *counters, hipStream_t s, int *rounds, Round round, AfterBatch after_batch) {
+    *rounds = 0;
+    int32_t n_alive = 1;
+    while (n_alive > 0) {
+        hipError_t e;
+        if ((e = hipMemsetAsync(counters, 0, COVER_BATCH * 4, s)) != hipSuccess) return e;
+        for (int r = 0; r < COVER_BATCH; ++r) round(counters + r);
+        *rounds += COVER_BATCH;
+        if ((e = hipMemcpyAsync(&n_alive, counters + COVER_BATCH - 1, 4, hipMemcpyDeviceToHost, s)) != hipSuccess)
+            return e;
+        if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        after_batch();
+    }
+    return hipSuccess;
 }
 
 // (the same layout serves run_cover_pass and the sharded steps; n does not enter it)
@@ -783,44 +846,30 @@ hipError_t run_cover_pass(uint8_t *mask, const uint32_t *bits, long long bits_vo
     if (mark_bits && (G.Y < 2 * MARK_R + 1 || G.X < 2 * MARK_R + 1)) return hipErrorNotSupported;
     CoverWork W = carve(work, G);
     hipError_t e;
-    if ((e = hipMemsetD32Async((hipDeviceptr_t)W.key_vol, RANK_NONE, (size_t)G.V, s)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(W.dirty, 1, (size_t)G.V, s)) != hipSuccess) return e;   // count everything once
+    if ((e = round_reset(W, mask, G, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(W.witness, 0xFF, (size_t)G.V * 2, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(cleared, 0, (size_t)n * 4, s)) != hipSuccess) return e;
     const dim3 vgrid((unsigned)((G.V + 255) / 256)), block(256);
-    const long long n_words = (long long)G.Z * G.Y * row_words(G);
-    cover_pack_kernel<<<dim3((unsigned)((n_words + 255) / 256)), block, 0, s>>>(mask, W.mbits, G);
     cover_init_kernel<<<dim3((unsigned)((n + 255) / 256)), block, 0, s>>>(lin, state, (int)n, W.key_vol);
-    int32_t n_alive = 1;
-    while (n_alive > 0) {
-        if ((e = hipMemsetAsync(W.counters, 0, COVER_BATCH * 4, s)) != hipSuccess) return e;
-        const dim3 cgrid = count_grid(G), cblock(COUNT_THREADS);
-        const int mark_dirty = (pix_th != 0 || !witness_ok(G)) ? 1 : 0;
-        for (int r = 0; r < COVER_BATCH; ++r) {
-            if (mark_bits)
-                cover_marktest_kernel<<<dim3((unsigned)((G.V + 256 * MARKTEST_VPT - 1) / (256 * MARKTEST_VPT))), block, 0, s>>>(
-                    mark_bits, state, W.key_vol, G);
-            cover_count_kernel<<<cgrid, cblock, 0, s>>>(W.mbits, bits, W.dirty, pix_th, state, W.key_vol,
-                                                       W.counters + r, nullptr, witness_ok(G) ? W.witness : nullptr, bits_vox, G);
-            // x, y, z; radius p-1: two windows overlap iff |dc| <= p-1 on every axis
-            if (!mark_bits) {
-                minfilter_xy<int32_t>(W.key_vol, W.tmp, W.nbr_min, G, s);
-                cover_select_kernel<<<select_grid(G), block, 0, s>>>(W.mbits, bits, W.nbr_min, state, W.key_vol, cleared,
-                                                            W.dirty, nullptr, G.Z + G.oz, bits_vox, mark_dirty, G);
-            } else {
-                // (with marks: y / x radius max(p - 1, 3), see mark_box_row)
-                minfilter_xy<int32_t>(W.key_vol, W.tmp, W.nbr_min, G, mark_radius(G.px), mark_radius(G.py), s);
-                cover_select_marked_kernel<<<select_grid(G), block, 0, s>>>(W.mbits, bits, W.nbr_min, state, W.key_vol,
-                                                                   cleared, W.dirty, bits_vox, mark_dirty, mark_bits, G);
-            }
+    const int mark_dirty = (pix_th != 0 || !witness_ok(G)) ? 1 : 0;
+    e = run_rounds(W.counters, s, rounds, [&](int32_t *counter) {
+        if (mark_bits)
+            cover_marktest_kernel<<<dim3((unsigned)((G.V + 256 * MARKTEST_VPT - 1) / (256 * MARKTEST_VPT))), block, 0, s>>>(
+                mark_bits, state, W.key_vol, G);
+        cover_count_kernel<<<count_grid(G), dim3(COUNT_THREADS), 0, s>>>(
+            W.mbits, bits, W.dirty, pix_th, state, W.key_vol, counter, nullptr, witness_ok(G) ? W.witness : nullptr, bits_vox, G);
+        // x, y, z; radius p-1: two windows overlap iff |dc| <= p-1 on every axis
+        if (!mark_bits) {
+            minfilter_xy<int32_t>(W.key_vol, W.tmp, W.nbr_min, G, s);
+            cover_select_kernel<<<select_grid(G), block, 0, s>>>(W.mbits, bits, W.nbr_min, state, W.key_vol, cleared,
+                                                        W.dirty, nullptr, G.oz, G.Z + G.oz, bits_vox, mark_dirty, G);
+        } else {
+            // (with marks: y / x radius max(p - 1, 3), see mark_box_row)
+            minfilter_xy<int32_t>(W.key_vol, W.tmp, W.nbr_min, G, mark_radius(G.px), mark_radius(G.py), s);
+            cover_select_marked_kernel<<<select_grid(G), block, 0, s>>>(W.mbits, bits, W.nbr_min, state, W.key_vol, cleared,
+                                                               W.dirty, G.oz, G.Z + G.oz, bits_vox, mark_dirty, mark_bits, G);
         }
-        *rounds += COVER_BATCH;
-        // "any patch undecided" at the start of the batch's last round; if none, that round
-        // was a no-op and nothing is left
-        if ((e = hipMemcpyAsync(&n_alive, W.counters + COVER_BATCH - 1, 4, hipMemcpyDeviceToHost, s)) != hipSuccess)
-            return e;
-        if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }, [&] {
         static EnvSwitch trace("PPP_COVER_TRACE");
         if (trace.get()) {   // development aid: undecided / selected patches per batch
             std::vector<int32_t> h((size_t)n);
@@ -829,7 +878,8 @@ hipError_t run_cover_pass(uint8_t *mask, const uint32_t *bits, long long bits_vo
             for (long long i = 0; i < n; ++i) { a += h[i] == 0; sel += h[i] == 1; }
             fprintf(stderr, "cover rounds %d: undecided %lld selected %lld\n", *rounds, a, sel);
         }
-    }
+    });
+    if (e != hipSuccess) return e;
     cover_unpack_kernel<<<vgrid, block, 0, s>>>(W.mbits, mask, G);
     return hipGetLastError();
 }
@@ -1000,9 +1050,9 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-// COUNT_VPT voxels per thread, as in cover_count_kernel (the loads of a thread's voxels issued pass by
-// pass): the undecided patches of a workgroup whose neighbourhood changed are compacted in LDS, then
-// recounted in full; a patch that covers nothing any more is retired.
+// The count sweep over keys (the loads of a thread's voxels issued pass by pass): the undecided patches of a
+// workgroup whose neighbourhood changed are compacted in LDS, then recounted in full and their keys
+// rewritten; a patch that covers nothing any more is retired.
 __global__ void __launch_bounds__(COUNT_THREADS)
     thin_count_kernel(const uint32_t *__restrict__ mbits, const uint32_t *__restrict__ bits,
                       uint8_t *__restrict__ dirty, int32_t *__restrict__ state,
@@ -1013,6 +1063,7 @@ __global__ void __launch_bounds__(COUNT_THREADS)
     if (threadIdx.x == 0) s_n = 0;
     __syncthreads();
     const long long v0 = blockIdx.x * (long long)(COUNT_THREADS * COUNT_VPT);
+    int n;
     {
         long long vv[COUNT_VPT], key[COUNT_VPT];
         uint8_t mark[COUNT_VPT];
@@ -1033,53 +1084,15 @@ __global__ void __launch_bounds__(COUNT_THREADS)
             marked[j] = vv[j] < G.V && mark[j] != 0;
             if (marked[j]) dirty[vv[j]] = 0;
         }
-        bool rest = false;
-#pragma unroll
-        for (int j = 0; j < COUNT_VPT; ++j) {
-            const unsigned long long m = __ballot(alive[j] && marked[j]);
-            if (m != 0ull) {
-                const int lane = threadIdx.x & 63;
-                int base = 0;
-                if (lane == 0) base = atomicAdd(&s_n, __popcll(m));
-                base = __shfl(base, 0);
-                if (alive[j] && marked[j])
-                    s_list[base + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)(j * COUNT_THREADS + threadIdx.x);
-            }
-            rest = rest || (alive[j] && !marked[j]);
-        }
-        // undecided after this step: those not recounted now; recounted survivors report below
-        if (__ballot(rest) != 0 && (threadIdx.x & 63) == 0) *n_alive = 1;
+        n = compact_marked(alive, marked, s_list, &s_n, n_alive);
     }
-    __syncthreads();
-    const int n = s_n;
     for (int t = threadIdx.x; t < n; t += blockDim.x) {
         const long long v = v0 + s_list[t];
         const int k = (int)(key_vol[v] & 0xFFFFFFFFll);          // position in the (global) list: the key's tie-break
         const int kl = loc_vol ? loc_vol[v] : k;                 // row of `bits` / `state`
-        const int words = (G.C + 31) / 32, XW = row_words(G);
-        int cz, cy, cx;
-        centre_of(G, v, cz, cy, cx);
-        const uint32_t *b = bits + (long long)kl * words;
-        const int start = cx - G.rx, wi = start >> 5, sh = start & 31;
-        const bool two = sh + G.px > 32;
-        const uint32_t pmask = G.px >= 32 ? 0xFFFFFFFFu : ((1u << G.px) - 1u);
-        unsigned long long win = b[0] | ((unsigned long long)(words > 1 ? b[1] : 0u) << 32);
-        int have = 64, next = 2, hits = 0;
-        for (int dz = 0; dz < G.pz; ++dz) {
-            const uint32_t *row = mbits + ((long long)(cz + dz - G.rz) * G.Y + (cy - G.ry)) * XW + wi;
-            for (int dy = 0; dy < G.py; ++dy, row += XW) {
-                unsigned long long mw = row[0];
-                if (two) mw |= (unsigned long long)row[1] << 32;
-                hits += __popc((uint32_t)(mw >> sh) & (uint32_t)win & pmask);
-                win >>= G.px;
-                have -= G.px;
-                if (have <= 32) {
-                    win |= (unsigned long long)(next < words ? b[next] : 0u) << have;
-                    ++next;
-                    have += 32;
-                }
-            }
-        }
+        unsigned wit;
+        // (the full count, row by row: without the plane preload the sweep keeps its 44 registers)
+        const int hits = window_hits<false, false, false>(mbits, bits + (long long)kl * ((G.C + 31) / 32), v, 0, wit, G);
         if (hits == 0) {
             state[kl] = 2;
             key_vol[v] = THIN_NONE;
@@ -1090,71 +1103,28 @@ __global__ void __launch_bounds__(COUNT_THREADS)
     }
 }
 
-// SELECT_VPT voxels per thread: the patch with the best key of its neighbourhood keeps itself; its wave
-// clears the voxels and marks the centres whose counts may have changed.
+// select_body for the thinning: the key's low word is the row where loc_vol does not give it, and the winner also
+// records the count it was kept with (the key's high word): the stop rule sorts by it
+struct ThinPick {
+    using K = long long;
+    int32_t *__restrict__ state, *__restrict__ sel_count, *__restrict__ cleared;
+    __device__ static int index(K key) { return (int)(key & 0xFFFFFFFFll); }
+    __device__ static long long bits_row(long long, int kk) { return kk; }
+    __device__ static constexpr bool marks_dirty() { return true; }
+    __device__ void record(int kk, K key, int n_cleared) const {
+        state[kk] = 1;
+        sel_count[kk] = (int32_t)(THIN_MAXC - (key >> 32));
+        cleared[kk] = n_cleared;
+    }
+};
 __global__ void __launch_bounds__(256)
     thin_select_kernel(uint32_t *__restrict__ mbits, const uint32_t *__restrict__ bits,
                        const long long *__restrict__ nbr_min, int32_t *__restrict__ state,
                        long long *__restrict__ key_vol, int32_t *__restrict__ sel_count,
                        int32_t *__restrict__ cleared_interior, uint8_t *__restrict__ dirty,
                        const int32_t *__restrict__ loc_vol, const int oz, const int gZ, const Geo G) {
-    const long long first = blockIdx.x * (long long)(256 * SELECT_VPT) + threadIdx.x;
-    const int lane = threadIdx.x & 63;
-    long long mine[SELECT_VPT];
-    unsigned ready_bits = ready_voxels<long long>(key_vol, nbr_min, first, mine, G);      // (xy-filtered keys)
-    if (__ballot(ready_bits != 0u) == 0ull) return;
-    if (loc_vol) {                                              // own centres only
-#pragma unroll
-        for (int j = 0; j < SELECT_VPT; ++j)
-            if (((ready_bits >> j) & 1u) && loc_vol[first + j * 256] < 0) ready_bits &= ~(1u << j);
-    }
-    const int words = (G.C + 31) / 32, XW = row_words(G);
-    for (int j = 0; j < SELECT_VPT; ++j) {
-        unsigned long long todo = __ballot((ready_bits >> j) & 1u);
-        while (todo) {
-            const int src = __builtin_ctzll(todo);
-            todo &= todo - 1;
-            const long long cc = first + j * 256 - lane + src;
-            const long long key = key_vol[cc];                        // (every lane the same word)
-            const int kk = loc_vol ? loc_vol[cc] : (int)(key & 0xFFFFFFFFll);     // local index
-            int cz, cy, cx;
-            centre_of(G, cc, cz, cy, cx);
-            const uint32_t *b = bits + (long long)kk * words;
-            const int start = cx - G.rx, sh = start & 31;
-            uint32_t xin = 0;
-            for (int i = 0; i < G.px; ++i)
-                if (start + i >= G.rx && start + i < G.X - G.rx) xin |= 1u << i;
-            int cleared = 0;
-            for (int r = lane; r < G.pz * G.py; r += 64) {
-                const int z = cz + r / G.py - G.rz, y = cy + r % G.py - G.ry;
-                uint32_t *row = mbits + ((long long)z * G.Y + y) * XW;
-                const uint32_t cl = bit_window(row, start, G.px, XW) & bit_window(b, r * G.px, G.px, words);
-                if (cl) {
-                    atomicAnd(row + (start >> 5), ~(cl << sh));
-                    if (sh && (cl >> (32 - sh))) atomicAnd(row + (start >> 5) + 1, ~(cl >> (32 - sh)));
-                    // (interior of the WHOLE volume: gZ slices, this buffer starts at its slice oz)
-                    if (z + oz >= G.rz && z + oz < gZ - G.rz && y >= G.ry && y < G.Y - G.ry)
-                        cleared += __popc(cl & xin);
-                }
-            }
-            for (int o = 32; o > 0; o >>= 1) cleared += __shfl_xor(cleared, o);
-            const int z0 = max(cz - (G.pz - 1), 0), z1 = min(cz + G.pz - 1, G.Z - 1);
-            const int y0 = max(cy - (G.py - 1), 0), y1 = min(cy + G.py - 1, G.Y - 1);
-            const int x0 = max(cx - (G.px - 1), 0), x1 = min(cx + G.px - 1, G.X - 1);
-            const int ny = y1 - y0 + 1, nx = x1 - x0 + 1;
-            const int rows = (z1 - z0 + 1) * ny;
-            for (int row = lane; row < rows; row += 64) {
-                uint8_t *d = dirty + vox(G, z0 + row / ny, y0 + row % ny, x0);
-                for (int x = 0; x < nx; ++x) d[x] = 1;
-            }
-            if (lane == src) {
-                state[kk] = 1;
-                key_vol[cc] = THIN_NONE;
-                sel_count[kk] = (int32_t)(THIN_MAXC - (key >> 32));
-                cleared_interior[kk] = cleared;
-            }
-        }
-    }
+    select_body<false>(mbits, bits, nbr_min, key_vol, dirty, loc_vol, oz, gZ, nullptr,
+                       ThinPick{state, sel_count, cleared_interior}, G);
 }
 
 // keep u8 [n] (device).  Synchronises the stream.
@@ -1167,34 +1137,24 @@ hipError_t run_thin_cover(const uint8_t *mask, const uint32_t *bits, const long 
     PPP_GRID_CHECK((G.V + 255) / 256, 256);
     ThinWork W = carve_thin(work, n, G);
     hipError_t e;
-    if ((e = hipMemsetD32Async((hipDeviceptr_t)W.key_vol, 0x7F7F7F7F, (size_t)G.V * 2, s)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(W.dirty, 1, (size_t)G.V, s)) != hipSuccess) return e;
+    if ((e = round_reset(W, mask, G, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(W.state, 0, (size_t)n * 4, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(W.sel_count, 0, (size_t)n * 4, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(W.cleared, 0, (size_t)n * 4, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(W.interior, 0, 8, s)) != hipSuccess) return e;
-    const dim3 vgrid((unsigned)((G.V + 255) / 256)), block(256);
+    const dim3 block(256);
     const long long n_words = (long long)G.Z * G.Y * row_words(G);
-    cover_pack_kernel<<<dim3((unsigned)((n_words + 255) / 256)), block, 0, s>>>(mask, W.mbits, G);
     thin_interior_kernel<<<dim3((unsigned)((n_words + 255) / 256)), block, 0, s>>>(W.mbits, W.interior, G);
     thin_init_kernel<<<dim3((unsigned)((n + 255) / 256)), block, 0, s>>>(lin, (int)n, W.key_vol);
     thin_dups_kernel<<<dim3((unsigned)((n + 255) / 256)), block, 0, s>>>(lin, (int)n, W.key_vol, W.state);
-    int32_t n_alive = 1;
-    while (n_alive > 0) {
-        if ((e = hipMemsetAsync(W.counters, 0, COVER_BATCH * 4, s)) != hipSuccess) return e;
-        for (int r = 0; r < COVER_BATCH; ++r) {
-            thin_count_kernel<<<count_grid(G), dim3(COUNT_THREADS), 0, s>>>(
-                W.mbits, bits, W.dirty, W.state, W.key_vol, W.counters + r, nullptr, G);
-            minfilter_xy<long long>(W.key_vol, W.tmp, W.nbr_min, G, s);
-            thin_select_kernel<<<select_grid(G), block, 0, s>>>(W.mbits, bits, W.nbr_min, W.state, W.key_vol,
-                                                       W.sel_count, W.cleared, W.dirty, nullptr, 0, G.Z, G);
-        }
-        *rounds += COVER_BATCH;
-        if ((e = hipMemcpyAsync(&n_alive, W.counters + COVER_BATCH - 1, 4, hipMemcpyDeviceToHost, s)) != hipSuccess)
-            return e;
-        if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
+    e = run_rounds(W.counters, s, rounds, [&](int32_t *counter) {
+        thin_count_kernel<<<count_grid(G), dim3(COUNT_THREADS), 0, s>>>(
+            W.mbits, bits, W.dirty, W.state, W.key_vol, counter, nullptr, G);
+        minfilter_xy<long long>(W.key_vol, W.tmp, W.nbr_min, G, s);
+        thin_select_kernel<<<select_grid(G), block, 0, s>>>(W.mbits, bits, W.nbr_min, W.state, W.key_vol,
+                                                   W.sel_count, W.cleared, W.dirty, nullptr, 0, G.Z, G);
+    }, [] {});
+    if (e != hipSuccess) return e;
     // ---- the stop rule: kept patches in the order the sequential loop picks them
     std::vector<int32_t> st((size_t)n), cnt((size_t)n), clr((size_t)n);
     unsigned long long interior = 0;
@@ -1269,17 +1229,13 @@ hipError_t cover_open(const uint8_t *mask, const long long *lin, const int32_t *
     PPP_GRID_CHECK((G.V + 255) / 256, 256);
     CoverWork W = carve(work, G);
     hipError_t e;
-    if ((e = hipMemsetD32Async((hipDeviceptr_t)W.key_vol, RANK_NONE, (size_t)G.V, s)) != hipSuccess) return e;
+    if ((e = round_reset(W, mask, G, s)) != hipSuccess) return e;
     if ((e = hipMemsetD32Async((hipDeviceptr_t)W.loc_vol, 0xFFFFFFFF, (size_t)G.V, s)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(W.dirty, 1, (size_t)G.V, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(W.witness, 0xFF, (size_t)G.V * 2, s)) != hipSuccess) return e;
     if (n && (e = hipMemsetAsync(cleared, 0, (size_t)n * 4, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(W.counters, 0, COVER_BATCH * 4, s)) != hipSuccess) return e;
-    const dim3 block(256);
-    const long long n_words = (long long)G.Z * G.Y * row_words(G);
-    cover_pack_kernel<<<dim3((unsigned)((n_words + 255) / 256)), block, 0, s>>>(mask, W.mbits, G);
     if (n)
-        cover_init_local_kernel<<<dim3((unsigned)((n + 255) / 256)), block, 0, s>>>(
+        cover_init_local_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(
             lin, rankid, state, (int)n, W.key_vol, W.loc_vol);
     return hipGetLastError();
 }
@@ -1298,7 +1254,8 @@ hipError_t cover_step_select(const uint32_t *bits, int pix_th, int32_t *state, i
                              int gZ, const Geo &G, hipStream_t s) {
     CoverWork W = carve(work, G);
     cover_select_kernel<<<select_grid(G), dim3(256), 0, s>>>(
-        W.mbits, bits, W.nbr_min, state, W.key_vol, cleared, W.dirty, W.loc_vol, gZ, -1ll, (pix_th != 0 || !witness_ok(G)) ? 1 : 0, G);
+        W.mbits, bits, W.nbr_min, state, W.key_vol, cleared, W.dirty, W.loc_vol, G.oz, gZ, -1ll,
+        (pix_th != 0 || !witness_ok(G)) ? 1 : 0, G);
     return hipGetLastError();
 }
 
@@ -1337,19 +1294,15 @@ hipError_t thin_open(const uint8_t *mask, const long long *lin, const int32_t *g
     PPP_GRID_CHECK((G.V + 255) / 256, 256);
     ThinShardWork W = carve_thin_shard(work, G);
     hipError_t e;
-    if ((e = hipMemsetD32Async((hipDeviceptr_t)W.key_vol, 0x7F7F7F7F, (size_t)G.V * 2, s)) != hipSuccess) return e;
+    if ((e = round_reset(W, mask, G, s)) != hipSuccess) return e;
     if ((e = hipMemsetD32Async((hipDeviceptr_t)W.loc_vol, 0xFFFFFFFF, (size_t)G.V, s)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(W.dirty, 1, (size_t)G.V, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(W.counters, 0, COVER_BATCH * 4, s)) != hipSuccess) return e;
     if (n) {
         if ((e = hipMemsetAsync(state, 0, (size_t)n * 4, s)) != hipSuccess) return e;
         if ((e = hipMemsetAsync(sel_count, 0, (size_t)n * 4, s)) != hipSuccess) return e;
         if ((e = hipMemsetAsync(cleared, 0, (size_t)n * 4, s)) != hipSuccess) return e;
     }
-    const dim3 block(256);
-    const long long n_words = (long long)G.Z * G.Y * row_words(G);
-    cover_pack_kernel<<<dim3((unsigned)((n_words + 255) / 256)), block, 0, s>>>(mask, W.mbits, G);
-    if (n) thin_init_local_kernel<<<dim3((unsigned)((n + 255) / 256)), block, 0, s>>>(lin, gidx, (int)n, W.key_vol, W.loc_vol);
+    if (n) thin_init_local_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(lin, gidx, (int)n, W.key_vol, W.loc_vol);
     return hipGetLastError();
 }
 hipError_t thin_step_count(const uint32_t *bits, int32_t *state, void *work, const Geo &G, hipStream_t s) {

@@ -96,7 +96,9 @@ def test_minfilter_xy_equals_sliding_minimum(shape, ps, torch_cuda):
 
 
 # ---- whole passes: the rounds compute what they computed -------------------------------------------------
-ROUND_CASES = {"p5": ((20, 12, 33), (5, 5, 5)), "p7": ((21, 13, 70), (7, 7, 7))}
+# (p3x5x7: a non-cubic window; p1x11x11: the recount's row-by-row branch, py > 9; both straddle a mask word)
+ROUND_CASES = {"p5": ((20, 12, 33), (5, 5, 5)), "p7": ((21, 13, 70), (7, 7, 7)),
+               "p3x5x7": ((12, 20, 40), (3, 5, 7)), "p1x11x11": ((3, 40, 70), (1, 11, 11))}
 PIX_THS = [10, 0]
 _MODEL = {}
 
