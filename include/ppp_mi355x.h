@@ -140,6 +140,11 @@ int ppp_consensus_short_form(void);
  * "patch_graph_pa_kernel", or "patch_graph_pa_kernel<small>" with the small chunk); "none" before the first */
 const char *ppp_rank_kernel_name(void);
 const char *ppp_patch_graph_kernel_name(void);
+/* which instantiation of the per-patch kernel the last ppp_patch_graph_by_patch* call took: "cube" = the
+ * window's sizes compiled in (pz == py == px in {3, 5, 7, 9}, and the development switch PPP_PA_CUBE not
+ * "0"), "generic" = read from the parameters at run time; "none" before the first such call and after a
+ * ppp_patch_graph call.  The kernel NAME above is the same for both.                                */
+const char *ppp_patch_graph_kernel_geometry(void);
 /* Development switches (PPP_* environment variables naming a kernel variant or a tile shape)
  * are read once per process, at their first use; ppp_reload_env() makes the next use read them
  * again (tests that compare variants within one process).                                   */

@@ -74,6 +74,7 @@ _SIGNATURES = {
     "ppp_consensus_short_form": (ctypes.c_int, []),
     "ppp_rank_kernel_name": (ctypes.c_char_p, []),
     "ppp_patch_graph_kernel_name": (ctypes.c_char_p, []),
+    "ppp_patch_graph_kernel_geometry": (ctypes.c_char_p, []),
     "ppp_reload_env": (None, []),
     "ppp_np_vote_planes": (ctypes.c_int64, [ctypes.POINTER(Params)]),
     "ppp_np_consensus": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,

@@ -144,6 +144,7 @@ const char *ppp_consensus_kernel_name(void) { return ppp::last_consensus_kernel(
 int ppp_consensus_short_form(void) { return ppp::last_consensus_short_form(); }
 const char *ppp_rank_kernel_name(void) { return ppp::last_rank_kernel(); }
 const char *ppp_patch_graph_kernel_name(void) { return ppp::last_patch_graph_kernel(); }
+const char *ppp_patch_graph_kernel_geometry(void) { return ppp::last_patch_graph_geometry(); }
 
 void ppp_reload_env(void) { ppp::env_reload(); }
 

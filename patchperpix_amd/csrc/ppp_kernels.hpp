@@ -60,7 +60,10 @@ void note_consensus_short_form(int on);
 const char *last_rank_kernel();
 void note_rank_kernel(const char *name);
 const char *last_patch_graph_kernel();
-void note_patch_graph_kernel(const char *name);
+// geometry: how the per-patch kernel got its window's sizes, "cube" (compiled in) or "generic" (read from
+// Geo); "none" for the other S5 kernels (ppp_patch_graph_kernel_geometry)
+const char *last_patch_graph_geometry();
+void note_patch_graph_kernel(const char *name, const char *geometry = "none");
 hipError_t launch_consensus_part(const void *pred, int dtype, const uint8_t *ov, float *cons, const Geo &G,
                                  hipStream_t s);
 bool consensus_v4_supported(const Geo &G);

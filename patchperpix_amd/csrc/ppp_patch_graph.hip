@@ -427,7 +427,9 @@ __global__ void __launch_bounds__(64 * PG_WAVES)
 
 static const char *g_s5_kernel = "none";
 const char *last_patch_graph_kernel() { return g_s5_kernel; }
-void note_patch_graph_kernel(const char *name) { g_s5_kernel = name; }
+static const char *g_s5_geometry = "none";
+const char *last_patch_graph_geometry() { return g_s5_geometry; }
+void note_patch_graph_kernel(const char *name, const char *geometry) { g_s5_kernel = name; g_s5_geometry = geometry; }
 
 hipError_t launch_patch_graph(const void *pred, int dtype, const float *cons,
                               const uint32_t *pairs, const uint32_t *order, uint64_t n,
@@ -442,7 +444,7 @@ hipError_t launch_patch_graph(const void *pred, int dtype, const float *cons,
     const bool vm_generic = generic_sw.get() != nullptr;
     if (G.layout == PPP_CONS_VOXEL_MAJOR && !vm_generic &&
         (G.px == 3 || G.px == 5 || G.px == 7 || G.px == 9)) {
-        g_s5_kernel = "patch_graph_vm2_kernel";
+        note_patch_graph_kernel("patch_graph_vm2_kernel");
 #define PPP_PG_CASE(P)                                                                                          \
     case P:                                                                                                     \
         return with_pred_type(dtype, [&](auto tag) {                                                            \
@@ -460,7 +462,7 @@ hipError_t launch_patch_graph(const void *pred, int dtype, const float *cons,
 #undef PPP_PG_CASE
     }
     if (G.layout == PPP_CONS_VOXEL_MAJOR) {
-        g_s5_kernel = "patch_graph_vm_kernel";
+        note_patch_graph_kernel("patch_graph_vm_kernel");
         {
             const hipError_t e_ = with_pred_type(dtype, [&](auto tag) {
                 using T = PPP_PRED_T(tag);
@@ -471,7 +473,7 @@ hipError_t launch_patch_graph(const void *pred, int dtype, const float *cons,
         }
         return hipGetLastError();
     }
-    g_s5_kernel = "patch_graph_kernel";
+    note_patch_graph_kernel("patch_graph_kernel");
     {
         const hipError_t e_ = with_pred_type(dtype, [&](auto tag) {
             using T = PPP_PRED_T(tag);

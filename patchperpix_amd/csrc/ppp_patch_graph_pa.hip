@@ -103,7 +103,15 @@ template <int PX> struct PaCfg {
 #ifndef PPP_PA_MINWAVES_SMALL9
 #define PPP_PA_MINWAVES_SMALL9 2
 #endif
-    static constexpr int MIN_WAVES_SMALL = PX >= 25 ? 1 : (PX >= 9 ? PPP_PA_MINWAVES_SMALL9 : 4);
+    // (Round 11, the cubic instantiations -- 96 VGPRs at 7^3 / 64, 114 at 9^3 / 128, nothing spilled -- with
+    // other bounds, alternating with the defaults in one call: 7^3 with 3 and 5 waves 35.07-35.24 ms against
+    // 35.15-35.25 ms per step at 140^3, 9^3 with 4 waves 5.188 s against 5.187 s at 512^3; the registers do
+    // not change with the bound and LDS, not registers, caps the workgroups per CU: the bounds stay,
+    // profiles/r11_a_bench_ab.txt.)
+#ifndef PPP_PA_MINWAVES_SMALL7
+#define PPP_PA_MINWAVES_SMALL7 4
+#endif
+    static constexpr int MIN_WAVES_SMALL = PX >= 25 ? 1 : (PX >= 9 ? PPP_PA_MINWAVES_SMALL9 : PPP_PA_MINWAVES_SMALL7);
 };
 // Patch widths whose per-patch kernel reads thinning masks made beforehand (patch_graph_lcg_kernel)
 // instead of running the generator: all 3-d widths.  How the masks reach the lanes decides whether
@@ -139,7 +147,10 @@ static constexpr int PA_MASKS_MAX_PX = PPP_PA_MASKS_MAX_PX;
 //   256-thread kernel the fourteen scalar registers of form 1 cost 8 more spilled VGPRs at its
 //   64-VGPR budget: it keeps form 0.)
 // Registers of patch_graph_pa_kernel<__half, 7, 64> with form 0 and with form 1 alike: 114 VGPRs,
-// 106 SGPRs, nothing spilled (profiles/r10_a_kernel_regs.txt).
+// 106 SGPRs, no VECTOR register spilled (profiles/r10_a_kernel_regs.txt) -- but 83 scalar ones, parked
+// in vector lanes (277 v_readlane / v_writelane, 119 of them in the pixel loop): the run-time window
+// geometry, see PaGeo below.  The cubic instantiation: 96 VGPRs, 80 SGPRs, no spill of either kind
+// (profiles/r11_a_kernel_regs.txt).
 // Not done: the row's seven LDS reads are still issued for every lane ahead of the statement (lanes
 // without work read slot 0); reading under the slot's lane mask as well would need the reads and
 // their wait inside the statement.
@@ -153,6 +164,53 @@ static constexpr int PA_MASKS_MAX_PX = PPP_PA_MASKS_MAX_PX;
 #define PPP_PA_EXEC_ADD 1
 #endif
 static constexpr int PA_PAD = 8;       // floats of slack either side of the staged row (a masked row read overshoots by < PX)
+
+// The window geometry the kernels of this file compute with.  CUBE = false reads it from Geo at run
+// time: any (pz, py, PX) window a PX case serves.  CUBE = true is a PX^3 window: every size is a
+// constant of the instantiation.  That is more than a few saved multiplies: with the row length W
+// a run-time value the staging loops of patch_graph_pa_kernel test `e < W` on every one of their
+// NST trips, each predicated load keeps its lane mask in a scalar register pair for the whole pixel
+// step (35 loads at 7^3 with 64 threads: ~70 scalar registers), and the kernel parks scalars in
+// vector lanes: 83 spilled SGPRs, 119 v_readlane / v_writelane in the pixel loop.  With W a constant
+// only the last trip is tested.  Same arithmetic, same order: the bits cannot differ.
+// PPP_PA_CUBE=0 sends cubic windows to the run-time instantiation (tests, A/B runs).
+template <int PX, bool CUBE> struct PaGeo {
+    const Geo &G;
+    __host__ __device__ explicit PaGeo(const Geo &g) : G(g) {}
+    __host__ __device__ int pz() const { return G.pz; }
+    __host__ __device__ int py() const { return G.py; }
+    __host__ __device__ int px() const { return G.px; }
+    __host__ __device__ int rz() const { return G.rz; }
+    __host__ __device__ int ry() const { return G.ry; }
+    __host__ __device__ int wy() const { return G.wy; }
+    __host__ __device__ int wx() const { return G.wx; }
+    __host__ __device__ int C() const { return G.C; }
+    __host__ __device__ int words() const { return (G.C + 31) / 32; }
+    __host__ __device__ int W() const { return (2 * G.pz - 1) * G.wy * G.wx; }             // floats per consensus row
+    __host__ __device__ int Lc() const { return (W() - 1) / 2; }
+    __host__ __device__ int WB() const { return (W() + 2 * PA_PAD + 3) & ~3; }             // floats per row buffer
+};
+template <int PX> struct PaGeo<PX, true> {
+    __host__ __device__ explicit PaGeo(const Geo &) {}
+    static constexpr int pz() { return PX; }
+    static constexpr int py() { return PX; }
+    static constexpr int px() { return PX; }
+    static constexpr int rz() { return PX / 2; }
+    static constexpr int ry() { return PX / 2; }
+    static constexpr int wy() { return 2 * PX - 1; }
+    static constexpr int wx() { return 2 * PX - 1; }
+    static constexpr int C() { return PX * PX * PX; }
+    static constexpr int words() { return (PX * PX * PX + 31) / 32; }
+    static constexpr int W() { return (2 * PX - 1) * (2 * PX - 1) * (2 * PX - 1); }
+    static constexpr int Lc() { return (W() - 1) / 2; }
+    static constexpr int WB() { return (W() + 2 * PA_PAD + 3) & ~3; }
+};
+// the windows the cubic instantiations serve (the launchers of this file ask this, nobody else)
+static bool pa_cube(const Geo &G) {
+    static EnvSwitch cube_sw("PPP_PA_CUBE");
+    if (cube_sw.get() && cube_sw.get()[0] == '0') return false;
+    return G.pz == G.px && G.py == G.px && (G.px == 3 || G.px == 5 || G.px == 7 || G.px == 9);
+}
 
 // bits b in [0, n) with lo <= b <= hi
 __device__ __forceinline__ uint32_t rmask(int lo, int hi, int n) {
@@ -185,7 +243,7 @@ __device__ __forceinline__ AxisMasks axis_masks(int dd, int a, int p) {
     return m;
 }
 
-template <typename T, int PX, int PA_THREADS>
+template <typename T, int PX, int PA_THREADS, bool CUBE>
 __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ? PaCfg<PX>::MIN_WAVES
                                                                                : PaCfg<PX>::MIN_WAVES_SMALL)
     patch_graph_pa_kernel(const T *__restrict__ pred, const float *__restrict__ S,
@@ -198,15 +256,20 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
                           const uint32_t *__restrict__ bits, const Geo G) {
     extern __shared__ uint32_t lds_raw[];
     const int tid = threadIdx.x, lane = tid & 63;
-    const int words = (G.C + 31) / 32;
-    const int W = (2 * G.pz - 1) * G.wy * G.wx, Lc = (W - 1) / 2;
-    const int WB = (W + 2 * PA_PAD + 3) & ~3;                     // floats per row buffer
+    const PaGeo<PX, CUBE> geo(G);                                 // the window's sizes: constants when CUBE
+    const int words = geo.words();
+    const int W = geo.W(), Lc = geo.Lc();
+    const int WB = geo.WB();                                      // floats per row buffer
     // staged floats per thread (the launcher checks W <= NST * PA_THREADS): a (2 PX - 1)^3 row --
     // for the wide kernel (25 x 25: 2-d patches only) a (2 PX - 1)^2 one.  (Sized for a cube it was
     // 1 839 floats per thread at PX = 25 with 64 threads: the staging array lived in scratch and
     // every pixel step walked 1 839 predicated iterations to move 38 floats -- what the "mask
     // algebra" of profiles/r04_zy_s5_p25_ablations.txt really was.)
     constexpr int NST = ((PX > 16 ? 1 : 2 * PX - 1) * (2 * PX - 1) * (2 * PX - 1) + PA_THREADS - 1) / PA_THREADS;
+    // staging trips on which EVERY thread has an element: with a constant row length all but the
+    // last one, and they run without a test (staged(i, e) folds to true)
+    constexpr int NFULL = CUBE ? PaGeo<PX, true>::W() / PA_THREADS : 0;
+    auto staged = [&](int i, int e) -> bool { return i < NFULL || e < W; };
     constexpr int ROW_BUFS = PaCfg<PX>::ROW_BUFS;
     float *rowbuf = reinterpret_cast<float *>(lds_raw);           // [ROW_BUFS][WB]
     uint32_t *faw = lds_raw + ROW_BUFS * WB;                      // [words]
@@ -279,11 +342,11 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
         const uint32_t *src = bits + bits_slot(vox(G, az, ay, ax)) * words;
         for (int w = tid; w < words; w += PA_THREADS) faw[w] = src[w];
     } else
-    for (int base = 0; base < G.C; base += PA_THREADS) {
+    for (int base = 0; base < geo.C(); base += PA_THREADS) {
         const int r = base + tid;
         bool on = false;
-        if (r < G.C) {
-            const int z = az + r / (G.py * PX) - G.rz, y = ay + (r / PX) % G.py - G.ry,
+        if (r < geo.C()) {
+            const int z = az + r / (geo.py() * PX) - geo.rz(), y = ay + (r / PX) % geo.py() - geo.ry(),
                       x = ax + r % PX - PX / 2;
             on = ldf(mid, vox(G, z, y, x)) > G.th_gt &&
                  ldf(pred, (long long)r * G.V + vox(G, az, ay, ax)) > G.th_gt;
@@ -318,8 +381,8 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
         } else
         for (int w = 0; w < words; ++w) {
             uint32_t bits = 0;
-            for (int b = 0; b < 32 && r < G.C; ++b, ++r) {
-                const int z = bz + r / (G.py * PX) - G.rz, y = by + (r / PX) % G.py - G.ry,
+            for (int b = 0; b < 32 && r < geo.C(); ++b, ++r) {
+                const int z = bz + r / (geo.py() * PX) - geo.rz(), y = by + (r / PX) % geo.py() - geo.ry(),
                           x = bx + r % PX - PX / 2;
                 const bool on = ldf(mid, vox(G, z, y, x)) > G.th_gt &&
                                 ldf(pred, (long long)r * G.V + lb) > G.th_gt;
@@ -364,8 +427,8 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
     // (pixel indices are workgroup-uniform scalars: the row address arithmetic stays on the
     // scalar unit and the staging loads take the saddr + voffset form)
     auto row_of = [&](int r1) -> const float * {
-        const int z1o = r1 / (G.py * PX), y1o = (r1 / PX) % G.py, x1o = r1 % PX;
-        return S + (baseA + (long long)row_slice(G, az + z1o - G.rz) * sZ + (long long)(y1o - G.ry) * sY + (x1o - PX / 2)) * W;
+        const int z1o = r1 / (geo.py() * PX), y1o = (r1 / PX) % geo.py(), x1o = r1 % PX;
+        return S + (baseA + (long long)row_slice(G, az + z1o - geo.rz()) * sZ + (long long)(y1o - geo.ry()) * sY + (x1o - PX / 2)) * W;
     };
     float acc = 0.0f;               // (+0.0f: the masked add of PPP_PA_EXEC_ADD relies on it)
     unsigned fg_cnt = 0;
@@ -381,13 +444,13 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
 #pragma unroll
         for (int i = 0; i < NST; ++i) {
             const int e = tid + i * PA_THREADS;
-            if (e < W) rowbuf[PA_PAD + e] = src[e];
+            if (staged(i, e)) rowbuf[PA_PAD + e] = src[e];
         }
     }
     __syncthreads();
 
     int prev_z1o = -1, prev_y1o = -1;
-    AxisMasks mz = axis_masks(dz, 0, G.pz), my = axis_masks(dy, 0, G.py);
+    AxisMasks mz = axis_masks(dz, 0, geo.pz()), my = axis_masks(dy, 0, geo.py());
     // expanded y masks per chunk: cached across the pixels of a row of A while a plane has few
     // chunks (3-d patches: 1-2); a 25-wide 2-d patch has 13 chunks of two rows -- 156 registers
     // of masks -- and expands them inside the chunk instead (a dozen instructions per chunk)
@@ -398,7 +461,7 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
     for (int c = 0; c < NEY; ++c) EYf[c] = EYbk[c] = EYpos[c] = EYzero[c] = EYst[c] = EYin[c] = 0ull;
     for (int k = 0; k < n_u; ++k) {
         const int r1 = r_next;
-        const int z1o = r1 / (G.py * PX), y1o = (r1 / PX) % G.py, x1o = r1 % PX;
+        const int z1o = r1 / (geo.py() * PX), y1o = (r1 / PX) % geo.py(), x1o = r1 % PX;
         const float *cur = rowbuf + (ROW_BUFS == 2 ? (k & 1) * WB : 0) + PA_PAD;
         // ---- fetch the next row into registers while this one is consumed
         const bool more = k + 1 < n_u;
@@ -409,19 +472,19 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
 #pragma unroll
                 for (int i = 0; i < NST; ++i) {
                     const int e = tid + i * PA_THREADS;
-                    st[i] = e < W ? src[e] : 0.0f;
+                    st[i] = staged(i, e) ? src[e] : 0.0f;
                 }
             }
         }
         // union of the lanes' candidate ranges: -p <= d + b - a <= p (wave-uniform)
-        const int z_lo = max(0, z1o - dz_hi - G.pz), z_hi = min(G.pz - 1, z1o - dz_lo + G.pz);
-        const int y_lo = max(0, y1o - dy_hi - G.py), y_hi = min(G.py - 1, y1o - dy_lo + G.py);
+        const int z_lo = max(0, z1o - dz_hi - geo.pz()), z_hi = min(geo.pz() - 1, z1o - dz_lo + geo.pz());
+        const int y_lo = max(0, y1o - dy_hi - geo.py()), y_hi = min(geo.py() - 1, y1o - dy_lo + geo.py());
         if (wave_live && z_lo <= z_hi && y_lo <= y_hi) {
             PA_STAT(0, lane == 0 ? 1 : 0);
             PA_STAT(5, live ? 1 : 0);
-            if (z1o != prev_z1o) { mz = axis_masks(dz, z1o, G.pz); prev_z1o = z1o; }
+            if (z1o != prev_z1o) { mz = axis_masks(dz, z1o, geo.pz()); prev_z1o = z1o; }
             if (y1o != prev_y1o) {
-                my = axis_masks(dy, y1o, G.py);   // (bits >= py are clear: the masks stop at py)
+                my = axis_masks(dy, y1o, geo.py());   // (bits >= py are clear: the masks stop at py)
                 prev_y1o = y1o;
                 if constexpr (EY_CACHED) {
 #pragma unroll
@@ -432,8 +495,8 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
                 }
             }
             const int q0x = dx - x1o;
-            const bool in_b = abs(x1o - PX / 2 - dx) <= PX / 2 && abs(y1o - G.ry - dy) <= G.ry &&
-                              abs(z1o - G.rz - dz) <= G.rz;
+            const bool in_b = abs(x1o - PX / 2 - dx) <= PX / 2 && abs(y1o - geo.ry() - dy) <= geo.ry() &&
+                              abs(z1o - geo.rz() - dz) <= geo.rz();
             // (a workgroup table of these masks in LDS, indexed by q0x, was measured: fewer
             // VALU instructions but 4 % slower -- five dependent LDS reads at the head of
             // every pixel step)
@@ -441,7 +504,7 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
             long long blk = 0;
             const bool has_blk = MASKS && soff >= 0 && in_b;
             if (has_blk) {
-                const int nzl = G.pz - abs(dz), nyl = G.py - abs(dy), nxl = PX - abs(dx);
+                const int nzl = geo.pz() - abs(dz), nyl = geo.py() - abs(dy), nxl = PX - abs(dx);
                 const int i1 = ((z1o - max(dz, 0)) * nyl + (y1o - max(dy, 0))) * nxl + (x1o - max(dx, 0));
                 blk = soff + ((long long)i1 * nzl - max(-dz, 0)) * NCH;   // + z2o * NCH + chunk
             }
@@ -452,7 +515,7 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
 #if PPP_PA_MASK_AHEAD
             // (planes outside the lane's intersection are not fetched)
             auto fetch = [&](int z, int c) -> u64 {
-                return has_blk && z < G.pz && ((mz.in >> z) & 1u) ? drops[blk + z * NCH + c] : 0ull;
+                return has_blk && z < geo.pz() && ((mz.in >> z) & 1u) ? drops[blk + z * NCH + c] : 0ull;
             };
             u64 pend = fetch(z_lo, 0);
 #endif
@@ -475,7 +538,7 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
                     // per plane and pixel at 25 x 25: what this kernel spent its time on,
                     // profiles/r04_zy_s5_p25_ablations.txt).  Same candidates, same order (rows
                     // ascending, x ascending inside a row), same LCG stream.
-                    const int idx0 = Lc + (qz * G.wy + my.q0) * G.wx + q0x;
+                    const int idx0 = Lc + (qz * geo.wy() + my.q0) * geo.wx() + q0x;
                     const uint32_t xin = in_b ? mx.in : 0u;
 #pragma unroll 1
                     for (int y2o = y_lo; y2o <= y_hi; ++y2o) {
@@ -492,7 +555,7 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
                         // foreground bits of patch B on this candidate row
                         uint32_t valid;
                         {
-                            const int o = (z2o * G.py + y2o) * PX, w0 = o >> 5, sh = o & 31;
+                            const int o = (z2o * geo.py() + y2o) * PX, w0 = o >> 5, sh = o & 31;
                             const uint32_t lo = fbw[w0 * PA_THREADS + tid];
                             const uint32_t hi = w0 + 1 < words ? fbw[(w0 + 1) * PA_THREADS + tid] : 0u;
                             valid = (uint32_t)(((((u64)hi) << 32) | lo) >> sh) & RM;
@@ -516,7 +579,7 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
                         if (__ballot(rb != 0u) == 0ull) continue;
                         PA_STAT(2, lane == 0 ? 1 : 0);
                         PA_STAT(3, __popc(rb));
-                        const float *rowq = cur + (rb != 0u ? idx0 + y2o * G.wx : 0);
+                        const float *rowq = cur + (rb != 0u ? idx0 + y2o * geo.wx() : 0);
 #pragma unroll
                         for (int t = 0; t < PX; ++t) {
                             const int sel = ((int)(rb << (31 - t))) >> 31;
@@ -534,7 +597,7 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
                     pend = c + 1 < NCH ? fetch(z2o, c + 1) : fetch(z2o + 1, 0);
 #endif
                     const int c_first = c * RPC;                       // first row of the chunk
-                    const int c_rows = min(RPC, G.py - c_first);
+                    const int c_rows = min(RPC, geo.py() - c_first);
                     if (c_rows <= 0) return;
                     const int ya = max(y_lo, c_first), yb = min(y_hi, c_first + c_rows - 1);
                     if (ya > yb) return;
@@ -558,7 +621,7 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
                     M valid;
                     {
                         const int nb = c_rows * PX;
-                        const int o = (z2o * G.py + c_first) * PX, w0 = o >> 5, sh = o & 31;
+                        const int o = (z2o * geo.py() + c_first) * PX, w0 = o >> 5, sh = o & 31;
                         const uint32_t lo = fbw[w0 * PA_THREADS + tid];
                         const uint32_t mi = w0 + 1 < words ? fbw[(w0 + 1) * PA_THREADS + tid] : 0u;
                         const uint32_t hi = w0 + 2 < words ? fbw[(w0 + 2) * PA_THREADS + tid] : 0u;
@@ -612,7 +675,7 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
                     return;
 #endif
                     // this lane's offset into the staged row for candidate (y2o = 0, x2o = 0)
-                    const int idx0 = Lc + (qz * G.wy + my.q0) * G.wx + q0x;
+                    const int idx0 = Lc + (qz * geo.wy() + my.q0) * geo.wx() + q0x;
 // (measured and rejected: 73 -> 79 ms on the thinned list, 540 -> 640 ms on the dense one --
 // the extra PX registers cost spills at the 64 / 128-VGPR budgets and every row is read)
 #ifndef PPP_PA_ROW_PIPELINE
@@ -628,7 +691,7 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
                         float nx[PX];
                         auto fetch = [&](int y2o, float (&dst)[PX]) {
                             const uint32_t rbn = (uint32_t)(add >> (PX * (y2o - c_first))) & RM;
-                            const float *rowq = cur + (rbn != 0u ? idx0 + y2o * G.wx : 0);
+                            const float *rowq = cur + (rbn != 0u ? idx0 + y2o * geo.wx() : 0);
 #pragma unroll
                             for (int t = 0; t < PX; ++t) dst[t] = rowq[t];
                         };
@@ -656,7 +719,7 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
                         PA_STAT(3, __popc(rb));
                         // lanes with nothing to add on this row may point anywhere: they read
                         // slot 0 (one broadcast address; what they read is masked to zero)
-                        const float *rowq = cur + (rb != 0u ? idx0 + y2o * G.wx : 0);
+                        const float *rowq = cur + (rb != 0u ? idx0 + y2o * geo.wx() : 0);
                         if constexpr (PPP_PA_EXEC_ADD != 0 && PX == 7 && PA_THREADS != PaCfg<PX>::THREADS) {
                             // Two vector instructions per add slot instead of three (bit-field
                             // extract, and, add): the row's mask is reversed once, every doubling
@@ -725,13 +788,13 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
 #pragma unroll
                 for (int i = 0; i < NST; ++i) {
                     const int e = tid + i * PA_THREADS;
-                    st[i] = e < W ? src[e] : 0.0f;
+                    st[i] = staged(i, e) ? src[e] : 0.0f;
                 }
             }
 #pragma unroll
             for (int i = 0; i < NST; ++i) {
                 const int e = tid + i * PA_THREADS;
-                if (e < W) dst[e] = st[i];
+                if (staged(i, e)) dst[e] = st[i];
             }
         }
         __syncthreads();
@@ -767,7 +830,7 @@ extern "C" void ppp_pa_stats(unsigned long long *out) {
 // candidate rows of that plane (the chunk layout of the kernel above: bit (y2o - first row) * PX
 // + x2o), the mask of DROPPED candidates.  The kernel above reads one mask per chunk instead of
 // running the generator.
-template <typename T, int PX>
+template <typename T, int PX, bool CUBE>
 __global__ void __launch_bounds__(64)
     patch_graph_lcg_kernel(const T *__restrict__ pred, const uint32_t *__restrict__ rows,
                            const uint32_t *__restrict__ order, const long long *__restrict__ lcg_pos,
@@ -776,7 +839,8 @@ __global__ void __launch_bounds__(64)
     typedef unsigned long long u64;
     extern __shared__ uint32_t lds_raw[];
     const int lane = threadIdx.x;
-    const int words = (G.C + 31) / 32;
+    const PaGeo<PX, CUBE> geo(G);
+    const int words = geo.words();
     uint32_t *fa = lds_raw;                 // [words][64]  F_A inside the intersection (A's window raster)
     uint32_t *fb = lds_raw + words * 64;    // [words + 2][64]  F_B inside the intersection (B's window raster)
     constexpr uint32_t RM = (1u << PX) - 1u;
@@ -795,7 +859,7 @@ __global__ void __launch_bounds__(64)
     }
     const int dz = bz - az, dy = by - ay, dx = bx - ax;
     // intersection box: n per axis, first window coordinate in A (lo1) and in B (lo2)
-    const int nz = live ? G.pz - abs(dz) : 0, ny = live ? G.py - abs(dy) : 0, nx = live ? PX - abs(dx) : 0;
+    const int nz = live ? geo.pz() - abs(dz) : 0, ny = live ? geo.py() - abs(dy) : 0, nx = live ? PX - abs(dx) : 0;
     const int z1lo = max(dz, 0), y1lo = max(dy, 0), x1lo = max(dx, 0);
     const int z2lo = max(-dz, 0), y2lo = max(-dy, 0), x2lo = max(-dx, 0);
     uint32_t rnd = pair_seed(G, az, ay, ax, bz, by, bx);
@@ -809,15 +873,15 @@ __global__ void __launch_bounds__(64)
             const int iz = t / (ny * nx), iy = (t / nx) % ny, ix = t % nx;
             {
                 const int zo = z1lo + iz, yo = y1lo + iy, xo = x1lo + ix;
-                const int r = (zo * G.py + yo) * PX + xo;
-                const bool on = ldf(mid, vox(G, az + zo - G.rz, ay + yo - G.ry, ax + xo - PX / 2)) > G.th_gt &&
+                const int r = (zo * geo.py() + yo) * PX + xo;
+                const bool on = ldf(mid, vox(G, az + zo - geo.rz(), ay + yo - geo.ry(), ax + xo - PX / 2)) > G.th_gt &&
                                 ldf(pred, (long long)r * G.V + la) > G.th_gt;
                 if (on) fa[(r >> 5) * 64 + lane] |= 1u << (r & 31);
             }
             {
                 const int zo = z2lo + iz, yo = y2lo + iy, xo = x2lo + ix;
-                const int r = (zo * G.py + yo) * PX + xo;
-                const bool on = ldf(mid, vox(G, bz + zo - G.rz, by + yo - G.ry, bx + xo - PX / 2)) > G.th_gt &&
+                const int r = (zo * geo.py() + yo) * PX + xo;
+                const bool on = ldf(mid, vox(G, bz + zo - geo.rz(), by + yo - geo.ry(), bx + xo - PX / 2)) > G.th_gt &&
                                 ldf(pred, (long long)r * G.V + lb) > G.th_gt;
                 if (on) fb[(r >> 5) * 64 + lane] |= 1u << (r & 31);
             }
@@ -830,21 +894,21 @@ __global__ void __launch_bounds__(64)
             const bool act = m != 0u;
             const int r1 = w * 32 + (act ? __builtin_ctz(m) : 0);
             m &= m - 1u;
-            const int z1o = r1 / (G.py * PX), y1o = (r1 / PX) % G.py, x1o = r1 % PX;
+            const int z1o = r1 / (geo.py() * PX), y1o = (r1 / PX) % geo.py(), x1o = r1 % PX;
             const int i1 = ((z1o - z1lo) * ny + (y1o - y1lo)) * nx + (x1o - x1lo);
             const long long blk = soff + (long long)i1 * nz * NCH;
-            for (int z2o = 0; z2o < G.pz; ++z2o) {
+            for (int z2o = 0; z2o < geo.pz(); ++z2o) {
                 const bool inz = act && z2o >= z2lo && z2o < z2lo + nz;
                 if (__ballot(inz) == 0ull) continue;
 #pragma unroll 1
                 for (int c = 0; c < NCH; ++c) {
                     const int c_first = c * RPC;
-                    const int c_rows = min(RPC, G.py - c_first);
+                    const int c_rows = min(RPC, geo.py() - c_first);
                     if (c_rows <= 0) break;
                     u64 hits;
                     {
                         const int nb = c_rows * PX;
-                        const int o = (z2o * G.py + c_first) * PX, w0 = o >> 5, sh = o & 31;
+                        const int o = (z2o * geo.py() + c_first) * PX, w0 = o >> 5, sh = o & 31;
                         const uint32_t lo = fb[w0 * 64 + lane], mi = fb[(w0 + 1) * 64 + lane],
                                        hi = fb[(w0 + 2) * 64 + lane];
                         hits = ((((u64)mi << 32) | lo) >> sh) | (sh ? ((u64)hi << (64 - sh)) : 0ull);
@@ -894,7 +958,7 @@ __device__ __forceinline__ uint32_t lcg_pow(uint32_t base, uint32_t e) {      //
     return r;
 }
 static constexpr int LCGW_WAVES = 4;
-template <typename T, int PX>
+template <typename T, int PX, bool CUBE>
 __global__ void __launch_bounds__(64 * LCGW_WAVES)
     patch_graph_lcg_wave_kernel(const T *__restrict__ pred, const uint32_t *__restrict__ rows,
                                 const uint32_t *__restrict__ order, const long long *__restrict__ lcg_pos,
@@ -903,7 +967,8 @@ __global__ void __launch_bounds__(64 * LCGW_WAVES)
     typedef unsigned long long u64;
     extern __shared__ uint32_t lds_raw[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int words = (G.C + 31) / 32;
+    const PaGeo<PX, CUBE> geo(G);
+    const int words = geo.words();
     uint32_t *fa = lds_raw + wave * (2 * words + 2);      // F_A inside the intersection (A's window raster)
     uint32_t *fb = fa + words;                            // [words + 2]  F_B (B's window raster)
     constexpr int RPC = 64 / PX;
@@ -916,7 +981,7 @@ __global__ void __launch_bounds__(64 * LCGW_WAVES)
     const uint32_t *rw = rows + (size_t)order[pos] * 6;
     const int az = (int)rw[0], ay = (int)rw[1], ax = (int)rw[2], bz = (int)rw[3], by = (int)rw[4], bx = (int)rw[5];
     const int dz = bz - az, dy = by - ay, dx = bx - ax;
-    const int nz = G.pz - abs(dz), ny = G.py - abs(dy), nx = PX - abs(dx);
+    const int nz = geo.pz() - abs(dz), ny = geo.py() - abs(dy), nx = PX - abs(dx);
     if (nz <= 0 || ny <= 0 || nx <= 0) return;
     const int z1lo = max(dz, 0), y1lo = max(dy, 0), x1lo = max(dx, 0);
     const int z2lo = max(-dz, 0), y2lo = max(-dy, 0), x2lo = max(-dx, 0);
@@ -929,11 +994,11 @@ __global__ void __launch_bounds__(64 * LCGW_WAVES)
         const int n_i = nz * ny * nx;
         for (int t = lane; t < n_i; t += 64) {
             const int iz = t / (ny * nx), iy = (t / nx) % ny, ix = t % nx;
-            const int ra = ((z1lo + iz) * G.py + (y1lo + iy)) * PX + (x1lo + ix);
-            const int rb = ((z2lo + iz) * G.py + (y2lo + iy)) * PX + (x2lo + ix);
-            const float ma = ldf(mid, vox(G, az + z1lo + iz - G.rz, ay + y1lo + iy - G.ry, ax + x1lo + ix - PX / 2));
+            const int ra = ((z1lo + iz) * geo.py() + (y1lo + iy)) * PX + (x1lo + ix);
+            const int rb = ((z2lo + iz) * geo.py() + (y2lo + iy)) * PX + (x2lo + ix);
+            const float ma = ldf(mid, vox(G, az + z1lo + iz - geo.rz(), ay + y1lo + iy - geo.ry(), ax + x1lo + ix - PX / 2));
             const float pa = ldf(pred, (long long)ra * G.V + la);
-            const float mb = ldf(mid, vox(G, bz + z2lo + iz - G.rz, by + y2lo + iy - G.ry, bx + x2lo + ix - PX / 2));
+            const float mb = ldf(mid, vox(G, bz + z2lo + iz - geo.rz(), by + y2lo + iy - geo.ry(), bx + x2lo + ix - PX / 2));
             const float pb = ldf(pred, (long long)rb * G.V + lb);
             if (ma > G.th_gt && pa > G.th_gt) atomicOr(&fa[ra >> 5], 1u << (ra & 31));
             if (mb > G.th_gt && pb > G.th_gt) atomicOr(&fb[rb >> 5], 1u << (rb & 31));
@@ -964,7 +1029,7 @@ __global__ void __launch_bounds__(64 * LCGW_WAVES)
                 left -= c;
             }
         }
-        const int z1o = r1 / (G.py * PX), y1o = (r1 / PX) % G.py, x1o = r1 % PX;
+        const int z1o = r1 / (geo.py() * PX), y1o = (r1 / PX) % geo.py(), x1o = r1 % PX;
         const int i1 = ((z1o - z1lo) * ny + (y1o - y1lo)) * nx + (x1o - x1lo);
         const long long blk = soff + (long long)i1 * nz * NCH;
         uint32_t rnd = seed * lcg_pow(g, (uint32_t)(act ? j : 0));
@@ -972,10 +1037,10 @@ __global__ void __launch_bounds__(64 * LCGW_WAVES)
 #pragma unroll 1
             for (int c = 0; c < NCH; ++c) {
                 const int c_first = c * RPC;
-                const int c_rows = min(RPC, G.py - c_first);
+                const int c_rows = min(RPC, geo.py() - c_first);
                 if (c_rows <= 0) break;
                 const int nb = c_rows * PX;
-                const int o = (z2o * G.py + c_first) * PX, w0 = o >> 5, sh = o & 31;
+                const int o = (z2o * geo.py() + c_first) * PX, w0 = o >> 5, sh = o & 31;
                 const uint32_t lo = fb[w0], mi = fb[w0 + 1], hi = fb[w0 + 2];
                 u64 hits = ((((u64)mi << 32) | lo) >> sh) | (sh ? ((u64)hi << (64 - sh)) : 0ull);
                 hits &= nb >= 64 ? ~0ull : ((1ull << nb) - 1ull);
@@ -1004,7 +1069,7 @@ long long patch_graph_lcg_words(const Geo &G, int dz, int dy, int dx) {
     return (long long)nz * ny * nx * nz * nch;
 }
 
-template <typename T, int PX>
+template <typename T, int PX, bool CUBE>
 static hipError_t launch_lcg(const T *pred, const uint32_t *rows, const uint32_t *order, const long long *lcg_pos,
                              long long n, const long long *drop_off, unsigned long long *drops, const Geo &G,
                              hipStream_t s) {
@@ -1015,11 +1080,11 @@ static hipError_t launch_lcg(const T *pred, const uint32_t *rows, const uint32_t
     if (!(wave_sw.get() && wave_sw.get()[0] == '0') &&
         !grid_too_big((unsigned long long)((n + LCGW_WAVES - 1) / LCGW_WAVES), 64 * LCGW_WAVES)) {
         const size_t ldsw = (size_t)(2 * words + 2) * LCGW_WAVES * 4;
-        patch_graph_lcg_wave_kernel<T, PX><<<dim3((unsigned)((n + LCGW_WAVES - 1) / LCGW_WAVES)), dim3(64 * LCGW_WAVES), ldsw, s>>>(
+        patch_graph_lcg_wave_kernel<T, PX, CUBE><<<dim3((unsigned)((n + LCGW_WAVES - 1) / LCGW_WAVES)), dim3(64 * LCGW_WAVES), ldsw, s>>>(
             pred, rows, order, lcg_pos, n, drop_off, drops, G);
         return hipGetLastError();
     }
-    patch_graph_lcg_kernel<T, PX><<<dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s>>>(
+    patch_graph_lcg_kernel<T, PX, CUBE><<<dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s>>>(
         pred, rows, order, lcg_pos, n, drop_off, drops, G);
     return hipGetLastError();
 }
@@ -1039,8 +1104,11 @@ hipError_t launch_patch_graph_lcg(const void *pred, int dtype, const uint32_t *r
     case P:                                                                                              \
         return with_pred_type(dtype, [&](auto tag) {                                                     \
             using T = PPP_PRED_T(tag);                                                                   \
-            return launch_lcg<T, P>((const T *)pred, rows, order, lcg_pos, n, drop_off, drops, G, s);    \
+            if constexpr (P <= 9)                                                                        \
+                if (cube) return launch_lcg<T, P, true>((const T *)pred, rows, order, lcg_pos, n, drop_off, drops, G, s); \
+            return launch_lcg<T, P, false>((const T *)pred, rows, order, lcg_pos, n, drop_off, drops, G, s); \
         });
+    const bool cube = pa_cube(G);
     switch (G.px) {
         PPP_LCG_CASE(3)
         PPP_LCG_CASE(5)
@@ -1064,7 +1132,7 @@ int patch_graph_pa_chunk(const Geo &G, bool small) {
     return 0;
 }
 
-template <typename T, int PX, int THREADS>
+template <typename T, int PX, int THREADS, bool CUBE>
 static hipError_t launch_pa(const T *pred, const float *S, const uint32_t *rows, const uint32_t *order,
                             const long long *group_start, const long long *chunk_offsets, int n_groups,
                             long long n_blocks, float *aff, const long long *drop_off,
@@ -1072,11 +1140,11 @@ static hipError_t launch_pa(const T *pred, const float *S, const uint32_t *rows,
                             const uint32_t *bits, const Geo &G, size_t lds, hipStream_t s) {
     // (dynamic LDS above 64 KB -- the 9^3 rows -- is an opt-in per kernel)
     if (lds > 64 * 1024) {
-        hipError_t ea = hipFuncSetAttribute((const void *)patch_graph_pa_kernel<T, PX, THREADS>,
+        hipError_t ea = hipFuncSetAttribute((const void *)patch_graph_pa_kernel<T, PX, THREADS, CUBE>,
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (ea != hipSuccess) return ea;
     }
-    patch_graph_pa_kernel<T, PX, THREADS><<<dim3((unsigned)n_blocks), dim3(THREADS), lds, s>>>(
+    patch_graph_pa_kernel<T, PX, THREADS, CUBE><<<dim3((unsigned)n_blocks), dim3(THREADS), lds, s>>>(
         pred, S, rows, order, group_start, chunk_offsets, n_groups, aff, drop_off, drops, bits_centres, n_bits,
         bits, G);
     return hipGetLastError();
@@ -1086,22 +1154,23 @@ static hipError_t launch_pa(const T *pred, const float *S, const uint32_t *rows,
 // is  mid[u_r] > th_gt && pred[r][c] > th_gt  (u_r = the r-th voxel of c's window) -- the expression
 // the per-patch kernel evaluates for A and for every B.  A wave per centre; centres[] holds linear
 // voxel indices of the frame `pred` lives in, windows inside the volume.
-template <typename T>
+template <typename T, int PX, bool CUBE>      // (PX = 0 with CUBE = false: any window)
 __global__ void __launch_bounds__(64)
     patch_fg_bits_kernel(const T *__restrict__ pred, const long long *__restrict__ centres, const long long n,
                          uint32_t *__restrict__ table, const Geo G) {
     const long long i = blockIdx.x;
     if (i >= n) return;
-    const int lane = threadIdx.x, words = (G.C + 31) / 32;
+    const PaGeo<PX, CUBE> geo(G);
+    const int lane = threadIdx.x, words = geo.words();
     const long long lin = centres[i];
     const int cz = (int)(lin / ((long long)G.Y * G.X)), cy = (int)((lin / G.X) % G.Y), cx = (int)(lin % G.X);
     const T *mid = pred + (long long)G.mid * G.V;
-    for (int base = 0; base < G.C; base += 64) {
+    for (int base = 0; base < geo.C(); base += 64) {
         const int r = base + lane;
         bool on = false;
-        if (r < G.C) {
-            const int z = cz + r / (G.py * G.px) - G.rz, y = cy + (r / G.px) % G.py - G.ry,
-                      x = cx + r % G.px - G.px / 2;
+        if (r < geo.C()) {
+            const int z = cz + r / (geo.py() * geo.px()) - geo.rz(), y = cy + (r / geo.px()) % geo.py() - geo.ry(),
+                      x = cx + r % geo.px() - geo.px() / 2;
             on = ldf(mid, vox(G, z, y, x)) > G.th_gt && ldf(pred, (long long)r * G.V + lin) > G.th_gt;
         }
         const unsigned long long m = __ballot(on);
@@ -1120,7 +1189,18 @@ hipError_t launch_patch_fg_bits(const void *pred, int dtype, const long long *ce
     {
         const hipError_t e_ = with_pred_type(dtype, [&](auto tag) {
             using T = PPP_PRED_T(tag);
-            patch_fg_bits_kernel<T><<<dim3((unsigned)n), dim3(64), 0, s>>>((const T *)pred, centres, n, table, G);
+#define PPP_BITS_CASE(P)                                                                                 \
+    case P:                                                                                              \
+        patch_fg_bits_kernel<T, P, true><<<dim3((unsigned)n), dim3(64), 0, s>>>((const T *)pred, centres, n, table, G); \
+        return hipSuccess;
+            switch (pa_cube(G) ? G.px : 0) {
+                PPP_BITS_CASE(3)
+                PPP_BITS_CASE(5)
+                PPP_BITS_CASE(7)
+                PPP_BITS_CASE(9)
+            }
+#undef PPP_BITS_CASE
+            patch_fg_bits_kernel<T, 0, false><<<dim3((unsigned)n), dim3(64), 0, s>>>((const T *)pred, centres, n, table, G);
             return hipSuccess;
         });
         if (e_ != hipSuccess) return e_;
@@ -1152,13 +1232,19 @@ hipError_t launch_patch_graph_pa(const void *pred, int dtype, const float *S, co
     const size_t lds = (size_t)(row_bufs * WB + ((words + 3) & ~3) + ((words * threads + 1) & ~1)) * 4;
     if (lds > 80 * 1024 || n_blocks >= (1ll << 31) || grid_too_big((unsigned long long)n_blocks, threads))
         return hipErrorNotSupported;
-    note_patch_graph_kernel(small ? "patch_graph_pa_kernel<small>" : "patch_graph_pa_kernel");
+    // the cubic instantiation: the window's sizes compiled in (PaGeo above)
+    const bool cubic = pa_cube(G);
+    note_patch_graph_kernel(small ? "patch_graph_pa_kernel<small>" : "patch_graph_pa_kernel", cubic ? "cube" : "generic");
+#define PPP_PA_ARGS (const T *)pred, S, rows, order, group_start, chunk_offsets, n_groups, n_blocks, aff, drop_off, drops, bits_centres, n_bits, bits, G, lds, s
 #define PPP_PA_CASE(P)                                                                                  \
     case P:                                                                                             \
         return with_pred_type(dtype, [&](auto tag) {                                                    \
             using T = PPP_PRED_T(tag);                                                                  \
-            return small ? launch_pa<T, P, PaCfg<P>::THREADS_SMALL>((const T *)pred, S, rows, order, group_start, chunk_offsets, n_groups, n_blocks, aff, drop_off, drops, bits_centres, n_bits, bits, G, lds, s) \
-                         : launch_pa<T, P, PaCfg<P>::THREADS>((const T *)pred, S, rows, order, group_start, chunk_offsets, n_groups, n_blocks, aff, drop_off, drops, bits_centres, n_bits, bits, G, lds, s); \
+            if constexpr (P <= 9)                                                                       \
+                if (cubic) return small ? launch_pa<T, P, PaCfg<P>::THREADS_SMALL, true>(PPP_PA_ARGS)    \
+                                       : launch_pa<T, P, PaCfg<P>::THREADS, true>(PPP_PA_ARGS);         \
+            return small ? launch_pa<T, P, PaCfg<P>::THREADS_SMALL, false>(PPP_PA_ARGS)                 \
+                         : launch_pa<T, P, PaCfg<P>::THREADS, false>(PPP_PA_ARGS);                      \
         });
     switch (G.px) {
         PPP_PA_CASE(3)
@@ -1170,6 +1256,7 @@ hipError_t launch_patch_graph_pa(const void *pred, int dtype, const float *S, co
         return hipErrorNotSupported;
     }
 #undef PPP_PA_CASE
+#undef PPP_PA_ARGS
 }
 
 }  // namespace ppp

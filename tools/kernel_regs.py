@@ -1,4 +1,4 @@
-"""Registers / spills / LDS of every kernel in an AMDGPU assembly file (hipcc --save-temps *.s).
+"""Registers / vector and scalar spills / LDS of every kernel in an AMDGPU assembly file (hipcc --save-temps *.s).
 usage: python tools/kernel_regs.py file.s [name filter]"""
 import re
 import subprocess
@@ -15,6 +15,6 @@ for blk in txt.split("  - .agpr_count:")[1:]:
         pass
     name = name.split("(")[0]
     if flt in name:
-        print("%-70s vgpr %3s spill %3s scratch %4s lds %6s sgpr %3s" % (
+        print("%-70s vgpr %3s spill %3s scratch %4s lds %6s sgpr %3s sgpr_spill %3s" % (
             name[-70:], f.get("vgpr_count"), f.get("vgpr_spill_count"), f.get("private_segment_fixed_size"),
-            f.get("group_segment_fixed_size"), f.get("sgpr_count")))
+            f.get("group_segment_fixed_size"), f.get("sgpr_count"), f.get("sgpr_spill_count")))
