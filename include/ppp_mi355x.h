@@ -243,6 +243,15 @@ int64_t ppp_rank_workspace_bytes(const ppp_box *score_box, const ppp_params *p);
 int ppp_rank_patches_vm(const void *d_pred, int pred_dtype, const float *d_cons_vm,
                         const uint8_t *d_overlap, float *d_score, const ppp_box *score_box,
                         void *d_work, const ppp_params *p, void *stream);
+/* How ppp_rank_patches_vm would launch the workgroup-per-tile kernel (cubic 5 / 7 / 9 patches) for this box,
+ * without launching: plan[0..2] the tile of centres of the kernel (z, y, x), plan[3] the thickness in z the
+ * tiles are cut at (<= plan[0]), plan[4] the tiles, plan[5] the tiles per XCD that are split into halves,
+ * plan[6] the order slots per XCD (grid = 8 x slots workgroups), plan[7] 1 when the XCDs take ranges of equal
+ * weight and 0 for ranges of equal tile count.  The plan is a function of the box, the patch size, the
+ * workgroups a CU holds and the CUs of an XCD: pass the last two to ask about a device that is not there
+ * (no GPU is touched then), or <= 0 for the current device's.  PPP_ERR_UNSUPPORTED where another kernel ranks. */
+int ppp_rank_wg_plan(const ppp_box *score_box, const ppp_params *p, int resident_per_cu, int cus_per_xcd,
+                     int32_t plan[8]);
 
 /* --- S5: patch graph (edge emission) --------------------------------------------------
  * replaces computePatchGraph_cuda (aff_patch_graph.py:113-187) + kernel computePatchGraph

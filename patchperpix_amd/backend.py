@@ -117,6 +117,8 @@ _SIGNATURES = {
                                         ctypes.POINTER(Box), ctypes.POINTER(Params),
                                         ctypes.c_void_p]),
     "ppp_rank_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(Box), ctypes.POINTER(Params)]),
+    "ppp_rank_wg_plan": (ctypes.c_int, [ctypes.POINTER(Box), ctypes.POINTER(Params), ctypes.c_int, ctypes.c_int,
+                                        ctypes.POINTER(ctypes.c_int32)]),
     "ppp_rank_patches_vm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(Box),
                                            ctypes.c_void_p, ctypes.POINTER(Params), ctypes.c_void_p]),
@@ -915,6 +917,17 @@ def rank_patches(pred, cons, overlap, P, score_box=None, out=None):
                                      _dev_ptr(overlap), _dev_ptr(out), box, ctypes.byref(P),
                                      _stream()))
     return out
+
+
+def rank_wg_plan(P, score_box=None, resident_per_cu=0, cus_per_xcd=0):
+    """How ppp_rank_patches_vm would launch the workgroup-per-tile ranking kernel for this box, without
+    launching (ppp_rank_wg_plan): tile, z step, tiles, splits and order slots per XCD, range kind.  With
+    resident_per_cu and cus_per_xcd given no device is asked."""
+    box = None if score_box is None else ctypes.byref(Box(*[int(v) for v in score_box]))
+    out = (ctypes.c_int32 * 8)()
+    check(lib().ppp_rank_wg_plan(box, ctypes.byref(P), int(resident_per_cu), int(cus_per_xcd), out))
+    return dict(tile=(out[0], out[1], out[2]), tz_step=out[3], tiles=out[4], splits=out[5], slots=out[6],
+                ranges="weight" if out[7] else "count")
 
 
 def rank_vm_available(P):

@@ -79,6 +79,9 @@ hipError_t launch_rank_vm(const void *pred, int dtype, const float *S, const uin
                           const ppp_box &sb, void *work, const Geo &G, hipStream_t s);
 bool rank_wg_supported(const Geo &G);
 size_t rank_wg_workspace_bytes(const ppp_box &sb, const Geo &G);
+// the launcher's plan for this box, without a launch: out = tile z, y, x; z step; tiles; splits and order
+// slots per XCD; 1 for XCD ranges of equal weight.  resident_per_cu / cus_per_xcd <= 0: ask the device
+void rank_wg_plan(const ppp_box &sb, const Geo &G, int resident_per_cu, int cus_per_xcd, int32_t out[8]);
 #ifdef PPP_RW_STAMPS
 size_t rank_wg_stamps_offset(const ppp_box &sb, const Geo &G);   // where the stamps lie in that workspace
 #endif

@@ -76,6 +76,20 @@
 //     16 x 8 x 16 tiles for the whole launch (66.4 / 66.1 against 66.5 ms on the parent).
 //   * not done: the XCDs of the launch still end between 36 and 56 ms (the y-edge slabs of the y-major
 //     numbering are light): ranges of equal WEIGHT instead of equal tile count would need slots to spare.
+//
+// Round 12, the SHAPE of that launch (profiles/r12_a_*; tools/s2_tile_model.py is the CPU
+// model the sweep is set against).  1 458 tiles of 8 x 16 x 16 are 183 per XCD for 160 resident slots (five workgroups
+// per CU): one round and a tail.  All kept, all bit-identical (same kernel body, same summation order per centre):
+//   * TILE FIT: the tile's thickness in z is a run-time value (template parameter DZ; TZ = 16 sizes the LDS arrays:
+//     29 KB, 91 VGPRs, still five workgroups per CU).  A 7^3 launch that 8 x 16 x 16 puts between one and two rounds
+//     per XCD takes the smallest z step in 8 .. 16 whose tiles fit the resident slots (rw_plan): 10 at 140^3, 142 tiles
+//     per XCD, no splits.  S2 call 53.9 -> 49.1 ms; z step 9 (162, two over) 50.0; z steps 11 .. 16 are SLOWER than the
+//     parent's launch (54.4 .. 62.8 ms) although they stage fewer rows: fewer than 4.4 workgroups per CU cost more.
+//   * RANGES OF EQUAL WEIGHT (rank_tile_order_kernel cuts the y-major sequence at the prefix sums of the weight; an
+//     XCD's range may grow by a quarter, clamped): 49.1 -> 48.3 ms at z step 10 (XCD ends 38.0 - 50.6 -> 42.6 - 49.8 ms).
+//     Chosen with the tile fit only; PPP_RANK_WG_XCD=weight gives them to any launch (the parent's: 53.9 -> 50.2 ms).
+//   * PRE-PASS with the cubic window compiled in and partner validity read from `valid`: 55.5 -> 53.9 ms per call.
+//   5^3 and 9^3 launches keep their code and their plan: no workload of theirs was swept.
 #include <stdlib.h>
 #include <string.h>
 
@@ -196,10 +210,15 @@ __host__ __device__ __forceinline__ uint32_t interleave16(uint32_t p, uint32_t n
 // ---- pre-pass: interleaved masks, pair counts, border / background scores ------------------
 // thread per centre of the score box; masks word-major over the box (lanes = neighbouring
 // centres coalesce in the main kernel)
-template <typename T>
+// Round 12: P = 5 / 7 / 9 compiles the cubic window in (RwPreGeo, as PaGeo does for S5): the partner loop runs
+// over (dz, dy, dx) with constant bounds -- no division per partner -- and reads the partner's validity from
+// `valid`, which rank_valid2_kernel wrote one launch earlier, instead of evaluating pred[mid] > th && ov == 0
+// again for each of the C partners.  P = 0: the run-time loop (other shapes; PPP_RANK_PRE_CUBE=0 sends the
+// cubic windows there too: tests, A/B runs).  Same masks, info and scores either way.
+template <typename T, int P>
 __global__ void __launch_bounds__(256)
-    rank_masks_il_kernel(const T *__restrict__ pred, const uint8_t *__restrict__ ov, const ppp_box sb,
-                         uint32_t *__restrict__ M, uint32_t *__restrict__ info,
+    rank_masks_il_kernel(const T *__restrict__ pred, const uint8_t *__restrict__ ov, const uint8_t *__restrict__ valid_v,
+                         const ppp_box sb, uint32_t *__restrict__ M, uint32_t *__restrict__ info,
                          float *__restrict__ score, const int *__restrict__ any_e, const Geo G) {
     if (any_e && *any_e == 0) return;         // (the one-bit masks serve this launch)
     const int sX = sb.x1 - sb.x0, sY = sb.y1 - sb.y0, sZ = sb.z1 - sb.z0;
@@ -219,6 +238,29 @@ __global__ void __launch_bounds__(256)
         const long long q0 = rw_mask_quad0(t / sX, (int)(t % sX), sX, rw_mask_words(G.C) / 4);
         unsigned nP = 0, nV = 0;
         int r = 0;
+        if constexpr (P != 0) {
+            constexpr int R = P / 2, C = P * P * P;
+            uint32_t p = 0, n = 0;
+            for (int dz = 0; dz < P; ++dz)
+                for (int dy = 0; dy < P; ++dy) {
+                    const uint8_t *vrow = valid_v + vox(G, cz + dz - R, cy + dy - R, cx - R);
+#pragma unroll
+                    for (int dx = 0; dx < P; ++dx, ++r) {
+                        const bool valid = vrow[dx] != 0;
+                        const float val = ldf(pred, (long long)r * G.V + lc);
+                        const int b = r & 15;
+                        if (valid) ++nV;
+                        if (valid && val > G.th_gt) p |= 1u << b;
+                        if (valid && val < G.bg_lt) n |= 1u << b;
+                        if (b == 15 || r == C - 1) {
+                            const int w = r >> 4;
+                            M[(q0 + (long long)(w >> 2) * RW_QSTRIDE) * 4 + (w & 3)] = interleave16(p, n);
+                            nP += __popc(p);
+                            p = n = 0;
+                        }
+                    }
+                }
+        } else
         for (int w = 0; w < words16; ++w) {
             uint32_t p = 0, n = 0;
             for (int b = 0; b < 16 && r < G.C; ++b, ++r) {
@@ -254,10 +296,10 @@ __global__ void __launch_bounds__(256)
 // raises `any_e`, the one-bit main kernel returns at once and the two-bit pre-pass + kernel, launched
 // behind it, run (they return at once otherwise).
 static constexpr int rw_p1_words(int C) { return (((C + 31) / 32) + 3) & ~3; }
-template <typename T>
+template <typename T, int P>
 __global__ void __launch_bounds__(256)
-    rank_masks_p1_kernel(const T *__restrict__ pred, const uint8_t *__restrict__ ov, const ppp_box sb,
-                         uint32_t *__restrict__ M, uint32_t *__restrict__ info, int *__restrict__ any_e,
+    rank_masks_p1_kernel(const T *__restrict__ pred, const uint8_t *__restrict__ ov, const uint8_t *__restrict__ valid_v,
+                         const ppp_box sb, uint32_t *__restrict__ M, uint32_t *__restrict__ info, int *__restrict__ any_e,
                          float *__restrict__ score, const Geo G) {
     const int sX = sb.x1 - sb.x0, sY = sb.y1 - sb.y0, sZ = sb.z1 - sb.z0;
     const long long sbV = (long long)sX * sY * sZ;
@@ -276,6 +318,27 @@ __global__ void __launch_bounds__(256)
         unsigned nP = 0, nV = 0;
         bool e = false;
         int r = 0;
+        if constexpr (P != 0) {
+            // (the cubic window compiled in: see rank_masks_il_kernel)
+            constexpr int R = P / 2, C = P * P * P;
+            uint32_t p = 0;
+            for (int dz = 0; dz < P; ++dz)
+                for (int dy = 0; dy < P; ++dy) {
+                    const uint8_t *vrow = valid_v + vox(G, cz + dz - R, cy + dy - R, cx - R);
+#pragma unroll
+                    for (int dx = 0; dx < P; ++dx, ++r) {
+                        const bool valid = vrow[dx] != 0;
+                        const float val = ldf(pred, (long long)r * G.V + lc);
+                        const bool isp = val > G.th_gt;
+                        const int b = r & 31;
+                        if (valid) ++nV;
+                        if (valid && isp) ++nP;
+                        if (valid && !isp && !(val < G.bg_lt)) e = true;
+                        if (isp) p |= 1u << b;
+                        if (b == 31 || r == C - 1) { M[t * (long long)wp + (r >> 5)] = p; p = 0; }
+                    }
+                }
+        } else
         for (int w = 0; w < words; ++w) {
             uint32_t p = 0;
             for (int b = 0; b < 32 && r < G.C; ++b, ++r) {
@@ -388,15 +451,54 @@ __global__ void __launch_bounds__(256)
 // are dealt heaviest first.  record = tile | RW_HALF_LO / RW_HALF_HI; an XCD's range
 // of the order array has per_xcd + splits slots.
 static constexpr int32_t RW_HALF_LO = 1 << 28, RW_HALF_HI = 2 << 28, RW_TILE_MASK = (1 << 28) - 1;
+// Round 12, ranges of equal WEIGHT (by_weight; PPP_RANK_WG_XCD=weight): the y-major tile sequence is cut where
+// the prefix sum of the weights passes k / 8 of the total instead of every per_xcd tiles -- the y-edge slabs of
+// the numbering are light, so their XCDs take more tiles.  The ranges stay contiguous (neighbours meet in one
+// L2) and heaviest first inside.  The grid is made before the weights exist: an XCD's part of the order array
+// has `slots` entries, so a range is clamped to cap = slots - splits tiles (and to what the ranges after it
+// can still hold: cap >= per_xcd, so every tile finds a slot).  Every workgroup works out all eight cuts.
 __global__ void __launch_bounds__(256)
     rank_tile_order_kernel(const int32_t *__restrict__ weight, const int n_tiles, const int per_xcd, const int splits,
-                           int32_t *__restrict__ order) {
+                           const int slots, const int by_weight, int32_t *__restrict__ order) {
     __shared__ int32_t w[RW_ORDER_MAX / 8 + 8];
     __shared__ int32_t key[RW_ORDER_MAX / 8 + 8];      // weight of the tile's records; bit 30: the tile is split
-    const int lo = blockIdx.x * per_xcd, hi = min(lo + per_xcd, n_tiles), n = max(hi - lo, 0);
-    const int slot0 = blockIdx.x * (per_xcd + splits);
+    __shared__ int part_sum[256];
+    __shared__ int cut[9];
+    int lo = blockIdx.x * per_xcd, hi = min(lo + per_xcd, n_tiles);
+    if (by_weight) {
+        // chunk sums, then cut k = the first tile at which the running weight reaches k / 8 of the total
+        const int ch = (n_tiles + 255) / 256;
+        int ps = 0;
+        for (int i = threadIdx.x * ch; i < min((threadIdx.x + 1) * ch, n_tiles); ++i) ps += weight[i];
+        part_sum[threadIdx.x] = ps;
+        __syncthreads();
+        if (threadIdx.x < 9) {
+            long long total = 0;
+            for (int c = 0; c < 256; ++c) total += part_sum[c];
+            int at = threadIdx.x == 8 ? n_tiles : 0;
+            if (threadIdx.x > 0 && threadIdx.x < 8) {
+                const long long want = (total * threadIdx.x + 7) / 8;
+                long long run = 0;
+                int c = 0;
+                while (c < 256 && run + part_sum[c] < want) run += part_sum[c++];
+                at = min(c * ch, n_tiles);
+                while (at < n_tiles && run < want) run += weight[at++];
+            }
+            cut[threadIdx.x] = at;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int cap = min(slots - splits, RW_ORDER_MAX / 8);
+            for (int k = 1; k < 8; ++k)
+                cut[k] = min(max(max(cut[k], cut[k - 1]), n_tiles - (8 - k) * cap), cut[k - 1] + cap);
+        }
+        __syncthreads();
+        lo = cut[blockIdx.x]; hi = cut[blockIdx.x + 1];
+    }
+    const int n = max(hi - lo, 0);
+    const int slot0 = blockIdx.x * slots;
     for (int i = threadIdx.x; i < n; i += blockDim.x) w[i] = weight[lo + i];
-    for (int t = threadIdx.x; t < per_xcd + splits; t += blockDim.x) order[slot0 + t] = -1;
+    for (int t = threadIdx.x; t < slots; t += blockDim.x) order[slot0 + t] = -1;
     __syncthreads();
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
         const int wi = w[i];
@@ -477,13 +579,17 @@ __global__ void __launch_bounds__(32) rank_deal_table_kernel(uint16_t *__restric
 }
 
 // ---- main kernel ---------------------------------------------------------------------------
-template <int PZ, int PY, int PX, int TZ, int TY, int TX, bool P1>
+// DZ (round 12): the tile's thickness in z is the run-time `tz_step` <= TZ -- TZ then only sizes accs, act_bits and
+// uvalid_bits; the tile origin is tz_i * tz_step and the kernel's ragged-tile handling does the rest.  !DZ:
+// tz_step is TZ (the launches that do not choose their thickness keep their code).
+template <int PZ, int PY, int PX, int TZ, int TY, int TX, bool P1, bool DZ = false>
 __global__ void __launch_bounds__(64 * RW_WAVES, PPP_RW_MINWAVES(PX))
     rank_wg_kernel(const float *__restrict__ S, const uint32_t *__restrict__ M,
                    const uint32_t *__restrict__ info, const uint8_t *__restrict__ valid,
                    float *__restrict__ score, const ppp_box sb, const Geo G, const int tiles_y,
                    const int tiles_x, const int n_tiles, const int *__restrict__ any_e,
-                   const int32_t *__restrict__ order, const int y_major, const uint16_t *__restrict__ dealT
+                   const int32_t *__restrict__ order, const int y_major, const uint16_t *__restrict__ dealT,
+                   const int tz_step
 #ifdef PPP_RW_STAMPS
                    , uint32_t *__restrict__ stamps
 #endif
@@ -532,8 +638,9 @@ __global__ void __launch_bounds__(64 * RW_WAVES, PPP_RW_MINWAVES(PX))
     if (bid >= n_tiles) return;
     int tx_i, ty_i, tz_i;
     rw_tile_decode(bid, n_tiles, tiles_y, tiles_x, y_major, tz_i, ty_i, tx_i);
-    const int c0z = sb.z0 + tz_i * TZ, c0y = sb.y0 + ty_i * TY + half_hi * (TY / 2), c0x = sb.x0 + tx_i * TX;
-    const int tz = min(TZ, sb.z1 - c0z), ty = min(halved ? TY / 2 : TY, sb.y1 - c0y), tx = min(TX, sb.x1 - c0x);
+    const int tzs = DZ ? min(tz_step, TZ) : TZ;
+    const int c0z = sb.z0 + tz_i * tzs, c0y = sb.y0 + ty_i * TY + half_hi * (TY / 2), c0x = sb.x0 + tx_i * TX;
+    const int tz = min(tzs, sb.z1 - c0z), ty = min(halved ? TY / 2 : TY, sb.y1 - c0y), tx = min(TX, sb.x1 - c0x);
     if (tz <= 0 || ty <= 0 || tx <= 0) return;
 
     auto sb_index = [&](int lz, int ly, int lx) -> long long {
@@ -548,8 +655,9 @@ __global__ void __launch_bounds__(64 * RW_WAVES, PPP_RW_MINWAVES(PX))
     }
     if (tid == 0) any_act = 0;
     __syncthreads();
-    static_assert(NT % 64 == 0, "tile size must be a multiple of the wave size");
-    for (int cl = tid; cl < NT; cl += NTHR) {
+    static_assert(NT % 64 == 0 && (TY * TX) % 64 == 0, "tile size must be a multiple of the wave size");
+    const int nt_used = DZ ? tz * TY * TX : NT;      // (a multiple of 64 either way)
+    for (int cl = tid; cl < nt_used; cl += NTHR) {
         const int lx = cl % TX, ly = (cl / TX) % TY, lz = cl / (TX * TY);
         uint32_t v = 0;
         if (lz < tz && ly < ty && lx < tx) v = info[sb_index(lz, ly, lx)];
@@ -857,7 +965,7 @@ __global__ void __launch_bounds__(64 * RW_WAVES, PPP_RW_MINWAVES(PX))
         uk = uk_next;
     }
     // ---- scores of the tile
-    for (int cl = tid; cl < NT; cl += NTHR) {
+    for (int cl = tid; cl < nt_used; cl += NTHR) {
         const int lx = cl % TX, ly = (cl / TX) % TY, lz = cl / (TX * TY);
         if (lz < tz && ly < ty && lx < tx && ((act_bits[cl >> 5] >> (cl & 31)) & 1u)) {
             const unsigned fg_cnt = info[sb_index(lz, ly, lx)] & 0x7FFFFFFFu;
@@ -931,14 +1039,17 @@ static int rw_choose_splits(int tiles_per_xcd, int slots_per_xcd) {
     const int rem = tiles_per_xcd % slots_per_xcd;
     return 2 * rem <= slots_per_xcd ? rem : 0;
 }
-// workgroups of the 8 x 16 x 16 kernel a CU holds (registers and LDS; asked once per patch size)
-template <int P>
+// workgroups of the kernel that is launched a CU holds (registers and LDS; asked once per instantiation):
+// the 8 x 16 x 16 tile, or (FIT, 7^3 only) the tile of run-time thickness up to 16
+template <int P, bool FIT>
 static int rw_resident_per_cu() {
     static thread_local int memo = 0;
     if (memo == 0) {
         int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rank_wg_kernel<P, P, P, 8, 16, 16, false>, 64 * RW_WAVES, 0) != hipSuccess || nb < 1)
-            nb = PPP_RW_MINWAVES(P);
+        hipError_t e;
+        if constexpr (FIT) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rank_wg_kernel<P, P, P, 16, 16, 16, false, true>, 64 * RW_WAVES, 0);
+        else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rank_wg_kernel<P, P, P, 8, 16, 16, false>, 64 * RW_WAVES, 0);
+        if (e != hipSuccess || nb < 1) nb = PPP_RW_MINWAVES(P);
         memo = nb;
     }
     return memo;
@@ -952,6 +1063,103 @@ static int rw_cus_per_xcd() {
         memo = cus / 8;
     }
     return memo;
+}
+
+// ---- the plan of a launch (round 12) -----------------------------------------------------------
+// Which tile, how thick in z, how many tiles, splits and order slots per XCD, which kind of XCD ranges: a host
+// function of the score box, the patch size, the workgroups a CU holds and the CUs of an XCD -- all known when
+// the launch is made (ppp_rank_wg_plan asks it without launching).
+//   * The tile: 8 x 16 x 16 when that still gives every CU four workgroups (a row is then staged 4.5 times per
+//     centre at 9^3), else 8 x 8 x 16 (6 times).  9^3 with the z-run enumeration: 8 x 8 x 16 also at large boxes
+//     (a 112 x 176 x 176 launch: 256 ms against 265 ms for 8 x 16 x 16 -- and for a 16 x 8 x 16 tile, which has
+//     half of its items in conflict-free rows: profiles/r04_k_s2_tiles*.txt).  ppp_params.rank_tile is the
+//     caller's choice (which shape is faster depends on the box: profiles/r06_l_bench_ab_tiles.txt), and
+//     PPP_RANK_WG_TILE=8x8x16 | 8x16x16 | 16x8x16, a development aid, wins over both.
+//   * Splits: rw_choose_splits for the 8 x 16 x 16 tile chosen by the rule; PPP_RANK_WG_SPLIT=<tiles per XCD>
+//     overrides (0: whole tiles only), also with a forced tile shape.
+//   * Tile fit (7^3 only): a launch that the 8 x 16 x 16 tiling puts between one and two rounds per XCD takes the
+//     smallest z step in 8 .. 16 whose tiles all fit the resident slots -- one round, no tail, no splits, and
+//     (t + 6) / t instead of 14 / 8 rows staged per centre in z.  PPP_RANK_WG_TZ=<t> forces the z step (tile
+//     t x 16 x 16, 7^3 only; it wins over the tile switches).
+//   * XCD ranges: by tile count, or of equal weight (rank_tile_order_kernel) -- PPP_RANK_WG_XCD=count | weight.
+struct RwPlan {
+    int TZ, TY, TX;            // the instantiation's tile
+    int tz_step;               // thickness of a tile in z (= TZ unless `fit`)
+    bool fit;                  // the instantiation with a run-time z step
+    int tiles_z, tiles_y, tiles_x;
+    long long n_tiles;
+    int per_xcd, splits, slots;   // slots: an XCD's part of the order array = grid / 8
+    bool ordered, by_weight;
+};
+static int rw_env_int(EnvSwitch &sw, int none) {
+    const char *e = sw.get();
+    return (e && e[0] >= '0' && e[0] <= '9') ? atoi(e) : none;
+}
+// resident / resident_fit: workgroups per CU of the 8 x 16 x 16 and of the run-time-thickness instantiation
+static RwPlan rw_plan(const ppp_box &sb, const Geo &G, int resident, int resident_fit, int cus_per_xcd) {
+    const int sX = sb.x1 - sb.x0, sY = sb.y1 - sb.y0, sZ = sb.z1 - sb.z0;
+    RwPlan p{};
+    const long long big_tiles = (long long)((sZ + 7) / 8) * ((sY + 15) / 16) * ((sX + 15) / 16);
+    bool big = big_tiles >= 4 * 256;
+    static EnvSwitch tile_sw("PPP_RANK_WG_TILE");
+    if (const char *e = tile_sw.get()) big = strcmp(e, "8x16x16") == 0 ? true : (strcmp(e, "8x8x16") == 0 ? false : big);
+    if (G.px == 9 && PPP_RW_ZRUNS(9) && !tile_sw.get()) big = false;
+    bool tall = tile_sw.get() && strcmp(tile_sw.get(), "16x8x16") == 0;
+    if (G.rank_tile && !tile_sw.get()) { big = G.rank_tile == 2; tall = G.rank_tile == 3; }
+    const bool by_rule = big && !tall && !tile_sw.get() && !G.rank_tile;
+    p.TZ = tall ? 16 : 8; p.TY = tall ? 8 : (big ? 16 : 8); p.TX = 16;
+    p.tz_step = p.TZ;
+    static EnvSwitch order_sw("PPP_RANK_ORDER");
+    static EnvSwitch split_sw("PPP_RANK_WG_SPLIT");
+    static EnvSwitch tz_sw("PPP_RANK_WG_TZ");
+    static EnvSwitch xcd_sw("PPP_RANK_WG_XCD");
+    const int split_env = rw_env_int(split_sw, -1);
+    const int tz_env = G.px == 7 ? rw_env_int(tz_sw, 0) : 0;
+    const int slots_res = resident * cus_per_xcd, slots_fit = resident_fit * cus_per_xcd;
+    auto tiles_of = [&](int t, int ty) { return (long long)((sZ + t - 1) / t) * ((sY + ty - 1) / ty) * ((sX + 15) / 16); };
+    if (tz_env > 0) {
+        p.fit = true; p.TZ = 16; p.TY = 16; p.TX = 16;
+        p.tz_step = tz_env < 16 ? tz_env : 16;
+    } else if (by_rule && G.px == 7 && split_env < 0) {
+        const long long per0 = (tiles_of(8, 16) + 7) / 8;
+        if (slots_res > 0 && per0 > slots_res && per0 < 2LL * slots_res)
+            for (int t = 9; t <= 16; ++t)
+                if ((tiles_of(t, 16) + 7) / 8 <= slots_fit) { p.fit = true; p.TZ = 16; p.tz_step = t; break; }
+    }
+    p.tiles_z = (sZ + p.tz_step - 1) / p.tz_step; p.tiles_y = (sY + p.TY - 1) / p.TY; p.tiles_x = (sX + p.TX - 1) / p.TX;
+    p.n_tiles = (long long)p.tiles_z * p.tiles_y * p.tiles_x;
+    p.per_xcd = (int)((p.n_tiles + 7) / 8);
+    // heavy tiles first (PPP_RANK_ORDER=0: spatial order)
+    p.ordered = !(p.n_tiles > RW_ORDER_MAX || (order_sw.get() && order_sw.get()[0] == '0'));
+    p.slots = p.per_xcd;
+    if (p.ordered) {
+        if (split_env >= 0) p.splits = split_env;
+        else if (by_rule && !p.fit) p.splits = rw_choose_splits(p.per_xcd, slots_res);
+        p.splits = p.splits < p.per_xcd ? p.splits : p.per_xcd;
+        if (8LL * (p.per_xcd + p.splits) > RW_ORDER_MAX) p.splits = RW_ORDER_MAX / 8 - p.per_xcd;
+        // ranges of equal weight: where the rule fitted the tiles to one round (the spare slots are what such
+        // ranges need), or by the switch; a range may grow by a quarter beyond per_xcd (clamped in the kernel)
+        p.by_weight = p.fit && tz_env == 0;
+        if (const char *e = xcd_sw.get()) p.by_weight = strcmp(e, "weight") == 0 ? true : (strcmp(e, "count") == 0 ? false : p.by_weight);
+        p.slots = p.per_xcd + p.splits;
+        if (p.by_weight) {
+            p.slots += (p.per_xcd + 3) / 4;
+            if (8LL * p.slots > RW_ORDER_MAX) p.slots = RW_ORDER_MAX / 8;
+        }
+    }
+    return p;
+}
+static RwPlan rw_plan_device(const ppp_box &sb, const Geo &G) {
+    const int res = G.px == 5 ? rw_resident_per_cu<5, false>() : (G.px == 7 ? rw_resident_per_cu<7, false>() : rw_resident_per_cu<9, false>());
+    return rw_plan(sb, G, res, G.px == 7 ? rw_resident_per_cu<7, true>() : res, rw_cus_per_xcd());
+}
+// out: tile z, y, x; z step; tiles; splits per XCD; slots per XCD; 1 = ranges of equal weight.
+// resident_per_cu / cus_per_xcd <= 0: ask the device
+void rank_wg_plan(const ppp_box &sb, const Geo &G, int resident_per_cu, int cus_per_xcd, int32_t out[8]) {
+    const RwPlan p = (resident_per_cu > 0 && cus_per_xcd > 0) ? rw_plan(sb, G, resident_per_cu, resident_per_cu, cus_per_xcd)
+                                                              : rw_plan_device(sb, G);
+    out[0] = p.TZ; out[1] = p.TY; out[2] = p.TX; out[3] = p.tz_step;
+    out[4] = (int32_t)p.n_tiles; out[5] = p.splits; out[6] = p.slots; out[7] = p.by_weight ? 1 : 0;
 }
 
 template <typename T>
@@ -975,49 +1183,30 @@ static hipError_t launch_rwg(const T *pred, const float *S, const uint8_t *ov, f
     static EnvSwitch p1_sw("PPP_RANK_P1");
     const bool p1 = G.bg_lt >= G.th_gt && p1_sw.get() && p1_sw.get()[0] == '1';
     note_rank_kernel(p1 ? "rank_wg_kernel<p1>" : "rank_wg_kernel");
+    // the pre-pass with the cubic window compiled in (PPP_RANK_PRE_CUBE=0: the run-time loop)
+    static EnvSwitch cube_sw("PPP_RANK_PRE_CUBE");
+    const int pre_p = (cube_sw.get() && cube_sw.get()[0] == '0') ? 0 : G.px;
+    const dim3 pre_grid((unsigned)((sbV + 255) / 256));
+#define PPP_RW_PRE(KERNEL_, ...)                                                                            \
+    do {                                                                                                    \
+        if (pre_p == 5) KERNEL_<T, 5><<<pre_grid, dim3(256), 0, s>>>(__VA_ARGS__);                          \
+        else if (pre_p == 7) KERNEL_<T, 7><<<pre_grid, dim3(256), 0, s>>>(__VA_ARGS__);                     \
+        else if (pre_p == 9) KERNEL_<T, 9><<<pre_grid, dim3(256), 0, s>>>(__VA_ARGS__);                     \
+        else KERNEL_<T, 0><<<pre_grid, dim3(256), 0, s>>>(__VA_ARGS__);                                     \
+    } while (0)
     if (p1) {
         hipError_t em = hipMemsetAsync(any_e, 0, 4, s);
         if (em != hipSuccess) return em;
-        rank_masks_p1_kernel<T><<<dim3((unsigned)((sbV + 255) / 256)), dim3(256), 0, s>>>(pred, ov, sb, M, info, any_e,
-                                                                                          score, G);
+        PPP_RW_PRE(rank_masks_p1_kernel, pred, ov, valid, sb, M, info, any_e, score, G);
     }
-    // Tile of centres per workgroup: 8 x 16 x 16 when that still gives every CU four workgroups
-    // (a row is then staged 4.5 times per centre at 9^3), else 8 x 8 x 16 (6 times).
-    // PPP_RANK_WG_TILE=8x8x16 | 8x16x16 overrides.
-    const long long big_tiles = (long long)((sZ + 7) / 8) * ((sY + 15) / 16) * ((sX + 15) / 16);
-    bool big = big_tiles >= 4 * 256;
-    static EnvSwitch tile_sw("PPP_RANK_WG_TILE");
-    if (const char *e = tile_sw.get()) big = strcmp(e, "8x16x16") == 0 ? true : (strcmp(e, "8x8x16") == 0 ? false : big);
-    // 9^3 with the z-run enumeration: 8 x 8 x 16 also at large boxes (a 112 x 176 x 176 launch,
-    // the size of the 512^3 tiles: 256 ms against 265 ms for 8 x 16 x 16 -- and for a 16 x 8 x 16 tile,
-    // which has half of its items in conflict-free rows: profiles/r04_k_s2_tiles*.txt)
-    if (G.px == 9 && PPP_RW_ZRUNS(9) && !tile_sw.get()) big = false;
-    bool tall = tile_sw.get() && strcmp(tile_sw.get(), "16x8x16") == 0;
-    // the caller's choice (ppp_params.rank_tile; the environment switch, a development aid, wins): which
-    // shape is faster depends on the box -- 8 x 8 x 16 by 3 % where the ranking kernel runs at 161 ms per
-    // 2 048-tile launch, 16 x 8 x 16 by 12 % where it runs at 215 ms (profiles/r06_l_bench_ab_tiles.txt)
-    if (G.rank_tile && !tile_sw.get()) { big = G.rank_tile == 2; tall = G.rank_tile == 3; }
-    const int TZ = tall ? 16 : 8, TY = tall ? 8 : (big ? 16 : 8), TX = 16;
-    const int tiles_z = (sZ + TZ - 1) / TZ, tiles_y = (sY + TY - 1) / TY, tiles_x = (sX + TX - 1) / TX;
-    const long long n_tiles = (long long)tiles_z * tiles_y * tiles_x;
-    const int per_xcd = (int)((n_tiles + 7) / 8);
-    // heavy tiles first (PPP_RANK_ORDER=0: spatial order)
-    static EnvSwitch order_sw("PPP_RANK_ORDER");
-    if (n_tiles > RW_ORDER_MAX || (order_sw.get() && order_sw.get()[0] == '0')) order = nullptr;
-    // 8 x 16 x 16 tiles by the rule above: the lightest tiles of every XCD's range are split in two so that the
-    // launch's last round runs halves side by side instead of a few whole tiles (rw_choose_splits).
-    // PPP_RANK_WG_SPLIT=<tiles per XCD> overrides (0: whole tiles only), also with a forced tile shape.
-    static EnvSwitch split_sw("PPP_RANK_WG_SPLIT");
-    int splits = 0;
-    if (order) {
-        if (split_sw.get() && split_sw.get()[0] >= '0' && split_sw.get()[0] <= '9') splits = atoi(split_sw.get());
-        else if (big && !tall && !tile_sw.get() && !G.rank_tile)
-            splits = rw_choose_splits(per_xcd, rw_cus_per_xcd() * (G.px == 5 ? rw_resident_per_cu<5>() : (G.px == 7 ? rw_resident_per_cu<7>() : rw_resident_per_cu<9>())));
-        splits = splits < per_xcd ? splits : per_xcd;
-        if (8LL * (per_xcd + splits) > RW_ORDER_MAX) splits = RW_ORDER_MAX / 8 - per_xcd;
-    }
-    const long long n_blocks = 8LL * (per_xcd + splits);
+    const RwPlan plan = rw_plan_device(sb, G);
+    const bool tall = plan.TZ == 16 && !plan.fit, big = plan.TY == 16, fit = plan.fit;
+    const int tiles_y = plan.tiles_y, tiles_x = plan.tiles_x, per_xcd = plan.per_xcd, splits = plan.splits, tz_step = plan.tz_step;
+    const long long n_tiles = plan.n_tiles;
+    if (!plan.ordered) order = nullptr;
+    const long long n_blocks = 8LL * plan.slots;
     PPP_GRID_CHECK(n_blocks, 64 * RW_WAVES);
+    static EnvSwitch order_sw("PPP_RANK_ORDER");
     const bool by_centres = order_sw.get() && order_sw.get()[0] == 'c';
     static EnvSwitch major_sw("PPP_RANK_TILE_MAJOR");
     const int y_major = (major_sw.get() && major_sw.get()[0] == 'z') ? 0 : 1;
@@ -1029,19 +1218,19 @@ static hipError_t launch_rwg(const T *pred, const float *S, const uint8_t *ov, f
 #else
 #define PPP_RW_STAMP_ARG
 #endif
-#define PPP_RW_LAUNCH1(A_, D_, E_, F_, P1_)                                                                 \
-    rank_wg_kernel<A_, A_, A_, D_, E_, F_, P1_><<<dim3((unsigned)n_blocks), dim3(64 * RW_WAVES), dyn_lds, s>>>( \
-        S, M, info, valid, score, sb, G, tiles_y, tiles_x, (int)n_tiles, p1 ? any_e : nullptr, order, y_major, dealT PPP_RW_STAMP_ARG)
-#define PPP_RW_LAUNCH(A_, D_, E_, F_)                                                                       \
+#define PPP_RW_LAUNCH1(A_, D_, E_, F_, P1_, DZ_)                                                            \
+    rank_wg_kernel<A_, A_, A_, D_, E_, F_, P1_, DZ_><<<dim3((unsigned)n_blocks), dim3(64 * RW_WAVES), dyn_lds, s>>>( \
+        S, M, info, valid, score, sb, G, tiles_y, tiles_x, (int)n_tiles, p1 ? any_e : nullptr, order, y_major, dealT, tz_step PPP_RW_STAMP_ARG)
+#define PPP_RW_LAUNCH(A_, D_, E_, F_, DZ_)                                                                  \
     do {                                                                                                    \
-        if (p1 && pass == 0) PPP_RW_LAUNCH1(A_, D_, E_, F_, true);                                          \
-        else PPP_RW_LAUNCH1(A_, D_, E_, F_, false);                                                         \
+        if (p1 && pass == 0) PPP_RW_LAUNCH1(A_, D_, E_, F_, true, DZ_);                                     \
+        else PPP_RW_LAUNCH1(A_, D_, E_, F_, false, DZ_);                                                    \
     } while (0)
 #define PPP_RW_CASE(P)                                                                                      \
     case P:                                                                                                 \
-        if (tall) PPP_RW_LAUNCH(P, 16, 8, 16);                                                              \
-        else if (big) PPP_RW_LAUNCH(P, 8, 16, 16);                                                          \
-        else PPP_RW_LAUNCH(P, 8, 8, 16);                                                                    \
+        if (tall) PPP_RW_LAUNCH(P, 16, 8, 16, false);                                                       \
+        else if (big) PPP_RW_LAUNCH(P, 8, 16, 16, false);                                                   \
+        else PPP_RW_LAUNCH(P, 8, 8, 16, false);                                                             \
         break;
     // pass 0: the one-bit form (when possible); then the two-bit pre-pass and kernel -- both return
     // at once unless the one-bit pre-pass found a partner that equals the threshold
@@ -1049,17 +1238,21 @@ static hipError_t launch_rwg(const T *pred, const float *S, const uint8_t *ov, f
     if (PPP_RW_BANKDEAL(7) && G.px == 7)
         rank_deal_table_kernel<7><<<dim3(7 * 7 * 7), dim3(32), 0, s>>>(dealT, 2 * 7 - 1, (2 * 7 - 1) * (2 * 7 - 1));
     for (int pass = p1 ? 0 : 1; pass < 2; ++pass) {
-        if (pass == 1)
-            rank_masks_il_kernel<T><<<dim3((unsigned)((sbV + 255) / 256)), dim3(256), 0, s>>>(pred, ov, sb, M, info, score,
-                                                                                              p1 ? any_e : nullptr, G);
+        if (pass == 1) PPP_RW_PRE(rank_masks_il_kernel, pred, ov, valid, sb, M, info, score, p1 ? any_e : nullptr, G);
         if (order && pass == (p1 ? 0 : 1)) {      // (`info` is the same from either pre-pass)
-            rank_tile_weight_kernel<<<dim3((unsigned)n_tiles), dim3(256), 0, s>>>(info, valid, sb, TZ, TY, TX, tiles_y, tiles_x,
+            rank_tile_weight_kernel<<<dim3((unsigned)n_tiles), dim3(256), 0, s>>>(info, valid, sb, tz_step, plan.TY, plan.TX, tiles_y, tiles_x,
                                                                                   by_centres ? 1 : 0, y_major, weight, G);
-            rank_tile_order_kernel<<<dim3(8), dim3(256), 0, s>>>(weight, (int)n_tiles, per_xcd, splits, order);
+            rank_tile_order_kernel<<<dim3(8), dim3(256), 0, s>>>(weight, (int)n_tiles, per_xcd, splits, plan.slots,
+                                                                 plan.by_weight ? 1 : 0, order);
         }
 #ifdef PPP_RW_STAMPS
         (void)hipMemsetAsync(weight, 0, (size_t)RW_ORDER_MAX * 4, s);      // (the weights are spent: room for the stamps)
 #endif
+        if (fit) {
+            // (the tile of run-time thickness: built for 7^3 alone, the only size the plan gives it to)
+            if (G.px != 7) return hipErrorNotSupported;
+            PPP_RW_LAUNCH(7, 16, 16, 16, true);
+        } else
         switch (G.px) {
             PPP_RW_CASE(5)
             PPP_RW_CASE(7)
@@ -1072,6 +1265,7 @@ static hipError_t launch_rwg(const T *pred, const float *S, const uint8_t *ov, f
 #undef PPP_RW_LAUNCH1
 #undef PPP_RW_STAMP_ARG
 #undef PPP_RW_CASE
+#undef PPP_RW_PRE
     return hipGetLastError();
 }
 
