@@ -22,8 +22,8 @@
 // round is a coalesced sweep over that volume: no lists, no compaction, no atomics on the data
 // path.  A patch is only recounted when a patch selected in the previous round overlaps it
 // (the selecting wave marks the (2p-1)^3 box of centres it can affect in a byte volume), the
-// recount stops at the first window row that settles "more than pixTh", and the host only
-// synchronises once per batch of rounds.
+// recount is one load stage for a group of lanes, and the host only synchronises once per batch
+// of rounds.
 //
 // The sweeps at volumes that fit the caches (140^3, 7^3: 240 cover + 48 thinning rounds per step).
 // profiles/r07_a_*_kernel_stats.txt has a cover round at 31 + 25 + 17 = 73 us and a thinning round at
@@ -35,13 +35,32 @@
 //   count       670 workgroups of 1024 threads, 512 resident -> 512 threads x 8 voxels, all resident, eight
 //               loads in flight per pass.  ONE sweep, two instantiations: cover_count_kernel and
 //               thin_count_kernel load and classify their voxels (ranks and witnesses / keys), then share the
-//               compaction (compact_marked) and the window recount (window_hits: the cover's stops early,
-//               records a witness and preloads a plane of rows; the thinning's counts in full);
+//               compaction (compact_marked) and the window recount (group_hits);
 //   select      one voxel per thread, 10 719 workgroups, each the chain own value -> own slice of the
-//               filtered volume -> eight voxels per thread, both loads of all eight issued together, the
-//               other slices asked nearest first for all of a thread's candidates at once (ready_voxels).
-//               ONE body (select_body) over what the algorithm makes of a key (CoverPick, ThinPick):
-//               cover_select_kernel, cover_select_marked_kernel and thin_select_kernel instantiate it.
+//               filtered volume -> eight voxels per thread, both loads of all eight issued together
+//               (ready_voxels).  ONE body (select_body) over what the algorithm makes of a key (CoverPick,
+//               ThinPick): cover_select_kernel, cover_select_marked_kernel and thin_select_kernel instantiate it.
+// After that (profiles/r12_a_*_kernel_stats.txt: count 27.5 / 21 us, select 17.2 / 25 us per launch, cover /
+// thinning) the time left in count and select was again load latency paid in series inside a launch:
+//   recount     a thread walked its patch's window plane by plane, each plane behind the last one's sum and the
+//               next word of the bit string (up to 12 dependent stages at 7^3; the thinning row by row: 49), after
+//               reloading the rank -> a GROUP of lanes per listed patch strides over the window rows, every load
+//               of a patch in flight at once, sum and witness by shuffles, the table row carried in the list
+//               (group_hits, compact_marked);
+//   classify    the dirty bytes were read one by one, each behind the store that clears the one before; the
+//               addresses of the witness words cost some 1 800 instructions a thread, most of them 64-bit
+//               divisions -> the bytes asked for with the ranks, rows by steps (cover_count_kernel);
+//   other slices  up to 2 (pz - 1) = 12 passes over the slices, each behind a wave-wide ballot -> the wave's few
+//               candidates are dealt to groups of 16 lanes, one slice a lane, one stage (ready_voxels);
+//   winners     one after another, each the chain key -> bit rows and mask rows -> atomics -> keys from the
+//               registers, the rows of two winners asked for together, before the first atomic (select_body).
+// profiles/r13_a_*: count 22.6 / 12.8 us, select 10.3 / 16.4 us, the step 173.6 -> 169.4 ms (medians of three).
+// Measured and dropped (same profiles): the recount in two stages -- the first plane of rows, the others only
+// where that does not settle "more than pix_th", second words only where the bits reach them -- asks for a
+// seventh of the words for a surviving patch, and was SLOWER: cover 12.8 ms per step against 11.3 (parent
+// 14.1): the recount's time is the number of its dependent stages, not its loads.  Four winners of a wave
+// together: 78 / 88 VGPRs (two: 57 / 65), the 1 340 select workgroups no longer resident at once.  The witness
+// loaded with the rank (2 more bytes per voxel where the sweep is bandwidth-bound, 512^3): not measured.
 // The round keeps its three launches and every step leaves the state it left before (tests/test_shard_steps.py
 // compares it step by step, tests/test_cover_sweeps.py the filter alone and the number of rounds):
 //   * the xy minimum is NOT fused into select -- a workgroup would read a neighbour's rank that another
@@ -95,6 +114,13 @@ static inline bool witness_ok(const Geo &G) { return G.pz * G.py < 2047 && G.px 
 __host__ __device__ __forceinline__ int row_words(const Geo &G) { return (G.X + 31) / 32 + 1; }
 
 __device__ __forceinline__ void centre_of(const Geo &G, long long c, int &cz, int &cy, int &cx) {
+    if (G.V < (1ll << 31)) {                                    // (32-bit divisions where the volume allows them)
+        const int ci = (int)c, plane = G.X * G.Y;
+        cz = ci / plane;
+        cy = (ci - cz * plane) / G.X;
+        cx = ci - cz * plane - cy * G.X;
+        return;
+    }
     cx = (int)(c % G.X);
     cy = (int)((c / G.X) % G.Y);
     cz = (int)(c / ((long long)G.X * G.Y));
@@ -155,6 +181,9 @@ __global__ void __launch_bounds__(256)
 // and a thread has eight loads in flight per pass instead of four)
 static constexpr int COUNT_THREADS = 512;
 static constexpr int COUNT_VPT = 8;     // voxels per thread of the count sweeps
+// (at least 6 waves a SIMD = three workgroups a CU: with more than 80 VGPRs the 670 workgroups of 140^3 are not
+// resident at once; the recount's 32 loads in flight would take 89)
+#define PPP_COUNT_BOUNDS __launch_bounds__(COUNT_THREADS, 6)
 static inline dim3 count_grid(const Geo &G) {
     return dim3((unsigned)((G.V + COUNT_THREADS * COUNT_VPT - 1) / (COUNT_THREADS * COUNT_VPT)));
 }
@@ -163,8 +192,11 @@ static inline dim3 count_grid(const Geo &G) {
 // patch of the rank's own; marked: its neighbourhood changed): the workgroup's voxels that are both are
 // compacted into s_list (offsets from the block's first voxel; *s_n was zeroed before a barrier).  Returns
 // their number, after a barrier.
+// (row[j]: the voxel's row of the bit / state tables, carried with the list entry in s_row -- the recount
+// starts from LDS, not from another load of the rank before the bits can be asked for)
 __device__ __forceinline__ int compact_marked(const bool (&alive)[COUNT_VPT], const bool (&marked)[COUNT_VPT],
-                                              uint16_t *s_list, int *s_n, int32_t *__restrict__ n_alive) {
+                                              const int (&row)[COUNT_VPT], uint16_t *s_list, int32_t *s_row,
+                                              int *s_n, int32_t *__restrict__ n_alive) {
     bool rest = false;
 #pragma unroll
     for (int j = 0; j < COUNT_VPT; ++j) {
@@ -174,8 +206,11 @@ __device__ __forceinline__ int compact_marked(const bool (&alive)[COUNT_VPT], co
             int base = 0;
             if (lane == 0) base = atomicAdd(s_n, __popcll(m));
             base = __shfl(base, 0);
-            if (alive[j] && marked[j])
-                s_list[base + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)(j * COUNT_THREADS + threadIdx.x);
+            if (alive[j] && marked[j]) {
+                const int at = base + __popcll(m & ((1ull << lane) - 1ull));
+                s_list[at] = (uint16_t)(j * COUNT_THREADS + threadIdx.x);
+                s_row[at] = row[j];
+            }
         }
         rest = rest || (alive[j] && !marked[j]);
     }
@@ -187,67 +222,85 @@ __device__ __forceinline__ int compact_marked(const bool (&alive)[COUNT_VPT], co
     return *s_n;
 }
 
-// Second phase: |mask bits & patch bits| over the pz * py rows of the window of the patch centred at voxel v
-// (b: its bit string, px bits per row), with a sliding 64-bit window over the bit string and the mask row
-// read as two words where the window straddles one.  What the cover needs on top, at compile time:
-//   STOP_EARLY  only "more than pix_th" matters: stop after the first plane of rows that settles it (with
-//               pix_th = 0 a surviving patch is usually done after the first plane);
-//   WITNESS     wit = the first covered voxel found, window row << 5 | x offset (WIT_NONE: none);
-//   PRELOAD     py <= 9: the mask words of a whole plane are loaded before any of them is used.
-template <bool STOP_EARLY, bool WITNESS, bool PRELOAD>
-__device__ __forceinline__ int window_hits(const uint32_t *__restrict__ mbits, const uint32_t *__restrict__ b,
-                                           const long long v, const int pix_th, unsigned &wit, const Geo &G) {
-    const int words = (G.C + 31) / 32, XW = row_words(G);
+// n (<= 32) bits from bit `sh` (< 32) of the 64-bit string hi:lo.  (hi may be any readable word where the
+// bits do not reach it: what it shifts in lies at or above bit 32 - sh >= n)
+__device__ __forceinline__ uint32_t window_of(uint32_t lo, uint32_t hi, int sh, int n) {
+    const uint32_t v = (uint32_t)((((unsigned long long)hi << 32) | lo) >> sh);
+    return n >= 32 ? v : (v & ((1u << n) - 1u));
+}
+
+__device__ __forceinline__ uint32_t low_bits(int n) { return n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1u); }
+
+// Second phase: |mask bits & patch bits| over the R = pz * py rows of the window of the patch centred at voxel
+// v (b: its bit string, px bits per row), by a GROUP of gw lanes (a power of two, at most a wave; sub = the
+// lane's place in it).  Lane `sub` takes the rows sub, sub + gw, ...: it asks for the two mask words and the two
+// bit-string words of RECOUNT_ROWS rows at once -- every address follows from v and the row number alone,
+// so all loads of a patch are in flight together -- forms the rows' hits, and the group adds up by
+// shuffles.  Every lane of the group returns the full count; nothing stops early ("more than pix_th" is
+// decided from the sum: the same decision), a rejected patch costs what a surviving one does.
+//   WITNESS     wit = the first covered voxel in row order, window row << 5 | x offset: the minimum of the
+//               lanes' codes (WIT_NONE, "none", is the largest).
+// The sequential walk this replaces -- plane by plane, each plane behind the last one's sum and the next
+// word of the bit string, up to 12 dependent load stages at 7^3, 49 in the thinning -- was the count kernels'
+// time (profiles/r12_a_*_kernel_stats.txt: 27.5 and 21 us for sweeps whose bytes cost 5-8 us).
+// All lanes of a wave call this together (the shuffles); a group without a patch repeats another one's.
+static constexpr int RECOUNT_ROWS = 7;      // rows a lane has in flight (8 spills: the count kernels are held to 80 VGPRs)
+// lanes per listed patch: the fewest that leave a lane at most RECOUNT_ROWS rows (5^3: 4 lanes x 7 rows, 7^3: 8 x
+// 7, 64 patches per trip of a workgroup; 9^3: 16 x 6; 1 x 25 x 25: 4 x 7), a wave and several trips
+// beyond 448 rows
+__device__ __forceinline__ int recount_group(const Geo &G) {
+    int w = 1;
+    while (w < 64 && w * RECOUNT_ROWS < G.pz * G.py) w <<= 1;
+    return w;
+}
+template <bool WITNESS>
+__device__ __forceinline__ int group_hits(const uint32_t *__restrict__ mbits, const uint32_t *__restrict__ b,
+                                          const long long v, const int sub, const int gw, unsigned &wit,
+                                          const Geo &G) {
+    const int words = (G.C + 31) / 32, XW = row_words(G), R = G.pz * G.py;
     int cz, cy, cx;
     centre_of(G, v, cz, cy, cx);
     const int start = cx - G.rx, wi = start >> 5, sh = start & 31;
-    const bool two = sh + G.px > 32;
-    const uint32_t pmask = G.px >= 32 ? 0xFFFFFFFFu : ((1u << G.px) - 1u);
-    unsigned long long win = b[0] | ((unsigned long long)(words > 1 ? b[1] : 0u) << 32);
-    int have = 64, next = 2, hits = 0;
-    // (the witness stays a local until the end: carried through the rows in the caller's variable, the unrolled
-    // plane of the cover's count takes 81 registers instead of 71)
-    unsigned wloc = WIT_NONE;
-    auto add_row = [&](const unsigned long long mw, const int r) {
-        const uint32_t hm = (uint32_t)(mw >> sh) & (uint32_t)win & pmask;
-        const int rh = __popc(hm);
-        if (WITNESS && rh && wloc == WIT_NONE) wloc = ((unsigned)r << 5) | (unsigned)__builtin_ctz(hm);
-        hits += rh;
-        win >>= G.px;
-        have -= G.px;
-        if (have <= 32) {
-            win |= (unsigned long long)(next < words ? b[next] : 0u) << have;
-            ++next;
-            have += 32;
+    const uint32_t *m0 = mbits + ((long long)(cz - G.rz) * G.Y + (cy - G.ry)) * XW;
+    int hits = 0;
+    unsigned code = WIT_NONE;
+    const int step_z = gw / G.py, step_y = gw - step_z * G.py;  // (one division a trip: the rows after the first by steps)
+    for (int r0 = sub; r0 < R; r0 += gw * RECOUNT_ROWS) {
+        uint32_t ml[RECOUNT_ROWS], mh[RECOUNT_ROWS], bl[RECOUNT_ROWS], bh[RECOUNT_ROWS];
+        int dz = r0 / G.py, dy = r0 - dz * G.py;
+#pragma unroll
+        for (int i = 0; i < RECOUNT_ROWS; ++i) {
+            // (a row past the window reads the last one: clamped, no branch between the loads)
+            const bool in = r0 + i * gw < R;
+            const int bi = ((in ? r0 + i * gw : R - 1) * G.px) >> 5;
+            const uint32_t *row = m0 + ((long long)(in ? dz : G.pz - 1) * G.Y + (in ? dy : G.py - 1)) * XW;
+            ml[i] = row[wi];
+            mh[i] = row[min(wi + 1, XW - 1)];
+            bl[i] = b[bi];
+            bh[i] = b[min(bi + 1, words - 1)];
+            dz += step_z;
+            dy += step_y;
+            if (dy >= G.py) { dy -= G.py; ++dz; }
         }
-    };
-    constexpr int MAXPY = 9;
-    for (int dz = 0; dz < G.pz && !(STOP_EARLY && hits > pix_th); ++dz) {
-        const uint32_t *row = mbits + ((long long)(cz + dz - G.rz) * G.Y + (cy - G.ry)) * XW + wi;
-        if (PRELOAD && G.py <= MAXPY) {
-            uint32_t lo[MAXPY], hi[MAXPY];
 #pragma unroll
-            for (int dy = 0; dy < MAXPY; ++dy) {
-                const bool in_p = dy < G.py;
-                lo[dy] = in_p ? row[(long long)dy * XW] : 0u;
-                hi[dy] = (in_p && two) ? row[(long long)dy * XW + 1] : 0u;
-            }
-#pragma unroll
-            for (int dy = 0; dy < MAXPY; ++dy)
-                if (dy < G.py) add_row(lo[dy] | ((unsigned long long)hi[dy] << 32), dz * G.py + dy);
-        } else {
-            for (int dy = 0; dy < G.py; ++dy, row += XW) {
-                unsigned long long mw = row[0];
-                if (two) mw |= (unsigned long long)row[1] << 32;
-                add_row(mw, dz * G.py + dy);
+        for (int i = 0; i < RECOUNT_ROWS; ++i) {
+            const int r = r0 + i * gw;
+            if (r < R) {
+                const uint32_t hm = window_of(ml[i], mh[i], sh, G.px) & window_of(bl[i], bh[i], (r * G.px) & 31, G.px);
+                hits += __popc(hm);
+                if (WITNESS && hm) code = min(code, ((unsigned)r << 5) | (unsigned)__builtin_ctz(hm));
             }
         }
     }
-    wit = wloc;
+    for (int o = gw >> 1; o > 0; o >>= 1) {
+        hits += __shfl_xor(hits, o);
+        if (WITNESS) code = min(code, (unsigned)__shfl_xor((int)code, o));
+    }
+    wit = code;
     return hits;
 }
 
-__global__ void __launch_bounds__(COUNT_THREADS)
+__global__ void PPP_COUNT_BOUNDS
     cover_count_kernel(const uint32_t *__restrict__ mbits, const uint32_t *__restrict__ bits,
                        uint8_t *__restrict__ dirty, const int pix_th, int32_t *__restrict__ state,
                        int32_t *__restrict__ rank_vol, int32_t *__restrict__ n_alive,
@@ -257,7 +310,9 @@ __global__ void __launch_bounds__(COUNT_THREADS)
     // sweep is a chain of dependent loads per voxel -- rank, then witness, then one word of the mask --
     // and its time was their latency (1.17 ms for the 134 M voxels of 512^3 with one voxel per thread:
     // 0.8 TB/s); the loads of a thread's voxels are issued pass by pass, COUNT_VPT in flight each.
+    // (the list: 24 KB of LDS, so the four workgroups a CU can hold by threads still fit it)
     __shared__ uint16_t s_list[COUNT_THREADS * COUNT_VPT];
+    __shared__ int32_t s_row[COUNT_THREADS * COUNT_VPT];
     __shared__ int s_n;
     if (threadIdx.x == 0) s_n = 0;
     __syncthreads();
@@ -269,17 +324,33 @@ __global__ void __launch_bounds__(COUNT_THREADS)
         int kk[COUNT_VPT];
         bool alive[COUNT_VPT], marked[COUNT_VPT];
         unsigned wv[COUNT_VPT];
+        // (the dirty bytes are asked for with the ranks: read one by one where they are cleared, each load
+        // waited behind the store before it -- eight round trips in series in every pass with pix_th > 0)
+        uint8_t mark[COUNT_VPT];
 #pragma unroll
         for (int j = 0; j < COUNT_VPT; ++j) {
             vv[j] = v0 + j * COUNT_THREADS + threadIdx.x;
-            kk[j] = vv[j] < G.V ? rank_vol[vv[j]] : RANK_NONE;
+            kk[j] = rank_vol[min(vv[j], G.V - 1)];              // (clamped: no branch between the loads)
         }
+        if (!use_wit) {
+#pragma unroll
+            for (int j = 0; j < COUNT_VPT; ++j) mark[j] = dirty[min(vv[j], G.V - 1)];
+        }
+#pragma unroll
+        for (int j = 0; j < COUNT_VPT; ++j)
+            if (vv[j] >= G.V) kk[j] = RANK_NONE;
         // sharded: rank_vol holds GLOBAL ranks (also of the neighbour's patches in the halo);
         // only the own centres are worked on, through their local table index
         if (loc_vol) {
+            int loc[COUNT_VPT];
+#pragma unroll
+            for (int j = 0; j < COUNT_VPT; ++j) {
+                loc[j] = -1;
+                if (kk[j] != RANK_NONE) loc[j] = loc_vol[vv[j]];
+            }
 #pragma unroll
             for (int j = 0; j < COUNT_VPT; ++j)
-                if (kk[j] != RANK_NONE) { const int l = loc_vol[vv[j]]; kk[j] = l < 0 ? RANK_NONE : l; }
+                if (kk[j] != RANK_NONE) kk[j] = loc[j] < 0 ? RANK_NONE : loc[j];
         }
         // pix_th == 0 ("does the patch still cover ANY voxel"): a patch stays undecided as long as
         // its witness voxel is uncovered -- one bit of the running mask (16 MB at 512^3: cache
@@ -291,35 +362,56 @@ __global__ void __launch_bounds__(COUNT_THREADS)
             alive[j] = kk[j] != RANK_NONE;
             wv[j] = WIT_NONE;
             if (use_wit) { if (alive[j]) wv[j] = witness[vv[j]]; }
-            else { marked[j] = vv[j] < G.V && dirty[vv[j]] != 0; if (marked[j]) dirty[vv[j]] = 0; }
+            else { marked[j] = vv[j] < G.V && mark[j] != 0; if (marked[j]) dirty[vv[j]] = 0; }
         }
         if (use_wit) {
             uint32_t mw[COUNT_VPT];
             int xb[COUNT_VPT];
+            // (row and x of a thread's voxels by steps from its first voxel, the witness row split by a
+            // multiplication: written as vv / X, vv % X, wr / py and wr % py per voxel the addresses of the
+            // eight mask words were some 1 800 instructions, two thirds of them 64-bit divisions)
+            const long long vf = v0 + threadIdx.x;
+            long long vrow = G.V < (1ll << 31) ? (long long)((int)vf / G.X) : vf / G.X;
+            int vx = (int)(vf - vrow * G.X);
+            const int step_row = COUNT_THREADS / G.X, step_x = COUNT_THREADS - step_row * G.X;
+            const float inv_py = 1.0f / (float)G.py;
 #pragma unroll
             for (int j = 0; j < COUNT_VPT; ++j) {
                 mw[j] = 0u; xb[j] = 0;
                 if (alive[j] && wv[j] != WIT_NONE) {
                     const int wr = (int)(wv[j] >> 5), xo = (int)(wv[j] & 0x1Fu);
-                    const long long row = vv[j] / G.X + (long long)(wr / G.py - G.rz) * G.Y + (wr % G.py - G.ry);
-                    const int x = (int)(vv[j] % G.X) - G.rx + xo;
+                    // wr / py (wr < 2047): the float quotient is within one of it
+                    int wz = (int)((float)wr * inv_py), wy = wr - wz * G.py;
+                    if (wy < 0) { --wz; wy += G.py; }
+                    if (wy >= G.py) { ++wz; wy -= G.py; }
+                    const long long row = vrow + (long long)(wz - G.rz) * G.Y + (wy - G.ry);
+                    const int x = vx - G.rx + xo;
                     mw[j] = mbits[row * row_words(G) + (x >> 5)];
                     xb[j] = x & 31;
                 }
+                vrow += step_row;
+                vx += step_x;
+                if (vx >= G.X) { vx -= G.X; ++vrow; }
             }
 #pragma unroll
             for (int j = 0; j < COUNT_VPT; ++j) marked[j] = alive[j] && ((mw[j] >> xb[j]) & 1u) == 0u;
         }
-        n = compact_marked(alive, marked, s_list, &s_n, n_alive);
+        n = compact_marked(alive, marked, kk, s_list, s_row, &s_n, n_alive);
     }
-    for (int t = threadIdx.x; t < n; t += blockDim.x) {
-        const long long v = v0 + s_list[t];
-        int k = rank_vol[v];
-        if (loc_vol) k = loc_vol[v];
+    // the listed patches, a group of lanes each (group_hits); a wave's groups take neighbouring entries and
+    // every wave runs whole trips: a group past the end repeats the trip's first entry and writes nothing
+    const int gw = recount_group(G), per_wave = 64 / gw;
+    const int sub = threadIdx.x & (gw - 1), in_wave = (threadIdx.x & 63) / gw;
+    for (int base = (threadIdx.x >> 6) * per_wave; base < n; base += COUNT_THREADS / gw) {
+        const bool mine = base + in_wave < n;
+        const int e = mine ? base + in_wave : base;
+        const long long v = v0 + s_list[e];
+        const int k = s_row[e];
         // (bits_vox >= 0: the table has a row per VOXEL, its first row belongs to voxel bits_vox)
         const uint32_t *b = bits + (bits_vox >= 0 ? v - bits_vox : (long long)k) * ((G.C + 31) / 32);
         unsigned wit_new;
-        const int hits = window_hits<true, true, true>(mbits, b, v, pix_th, wit_new, G);
+        const int hits = group_hits<true>(mbits, b, v, sub, gw, wit_new, G);
+        if (!mine || sub != 0) continue;
         if (hits <= pix_th) {
             state[k] = 2;
             rank_vol[v] = RANK_NONE;
@@ -555,12 +647,32 @@ __device__ __forceinline__ T zmin_at(const T *__restrict__ xy, long long v, cons
 // Returns the voxels j for which it is, one bit each; mine[j] = the thread's own values.
 // The own value and the own slice of the filtered volume are loaded for all of a thread's voxels before
 // anything is tested (one thread per voxel was the dependent chain rank -> nbr_min in 10 719 workgroups of
-// 256 at 140^3: five generations, each two memory latencies long).  The other slices are asked nearest
-// first, all of a thread's remaining candidates together, and a wave stops as soon as every candidate lane
-// has met a smaller value -- on a dense volume a patch has a better ranked undecided neighbour in its own
-// slice in all but a few thousand cases per round, so a wave reads ONE slice instead of 2 pz - 1.
+// 256 at 140^3: five generations, each two memory latencies long).  On a dense volume a patch has a better
+// ranked undecided neighbour in its own slice in all but a few thousand cases per round, so most waves read
+// ONE slice instead of 2 pz - 1 and are done; the others ask for the remaining slices of their few
+// candidates in one stage (below).
 static constexpr int SELECT_VPT = 8;
+static constexpr int READY_LANES = 16, READY_SLOTS = 64 / READY_LANES;   // lanes per candidate, candidates per trip
+// winners of a wave handled together, window rows a lane each: 128 rows a trip (9^3 has 81).  (4 x 2 takes 78 /
+// 88 VGPRs -- the 1 340 workgroups of 140^3 are resident at once up to 80 -- and spills 80-110 SGPRs; 2 x 2: 57 / 65)
+static constexpr int SELECT_WINNERS = 2, SELECT_ROWS = 2;
 static inline dim3 select_grid(const Geo &G) { return dim3((unsigned)((G.V + 256 * SELECT_VPT - 1) / (256 * SELECT_VPT))); }
+// a[j] for a wave-uniform j, by masks: written as a chain of selects the compiler sees an indexed array and
+// moves it to LDS
+template <typename T>
+__device__ __forceinline__ T pick_voxel(const T (&a)[SELECT_VPT], const int j) {
+    T r = 0;
+#pragma unroll
+    for (int i = 0; i < SELECT_VPT; ++i) r |= a[i] & -(T)(j == i);
+    return r;
+}
+// lane src's value of v, wave-uniform
+__device__ __forceinline__ int32_t lane_value(const int32_t v, const int src) { return __builtin_amdgcn_readlane(v, src); }
+__device__ __forceinline__ long long lane_value(const long long v, const int src) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((unsigned long long)v >> 32), src);
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
 template <typename T>
 __device__ __forceinline__ unsigned ready_voxels(const T *own, const T *__restrict__ xy,
                                                  const long long first, T (&mine)[SELECT_VPT], const Geo &G) {
@@ -576,30 +688,49 @@ __device__ __forceinline__ unsigned ready_voxels(const T *own, const T *__restri
 #pragma unroll
     for (int j = 0; j < SELECT_VPT; ++j)
         if (first + j * 256 < G.V && mine[j] != NONE && !(here[j] < mine[j])) cand |= 1u << j;
-    if (__ballot(cand != 0u) == 0ull) return 0u;
+    if (__ballot(cand != 0u) == 0ull || G.pz == 1) return cand;
+    // The other slices.  The survivors of the own-slice test are few, so the wave deals them out, READY_SLOTS
+    // at a time, to groups of READY_LANES lanes: lane i of a group asks for slice -1, +1, -2, +2, ... number i of
+    // its candidate (a slice outside the volume, or a group without a candidate, reads a voxel of its own
+    // again: a select between addresses, not a branch around the load), the group takes the minimum by
+    // shuffles and the candidate's lane learns the outcome from a ballot.  One load stage for all slices of
+    // up to four candidates (pz <= 9), where the pass-by-pass loop this replaces paid up to 2 (pz - 1) = 12
+    // round trips in series, each behind a wave-wide ballot.
     const long long plane = (long long)G.X * G.Y;
-    const bool small = G.V < (1ll << 31);                         // (32-bit division where the volume allows it)
-    int z[SELECT_VPT];
+    const int lane = threadIdx.x & 63, slot = lane / READY_LANES, sub = lane % READY_LANES;
+    const long long wave_first = first - lane;
+    unsigned todo = cand;
+    for (;;) {
+        int srcs[READY_SLOTS] = {}, js[READY_SLOTS] = {}, n_slots = 0;   // (wave-uniform)
+        int my_src = -1, my_j = 0;                                // the group's candidate
+        T my_val = NONE;
 #pragma unroll
-    for (int j = 0; j < SELECT_VPT; ++j) {
-        const long long v = first + j * 256;
-        z[j] = !((cand >> j) & 1u) ? 0 : small ? (int)v / (int)plane : (int)(v / plane);
-    }
-    for (int i = 1; i <= 2 * (G.pz - 1); ++i) {
-        if (__ballot(cand != 0u) == 0ull) break;
-        const int d = (i & 1) ? -((i + 1) >> 1) : (i >> 1);            // -1, +1, -2, +2, ...
-        // (a voxel that does not ask reads its own slice again: a select between addresses, not a branch
-        // around the load, so the loads of a pass are in flight together)
-        T there[SELECT_VPT];
-        unsigned ask = 0;
-#pragma unroll
-        for (int j = 0; j < SELECT_VPT; ++j) {
-            if (((cand >> j) & 1u) && z[j] + d >= 0 && z[j] + d < G.Z) ask |= 1u << j;
-            there[j] = xy[((ask >> j) & 1u) ? first + j * 256 + (long long)d * plane : min(first + j * 256, G.V - 1)];
+        for (int s = 0; s < READY_SLOTS; ++s) {
+            const unsigned long long m = __ballot(todo != 0u);
+            if (m != 0ull) {
+                const int src = __builtin_ctzll(m);
+                const int j = __builtin_ctz((unsigned)__builtin_amdgcn_readlane((int)todo, src));
+                if (lane == src) todo &= todo - 1u;
+                const T val = lane_value(pick_voxel(mine, j), src);
+                if (slot == s) { my_src = src; my_j = j; my_val = val; }
+                srcs[s] = src; js[s] = j; n_slots = s + 1;
+            }
         }
+        if (n_slots == 0) break;
+        const long long vc = my_src >= 0 ? wave_first + my_src + my_j * 256 : min(first, G.V - 1);
+        const int z = G.V < (1ll << 31) ? (int)vc / (int)plane : (int)(vc / plane);   // (32-bit division where it can be)
+        T m = NONE;
+        for (int i = sub; i < 2 * (G.pz - 1); i += READY_LANES) {
+            const int d = (i & 1) ? (i >> 1) + 1 : -((i >> 1) + 1);
+            const bool ask = my_src >= 0 && z + d >= 0 && z + d < G.Z;
+            const T there = xy[ask ? vc + (long long)d * plane : vc];
+            if (ask) m = min(m, there);
+        }
+        for (int o = READY_LANES >> 1; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o));
+        const unsigned long long beaten = __ballot(sub == 0 && my_src >= 0 && m < my_val);
 #pragma unroll
-        for (int j = 0; j < SELECT_VPT; ++j)
-            if (((ask >> j) & 1u) && there[j] < mine[j]) cand &= ~(1u << j);
+        for (int s = 0; s < READY_SLOTS; ++s)
+            if (s < n_slots && ((beaten >> (s * READY_LANES)) & 1ull) && lane == srcs[s]) cand &= ~(1u << js[s]);
     }
     return cand;
 }
@@ -696,36 +827,99 @@ __device__ __forceinline__ void
         for (int j = 0; j < SELECT_VPT; ++j)
             if (((ready_bits >> j) & 1u) && loc_vol[first + j * 256] < 0) ready_bits &= ~(1u << j);
     }
-    const int words = (G.C + 31) / 32, XW = row_words(G);
-    for (int j = 0; j < SELECT_VPT; ++j) {
-        unsigned long long todo = __ballot((ready_bits >> j) & 1u);
-        while (todo) {
-            const int src = __builtin_ctzll(todo);
-            todo &= todo - 1;
-            const long long cc = first + j * 256 - lane + src;
-            const K key = key_vol[cc];                                // (every lane the same word)
-            const int kk = loc_vol ? loc_vol[cc] : P::index(key);     // local index
-            int cz, cy, cx;
-            centre_of(G, cc, cz, cy, cx);
-            const uint32_t *b = bits + pick.bits_row(cc, kk) * words;
-            const int start = cx - G.rx, sh = start & 31;
-            // window bits whose voxel is an interior x position
-            uint32_t xin = 0;
-            for (int i = 0; i < G.px; ++i)
-                if (start + i >= G.rx && start + i < G.X - G.rx) xin |= 1u << i;
-            int cleared = 0;
-            for (int r = lane; r < G.pz * G.py; r += 64) {
-                const int z = cz + r / G.py - G.rz, y = cy + r % G.py - G.ry;
-                uint32_t *row = mbits + ((long long)z * G.Y + y) * XW;
-                const uint32_t cl = bit_window(row, start, G.px, XW) & bit_window(b, r * G.px, G.px, words);
-                if (cl) {
-                    atomicAnd(row + (start >> 5), ~(cl << sh));
-                    if (sh && (cl >> (32 - sh))) atomicAnd(row + (start >> 5) + 1, ~(cl >> (32 - sh)));
-                    if (z + oz >= G.rz && z + oz < gZ - G.rz && y >= G.ry && y < G.Y - G.ry)
-                        cleared += __popc(cl & xin);
+    // The wave's winners, over all of its voxels, SELECT_WINNERS at a time: the key comes from the registers
+    // of the lane that holds it, and the mask rows and bit rows of ALL of them (lane per window row,
+    // SELECT_ROWS rows a lane) are asked for before the first atomic -- ready patches never share a voxel,
+    // so the bits a winner clears are the same whether its rows are read before or after another winner's
+    // atomics.  The cleared counts, the dirty boxes and the mark rows stay per winner.  (One winner after
+    // another, each the chain key -> bit rows and mask rows -> atomics, was a chain per winner.)
+    const int words = (G.C + 31) / 32, XW = row_words(G), R = G.pz * G.py;
+    const long long wave_first = blockIdx.x * (long long)(256 * SELECT_VPT) +
+                                 __builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u));
+    unsigned todo = ready_bits;
+    for (;;) {
+        long long ccs[SELECT_WINNERS] = {};                             // (wave-uniform, all of these)
+        K keys[SELECT_WINNERS] = {};
+        int srcs[SELECT_WINNERS] = {}, kks[SELECT_WINNERS] = {}, n_win = 0;
+#pragma unroll
+        for (int s = 0; s < SELECT_WINNERS; ++s) {
+            const unsigned long long m = __ballot(todo != 0u);
+            if (m != 0ull) {
+                const int src = __builtin_ctzll(m);
+                const int j = __builtin_ctz((unsigned)__builtin_amdgcn_readlane((int)todo, src));
+                if (lane == src) todo &= todo - 1u;
+                keys[s] = lane_value(pick_voxel(mine, j), src);
+                ccs[s] = wave_first + src + j * 256;
+                srcs[s] = src;
+                n_win = s + 1;
+            }
+        }
+        if (n_win == 0) break;
+        int cleared[SELECT_WINNERS] = {}, czs[SELECT_WINNERS] = {}, cys[SELECT_WINNERS] = {}, cxs[SELECT_WINNERS] = {};
+#pragma unroll
+        for (int s = 0; s < SELECT_WINNERS; ++s)
+            if (s < n_win) {
+                kks[s] = loc_vol ? loc_vol[ccs[s]] : P::index(keys[s]);                 // local index
+                centre_of(G, ccs[s], czs[s], cys[s], cxs[s]);
+            }
+        for (int rb = 0; rb < R; rb += 64 * SELECT_ROWS) {
+            uint32_t ml[SELECT_WINNERS][SELECT_ROWS], mh[SELECT_WINNERS][SELECT_ROWS];
+            uint32_t bl[SELECT_WINNERS][SELECT_ROWS], bh[SELECT_WINNERS][SELECT_ROWS];
+            // the lane's rows (the same for every winner; a row past the window reads the last one: clamped, no
+            // branch between the loads)
+            int dzs[SELECT_ROWS], dys[SELECT_ROWS];
+#pragma unroll
+            for (int i = 0; i < SELECT_ROWS; ++i) {
+                const int r = min(rb + i * 64 + lane, R - 1);
+                dzs[i] = r / G.py;
+                dys[i] = r - dzs[i] * G.py;
+            }
+#pragma unroll
+            for (int s = 0; s < SELECT_WINNERS; ++s) {
+                if (s >= n_win) continue;
+                const int cz = czs[s], cy = cys[s], cx = cxs[s];
+                const uint32_t *b = bits + pick.bits_row(ccs[s], kks[s]) * words;
+                const int wi = (cx - G.rx) >> 5;
+#pragma unroll
+                for (int i = 0; i < SELECT_ROWS; ++i) {
+                    if (rb + i * 64 >= R) continue;
+                    const int dz = dzs[i], dy = dys[i], bi = (min(rb + i * 64 + lane, R - 1) * G.px) >> 5;
+                    const uint32_t *row = mbits + ((long long)(cz + dz - G.rz) * G.Y + (cy + dy - G.ry)) * XW;
+                    ml[s][i] = row[wi];
+                    mh[s][i] = row[min(wi + 1, XW - 1)];
+                    bl[s][i] = b[bi];
+                    bh[s][i] = b[min(bi + 1, words - 1)];
                 }
             }
-            for (int o = 32; o > 0; o >>= 1) cleared += __shfl_xor(cleared, o);
+#pragma unroll
+            for (int s = 0; s < SELECT_WINNERS; ++s) {
+                if (s >= n_win) continue;
+                const int cz = czs[s], cy = cys[s], cx = cxs[s];
+                const int start = cx - G.rx, sh = start & 31;
+                // window bits whose voxel is an interior x position: bits [lo, hi)
+                const int lo = max(G.rx - start, 0), hi = min(G.X - G.rx - start, G.px);
+                const uint32_t xin = hi > lo ? (low_bits(hi) & ~low_bits(lo)) : 0u;
+#pragma unroll
+                for (int i = 0; i < SELECT_ROWS; ++i) {
+                    const int r = rb + i * 64 + lane;
+                    if (r >= R) continue;
+                    const int z = cz + dzs[i] - G.rz, y = cy + dys[i] - G.ry;
+                    uint32_t *row = mbits + ((long long)z * G.Y + y) * XW;
+                    const uint32_t cl = window_of(ml[s][i], mh[s][i], sh, G.px) &
+                                        window_of(bl[s][i], bh[s][i], (r * G.px) & 31, G.px);
+                    if (cl) {
+                        atomicAnd(row + (start >> 5), ~(cl << sh));
+                        if (sh && (cl >> (32 - sh))) atomicAnd(row + (start >> 5) + 1, ~(cl >> (32 - sh)));
+                        if (z + oz >= G.rz && z + oz < gZ - G.rz && y >= G.ry && y < G.Y - G.ry)
+                            cleared[s] += __popc(cl & xin);
+                    }
+                }
+            }
+        }
+        auto finish = [&](const int s) {
+            const int cz = czs[s], cy = cys[s], cx = cxs[s];
+            int n_cleared = cleared[s];
+            for (int o = 32; o > 0; o >>= 1) n_cleared += __shfl_xor(n_cleared, o);
             // every centre within p-1 of this one has a window that overlaps the cleared voxels
             const int z0 = max(cz - (G.pz - 1), 0), z1 = min(cz + G.pz - 1, G.Z - 1);
             const int y0 = max(cy - (G.py - 1), 0), y1 = min(cy + G.py - 1, G.Y - 1);
@@ -737,11 +931,14 @@ __device__ __forceinline__ void
                 for (int x = 0; x < nx; ++x) d[x] = 1;
             }
             if (MARKS && lane < 7) mark_box_row(mark_bits, cz, cy, cx, lane, G);
-            if (lane == src) {
-                key_vol[cc] = FilterNone<K>::value;
-                pick.record(kk, key, cleared);
+            if (lane == srcs[s]) {
+                key_vol[ccs[s]] = FilterNone<K>::value;
+                pick.record(kks[s], keys[s], n_cleared);
             }
-        }
+        };
+#pragma unroll
+        for (int s = 0; s < SELECT_WINNERS; ++s)
+            if (s < n_win) finish(s);
     }
 }
 
@@ -1053,12 +1250,13 @@ __global__ void __launch_bounds__(256)
 // The count sweep over keys (the loads of a thread's voxels issued pass by pass): the undecided patches of a
 // workgroup whose neighbourhood changed are compacted in LDS, then recounted in full and their keys
 // rewritten; a patch that covers nothing any more is retired.
-__global__ void __launch_bounds__(COUNT_THREADS)
+__global__ void PPP_COUNT_BOUNDS
     thin_count_kernel(const uint32_t *__restrict__ mbits, const uint32_t *__restrict__ bits,
                       uint8_t *__restrict__ dirty, int32_t *__restrict__ state,
                       long long *__restrict__ key_vol, int32_t *__restrict__ n_alive,
                       const int32_t *__restrict__ loc_vol, const Geo G) {
     __shared__ uint16_t s_list[COUNT_THREADS * COUNT_VPT];
+    __shared__ int32_t s_row[COUNT_THREADS * COUNT_VPT];
     __shared__ int s_n;
     if (threadIdx.x == 0) s_n = 0;
     __syncthreads();
@@ -1067,6 +1265,7 @@ __global__ void __launch_bounds__(COUNT_THREADS)
     {
         long long vv[COUNT_VPT], key[COUNT_VPT];
         uint8_t mark[COUNT_VPT];
+        int kl[COUNT_VPT];                                       // row of `bits` / `state`
         bool alive[COUNT_VPT], marked[COUNT_VPT];
 #pragma unroll
         for (int j = 0; j < COUNT_VPT; ++j) {
@@ -1080,19 +1279,26 @@ __global__ void __launch_bounds__(COUNT_THREADS)
 #pragma unroll
         for (int j = 0; j < COUNT_VPT; ++j) {
             alive[j] = vv[j] < G.V && key[j] != THIN_NONE;
-            if (loc_vol && alive[j]) alive[j] = loc_vol[vv[j]] >= 0;
+            kl[j] = (int)(key[j] & 0xFFFFFFFFll);
+            if (loc_vol && alive[j]) { kl[j] = loc_vol[vv[j]]; alive[j] = kl[j] >= 0; }
             marked[j] = vv[j] < G.V && mark[j] != 0;
             if (marked[j]) dirty[vv[j]] = 0;
         }
-        n = compact_marked(alive, marked, s_list, &s_n, n_alive);
+        n = compact_marked(alive, marked, kl, s_list, s_row, &s_n, n_alive);
     }
-    for (int t = threadIdx.x; t < n; t += blockDim.x) {
-        const long long v = v0 + s_list[t];
-        const int k = (int)(key_vol[v] & 0xFFFFFFFFll);          // position in the (global) list: the key's tie-break
-        const int kl = loc_vol ? loc_vol[v] : k;                 // row of `bits` / `state`
+    // the listed patches, a group of lanes each, as in cover_count_kernel: the full count, no witness
+    const int gw = recount_group(G), per_wave = 64 / gw;
+    const int sub = threadIdx.x & (gw - 1), in_wave = (threadIdx.x & 63) / gw;
+    for (int base = (threadIdx.x >> 6) * per_wave; base < n; base += COUNT_THREADS / gw) {
+        const bool mine = base + in_wave < n;
+        const int e = mine ? base + in_wave : base;
+        const long long v = v0 + s_list[e];
+        const int kl = s_row[e];
+        // position in the (global) list, the key's tie-break: asked for beside the rows, not before them
+        const int k = (int)(key_vol[v] & 0xFFFFFFFFll);
         unsigned wit;
-        // (the full count, row by row: without the plane preload the sweep keeps its 44 registers)
-        const int hits = window_hits<false, false, false>(mbits, bits + (long long)kl * ((G.C + 31) / 32), v, 0, wit, G);
+        const int hits = group_hits<false>(mbits, bits + (long long)kl * ((G.C + 31) / 32), v, sub, gw, wit, G);
+        if (!mine || sub != 0) continue;
         if (hits == 0) {
             state[kl] = 2;
             key_vol[v] = THIN_NONE;
