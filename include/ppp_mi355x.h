@@ -948,6 +948,30 @@ int ppp_skeletonize_labels(const uint32_t *d_labels, uint32_t *d_out, int32_t Z,
                            int64_t *n_kept, int32_t *stats /* [3] as ppp_skeletonize_3d */,
                            void *d_work, void *stream);
 
+/* --- the patch mosaic of visualize_patches on the device (csrc/ppp_mosaic.hip) ------------------
+ * The reference's `reshape_affinities` / `reshape_affinities_3d` (PatchPerPix/visualize/patches.py:12-98)
+ * show the predicted patch of every voxel as one tile of a mosaic, with a Python loop over the voxels.
+ * Here it is one pass over a z-tile: a pure re-arrangement, no workspace.
+ *   d_pred   [C][tz][Y][X], elements of PPP_F32 / PPP_F16 / PPP_BF16, C = pz py px, patch = (pz, py, px), sides
+ *            >= 1 (neither odd nor equal sides are required); channel c = (k py + j) px + i.  Read-only:
+ *            the ones the reference writes into its input are NOT written.
+ *   d_out    [tz][Y py][X px] of the same element type:
+ *              out[z][y py + j][x px + i] = 1                                          if j == 0 or i == 0
+ *                                         = max over k of pred[(k py + j) px + i][z][y][x]   otherwise,
+ *            the maximum NumPy's: a NaN among the pz values gives NaN.  pz = 1 is the 2-d mosaic.
+ *   d_selected u8 [S][tz][Y][X] with S = 1 or 3 (pz = 1 only), or NULL with S = 0.  With it d_out is
+ *            [3][tz][Y py][X px] and the tile of a voxel goes to ONE channel: S = 1, channel 0 where
+ *            selected[0] is set, else channel 2; S = 3, the first of channels 0, 1, 2 whose flag is set, and
+ *            to none where no flag is.  The other channels are zero there.
+ * EVERY element of d_out is written, those zeros included: the caller does not clear it.  Channels with
+ * j == 0 or i == 0 are not read; every other element of d_pred is read exactly once.
+ * PPP_ERR_INVALID_ARG: C != pz py px, a side < 1, S not in {0, 1, 3}, S > 0 with pz > 1, d_selected and S
+ * disagreeing.  PPP_ERR_UNSUPPORTED, by the sizes alone: a z-tile of 2^31 voxels or more, Y py or X px of 2^31
+ * or more, px > 63 (the tile the kernel keeps in LDS), a grid the device would not run whole.
+ * PPP_ERR_NO_DEVICE without a device.  Does not synchronise the stream.                            */
+int ppp_patch_mosaic(const void *d_pred, int pred_dtype, int32_t C, const uint8_t *d_selected, int32_t S,
+                     void *d_out, int32_t tz, int32_t Y, int32_t X, const int32_t *patch /* [3] */, void *stream);
+
 /* --- synthetic input (bench / tests only; same hash as patchperpix_amd/synth.py) ------
  * fills d_pred (C,Z,Y,X) from a label volume d_labels int32 (Z,Y,X).  voxel_offset is the
  * linear index of local voxel 0 in the global volume (0 unless the buffers are a slab).    */

@@ -391,6 +391,10 @@ _SIGNATURES = {
     "ppp_skeletonize_labels": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                                               ctypes.c_int32, ctypes.POINTER(ctypes.c_int64),
                                               ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_void_p]),
+    # the patch mosaic of visualize_patches (ppp_mosaic.hip)
+    "ppp_patch_mosaic": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                        ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                        ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p]),
     # no_overlap_per_channel without the loop over components (ppp_pack_channels.hip, ppp_host_pack.cpp)
     "ppp_pack_scan_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(Params), ctypes.POINTER(Box)]),
     "ppp_pack_scan_count": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
@@ -2216,6 +2220,31 @@ def eval_patch(pred_tile, labels, patchshape, z0, thresholds, counts, want_maps=
                                    int(z0), tz, th, T, _dev_ptr(counts), _dev_ptr(inter), _dev_ptr(union),
                                    _dev_ptr(work), _stream()))
     return inter, union
+
+
+def patch_mosaic(pred_tile, patchshape, selected=None, out=None):
+    """ppp_patch_mosaic on one z-tile: `pred_tile` a contiguous (C, tz, Y, X) device tensor (float32 / float16 /
+    bfloat16, C = pz py px), `selected` None or a contiguous uint8 (S, tz, Y, X) device tensor with S = 1 or 3
+    (pz = 1 only).  Returns the mosaic, (tz, Y py, X px) of the same dtype, or (3, tz, Y py, X px) with
+    `selected`; `out`, when given, is that tensor and EVERY element of it is written.  Does not synchronise."""
+    torch = _torch()
+    assert pred_tile.dim() == 4, "patch_mosaic needs a (C, tz, Y, X) prediction"
+    C, tz, Y, X = [int(v) for v in pred_tile.shape]
+    pz, py, px = [int(p) for p in patchshape]
+    S = 0
+    if selected is not None:
+        assert selected.dtype == torch.uint8 and selected.dim() == 4 and tuple(selected.shape[1:]) == (tz, Y, X), \
+            "selected is a uint8 (S, tz, Y, X) tensor"
+        S = int(selected.shape[0])
+    shape = (tz, Y * py, X * px) if S == 0 else (3, tz, Y * py, X * px)
+    if out is None:
+        out = torch.empty(shape, dtype=pred_tile.dtype, device=pred_tile.device)
+    assert tuple(out.shape) == shape and out.dtype == pred_tile.dtype, "out must be %s of %s" % (shape, pred_tile.dtype)
+    patch = (ctypes.c_int32 * 3)(pz, py, px)
+    with _timed("patch_mosaic"):
+        check(lib().ppp_patch_mosaic(_dev_ptr(pred_tile), pred_dtype_code(pred_tile), C, _dev_ptr(selected), S,
+                                     _dev_ptr(out), tz, Y, X, patch, _stream()))
+    return out
 
 
 def host_cover_pass(mask_running, overlap, patchshape, ranked_lin, ranked_score, bits, pix_th,

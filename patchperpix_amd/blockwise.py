@@ -373,8 +373,16 @@ def main(pred_file, result_folder=".", **kwargs):
     foreground, _ = util.loadFg(in_f, **kwargs)
     foreground = np.squeeze(foreground)
     if kwargs.get("output_format", "hdf") == "hdf":
-        instances, datasets = postprocess.post_steps(instances, foreground, **dict(kwargs, res_key=res_key))
+        instances, datasets = postprocess.post_steps(instances, foreground, mip_stem=os.path.join(result_folder, sample),
+                                                     **dict(kwargs, res_key=res_key))
         write_result(os.path.join(result_folder, sample + ".hdf"), datasets)
-    elif kwargs.get("remove_small_comps", 0) > 0:
-        instances = postprocess.compact(instances, kwargs["remove_small_comps"])
+    else:
+        # (no result file of this driver's, but save_mip does not depend on the format: :823-847)
+        stem = os.path.join(result_folder, sample)
+        if kwargs.get("save_mip", False):
+            postprocess.save_mip_png(stem + ".png", instances)
+        if kwargs.get("remove_small_comps", 0) > 0:
+            instances = postprocess.compact(instances, kwargs["remove_small_comps"])
+            if kwargs.get("save_mip", False):
+                postprocess.save_mip_png(stem + "_cleaned.png", instances)
     return instances

@@ -1628,4 +1628,29 @@ int ppp_skeletonize_labels(const uint32_t *d_labels, uint32_t *d_out, int32_t Z,
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_skeletonize_labels");
 }
 
+/* ---- the patch mosaic of visualize_patches (ppp_mosaic.hip) ---- */
+int ppp_patch_mosaic(const void *d_pred, int pred_dtype, int32_t C, const uint8_t *d_selected, int32_t S, void *d_out,
+                     int32_t tz, int32_t Y, int32_t X, const int32_t *patch, void *stream) {
+    if (!patch) return fail(PPP_ERR_INVALID_ARG, "NULL patch");
+    if (tz <= 0 || Y <= 0 || X <= 0) return fail(PPP_ERR_INVALID_ARG, "bad z-tile %d x %d x %d", tz, Y, X);
+    for (int a = 0; a < 3; ++a)
+        if (patch[a] < 1) return fail(PPP_ERR_INVALID_ARG, "patch side %d must be positive", patch[a]);
+    PPP_TRY(check_dtype(pred_dtype));
+    if ((long long)C != (long long)patch[0] * patch[1] * patch[2])
+        return fail(PPP_ERR_INVALID_ARG, "%d channels, but the patch %d x %d x %d has %lld elements", C, patch[0], patch[1],
+                    patch[2], (long long)patch[0] * patch[1] * patch[2]);
+    if (S != 0 && S != 1 && S != 3) return fail(PPP_ERR_INVALID_ARG, "selected has %d channels: 0, 1 or 3", S);
+    if (S > 0 && patch[0] > 1) return fail(PPP_ERR_INVALID_ARG, "selected goes with the 2-d mosaic only (pz = %d)", patch[0]);
+    const char *why = "";
+    if (!ppp::patch_mosaic_supported(tz, Y, X, patch[0], patch[1], patch[2], &why))
+        return fail(PPP_ERR_UNSUPPORTED, "ppp_patch_mosaic: %s are not supported", why);
+    if (!d_pred || !d_out || (S > 0) != (d_selected != nullptr) || ((uintptr_t)d_pred & (pred_dtype == PPP_F32 ? 3 : 1)) ||
+        ((uintptr_t)d_out & (pred_dtype == PPP_F32 ? 3 : 1)))
+        return fail(PPP_ERR_INVALID_ARG, "NULL or misaligned pointer argument");
+    PPP_TRY(need_device());
+    hipError_t e = ppp::run_patch_mosaic(d_pred, pred_dtype, d_selected, S, d_out, tz, Y, X, patch[0], patch[1], patch[2],
+                                         (hipStream_t)stream);
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_patch_mosaic");
+}
+
 }  // extern "C"

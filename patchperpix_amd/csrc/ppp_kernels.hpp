@@ -274,6 +274,12 @@ hipError_t run_eval_patch(const void *pred, int dtype, const int32_t *labels, in
                           int px, int z0, int tz, const float *th, int T, long long *counts, int32_t *inter, int32_t *uni,
                           void *work, hipStream_t s);
 
+// the patch mosaic of visualize_patches (ppp_mosaic.hip): every element of `out` is written; no workspace
+constexpr int kMosaicMaxPx = 63;     // four LDS tiles of 128 voxels x (px | 1) 2-byte elements in 64 KiB
+bool patch_mosaic_supported(int tz, int Y, int X, int pz, int py, int px, const char **why);
+hipError_t run_patch_mosaic(const void *in, int dtype, const uint8_t *sel, int S, void *out, int tz, int Y, int X, int pz,
+                            int py, int px, hipStream_t s);
+
 // 3-d thinning of the foreground (ppp_skeleton.hip)
 size_t skeleton_workspace_bytes(int Z, int Y, int X);
 hipError_t run_skeletonize_3d(const uint8_t *mask, uint8_t *out, int Z, int Y, int X, long long *n_kept, int *stats,

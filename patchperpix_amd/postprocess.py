@@ -42,6 +42,25 @@ def relabel(array, start=None):
     return new[inverse].reshape(array.shape)
 
 
+def color(src, colormap=None):
+    """postprocess.py:55-74: an array of shape ``src.shape + (3,)`` and of ``src``'s dtype, zero where
+    ``src`` is 0; every other label takes ``np.random.randint(0, 255, 3)``.  The draws are the reference's,
+    call for call: ONE call per non-zero label, in ascending label order, from NumPy's global generator --
+    unseeded, so the colour of a label is no function of the input, but a caller who seeds ``np.random``
+    gets the reference's picture pixel for pixel.  ``colormap='glasbey'`` needs the ``colorcet`` package,
+    which is not a dependency here."""
+    src = np.asarray(src)
+    if colormap == "glasbey":
+        raise NotImplementedError("colormap='glasbey' needs the colorcet package, which this repository does not use")
+    labels, inverse = np.unique(src, return_inverse=True)
+    table = np.zeros((len(labels), 3), dtype=src.dtype)
+    for k, label in enumerate(labels):
+        if label == 0:
+            continue
+        table[k] = np.random.randint(0, 255, 3)
+    return table[inverse.reshape(src.shape)]
+
+
 def dilate_instances(instances, iterations=1):
     """stitch_patch_graph.py:871-880: every instance, in ascending id order, is dilated by one
     step of the cross-shaped structuring element and painted over what is there (later ids win,
@@ -446,15 +465,50 @@ def postprocess_fg(samples, output_folder, **kwargs):
                 mininrrd.write(stem + ".nrrd", np.asarray(skel))
 
 
-def post_steps(instances, foreground, res_key, **kw):
-    """What the label drivers do with the assembled uint32 map (stitch_patch_graph.py:831-894): small
+def max_projection(instances):
+    """``np.max(instances, axis=0)`` as a NumPy array: `torch.amax` on the device by the dispatch rule (ids
+    that fit the device's int32 storage), else NumPy on the host.  One small reduction, not a hot path."""
+    dev = _ids_to_device(instances) if use_device() and len(np.shape(instances)) >= 2 else None
+    if dev is None or dev[1] < 0:
+        inst = instances.cpu().numpy() if _is_tensor(instances) else np.asarray(instances)
+        return np.max(inst, axis=0)
+    import torch
+    mip = torch.amax(dev[0], dim=0).cpu().numpy().view(np.uint32)
+    dtype = np.dtype(str(instances.dtype).replace("torch.", ""))
+    return mip.astype(dtype)
+
+
+def save_mip_png(path, instances):
+    """stitch_patch_graph.py:823-829 / :842-847: ``color(np.max(instances, axis=0)).astype(np.uint8)`` as a
+    PNG (minipng).  The projection by `max_projection`, the colouring on the host on the 2-d image."""
+    from . import minipng
+    mip = max_projection(instances)
+    if mip.ndim != 2:
+        raise ValueError("save_mip needs a (Z, Y, X) instance map, not shape %s" % (np.shape(instances),))
+    minipng.write(path, color(mip).astype(np.uint8))
+
+
+def post_steps(instances, foreground, res_key, mip_stem=None, **kw):
+    """What the label drivers do with the assembled uint32 map (stitch_patch_graph.py:823-894): small
     components removed and the ids compacted when remove_small_comps asks for it, then the datasets of
     the result file, all uint16 like the reference's astype (ids above 65 535 that survive wrap,
     :852-870): <res_key>, vote_foreground, <res_key>_masked and -- dilate_instances --
-    <res_key>_dil_1, <res_key>_masked_dil_1.  Returns (instances, datasets)."""
+    <res_key>_dil_1, <res_key>_masked_dil_1.  Returns (instances, datasets).
+
+    ``save_mip`` (:823-829, :842-847; the drivers pass ``mip_stem`` = <result_folder>/<sample>): the
+    coloured maximum projection along z of the stitched map goes to ``<mip_stem>.png`` BEFORE the small
+    components are removed, and that of the cleaned map to ``<mip_stem>_cleaned.png`` when
+    remove_small_comps > 0.  Falsy or absent: no file is written."""
     foreground = np.asarray(foreground)
+    save_mip = bool(kw.get("save_mip", False))
+    if save_mip and mip_stem is None:
+        raise ValueError("save_mip needs the driver's mip_stem (<result_folder>/<sample>)")
+    if save_mip:
+        save_mip_png(mip_stem + ".png", instances)
     if kw.get("remove_small_comps", 0) > 0:
         instances = compact(instances, kw["remove_small_comps"])
+        if save_mip:
+            save_mip_png(mip_stem + "_cleaned.png", instances)
     if int(instances.max(initial=0)) > np.iinfo(np.uint16).max:
         logger.warning("instance ids up to %d are written as uint16 like the reference does "
                        "(stitch_patch_graph.py:852-856): set remove_small_comps > 0 to compact "

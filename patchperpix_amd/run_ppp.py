@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""`label`, `decode`, `postprocess`, `postprocess_fg` and `evaluate_prediction` tasks with the reference driver's interface
+"""`label`, `decode`, `postprocess`, `postprocess_fg`, `evaluate_prediction` and `visualize` tasks with the reference driver's interface
 (reference: experiments/run_ppp.py -- argument names :157-267, task dispatch :1974-2293,
 ``decode`` :682-746, ``vote_instances`` / ``vote_instances_sample`` :1054-1190, ``postprocess``
 :2230-2259).  The reference's ``postprocess`` has two branches: ``process_instances`` is this driver's
@@ -8,6 +8,9 @@
 
 ``evaluate_prediction`` (:1300-1443, the reference's ``[evaluation] prediction_only_test`` branch
 :2207-2211) scores the dense prediction against ``[data] test_data`` before any instance is voted.
+
+``visualize`` (:1539-1606): patch mosaics of the prediction (``show_patches``) and instance pictures
+(``show_instances``).
 
 Only the tasks on this repository's path are provided; training, prediction and the evaluation of
 instance segmentations stay with the reference.  Usage, as in the reference README:
@@ -195,6 +198,53 @@ def evaluate_prediction(args, config):
     return result
 
 
+def visualize(args, config):
+    """run_ppp.py:1539-1606, by ``[visualize]``'s switches, for the samples of ``samples_to_visualize``.
+
+    ``show_patches``: for every such sample present in --pred-folder as ``<sample>.<prediction.output_format>``
+    the patch mosaic of ``aff_key`` goes to ``<pred_folder>/<sample>.hdf``, dataset ``<aff_key>_patched``
+    (`visualize.visualize_patches`); a sample whose ``.hdf`` exists is skipped.
+
+    ``show_instances``: ``vote_instances`` of ``<output_folder>/<sample>.<vote_instances.output_format>`` as
+    ``<output_folder>/<sample>.png`` (`visualize.visualize_instances`), with ``max_axis = 0`` when
+    ``one_instance_per_channel`` is set; a sample whose PNG exists is skipped.  The reference loops over the
+    validation's parameter sets here and looks into one result folder per set, but its loop cannot run as
+    written: it reads ``params``, a name that exists only in the reference's ``main`` (:1572).  This task
+    serves the ONE folder the `label` task writes, --output-folder."""
+    from .visualize import visualize_instances, visualize_patches
+    cfg = config.get("visualize", {})
+    wanted = cfg.get("samples_to_visualize", [])
+    if cfg.get("show_patches"):
+        fmt = config["prediction"]["output_format"]
+        samples = get_list_samples(args.pred_folder, fmt)
+        aff_key = config["prediction"].get("aff_key", "volumes/pred_affs")
+        for sample in wanted:
+            if sample not in samples:
+                continue
+            infn = os.path.join(args.pred_folder, sample + "." + fmt)
+            outfn = os.path.join(args.pred_folder, sample + ".hdf")
+            if os.path.exists(outfn):
+                logger.info("Skipping patch mosaic for %s. Already exists!", outfn)
+                continue
+            t0 = time.time()
+            visualize_patches(infn, config["model"]["patchshape"], in_key=aff_key, out_file=outfn,
+                              out_key=aff_key + "_patched")
+            logger.info("time visualize_patches %s: %.2fs", sample, time.time() - t0)
+    if cfg.get("show_instances"):
+        fmt = config["vote_instances"].get("output_format", "hdf")
+        samples = get_list_samples(args.output_folder, fmt)
+        max_axis = 0 if config["vote_instances"].get("one_instance_per_channel") else None
+        for sample in wanted:
+            if sample not in samples:
+                continue
+            outfn = os.path.join(args.output_folder, sample + ".png")
+            if os.path.exists(outfn):
+                logger.info("Skipping instance picture %s. Already exists!", outfn)
+                continue
+            visualize_instances(os.path.join(args.output_folder, sample + "." + fmt), "vote_instances", outfn,
+                                max_axis=max_axis)
+
+
 def main(argv=None):
     from patchperpix_amd import backend as _backend
     _backend.tune_host_allocator(cli=True)     # (main(argv) IS the program, also behind a console script)
@@ -202,7 +252,7 @@ def main(argv=None):
     ap.add_argument("-c", "--config", action="append", required=True)
     ap.add_argument("-a", "--app", default="flylight")
     ap.add_argument("-s", "--setup", default="setup01")
-    ap.add_argument("-d", "--do", nargs="+", default=["label"], choices=["label", "decode", "postprocess", "postprocess_fg", "evaluate_prediction"])
+    ap.add_argument("-d", "--do", nargs="+", default=["label"], choices=["label", "decode", "postprocess", "postprocess_fg", "evaluate_prediction", "visualize"])
     ap.add_argument("--pred-folder", required=True)
     ap.add_argument("--output-folder", required=True)
     ap.add_argument("--checkpoint", default=None)
@@ -212,7 +262,7 @@ def main(argv=None):
     config = load_config(args.config)
     for task in args.do:
         {"label": label, "decode": decode, "postprocess": postprocess, "postprocess_fg": postprocess_fg,
-         "evaluate_prediction": evaluate_prediction}[task](args, config)
+         "evaluate_prediction": evaluate_prediction, "visualize": visualize}[task](args, config)
 
 
 if __name__ == "__main__":

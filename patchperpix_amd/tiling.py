@@ -2408,9 +2408,10 @@ def _stitch_streamed(provider, foreground, numinst, bb, shape, patchshape, pred_
                           patchshape, plan_slabs(bshape[0], n), _yx_tiles=(ny, nx), **kw)
     instances = np.zeros(shape, dtype=np.uint32)
     instances[bb] = inst_bb
-    instances, datasets = postprocess.post_steps(instances, foreground, **dict(kw, res_key=kw.get("res_key", "vote_instances")))
     os.makedirs(result_folder, exist_ok=True)
     fn = os.path.splitext(os.path.basename(pred_file.rstrip("/")))[0]
+    instances, datasets = postprocess.post_steps(instances, foreground, mip_stem=os.path.join(result_folder, fn),
+                                                 **dict(kw, res_key=kw.get("res_key", "vote_instances")))
     write_result(os.path.join(result_folder, fn + ".hdf"), datasets)
     return instances
 
@@ -2588,8 +2589,9 @@ def _stitch_main(stack, pred_file, result_folder=".", **kwargs):
     # every dataset is then written as uint16 (the reference's astype: ids above 65 535 that
     # survive wrap, :852-870) -- postprocess.post_steps, on the device when there is one
     from . import postprocess
-    instances, datasets = postprocess.post_steps(instances, foreground, **dict(kw, res_key=kw.get("res_key", "vote_instances")))
     os.makedirs(result_folder, exist_ok=True)
     fn = os.path.splitext(os.path.basename(pred_file.rstrip("/")))[0]
+    instances, datasets = postprocess.post_steps(instances, foreground, mip_stem=os.path.join(result_folder, fn),
+                                                 **dict(kw, res_key=kw.get("res_key", "vote_instances")))
     write_result(os.path.join(result_folder, fn + ".hdf"), datasets)
     return instances
