@@ -948,6 +948,47 @@ int ppp_skeletonize_labels(const uint32_t *d_labels, uint32_t *d_out, int32_t Z,
                            int64_t *n_kept, int32_t *stats /* [3] as ppp_skeletonize_3d */,
                            void *d_work, void *stream);
 
+/* --- the contingency table of two label stacks in one pass (csrc/ppp_overlap.hip) ---------------
+ * What every instance metric of the reference's `evaluate` step (run_ppp.py:1239-1262, evaluate_file of the
+ * package evaluate-instance-segmentation) needs of the volumes: which id of A meets which id of B in how
+ * many voxels, and every id's size.  The package is not vendored by the reference, so nothing here is
+ * pinned to it: the DEFINITION is the one below, stated again in NumPy as
+ * patchperpix_amd.evaluate_instances.overlap_counts_host.
+ * d_a u32 [La][Z][Y][X], d_b u32 [Lb][Z][Y][X]: 0 is background, every other 32-bit value is an id (2^31 and
+ * above and 0xFFFFFFFF included; no table, no id limit).  The result is a list of rows (a, b) with an int64
+ * count:
+ *   (a, b), a != 0 and b != 0 :  #{(i, j, v) : A[i][v] == a and B[j][v] == b}
+ *   (a, 0)                    :  #{(i, v) : A[i][v] == a}
+ *   (0, b)                    :  #{(j, v) : B[j][v] == b}
+ * Rows with a zero count do not exist; rows are sorted ascending by (a, b) as unsigned pairs, so the
+ * result is unique.  Integer sums only: bit-identical from run to run.
+ * *n_rows (host) ALWAYS receives the number of rows.  With n_rows <= cap the rows are written to d_rows
+ * u32 [cap][2] and d_counts i64 [cap]; with n_rows > cap NOTHING is written to either, the return code is
+ * PPP_OK and the caller calls again with a larger cap.  cap = 0 with NULL outputs is the size query.
+ * The call synchronises the stream twice: the number of partial counts sizes the rocPRIM sort on the host,
+ * and n_rows is a host value.  The rows are written by a launch after the second synchronisation.
+ * PPP_ERR_INVALID_ARG: La < 1, Lb < 1, cap < 0, a bad volume, NULL or misaligned pointers.
+ * PPP_ERR_UNSUPPORTED (the size query returns it as a negative value): volumes of 2^31 voxels or more,
+ * La Lb + La + Lb > 65535.  PPP_ERR_NO_DEVICE without a device.
+ * The workspace covers the worst case, every voxel its own pair: 32 bytes per voxel and key stream, of
+ * which there are La Lb + La + Lb (96 bytes per voxel for La = Lb = 1), plus rocPRIM's temporary storage
+ * (histograms and scan states: the sort works in the two halves of the list and keeps no copy).
+ * Cost: d_a is read once, d_b once per channel of d_a (one read of both for La = 1), and every voxel is
+ * La Lb + La + Lb keys of work: maps with hundreds of channels a side are slow, not a case this pass is for.
+ * ppp_label_overlap_table_entries: slots of the per-workgroup LDS table the pass counts in (tests size
+ * their table-pressure cases by it); ppp_label_overlap_slot: that table's hash, the home slot of key (a, b)
+ * (host function; tests build colliding keys from it); ppp_label_overlap_last_stats: of the last call in this
+ * process, stats[3] = partial counts written, table flushes inside the pass's loop, items that went past
+ * the table (tests assert by them that a case reached the path it is about). */
+int32_t ppp_label_overlap_table_entries(void);
+void ppp_label_overlap_last_stats(int64_t *stats /* [3] */);
+uint32_t ppp_label_overlap_slot(uint32_t a, uint32_t b);
+int64_t ppp_label_overlap_workspace_bytes(int32_t La, int32_t Lb, int32_t Z, int32_t Y, int32_t X);
+int ppp_label_overlap(const uint32_t *d_a, int32_t La, const uint32_t *d_b, int32_t Lb,
+                      int32_t Z, int32_t Y, int32_t X,
+                      uint32_t *d_rows /* [cap][2] */, int64_t *d_counts /* [cap] */, int64_t cap,
+                      int64_t *n_rows /* host */, void *d_work, void *stream);
+
 /* --- the patch mosaic of visualize_patches on the device (csrc/ppp_mosaic.hip) ------------------
  * The reference's `reshape_affinities` / `reshape_affinities_3d` (PatchPerPix/visualize/patches.py:12-98)
  * show the predicted patch of every voxel as one tile of a mosaic, with a Python loop over the voxels.

@@ -391,6 +391,16 @@ _SIGNATURES = {
     "ppp_skeletonize_labels": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                                               ctypes.c_int32, ctypes.POINTER(ctypes.c_int64),
                                               ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_void_p]),
+    # the contingency table of two label stacks (ppp_overlap.hip)
+    "ppp_label_overlap_table_entries": (ctypes.c_int32, []),
+    "ppp_label_overlap_slot": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32]),
+    "ppp_label_overlap_last_stats": (None, [ctypes.POINTER(ctypes.c_int64)]),
+    "ppp_label_overlap_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                           ctypes.c_int32, ctypes.c_int32]),
+    "ppp_label_overlap": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                         ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+                                         ctypes.c_void_p, ctypes.c_void_p]),
     # the patch mosaic of visualize_patches (ppp_mosaic.hip)
     "ppp_patch_mosaic": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                         ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
@@ -2350,6 +2360,97 @@ def skeletonize_labels(ids):
     if is_tensor:
         return (t & 0xFFFF).to(torch.uint16) if name == "uint16" else t.view(ids.dtype)
     return t.cpu().numpy().view(np.uint32).astype(a.dtype)
+
+
+def _overlap_stack(t, who):
+    torch = _torch()
+    assert torch.is_tensor(t) and t.is_cuda and t.dim() == 4, "label_overlap: %s must be a (L, Z, Y, X) device tensor" % who
+    assert str(t.dtype) in ("torch.uint32", "torch.int32"), "label_overlap: %s must hold 32-bit ids (uint32, or int32 storage)" % who
+    return t.contiguous().view(torch.int32)
+
+
+def label_overlap_raw(a, b, cap, rows=None, counts=None, work=None):
+    """ONE ppp_label_overlap call: `a` (La, Z, Y, X) and `b` (Lb, Z, Y, X) device tensors of 32-bit ids,
+    `rows` int32 storage [cap, 2] and `counts` int64 [cap] device tensors (None with cap = 0: the size
+    query), `work` the workspace (None: allocated here).  Returns n_rows; the rows are written when
+    n_rows <= cap."""
+    a, b = _overlap_stack(a, "a"), _overlap_stack(b, "b")
+    assert tuple(a.shape[1:]) == tuple(b.shape[1:]), "label_overlap: the stacks differ in (Z, Y, X)"
+    La, Z, Y, X = [int(v) for v in a.shape]
+    Lb = int(b.shape[0])
+    if work is None:
+        work = _workspace(lib().ppp_label_overlap_workspace_bytes(La, Lb, Z, Y, X), a.device)
+    n = ctypes.c_int64(0)
+    with _timed("label_overlap"):
+        check(lib().ppp_label_overlap(_dev_ptr(a), La, _dev_ptr(b), Lb, Z, Y, X, _dev_ptr(rows), _dev_ptr(counts),
+                                      int(cap), ctypes.byref(n), _dev_ptr(work), _stream()))
+    return int(n.value)
+
+
+OVERLAP_WORK_SHARE = 0.25      # label_overlap: the workspace of one call stays within this share of the free device memory
+
+
+def _overlap_once(a, b):
+    """one volume (or chunk of one) through ppp_label_overlap, size query and retry included"""
+    torch = _torch()
+    La, Z, Y, X = [int(v) for v in a.shape]
+    work = _workspace(lib().ppp_label_overlap_workspace_bytes(La, int(b.shape[0]), Z, Y, X), a.device)
+    cap = 1 << 16
+    while True:
+        rows = torch.empty((cap, 2), dtype=torch.int32, device=a.device)
+        counts = torch.empty((cap,), dtype=torch.int64, device=a.device)
+        n = label_overlap_raw(a, b, cap, rows, counts, work)
+        if n <= cap:
+            break
+        cap = n
+    return np.ascontiguousarray(rows[:n].cpu().numpy()).view(np.uint32), counts[:n].cpu().numpy()
+
+
+def label_overlap_last_stats():
+    """ppp_label_overlap_last_stats: (partial counts written, table flushes inside the pass's loop, items that went
+    past the table) of the last ppp_label_overlap call in this process."""
+    st = (ctypes.c_int64 * 3)()
+    lib().ppp_label_overlap_last_stats(st)
+    return tuple(int(v) for v in st)
+
+
+def label_overlap(a, b, work_bytes=None):
+    """ppp_label_overlap: the contingency table of two stacks of label maps, device tensors (La, Z, Y, X) and
+    (Lb, Z, Y, X) of 32-bit ids (uint32, or int32 storage read as uint32; 0 = background).  Returns
+    (rows uint32 [n, 2], counts int64 [n]) as host NumPy arrays: rows (a, b) with a, b != 0 count the
+    (channel pair, voxel) incidences, rows (a, 0) and (0, b) are the sizes of the ids; sorted by (a, b).
+    Equal to evaluate_instances.overlap_counts_host, integer for integer.  A call runs with room for the rows
+    of a typical map; one that needs more is repeated once with the size it reported.
+
+    The entry point's workspace covers the worst case, 32 bytes per voxel and key stream.  Where that exceeds
+    `work_bytes` (default: OVERLAP_WORK_SHARE of the free device memory) the flat volume is cut into chunks of
+    voxels that fit, each chunk is one call, and the tables -- counts of disjoint sets of voxels -- are added
+    on the host: the same rows."""
+    torch = _torch()
+    a, b = _overlap_stack(a, "a"), _overlap_stack(b, "b")
+    assert tuple(a.shape[1:]) == tuple(b.shape[1:]), "label_overlap: the stacks differ in (Z, Y, X)"
+    La, Lb = int(a.shape[0]), int(b.shape[0])
+    V = int(a[0].numel())
+    if V == 0:
+        return np.zeros((0, 2), dtype=np.uint32), np.zeros(0, dtype=np.int64)
+    if work_bytes is None:
+        work_bytes = int(OVERLAP_WORK_SHARE * torch.cuda.mem_get_info(a.device)[0])
+    need = int(lib().ppp_label_overlap_workspace_bytes(La, Lb, *[int(v) for v in a.shape[1:]]))
+    check(min(need, 0))
+    if need <= work_bytes:
+        return _overlap_once(a, b)
+    a, b = a.reshape(La, 1, 1, V), b.reshape(Lb, 1, 1, V)
+    chunk = max(1, min(V, int(work_bytes) // (40 * (La * Lb + La + Lb))))      # (32 bytes; 8 for the sort's temporary storage, 256-byte slots)
+    keys, counts = [], []
+    for v0 in range(0, V, chunk):
+        r, c = _overlap_once(a[..., v0:v0 + chunk].contiguous(), b[..., v0:v0 + chunk].contiguous())
+        keys.append(r[:, 0].astype(np.uint64) << np.uint64(32) | r[:, 1].astype(np.uint64))
+        counts.append(c)
+    u, inverse = np.unique(np.concatenate(keys), return_inverse=True)
+    total = np.zeros(len(u), dtype=np.int64)
+    np.add.at(total, inverse.reshape(-1), np.concatenate(counts))
+    rows = np.stack([(u >> np.uint64(32)).astype(np.uint32), (u & np.uint64(0xFFFFFFFF)).astype(np.uint32)], axis=1)
+    return rows.reshape(-1, 2), total
 
 
 def host_skel_rule_mismatches(first, count):

@@ -1628,6 +1628,46 @@ int ppp_skeletonize_labels(const uint32_t *d_labels, uint32_t *d_out, int32_t Z,
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_skeletonize_labels");
 }
 
+/* ---- the contingency table of two label stacks (ppp_overlap.hip) ---- */
+static int overlap_args(int32_t La, int32_t Lb, int32_t Z, int32_t Y, int32_t X, long long *V, long long *streams) {
+    if (La < 1 || Lb < 1) return fail(PPP_ERR_INVALID_ARG, "both stacks need at least one channel (La = %d, Lb = %d)", La, Lb);
+    PPP_TRY(post_volume(Z, Y, X, V));
+    *streams = (long long)La * Lb + La + Lb;
+    if (*streams > 65535)
+        return fail(PPP_ERR_UNSUPPORTED, "ppp_label_overlap: La Lb + La + Lb = %lld, more than 65535, is not supported", *streams);
+    return PPP_OK;
+}
+
+int32_t ppp_label_overlap_table_entries(void) { return ppp::overlap_table_entries(); }
+uint32_t ppp_label_overlap_slot(uint32_t a, uint32_t b) { return ppp::overlap_slot_host(a, b); }
+void ppp_label_overlap_last_stats(int64_t *stats) {
+    long long st[3];
+    ppp::overlap_last_stats(st);
+    if (stats) for (int i = 0; i < 3; ++i) stats[i] = st[i];
+}
+
+int64_t ppp_label_overlap_workspace_bytes(int32_t La, int32_t Lb, int32_t Z, int32_t Y, int32_t X) {
+    long long V, streams;
+    int rc = overlap_args(La, Lb, Z, Y, X, &V, &streams);
+    return rc != PPP_OK ? rc : (int64_t)ppp::label_overlap_workspace_bytes(V, streams);
+}
+
+int ppp_label_overlap(const uint32_t *d_a, int32_t La, const uint32_t *d_b, int32_t Lb, int32_t Z, int32_t Y, int32_t X,
+                      uint32_t *d_rows, int64_t *d_counts, int64_t cap, int64_t *n_rows, void *d_work, void *stream) {
+    long long V, streams;
+    PPP_TRY(overlap_args(La, Lb, Z, Y, X, &V, &streams));
+    if (cap < 0) return fail(PPP_ERR_INVALID_ARG, "cap must be >= 0");
+    if (!d_a || !d_b || !n_rows || !d_work || (cap > 0 && (!d_rows || !d_counts)) || ((uintptr_t)d_a & 3) ||
+        ((uintptr_t)d_b & 3) || ((uintptr_t)d_rows & 3) || ((uintptr_t)d_counts & 7) || ((uintptr_t)d_work & 7))
+        return fail(PPP_ERR_INVALID_ARG, "NULL or misaligned pointer argument");
+    PPP_TRY(need_device());
+    long long n = 0;
+    hipError_t e = ppp::run_label_overlap(d_a, La, d_b, Lb, V, d_rows, (long long *)d_counts, cap, &n, d_work,
+                                          (hipStream_t)stream);
+    *n_rows = n;
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_label_overlap");
+}
+
 /* ---- the patch mosaic of visualize_patches (ppp_mosaic.hip) ---- */
 int ppp_patch_mosaic(const void *d_pred, int pred_dtype, int32_t C, const uint8_t *d_selected, int32_t S, void *d_out,
                      int32_t tz, int32_t Y, int32_t X, const int32_t *patch, void *stream) {

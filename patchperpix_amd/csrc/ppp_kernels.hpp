@@ -289,4 +289,12 @@ size_t skeleton_labels_workspace_bytes(int Z, int Y, int X);
 hipError_t run_skeletonize_labels(const uint32_t *labels, uint32_t *out, int Z, int Y, int X, long long *n_kept, int *stats,
                                   void *work, hipStream_t s);
 
+// the contingency table of two label stacks (ppp_overlap.hip); streams = La*Lb + La + Lb
+int overlap_table_entries();
+void overlap_last_stats(long long *out /* [3] */);
+uint32_t overlap_slot_host(uint32_t a, uint32_t b);
+size_t label_overlap_workspace_bytes(long long V, long long streams);
+hipError_t run_label_overlap(const uint32_t *a, int La, const uint32_t *b, int Lb, long long V, uint32_t *rows,
+                             long long *counts, long long cap, long long *n_rows, void *work, hipStream_t s);
+
 }  // namespace ppp

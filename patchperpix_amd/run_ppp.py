@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""`label`, `decode`, `postprocess`, `postprocess_fg`, `evaluate_prediction` and `visualize` tasks with the reference driver's interface
+"""`label`, `decode`, `postprocess`, `postprocess_fg`, `evaluate_prediction`, `evaluate` and `visualize` tasks with the reference driver's interface
 (reference: experiments/run_ppp.py -- argument names :157-267, task dispatch :1974-2293,
 ``decode`` :682-746, ``vote_instances`` / ``vote_instances_sample`` :1054-1190, ``postprocess``
 :2230-2259).  The reference's ``postprocess`` has two branches: ``process_instances`` is this driver's
@@ -9,11 +9,14 @@
 ``evaluate_prediction`` (:1300-1443, the reference's ``[evaluation] prediction_only_test`` branch
 :2207-2211) scores the dense prediction against ``[data] test_data`` before any instance is voted.
 
+``evaluate`` (:1193-1262, :1447-1536): the voted instance maps of --output-folder scored against the ground
+truth instances (`evaluate_instances`: this project's own definitions, the reference's evaluation package
+is not vendored).
+
 ``visualize`` (:1539-1606): patch mosaics of the prediction (``show_patches``) and instance pictures
 (``show_instances``).
 
-Only the tasks on this repository's path are provided; training, prediction and the evaluation of
-instance segmentations stay with the reference.  Usage, as in the reference README:
+Only the tasks on this repository's path are provided; training and prediction stay with the reference.  Usage, as in the reference README:
 
     python -m patchperpix_amd.run_ppp --setup setup01 --config default.toml --do label \
         --pred-folder <dir with *.zarr|*.hdf|*.npy> --output-folder <dir> [--sample NAME]
@@ -198,6 +201,76 @@ def evaluate_prediction(args, config):
     return result
 
 
+def evaluate(args, config):
+    """run_ppp.py:1447-1536 with `evaluate_sample` (:1193-1262), without the ``conic``, ``add_partly_val`` and
+    ``Parallel`` branches; ``[evaluation] evaluate_skeleton_coverage``, ``[evaluation] print_f_factor_perc_gt_0_8`` and
+    ``[data] add_partly_val`` are refused by name.  With ``one_instance_per_channel``, ``[data]
+    one_instance_per_channel_gt`` names the ground-truth dataset in place of ``gt_key`` (:1215-1218), for every layout
+    of ``test_data`` as in the reference.  The samples are the
+    ``*.<vote_instances.output_format>`` files of --output-folder; the ground truth comes from ``[data]
+    test_data`` as `evaluate_prediction` resolves it: a ``.zarr`` / ``.hdf`` file with ``<sample>/<gt_key>``, or a
+    folder of ``<sample>.<input_format>`` files with ``gt_key``.  ``res_key`` and the switches come from
+    ``[evaluation]``, ``overlapping_inst`` from ``[vote_instances] one_instance_per_channel``.  Per sample
+    `evaluate_instances.evaluate_file` writes ``<output_folder>/<sample>.toml`` and ``<metric> sample <name>:
+    <value>`` is logged.  With ``[evaluation] summary`` (a list of dotted keys) ``summary.csv`` goes to
+    --output-folder: the header ``sample`` plus the keys, one row per sample, floats by repr -- this project's
+    own format, as ``prediction_metrics.json`` is.  Returns the mean of ``[evaluation] metric`` over the
+    samples."""
+    import numpy as np
+    from . import evaluate_instances as ei
+    cfg = config["evaluation"]
+    if cfg.get("evaluate_skeleton_coverage"):
+        raise NotImplementedError("[evaluation] evaluate_skeleton_coverage is not provided by this repository; unset it")
+    if cfg.get("print_f_factor_perc_gt_0_8"):
+        raise NotImplementedError("[evaluation] print_f_factor_perc_gt_0_8 is not provided by this repository; unset it")
+    if config["data"].get("add_partly_val"):
+        raise NotImplementedError("[data] add_partly_val is not provided by this repository; unset it")
+    fmt = config["vote_instances"].get("output_format", "hdf")
+    data = config["data"]["test_data"]
+    samples = get_list_samples(args.output_folder, fmt, args.sample)
+    t0 = time.time()
+    metrics, dicts = {}, []
+    for sample in samples:
+        if data.rstrip("/").endswith(("zarr", "hdf")):
+            gt_path, gt_key = data, sample + "/" + config["data"]["gt_key"]
+        else:
+            gt_path = os.path.join(data, sample + "." + config["data"]["input_format"])
+            gt_key = config["data"]["gt_key"]
+        if config["vote_instances"].get("one_instance_per_channel") and config["data"].get("one_instance_per_channel_gt"):
+            gt_key = config["data"]["one_instance_per_channel_gt"]
+            logger.info("call evaluation with key %s", gt_key)
+        metric_dict = ei.evaluate_file(
+            os.path.join(args.output_folder, sample + "." + fmt), gt_path, res_key=cfg["res_key"], gt_key=gt_key,
+            out_dir=args.output_folder, suffix="",
+            foreground_only=cfg.get("foreground_only", False),
+            debug=config.get("general", {}).get("debug", False),
+            from_scratch=cfg.get("from_scratch", False),
+            overlapping_inst=config["vote_instances"].get("one_instance_per_channel", False),
+            use_linear_sum_assignment=cfg.get("use_linear_sum_assignment", False),
+            metric=cfg.get("metric", None), filterSz=cfg.get("filterSz", None),
+            localization_criterion=cfg.get("localization_criterion", "iou"),
+            remove_small_components=cfg.get("remove_small_components", None),
+            keep_gt_shape=cfg.get("keep_gt_shape", False), partly=False,
+            visualize=cfg.get("visualize", False), visualize_type=cfg.get("visualize_type", "nuclei"),
+            assignment_strategy=cfg.get("assignment_strategy", "hungarian"),
+            evaluate_false_labels=cfg.get("evaluate_false_labels", False),
+            unique_false_labels=cfg.get("unique_false_labels", False),
+            add_general_metrics=cfg.get("add_general_metrics", []),
+            add_multi_thresh_metrics=cfg.get("add_multi_thresh_metrics", []))
+        dicts.append(metric_dict)
+        value = float(ei.lookup(metric_dict, cfg["metric"]))
+        logger.info("%s sample %-19s: %.4f", cfg["metric"], sample, value)
+        metrics[sample] = value
+    if "summary" in cfg:
+        with open(os.path.join(args.output_folder, "summary.csv"), "w") as f:
+            f.write(",".join(["sample"] + list(cfg["summary"])) + "\n")
+            for sample, metric_dict in zip(samples, dicts):
+                cells = [ei.lookup(metric_dict, k) for k in cfg["summary"]]
+                f.write(",".join([sample] + [repr(c) if isinstance(c, float) else str(c) for c in cells]) + "\n")
+    logger.info("time evaluate (%d samples): %.2fs", len(samples), time.time() - t0)
+    return float(np.mean(list(metrics.values()))) if metrics else float("nan")
+
+
 def visualize(args, config):
     """run_ppp.py:1539-1606, by ``[visualize]``'s switches, for the samples of ``samples_to_visualize``.
 
@@ -252,7 +325,7 @@ def main(argv=None):
     ap.add_argument("-c", "--config", action="append", required=True)
     ap.add_argument("-a", "--app", default="flylight")
     ap.add_argument("-s", "--setup", default="setup01")
-    ap.add_argument("-d", "--do", nargs="+", default=["label"], choices=["label", "decode", "postprocess", "postprocess_fg", "evaluate_prediction", "visualize"])
+    ap.add_argument("-d", "--do", nargs="+", default=["label"], choices=["label", "decode", "postprocess", "postprocess_fg", "evaluate_prediction", "evaluate", "visualize"])
     ap.add_argument("--pred-folder", required=True)
     ap.add_argument("--output-folder", required=True)
     ap.add_argument("--checkpoint", default=None)
@@ -262,7 +335,7 @@ def main(argv=None):
     config = load_config(args.config)
     for task in args.do:
         {"label": label, "decode": decode, "postprocess": postprocess, "postprocess_fg": postprocess_fg,
-         "evaluate_prediction": evaluate_prediction, "visualize": visualize}[task](args, config)
+         "evaluate_prediction": evaluate_prediction, "evaluate": evaluate, "visualize": visualize}[task](args, config)
 
 
 if __name__ == "__main__":
