@@ -38,12 +38,8 @@
 namespace ppp {
 
 static constexpr int V2_WAVES = 4;
-#ifndef PPP_S1_PREFETCH
-#define PPP_S1_PREFETCH(PX) ((PX) >= 9)
-#endif
-#ifndef PPP_S1_MINWAVES
-#define PPP_S1_MINWAVES(PX) ((PX) <= 7 ? 3 : 2)   // waves per SIMD the register budget must allow
-#endif
+static constexpr bool s1v2_prefetch(int PX) { return PX >= 9; }
+static constexpr int s1v2_minwaves(int PX) { return PX <= 7 ? 3 : 2; }   // waves per SIMD the register budget must allow
 
 // FLAT: the 64 base voxels of a wave are consecutive in the FLATTENED (y, x) order of a z-slice of
 // the consensus box, so a run may continue on the next line (two segments A / B, each with its
@@ -129,10 +125,8 @@ __device__ __forceinline__ bool tile_votes(const float *ia, const float *ib, con
             vote<VAL, EXACT, TH05>(th2, den, inv_den, ta, lim, ib[j * NC - kx], acc[j - kx + PX - 1],
                              cnt[j - kx + PX - 1], amb_min);
         }
-#ifndef PPP_V2_NOSCHED
         // keep the scheduler from interleaving all PX*PX votes (lane-mask register pressure)
         __builtin_amdgcn_sched_barrier(0);
-#endif
     }
     return amb_min <= 8u;
 }
@@ -144,7 +138,7 @@ __device__ __forceinline__ float ldf_at(const T *base, unsigned byte_off) {
 }
 
 template <typename T, int PX, int VAL, bool TH05, bool FLAT>
-__global__ void __launch_bounds__(64 * V2_WAVES, PPP_S1_MINWAVES(PX))
+__global__ void __launch_bounds__(64 * V2_WAVES, s1v2_minwaves(PX))
     consensus_v2_kernel(const T *__restrict__ pred, const uint8_t *__restrict__ ov,
                         float *__restrict__ cons, float *__restrict__ cnt_out, const Geo G,
                         const int n_rows, const int runs_per_line, const long long n_waves) {
@@ -304,7 +298,7 @@ __global__ void __launch_bounds__(64 * V2_WAVES, PPP_S1_MINWAVES(PX))
         // waves per SIMD anyway (9^3).  At 7^3 dropping it frees the registers for a third
         // wave WITHOUT spilling: 124 -> 102 ms (the spilled variant moved 22 GB of scratch
         // per launch); the load latency is covered by the other waves.
-        constexpr bool PREFETCH = PPP_S1_PREFETCH(PX);
+        constexpr bool PREFETCH = s1v2_prefetch(PX);
         bool have = next_tile(kz, ky);
         if (PREFETCH && have) load_tile(kz, ky);
         while (have) {
@@ -427,10 +421,7 @@ struct V2W {
     static constexpr int NC = 64 + (PX - 1);     // centres per run
     static constexpr int NT = 64 + 2 * (PX - 1); // target pixels per run
     static constexpr int NACC = 2 * PX - 1;
-#ifndef PPP_S1W_NW
-#define PPP_S1W_NW 25
-#endif
-    static constexpr int NW = PPP_S1W_NW;        // accumulators per wave
+    static constexpr int NW = 25;                // accumulators per wave
     static constexpr int NWIN = (NACC + NW - 1) / NW;
     static constexpr int IMG = 2 * PX * NC;
 };
@@ -529,10 +520,7 @@ __global__ void __launch_bounds__(64, 2)
                 bool big = false;
                 // U elements at a time: all their (independent) loads first, then the
                 // classification -- one element per iteration waits a full memory latency each
-#ifndef PPP_S1W_U
-#define PPP_S1W_U 8
-#endif
-                constexpr int U = PPP_S1W_U;
+                constexpr int U = 8;
                 int i = lane, j = 0;                       // element e = j * NC + i (+ PX*NC for "about w")
                 static_assert(K::NC >= 64, "one wrap per step of 64");
                 for (int e0 = lane; e0 < K::IMG; e0 += 64 * U) {

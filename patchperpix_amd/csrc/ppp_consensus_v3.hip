@@ -31,8 +31,6 @@
 //     multiplied into the "about u" operands; everything that depends on the TARGET pixels
 //     (u and w = u + d valid foreground) is constant per accumulator and applied once, when the
 //     accumulators are written.
-#include <stdlib.h>
-
 #include <algorithm>
 
 #include "ppp_kernels.hpp"
@@ -46,36 +44,22 @@ typedef const volatile __attribute__((address_space(3))) v4f *lds_v4f_cvp;
 
 // waves per workgroup: LDS (16 / 20 KB per wave at 7^3 / 9^3) decides how many waves a CU holds;
 // small workgroups waste less of it
-#ifndef PPP_S1V3_WAVES
-#define PPP_S1V3_WAVES(PX) 1
-#endif
+static constexpr int V3_WAVES = 1;
 // votes whose chains are interleaved (dependent packed operations issue back to back otherwise)
-#ifndef PPP_S1V3_GROUP
-#define PPP_S1V3_GROUP 3
-#endif
-#ifndef PPP_S1V3_PREFETCH
-#define PPP_S1V3_PREFETCH(PX) ((PX) >= 9)
-#endif
-#ifndef PPP_S1V3_MINWAVES
-#define PPP_S1V3_MINWAVES(PX) ((PX) <= 7 ? 3 : 2)
-#endif
+static constexpr int S1V3_GROUP = 3;
+static constexpr bool s1v3_prefetch(int PX) { return PX >= 9; }
+static constexpr int s1v3_minwaves(int PX) { return PX <= 7 ? 3 : 2; }
 
-// "about w" image: PPP_S1V3_SPLIT=1 keeps {t slice 0, t slice 1} (8 bytes) and the codes (4 bytes)
+// "about w" image: the split form keeps {t slice 0, t slice 1} (8 bytes) and the codes (4 bytes)
 // in two arrays -- a ds_read_b64 and a ds_read_b32 per vote pair, 12 bytes instead of the 16 of
 // the {t0, t1, codes, pad} element read by ds_read_b128: the LDS pipe is what this kernel keeps
 // busiest (~80 % next to 46 % VALU issue), and a quarter of its bytes were padding.
 // Measured (tools/time_s1.py, profiles/r04_q_s1_split.txt): 7^3 46.2 -> 41.3 ms on the 140^3 volume
 // and 66.0 -> 62.7 ms on the 512^2 slab; 9^3 264.7 -> 268.3 ms (the second LDS instruction per pair
 // costs more than the bytes save there): taken up to 7^3.
-#ifndef PPP_S1V3_SPLIT
-#define PPP_S1V3_SPLIT(PX) ((PX) <= 7)
-#endif
+static constexpr bool s1v3_split(int PX) { return PX <= 7; }
 // iterations of the classification whose chains are interleaved
-#ifndef PPP_S1V3_CGROUP
-#define PPP_S1V3_CGROUP 3
-#endif
-typedef const volatile __attribute__((address_space(3))) float *lds_f32_cvp;
-typedef const volatile __attribute__((address_space(3))) uint32_t *lds_u32_cvp;
+static constexpr int S1V3_CGROUP = 3;
 
 template <int PX, bool FLAT>
 struct V3 {
@@ -134,22 +118,15 @@ __device__ __forceinline__ void tile_votes3(const v2f *at, const v2f *cfp, lds_v
     // -- 4d/3 is never closer than 1/6 ulp to a rounding boundary; checked exhaustively by
     // tests/csrc/th05_quotient.c
     const v2f kq = splat(-0.25f), c43 = splat(0x1.555556p+0f), c43lo = splat(-0x1.555556p-25f);
-    constexpr int GS = PPP_S1V3_GROUP;
+    constexpr int GS = S1V3_GROUP;
     constexpr int NJG = (PX + GS - 1) / GS;     // groups per kx
     constexpr int NG = PX * NJG;                // groups per tile, n -> kx = PX-1 - n / NJG
     v4f bcur[GS], bnxt[GS];
     v2f ta, ta_nxt, fa, fa_nxt, ga, na;
     uint32_t ca = 0u;
-    // (experiment PPP_S1V3_ADDRREGS=1: the reads of a group through address registers of their own)
-#ifndef PPP_S1V3_ADDRREGS
-#define PPP_S1V3_ADDRREGS 0
-#endif
-    lds_v4f_cvp btg[GS];
+    lds_v4f_cvp btg[GS];      // (one copy of the image pointer per vote of a group)
 #pragma unroll
-    for (int g = 0; g < GS; ++g) {
-        btg[g] = bt;
-        if (PPP_S1V3_ADDRREGS) asm volatile("" : "+v"(btg[g]));
-    }
+    for (int g = 0; g < GS; ++g) btg[g] = bt;
     auto used = [](int kx, int j) { return j < PX && !(ROW0 && j <= kx); };
     auto load_group = [&](int n, v4f (&b)[GS], v2f &t, v2f &f) {
         const int kx = PX - 1 - n / NJG, jg = (n % NJG) * GS;
@@ -157,35 +134,19 @@ __device__ __forceinline__ void tile_votes3(const v2f *at, const v2f *cfp, lds_v
 #pragma unroll
         for (int g = 0; g < GS; ++g)
             if (used(kx, jg + g)) {
-                if constexpr (PPP_S1V3_SPLIT(PX)) {
+                if constexpr (s1v3_split(PX)) {
                     const v2f t2 = bt2[(jg + g) * NC - kx];
-#ifdef PPP_S1_ABL_NOCODEREAD
-                    b[g] = (v4f){t2.x, t2.y, __uint_as_float(0x00010001u), 0.0f};   // (timing experiment: 8 bytes per pair)
-#else
                     b[g] = (v4f){t2.x, t2.y, __uint_as_float(ct[(jg + g) * NC - kx]), 0.0f};
-#endif
                 } else {
-#ifdef PPP_S1_ABL_NOLDS
-                    b[g] = (v4f){t.x * 0.9f, t.y * 0.8f, __uint_as_float(0x00010001u), 0.0f};   // (timing experiment)
-#else
                     b[g] = btg[g][(jg + g) * NC - kx];
-#endif
                 }
             }
     };
-    // PPP_S1V3_DEPTH = 2 (experiment): the LDS reads run TWO groups ahead of the arithmetic
-#ifndef PPP_S1V3_DEPTH
-#define PPP_S1V3_DEPTH 1
-#endif
-    constexpr int DEPTH = (PPP_S1V3_DEPTH == 2 && NJG >= 2) ? 2 : 1;    // (one new kx per two groups at most)
-    v4f bnx2[GS];
     load_group(0, bcur, ta, fa);
-    if (DEPTH == 2 && NG > 1) load_group(1, bnxt, ta_nxt, fa_nxt);
 #pragma unroll
     for (int n = 0; n < NG; ++n) {
         const int kx = PX - 1 - n / NJG, jg = (n % NJG) * GS;
-        if (DEPTH == 1) { if (n + 1 < NG) load_group(n + 1, bnxt, ta_nxt, fa_nxt); }
-        else if (n + 2 < NG) load_group(n + 2, bnx2, ta_nxt, fa_nxt);
+        if (n + 1 < NG) load_group(n + 1, bnxt, ta_nxt, fa_nxt);
         if (jg == 0) {
             // centre factor {0, 1}.  EXACT (a value outside [0, 1] in the tile): select, so that an
             // infinite prediction at a centre that votes nothing contributes 0 like the reference's
@@ -241,13 +202,11 @@ __device__ __forceinline__ void tile_votes3(const v2f *at, const v2f *cfp, lds_v
             if (!used(kx, jg + g)) continue;
             const int i = jg + g - kx + PX - 1;
             acc[i] = acc[i] + y[g];
-#ifndef PPP_S1_ABL_NOCNT
             tc[i] = pk_mad_u16(ca, cb[g], tc[i]);
-#endif
         }
         if (n + 1 < NG) {
 #pragma unroll
-            for (int g = 0; g < GS; ++g) { bcur[g] = bnxt[g]; if (DEPTH == 2) bnxt[g] = bnx2[g]; }
+            for (int g = 0; g < GS; ++g) bcur[g] = bnxt[g];
             if ((n + 1) % NJG == 0) { ta = ta_nxt; fa = fa_nxt; }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -260,9 +219,7 @@ __device__ __forceinline__ void tile_votes3(const v2f *at, const v2f *cfp, lds_v
 // 48 x 512 x 512 volume: 252 vs 264 ms) -- but with the 512^3 block resident (channel stride
 // 268 MB, per-lane offsets up to 2.1 GB) the same launch takes 309 ms with buffer loads against
 // 281 ms with global loads and 291 ms for round 4's kernel (profiles/r05_l_s1_tile.txt).
-#ifndef PPP_S1V3_BUFLOAD
-#define PPP_S1V3_BUFLOAD 0
-#endif
+// The two centre values of a tile (row of `mid`, offsets far below 2 GB) stay buffer loads.
 // raw buffer loads: scalar base (the resource), 32-bit per-lane byte offset, scalar byte offset.
 // DATA_FORMAT_32 in word 3 (what gfx9 wants of an untyped buffer), num_records = 2^32 - 1.
 typedef __amdgpu_buffer_rsrc_t BufRsrc;
@@ -285,7 +242,7 @@ template <>
 __device__ __forceinline__ unsigned buf_ldraw<bf16_t>(BufRsrc r, unsigned voff, unsigned soff) {
     return (unsigned)__builtin_amdgcn_raw_buffer_load_b16(r, (int)voff, (int)soff, 0);
 }
-// (experiment switch PPP_S1V3_BUFLOAD=0: the same bits by global loads, saddr + 32-bit voffset)
+// the same bits by global loads, saddr + 32-bit voffset
 template <typename T>
 __device__ __forceinline__ unsigned glb_ldraw(const T *base, unsigned voff, unsigned soff);
 // (an empty asm pins a COPY of the offset per load: it keeps the zero extension next to the load --
@@ -348,15 +305,14 @@ __device__ __forceinline__ float ldf_at3(const T *base, unsigned byte_off) {
 enum { V3_DENSE = 0, V3_LIST = 1, V3_ZERO = 2 };
 
 template <typename T, int PX, bool FLAT, bool CLEAN, int MODE = V3_DENSE>
-__global__ void __launch_bounds__(64 * PPP_S1V3_WAVES(PX), PPP_S1V3_MINWAVES(PX))
+__global__ void __launch_bounds__(64 * V3_WAVES, s1v3_minwaves(PX))
     consensus_v3_kernel(const T *__restrict__ pred, const uint8_t *__restrict__ ov,
                         float *__restrict__ cons, float *__restrict__ cnt_out, const Geo G,
                         const int n_rows, const int runs_per_line, const int bZ2,
                         const long long n_waves, const uint32_t *__restrict__ items) {
     using K = V3<PX, FLAT>;
     constexpr int NIT = K::NIT;
-    constexpr int V3_WAVES = PPP_S1V3_WAVES(PX);
-    constexpr bool SPLIT = PPP_S1V3_SPLIT(PX);
+    constexpr bool SPLIT = s1v3_split(PX);
     constexpr bool VOTES = MODE != V3_ZERO;
     __shared__ v4f lds_bt[V3_WAVES][SPLIT || !VOTES ? 1 : K::NELP];
     __shared__ v2f lds_bt2[V3_WAVES][SPLIT && VOTES ? K::NELP : 1];
@@ -515,12 +471,11 @@ __global__ void __launch_bounds__(64 * PPP_S1V3_WAVES(PX), PPP_S1V3_MINWAVES(PX)
         };
         unsigned ra[2][NIT], rb[2][NIT], rc[2][2];             // loaded bits, [slice]
         bool lz0 = true, lz1 = false, la = true, lb = false;   // flags of the LOADED tile
-        // issue the (independent, unconditional) loads of one tile into registers: buffer loads
-        // -- a scalar resource per operand image (base = the tile's channel row at the centre
-        // row of slice 0), the lane's 32-bit element offset, the second slice as scalar offset;
-        // no vector instruction per load.  A slice whose centre slice is not interior reads the
-        // other slice's rows (in bounds; its centre factors are 0).  FLAT: both lines are inside
-        // the z-slice (see v2).
+        // issue the (independent, unconditional) loads of one tile into registers: a scalar base
+        // per operand image (the tile's channel row at the centre row of slice 0), the lane's
+        // 32-bit element offset, the second slice as scalar offset.  A slice whose centre slice
+        // is not interior reads the other slice's rows (in bounds; its centre factors are 0).
+        // FLAT: both lines are inside the z-slice (see v2).
         auto load_tile = [&](int z, int y) {
             lz0 = z_ok0; lz1 = z_ok1; la = row_a_ok; lb = row_b_ok;
             const int cz = uz - z + G.rz;
@@ -529,26 +484,13 @@ __global__ void __launch_bounds__(64 * PPP_S1V3_WAVES(PX), PPP_S1V3_MINWAVES(PX)
             const unsigned s1 = __builtin_amdgcn_readfirstlane((z_ok1 && z_ok0) ? (unsigned)(slice * (long long)sizeof(T)) : 0u);
             const long long cha = (long long)((z * G.py + y) * PX) * G.V;
             const long long chb = (long long)(((z + dz) * G.py + (y + dy)) * PX) * G.V;
-            const BufRsrc qa = buf_rsrc(pred + cha + crow0), qb = buf_rsrc(pred + chb + crow0),
-                          qc = buf_rsrc(mid + crow0);
+            const BufRsrc qc = buf_rsrc(mid + crow0);
 #pragma unroll
             for (int it = 0; it < NIT; ++it) {
-#ifdef PPP_S1_ABL_NOLOAD
-                ra[0][it] = ra[1][it] = 0x3b00u + ((el_off[it] + (unsigned)(cha + crow0)) & 15u);   // (timing experiment)
-                rb[0][it] = rb[1][it] = 0x2e00u + ((el_off[it] + (unsigned)(chb + crow0)) & 15u);
-#else
-#if PPP_S1V3_BUFLOAD
-                ra[0][it] = buf_ldraw<T>(qa, el_off[it], 0u);
-                ra[1][it] = buf_ldraw<T>(qa, el_off[it], s1);
-                rb[0][it] = buf_ldraw<T>(qb, el_off[it], 0u);
-                rb[1][it] = buf_ldraw<T>(qb, el_off[it], s1);
-#else
                 ra[0][it] = glb_ldraw<T>(pred + cha + crow0, el_off[it], 0u);
                 ra[1][it] = glb_ldraw<T>(pred + cha + crow0, el_off[it], s1);
                 rb[0][it] = glb_ldraw<T>(pred + chb + crow0, el_off[it], 0u);
                 rb[1][it] = glb_ldraw<T>(pred + chb + crow0, el_off[it], s1);
-#endif
-#endif
             }
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
@@ -556,7 +498,7 @@ __global__ void __launch_bounds__(64 * PPP_S1V3_WAVES(PX), PPP_S1V3_MINWAVES(PX)
                 rc[1][c] = buf_ldraw<T>(qc, cf_off[c], s1);
             }
         };
-        constexpr bool PREFETCH = PPP_S1V3_PREFETCH(PX);
+        constexpr bool PREFETCH = s1v3_prefetch(PX);
         const v2f big26 = splat(0x1p26f), nbig26 = splat(-0x1p26f), hb = splat(0x1p25f),
                   nhb = splat(-0x1p25f);
         int n_fold = 0;
@@ -581,7 +523,7 @@ __global__ void __launch_bounds__(64 * PPP_S1V3_WAVES(PX), PPP_S1V3_MINWAVES(PX)
             //      CG iterations at a time, their chains interleaved stage by stage (a dependent
             //      packed operation right behind its producer costs a wait state)
             unsigned bigmax = 0u;
-            constexpr int CG = PPP_S1V3_CGROUP;
+            constexpr int CG = S1V3_CGROUP;
 #pragma unroll
             for (int it = 0; it < NIT; ++it)       // (the widening stays here, not next to the load)
                 asm volatile("" : "+v"(ra[0][it]), "+v"(ra[1][it]), "+v"(rb[0][it]), "+v"(rb[1][it]));
@@ -824,11 +766,6 @@ static hipError_t launch_vm_zero(float *S, const Geo &G, int n_rows, hipStream_t
     return hipGetLastError();
 }
 
-// (also the two-wave kernel's, ppp_consensus_v4.hip)
-hipError_t launch_vm_zero_faces(float *S, const Geo &G, hipStream_t s) {
-    return launch_vm_zero(S, G, (G.pz - 1) * G.wy + G.py, s);
-}
-
 template <typename T, int PX, bool FLAT, bool CLEAN>
 static hipError_t launch_v3f(const T *pred, const uint8_t *ov, float *cons, float *cnt,
                              const Geo &G, hipStream_t s) {
@@ -836,7 +773,6 @@ static hipError_t launch_v3f(const T *pred, const uint8_t *ov, float *cons, floa
     const int runs_per_line = FLAT ? (int)(((long long)G.cX * G.cY + 63) / 64) : (G.cX + 63) / 64;
     const int bZ2 = (G.cZ + 1) / 2;
     const long long n_waves = (long long)runs_per_line * (FLAT ? 1 : G.cY) * bZ2 * n_rows;
-    constexpr int V3_WAVES = PPP_S1V3_WAVES(PX);
     const long long n_blocks = (n_waves + V3_WAVES - 1) / V3_WAVES;
     if (n_blocks >= (1ll << 31)) return hipErrorInvalidValue;
     PPP_GRID_CHECK(n_blocks, 64 * V3_WAVES);
@@ -845,17 +781,7 @@ static hipError_t launch_v3f(const T *pred, const uint8_t *ov, float *cons, floa
         const hipError_t ez = launch_vm_zero(cons, G, n_rows, s);
         if (ez != hipSuccess) return ez;
     }
-    // (experiment PPP_S1_DYNLDS=<bytes>: dynamic LDS nobody uses, to LOWER the waves a CU holds -- what a
-    // wave more or less per SIMD is worth: profiles/r06_d_s1_occupancy.txt)
-    static EnvSwitch dyn("PPP_S1_DYNLDS");
-    const char *ed = dyn.get();
-    const unsigned dyn_lds = ed ? (unsigned)atoi(ed) : 0u;
-    if (dyn_lds) {
-        const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(&consensus_v3_kernel<T, PX, FLAT, CLEAN>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds);
-        if (ea != hipSuccess) return ea;
-    }
-    consensus_v3_kernel<T, PX, FLAT, CLEAN><<<dim3((unsigned)n_blocks), dim3(64 * V3_WAVES), dyn_lds, s>>>(
+    consensus_v3_kernel<T, PX, FLAT, CLEAN><<<dim3((unsigned)n_blocks), dim3(64 * V3_WAVES), 0, s>>>(
         pred, ov, cons, cnt, G, n_rows, runs_per_line, bZ2, n_waves, nullptr);
     return hipGetLastError();
 }
@@ -870,7 +796,6 @@ static hipError_t launch_v3f_lists(const T *pred, const uint8_t *ov, float *cons
     const int runs_per_line = FLAT ? (int)(((long long)G.cX * G.cY + 63) / 64) : (G.cX + 63) / 64;
     const int bZ2 = (G.cZ + 1) / 2;
     const long long n_waves = (long long)runs_per_line * (FLAT ? 1 : G.cY) * bZ2 * n_rows;
-    constexpr int V3_WAVES = PPP_S1V3_WAVES(PX);
     if (n_active + n_inactive != n_waves || n_waves >= (1ll << 32)) return hipErrorInvalidValue;   // (items are uint32)
     if (((long long)(PX - 1) * G.V + 2ll * G.X) * (long long)sizeof(T) >= (1ll << 32)) return hipErrorNotSupported;
     if (G.layout == PPP_CONS_VOXEL_MAJOR && !G.vm_open) {

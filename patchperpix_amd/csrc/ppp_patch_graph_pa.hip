@@ -34,7 +34,7 @@
 //
 // The adds of a candidate row.  A lane adds the row's PX staged values under its own PX-bit mask;
 // about one slot in ten is useful, so the instructions per slot are what counts: see
-// PPP_PA_EXEC_ADD below (7^3 small kernel: the add runs under a lane mask instead of masking the
+// PA_EXEC_ADD below (7^3 small kernel: the add runs under a lane mask instead of masking the
 // value).
 //
 // Measured and dropped (140^3 / 7^3 benchmark, thinned list, S5 kernel per step against 48.2 ms):
@@ -71,16 +71,7 @@ __device__ unsigned long long pa_stats[8];   // steps, planes, rows, useful slot
 // threads (= pair rows) per workgroup: the [words][threads] foreground bits of the B patches and
 // two row buffers must fit 64 KB of LDS
 template <int PX> struct PaCfg {
-#ifndef PPP_PA_MINWAVES7
-#define PPP_PA_MINWAVES7 8
-#endif
-#ifndef PPP_PA_THREADS9
-#define PPP_PA_THREADS9 256
-#endif
-    static constexpr int THREADS = PX >= 9 ? PPP_PA_THREADS9 : 256;
-#ifndef PPP_PA_SINGLE_BUF_FROM
-#define PPP_PA_SINGLE_BUF_FROM 7
-#endif
+    static constexpr int THREADS = 256;
     // Occupancy is what this kernel lacks (measured, 140^3 / 7^3 and 128^3 / 9^3):
     //   7^3: two row buffers + 5 waves/SIMD (91 VGPRs) 621 ms; ONE buffer (two barriers per
     //        pixel, 21 KB LDS -> 7 workgroups per CU) + 7 waves/SIMD (72 VGPRs, 20 spilled)
@@ -91,27 +82,21 @@ template <int PX> struct PaCfg {
     //   7^3 with the pixel list replaced by a scalar bit iterator and 8 floats of row padding:
     //        20.2 KB of LDS -> 8 workgroups per CU, 8 waves/SIMD (64 VGPRs, 22 spilled): 542 ms
     // so PX >= 7 takes one row buffer.
-    static constexpr int ROW_BUFS = PX >= PPP_PA_SINGLE_BUF_FROM ? 1 : 2;
+    static constexpr int ROW_BUFS = PX >= 7 ? 1 : 2;
     // waves per SIMD the register budget must allow
-    static constexpr int MIN_WAVES = PX <= 7 ? PPP_PA_MINWAVES7 : (PX >= 25 ? 1 : (THREADS == 512 ? 4 : (ROW_BUFS == 1 ? 3 : 2)));
+    static constexpr int MIN_WAVES = PX <= 7 ? 8 : (PX >= 25 ? 1 : 3);
     // Small workgroups for lists with few rows per patch (after set-cover thinning a patch has
     // ~60 dispatched rows at 7^3): with 256 threads three of four waves only stage and wait
     // (29 % of the issued instructions on the thinned 140^3 volume), and the 11 KB of B-patch
     // bits they reserve cap the CU at 8 workgroups.  One or two waves: 11.6 KB -> 13 per CU, and
     // a register budget without spills.
     static constexpr int THREADS_SMALL = PX >= 25 ? 64 : (PX >= 9 ? 128 : 64);
-#ifndef PPP_PA_MINWAVES_SMALL9
-#define PPP_PA_MINWAVES_SMALL9 2
-#endif
     // (Round 11, the cubic instantiations -- 96 VGPRs at 7^3 / 64, 114 at 9^3 / 128, nothing spilled -- with
     // other bounds, alternating with the defaults in one call: 7^3 with 3 and 5 waves 35.07-35.24 ms against
     // 35.15-35.25 ms per step at 140^3, 9^3 with 4 waves 5.188 s against 5.187 s at 512^3; the registers do
     // not change with the bound and LDS, not registers, caps the workgroups per CU: the bounds stay,
     // profiles/r11_a_bench_ab.txt.)
-#ifndef PPP_PA_MINWAVES_SMALL7
-#define PPP_PA_MINWAVES_SMALL7 4
-#endif
-    static constexpr int MIN_WAVES_SMALL = PX >= 25 ? 1 : (PX >= 9 ? PPP_PA_MINWAVES_SMALL9 : PPP_PA_MINWAVES_SMALL7);
+    static constexpr int MIN_WAVES_SMALL = PX >= 25 ? 1 : (PX >= 9 ? 2 : 4);
 };
 // Patch widths whose per-patch kernel reads thinning masks made beforehand (patch_graph_lcg_kernel)
 // instead of running the generator: all 3-d widths.  How the masks reach the lanes decides whether
@@ -123,19 +108,7 @@ template <int PX> struct PaCfg {
 // 39 registers less) and the mask of a chunk requested while the chunk before it is worked on:
 // 1046 + 33 ms for the masks.  7^3 (140^3): 72 -> 48 + 5 ms.  The 25-wide 2-d kernel is not
 // generator-bound (235 -> 230 + 9 ms) and keeps it.
-#ifndef PPP_PA_MASKS_MAX_PX
-#define PPP_PA_MASKS_MAX_PX 9
-#endif
-static constexpr int PA_MASKS_MAX_PX = PPP_PA_MASKS_MAX_PX;
-// experiments: 1 / 0 = the next row loaded after the pixel step / into registers during it for
-// every width (default -1: after the step where masks are read); the mask of a chunk fetched at
-// its use (0) or one chunk ahead (1)
-#ifndef PPP_PA_NO_ROW_PREFETCH
-#define PPP_PA_NO_ROW_PREFETCH -1
-#endif
-#ifndef PPP_PA_MASK_AHEAD
-#define PPP_PA_MASK_AHEAD 1
-#endif
+static constexpr int PA_MASKS_MAX_PX = 9;
 // The masked add of a candidate row, 7^3 small kernel (140^3 benchmark, thinned list, S5 kernel per
 // step, parent and variants alternating in one call, three runs each; profiles/r10_a_bench_ab.txt):
 //   0  acc += rowq[t] & sel(t): bit-field extract, and, add per slot               47.9-48.0 ms
@@ -160,9 +133,7 @@ static constexpr int PA_MASKS_MAX_PX = PPP_PA_MASKS_MAX_PX;
 // when both operands are.  It also needs f32 denormals kept (the HIP default, and what this library
 // is built with): with them flushed, form 0's `acc + 0.0f` would flush a denormal acc that a skipped
 // slot leaves alone.
-#ifndef PPP_PA_EXEC_ADD
-#define PPP_PA_EXEC_ADD 1
-#endif
+static constexpr int PA_EXEC_ADD = 1;
 static constexpr int PA_PAD = 8;       // floats of slack either side of the staged row (a masked row read overshoots by < PX)
 
 // The window geometry the kernels of this file compute with.  CUBE = false reads it from Geo at run
@@ -288,22 +259,15 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
         for (int j = 0; j < RPC; ++j) e |= ((m >> (c * RPC + j)) & 1u) ? ((u64)RM << (PX * j)) : 0ull;
         return e;
     };
-    // x mask repeated in every row, by doubling (rows beyond the chunk are harmless: every use
-    // is ANDed with an EY mask, which is clear there)
+    // x mask repeated in every row (rows beyond the chunk are harmless: every use is ANDed with
+    // an EY mask, which is clear there)
     auto repeat_x = [&](uint32_t m) -> u64 {
-#ifdef PPP_PA_REPEAT_BY_DOUBLING
-        u64 e = m;
-#pragma unroll
-        for (int n = 1; n < RPC; n *= 2) e |= e << (PX * n);
-        return e;
-#else
         // one multiply by the constant with a 1 at the start of every row (the PX-bit fields
         // do not overlap, so there are no carries); rows >= RPC are not needed
         u64 rep = 0;
 #pragma unroll
         for (int j = 0; j < RPC; ++j) rep |= 1ull << (PX * j);
         return (u64)m * rep;
-#endif
     };
 
     // ---- which (patch, chunk) is this workgroup?  binary search in the chunk prefix sums
@@ -364,7 +328,7 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
     // thinning decisions made beforehand by patch_graph_lcg_kernel (below): position of this
     // pair's masks in `drops`, < 0 = none (this kernel runs the LCG itself)
     constexpr bool MASKS = PX <= PA_MASKS_MAX_PX;
-    constexpr bool NOPF = PPP_PA_NO_ROW_PREFETCH < 0 ? MASKS : PPP_PA_NO_ROW_PREFETCH != 0;
+    constexpr bool NOPF = MASKS;    // the next row is loaded after the pixel step where masks are read
     long long soff = -1;
     if (live) {
         if (MASKS && drops != nullptr) soff = drop_off[pos];
@@ -430,7 +394,7 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
         const int z1o = r1 / (geo.py() * PX), y1o = (r1 / PX) % geo.py(), x1o = r1 % PX;
         return S + (baseA + (long long)row_slice(G, az + z1o - geo.rz()) * sZ + (long long)(y1o - geo.ry()) * sY + (x1o - PX / 2)) * W;
     };
-    float acc = 0.0f;               // (+0.0f: the masked add of PPP_PA_EXEC_ADD relies on it)
+    float acc = 0.0f;               // (+0.0f: the masked add of PA_EXEC_ADD relies on it)
     unsigned fg_cnt = 0;
 #ifdef PA_STATS
     unsigned long long st_0 = 0, st_1 = 0, st_2 = 0, st_3 = 0, st_4 = 0, st_5 = 0;
@@ -512,21 +476,18 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
             const u64 RXf = repeat_x(mx.f), RXbk = repeat_x(mx.bk), RXst = repeat_x(mx.st),
                       RXin = in_b ? repeat_x(mx.in) : 0ull, RXnn = repeat_x(mx.pos | mx.zero),
                       RXzero = repeat_x(mx.zero);
-#if PPP_PA_MASK_AHEAD
+            // the mask of a chunk is requested one chunk ahead
             // (planes outside the lane's intersection are not fetched)
             auto fetch = [&](int z, int c) -> u64 {
                 return has_blk && z < geo.pz() && ((mz.in >> z) & 1u) ? drops[blk + z * NCH + c] : 0ull;
             };
             u64 pend = fetch(z_lo, 0);
-#endif
             for (int z2o = z_lo; z2o <= z_hi; ++z2o) {
                 const uint32_t zb = 1u << z2o;
                 const bool z_f = mz.f & zb, z_bk = mz.bk & zb, z_pos = mz.pos & zb, z_zero = mz.zero & zb,
                            z_st = mz.st & zb, z_in = mz.in & zb;
                 if (__ballot(z_f || z_bk || z_in) == 0ull) {
-#if PPP_PA_MASK_AHEAD
                     pend = fetch(z2o + 1, 0);
-#endif
                     continue;
                 }
                 const int qz = mz.q0 + z2o;
@@ -592,10 +553,8 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
                 // chunk of few rows (9^3: rows 7-8, 18 bits) -- half the mask arithmetic
                 auto chunk = [&](auto mtag, const int c) {
                     using M = decltype(mtag);
-#if PPP_PA_MASK_AHEAD == 1
                     const u64 dropped = pend;
                     pend = c + 1 < NCH ? fetch(z2o, c + 1) : fetch(z2o + 1, 0);
-#endif
                     const int c_first = c * RPC;                       // first row of the chunk
                     const int c_rows = min(RPC, geo.py() - c_first);
                     if (c_rows <= 0) return;
@@ -628,21 +587,13 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
                         valid = (M)(((((u64)mi << 32) | lo) >> sh) | (sh ? ((u64)hi << (64 - sh)) : 0ull));
                         valid &= nb >= (int)(8 * sizeof(M)) ? (M)~(M)0 : (M)(((M)1 << nb) - (M)1);
                     }
-#ifdef PPP_PA_ABL_NOLCG   // timing experiment only: results are wrong
-                    if (false) {
-#else
                     if (__ballot(inter != (M)0) != 0ull) {
-#endif
                         // thinning inside the patch intersection: the LCG advances on every
                         // foreground candidate of the intersection, in candidate order --
                         // either done beforehand (one mask of dropped candidates per chunk) ...
                         M lcg_hits = inter & valid;
                         if (has_blk) {
-#if PPP_PA_MASK_AHEAD == 1
                             valid &= (M) ~((M)dropped & inter);
-#else
-                            if (inter != (M)0) valid &= (M) ~((M)drops[blk + z2o * NCH + c] & inter);
-#endif
                             lcg_hits = (M)0;
                         }
                         // ... or here, for the lanes without precomputed masks
@@ -670,48 +621,8 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
                     fg_cnt += sizeof(M) == 8 ? __popcll((u64)(range & valid)) : __popc((uint32_t)(range & valid));
                     const M add = stored & valid;
                     if (__ballot(add != (M)0) == 0ull) return;
-#ifdef PPP_PA_ABL_NOADD   // timing experiment only: results are wrong
-                    if (add != (M)0) acc += 1.0f;
-                    return;
-#endif
                     // this lane's offset into the staged row for candidate (y2o = 0, x2o = 0)
                     const int idx0 = Lc + (qz * geo.wy() + my.q0) * geo.wx() + q0x;
-// (measured and rejected: 73 -> 79 ms on the thinned list, 540 -> 640 ms on the dense one --
-// the extra PX registers cost spills at the 64 / 128-VGPR budgets and every row is read)
-#ifndef PPP_PA_ROW_PIPELINE
-#define PPP_PA_ROW_PIPELINE 0
-#endif
-                    if constexpr (PPP_PA_ROW_PIPELINE && PX <= 9) {
-                        // The PX values of a row feed a chain of PX dependent adds; with the LDS
-                        // reads issued right in front of them a wave waits out the LDS latency
-                        // once per row (45 % of the wave-cycles parked at 3-4 waves per SIMD).
-                        // So the reads run ONE ROW AHEAD of the adds: row y2o + 1 is in flight
-                        // while row y2o is summed.  A row nobody needs is still read (lanes
-                        // without work point at slot 0): LDS bandwidth is not what is short.
-                        float nx[PX];
-                        auto fetch = [&](int y2o, float (&dst)[PX]) {
-                            const uint32_t rbn = (uint32_t)(add >> (PX * (y2o - c_first))) & RM;
-                            const float *rowq = cur + (rbn != 0u ? idx0 + y2o * geo.wx() : 0);
-#pragma unroll
-                            for (int t = 0; t < PX; ++t) dst[t] = rowq[t];
-                        };
-                        fetch(ya, nx);
-                        for (int y2o = ya; y2o <= yb; ++y2o) {
-                            float cv[PX];
-#pragma unroll
-                            for (int t = 0; t < PX; ++t) cv[t] = nx[t];
-                            if (y2o < yb) fetch(y2o + 1, nx);
-                            const uint32_t rb = (uint32_t)(add >> (PX * (y2o - c_first))) & RM;
-                            if (__ballot(rb != 0u) == 0ull) continue;
-                            PA_STAT(2, lane == 0 ? 1 : 0);
-                            PA_STAT(3, __popc(rb));
-#pragma unroll
-                            for (int t = 0; t < PX; ++t) {
-                                const int sel = ((int)(rb << (31 - t))) >> 31;
-                                acc += __int_as_float(__float_as_int(cv[t]) & sel);
-                            }
-                        }
-                    } else {
                     for (int y2o = ya; y2o <= yb; ++y2o) {
                         const uint32_t rb = (uint32_t)(add >> (PX * (y2o - c_first))) & RM;
                         if (__ballot(rb != 0u) == 0ull) continue;
@@ -720,13 +631,13 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
                         // lanes with nothing to add on this row may point anywhere: they read
                         // slot 0 (one broadcast address; what they read is masked to zero)
                         const float *rowq = cur + (rb != 0u ? idx0 + y2o * geo.wx() : 0);
-                        if constexpr (PPP_PA_EXEC_ADD != 0 && PX == 7 && PA_THREADS != PaCfg<PX>::THREADS) {
+                        if constexpr (PA_EXEC_ADD != 0 && PX == 7 && PA_THREADS != PaCfg<PX>::THREADS) {
                             // Two vector instructions per add slot instead of three (bit-field
                             // extract, and, add): the row's mask is reversed once, every doubling
                             // of it shifts one slot's bit out as the lane's carry, and the add runs
                             // under that lane mask (skipping a slot = adding +0.0: acc is never
                             // -0.0).  EXEC is changed and restored inside the one statement; the
-                            // row's values are its inputs.  See PPP_PA_EXEC_ADD above.
+                            // row's values are its inputs.  See PA_EXEC_ADD above.
                             uint32_t m = __builtin_bitreverse32(rb);      // slot t = bit 31 - t
                             const float v0 = rowq[0], v1 = rowq[1], v2 = rowq[2], v3 = rowq[3], v4 = rowq[4],
                                         v5 = rowq[5], v6 = rowq[6];
@@ -761,7 +672,6 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
                             acc += __int_as_float(__float_as_int(rowq[t]) & sel);
                         }
                         }
-                    }
                     }
                 };
                 // the last chunk of the 9-row planes holds (PX - (NCH-1) RPC) rows
@@ -1228,7 +1138,7 @@ hipError_t launch_patch_graph_pa(const void *pred, int dtype, const float *S, co
     if (W > (cube + threads - 1) / threads * threads) return hipErrorNotSupported;
     // candidate planes are handled as ceil(px / (64 / px)) 64-bit chunks of 64 / px rows
     if (G.py > (G.px + 64 / G.px - 1) / (64 / G.px) * (64 / G.px) || G.pz > 32) return hipErrorNotSupported;
-    const int row_bufs = G.px >= PPP_PA_SINGLE_BUF_FROM ? 1 : 2;
+    const int row_bufs = G.px >= 7 ? 1 : 2;
     const size_t lds = (size_t)(row_bufs * WB + ((words + 3) & ~3) + ((words * threads + 1) & ~1)) * 4;
     if (lds > 80 * 1024 || n_blocks >= (1ll << 31) || grid_too_big((unsigned long long)n_blocks, threads))
         return hipErrorNotSupported;

@@ -99,12 +99,10 @@
 
 namespace ppp {
 
-// waves per SIMD the register budget must allow (experiments: -DPPP_RW_MINWAVES(PX)=n).  More
+// waves per SIMD the register budget must allow.  More
 // resident waves do not help: 9^3 at 5 per SIMD (96 VGPRs, 14 spilled) 205 -> 247 ms on the 128^3
 // launch, 7^3 at 6 per SIMD (75 VGPRs, nothing spilled) 72.5 -> 73.1 ms at 140^3.
-#ifndef PPP_RW_MINWAVES
-#define PPP_RW_MINWAVES(PX) 4
-#endif
+static constexpr int RW_MINWAVES = 4;
 // LDS bank conflicts of the row reads.  A half-wave is 32 consecutive items; an item reads the row
 // image at -(plane * az + 17 * ay + ax) + const.  Enumerated (ax, ay, az) -- x-runs of nine lanes,
 // consecutive runs 17 floats apart -- the runs of ay and ay + 2 share seven banks: every read
@@ -112,7 +110,6 @@ namespace ppp {
 // (ax, az, ay) with the image's PLANE stride padded from 289 to 297 (= 9 mod 32), consecutive
 // runs sit 9 banks apart -- 0-8, 9-17, 18-26, 27-31 -- and conflicts remain only where a
 // half-wave straddles the step from the last az of one ay to the first of the next.
-// (-DPPP_RW_ZRUNS=0: the old enumeration and image.)
 // Measured (tools/time_s2.py, profiles/r04_j_s2_zruns.txt): 9^3 190 -> 166 ms at 128^3, 102 -> 84 ms
 // at 96^3; 7^3 62.2 -> 64.7 ms at 140^3 -- so only 9^3 takes it.  At 7^3 the conflicts were as bad as at
 // 9^3 -- SQ_LDS_BANK_CONFLICT 8.46e9 of SQ_LDS_IDX_ACTIVE 20.75e9, 41 % of the LDS cycles, at 140^3
@@ -122,25 +119,14 @@ namespace ppp {
 // 13 / 169, 0.38 at best for z-runs, 0.33 at best for any of the six enumerations on any pair of strides
 // (x-runs, line stride 39, plane stride 529), 0.30 with the enumeration chosen per row, and 0.10 with x-runs
 // padded to 8 lanes on a line stride of 40 -- which walks 1.4 x the chunks.  7^3 therefore deals its items
-// BY BANK (PPP_RW_BANKDEAL, round 7): 0.20 predicted on the unchanged image with the dense number of chunks.  With all nine az present (rows in the z-interior of a tile at
+// BY BANK (rw_bankdeal, round 7): 0.20 predicted on the unchanged image with the dense number of chunks.  With all nine az present (rows in the z-interior of a tile at
 // least 9 thick) the step to the next ay continues the lattice (81 = 17 mod 32 = the y stride):
 // the 16 x 8 x 16 tile has half of its items in such rows.
-#ifndef PPP_RW_ZRUNS
-#define PPP_RW_ZRUNS(PX) ((PX) == 9)
-#endif
+static constexpr bool rw_zruns(int PX) { return PX == 9; }
 // Round 7, 7^3: the items of a row are dealt to the lanes BY BANK (see rank_deal_table_kernel below).
-// (-DPPP_RW_BANKDEAL(PX)=0: the enumeration above for every patch size.)
-#ifndef PPP_RW_BANKDEAL
-#define PPP_RW_BANKDEAL(PX) ((PX) == 7)
-#endif
+static constexpr bool rw_bankdeal(int PX) { return PX == 7; }
 static constexpr int RW_PAD = 8;
-#ifndef PPP_RW_WAVES
-#define PPP_RW_WAVES 4
-#endif
-#ifndef PPP_RW_REVREADS
-#define PPP_RW_REVREADS 1
-#endif
-static constexpr int RW_WAVES = PPP_RW_WAVES;     // waves per workgroup
+static constexpr int RW_WAVES = 4;     // waves per workgroup
 // Mask words per centre, padded to whole 16-byte loads.  The masks are stored CENTRE-MAJOR,
 // M[centre][word]: a lane reads the 184 bytes of ITS centre with twelve 16-byte loads, and the
 // centres of a wave's chunk (9-runs of x neighbours) cover their cache lines densely.  The earlier
@@ -153,25 +139,17 @@ static constexpr int rw_mask_words(int C) { return (((C + 15) / 16) + 3) & ~3; }
 // Round 5: the two-bit masks in ROWS OF 16 X-NEIGHBOURS, M[row][quad of words][centre in row][4 words]:
 // the 16-byte load of quad q by the nine x-neighbours of a run touches 144 contiguous bytes (two or
 // three lines) instead of nine lines 184 bytes apart -- the bytes fetched stay the same, the
-// addresses the vector cache has to look up per load fall to a quarter.  PPP_RW_MASKBLK=0: centre-major.
-#ifndef PPP_RW_MASKBLK
-#define PPP_RW_MASKBLK 1
-#endif
+// addresses the vector cache has to look up per load fall to a quarter.
 // index (in 16-byte units) of quad 0 of the centre at x of line zy (score-box coordinates)
 __host__ __device__ __forceinline__ long long rw_mask_quad0(long long zy, int x, int sX, int quads) {
-    if (!PPP_RW_MASKBLK) return (zy * sX + x) * quads;
     return ((zy * ((sX + 15) >> 4) + (x >> 4)) * quads) * 16 + (x & 15);
 }
-static constexpr int RW_QSTRIDE = PPP_RW_MASKBLK ? 16 : 1;      // 16-byte units between a centre's quads
+static constexpr int RW_QSTRIDE = 16;      // 16-byte units between a centre's quads
 static size_t rw_mask_bytes(int sZ, int sY, int sX, int C) {
-    const size_t cols = PPP_RW_MASKBLK ? (size_t)((sX + 15) >> 4) * 16 : (size_t)sX;
+    const size_t cols = (size_t)((sX + 15) >> 4) * 16;
     return (size_t)sZ * sY * cols * rw_mask_words(C) * 4;
 }
-#ifndef PPP_RW_NOVOLATILE
 typedef const volatile __attribute__((address_space(3))) float *lds_f32_cvp2;
-#else
-typedef const __attribute__((address_space(3))) float *lds_f32_cvp2;
-#endif
 
 // acc + r * c with c a float16 in the low / high half of a register: the compiler selects
 // v_fma_mix_f32 (op_sel picks the half; the float16 -> float32 conversion is exact and part of the
@@ -542,7 +520,7 @@ __global__ void __launch_bounds__(256)
 // tools/s2_bank_sim.py restates this dealing and counts the passes.
 // entry: bit 15 = the slot holds an item, az << 8 | ay << 4 | ax relative to the row's first item.
 static constexpr int rw_deal_slots(int P) { return (P * P * P + 63) / 64 * 64; }
-static size_t rw_deal_bytes(int P) { return PPP_RW_BANKDEAL(P) ? (size_t)P * P * P * rw_deal_slots(P) * 2 : 0; }
+static size_t rw_deal_bytes(int P) { return rw_bankdeal(P) ? (size_t)P * P * P * rw_deal_slots(P) * 2 : 0; }
 template <int P>
 __global__ void __launch_bounds__(32) rank_deal_table_kernel(uint16_t *__restrict__ T, const int SY, const int SZ) {
     constexpr int SLOTS = rw_deal_slots(P), MAXOVER = 16;
@@ -583,7 +561,7 @@ __global__ void __launch_bounds__(32) rank_deal_table_kernel(uint16_t *__restric
 // uvalid_bits; the tile origin is tz_i * tz_step and the kernel's ragged-tile handling does the rest.  !DZ:
 // tz_step is TZ (the launches that do not choose their thickness keep their code).
 template <int PZ, int PY, int PX, int TZ, int TY, int TX, bool P1, bool DZ = false>
-__global__ void __launch_bounds__(64 * RW_WAVES, PPP_RW_MINWAVES(PX))
+__global__ void __launch_bounds__(64 * RW_WAVES, RW_MINWAVES)
     rank_wg_kernel(const float *__restrict__ S, const uint32_t *__restrict__ M,
                    const uint32_t *__restrict__ info, const uint8_t *__restrict__ valid,
                    float *__restrict__ score, const ppp_box sb, const Geo G, const int tiles_y,
@@ -610,9 +588,9 @@ __global__ void __launch_bounds__(64 * RW_WAVES, PPP_RW_MINWAVES(PX))
     constexpr int NST = (W + NTHR - 1) / NTHR;
     constexpr int NT = TZ * TY * TX;
     constexpr int UB = (TZ + 2 * RZ) * (TY + 2 * RY) * (TX + 2 * RX);
-    // plane stride of the row image (see PPP_RW_ZRUNS)
+    // plane stride of the row image (see rw_zruns)
     constexpr int SZ = WY * WX;
-    constexpr int SZP = PPP_RW_ZRUNS(PX) ? SZ + ((9 - SZ % 32) + 32) % 32 : SZ;
+    constexpr int SZP = rw_zruns(PX) ? SZ + ((9 - SZ % 32) + 32) % 32 : SZ;
     constexpr int LCP = LC + (PZ - 1) * (SZP - SZ);
     auto img = [](int e) -> int { return SZP == SZ ? e : (e / SZ) * SZP + e % SZ; };
     __shared__ float rowbuf[WZ * SZP + 2 * RW_PAD];
@@ -728,7 +706,7 @@ __global__ void __launch_bounds__(64 * RW_WAVES, PPP_RW_MINWAVES(PX))
     auto item_geom = [&](const RowG &r, int i0) -> ItemG {
         ItemG g;
         const int i = i0 + lane;
-        if constexpr (PPP_RW_BANKDEAL(PX)) {
+        if constexpr (rw_bankdeal(PX)) {
             // (dealt by bank: i0 + lane < 64 ceil(n_box / 64) <= the slots of a class; an empty slot reads
             // the row's first item, like a lane beyond the row in the enumeration below)
             const uint32_t e = dealT[r.cls * rw_deal_slots(PX) + i];
@@ -738,8 +716,8 @@ __global__ void __launch_bounds__(64 * RW_WAVES, PPP_RW_MINWAVES(PX))
         g.in = i < r.n_box;
         const int ii = g.in ? i : 0;
         g.ax = r.ax0 + ii % r.nx;
-        g.ay = PPP_RW_ZRUNS(PX) ? r.ay0 + ii / (r.nx * r.nz) : r.ay0 + (ii / r.nx) % r.ny;
-        g.az = PPP_RW_ZRUNS(PX) ? r.az0 + (ii / r.nx) % r.nz : r.az0 + ii / (r.nx * r.ny);
+        g.ay = rw_zruns(PX) ? r.ay0 + ii / (r.nx * r.nz) : r.ay0 + (ii / r.nx) % r.ny;
+        g.az = rw_zruns(PX) ? r.az0 + (ii / r.nx) % r.nz : r.az0 + ii / (r.nx * r.ny);
         }
         const int lz = r.uz + RZ - g.az - c0z, ly = r.uy + RY - g.ay - c0y, lx = r.ux + RX - g.ax - c0x;
         g.cl = (lz * TY + ly) * TX + lx;
@@ -750,11 +728,7 @@ __global__ void __launch_bounds__(64 * RW_WAVES, PPP_RW_MINWAVES(PX))
         return g;
     };
     // one-bit masks: the first PFQ 16-byte pieces of a centre's words + the word with P'[a], requested
-    // one chunk ahead (PPP_RW_PREFETCH=0: every chunk loads its masks when it starts, as the two-bit form)
-#ifndef PPP_RW_PREFETCH
-#define PPP_RW_PREFETCH 1
-#endif
-    constexpr bool PF = PPP_RW_PREFETCH != 0;
+    // one chunk ahead (the two-bit form loads a chunk's masks when the chunk starts)
     constexpr int PFQ = (W16P / 4) / 2;
     uint4 pfa[PFQ > 0 ? PFQ : 1];
     uint32_t pfw = 0u;
@@ -775,11 +749,7 @@ __global__ void __launch_bounds__(64 * RW_WAVES, PPP_RW_MINWAVES(PX))
 #pragma unroll
             for (int i = 0; i < NST; ++i) {
                 const int e = tid + i * NTHR;
-#ifdef PPP_RW_ABL_NOROW
-                st[i] = (float)e;                      // (timing experiment: no row fetches)
-#else
                 st[i] = e < W ? src[e] : 0.0f;
-#endif
             }
         }
         // pixels a of this voxel whose centre c = u + R - a lies in the tile
@@ -787,7 +757,7 @@ __global__ void __launch_bounds__(64 * RW_WAVES, PPP_RW_MINWAVES(PX))
         const int n_box = R.n_box;
         const int first = (wave + RW_WAVES - turn) % RW_WAVES;
         turn = (turn + ((n_box + 63) >> 6)) % RW_WAVES;
-        if constexpr (P1 && PF) {
+        if constexpr (P1) {
             // (the first chunk of a row is normally prefetched at the end of the row before)
             if (!pf_have && 64 * first < n_box) prefetch(R, 64 * first);
             pf_have = false;
@@ -800,7 +770,7 @@ __global__ void __launch_bounds__(64 * RW_WAVES, PPP_RW_MINWAVES(PX))
             (void)in; (void)q0;
             bool active = it.in && ((act_bits[cl >> 5] >> (cl & 31)) & 1u) != 0;
             uint32_t mw[NMW];
-            if constexpr (P1 && PF) {
+            if constexpr (P1) {
                 // ---- one-bit masks, software pipelined: the first half of this chunk's words and the
                 // word that holds P'[a] were requested a chunk ago; the second half is requested now
                 // and arrives behind the first half of the chain; then the next chunk's first half
@@ -832,32 +802,23 @@ __global__ void __launch_bounds__(64 * RW_WAVES, PPP_RW_MINWAVES(PX))
                 if (active) active = ((aword >> (a & 31)) & 1u) != 0;
                 if (__ballot(active) == 0) continue;
             } else {
-            // is a in P?  P bit of partner s: bit 8 (s >> 2 & 3) + (s & 3) of word s >> 4 (two-bit
-            // masks), bit s & 31 of word s >> 5 (one-bit masks)
-            if (active) {
-                if constexpr (P1) active = ((M[t * (long long)W16P + (a >> 5)] >> (a & 31)) & 1u) != 0;
-                else active = ((M[(q0 + (long long)(a >> 6) * RW_QSTRIDE) * 4 + ((a >> 4) & 3)] >> (8 * ((a >> 2) & 3) + (a & 3))) & 1u) != 0;
-            }
+            // is a in P?  P bit of partner s: bit 8 (s >> 2 & 3) + (s & 3) of word s >> 4
+            if (active)
+                active = ((M[(q0 + (long long)(a >> 6) * RW_QSTRIDE) * 4 + ((a >> 4) & 3)] >> (8 * ((a >> 2) & 3) + (a & 3))) & 1u) != 0;
             if (__ballot(active) == 0) continue;
             // (unconditional loads -- t is a centre of the tile for every lane -- then one select
             // per word: a predicated load is a branch per word)
-#ifdef PPP_RW_ABL_NOMASK
-            // (timing experiment: no mask loads -- every partner in P)
-#pragma unroll
-            for (int w = 0; w < NMW; ++w) mw[w] = (P1 ? 0xFFFFFFFFu : 0x0F0F0F0Fu) + (uint32_t)(t & 0);
-#else
             {
-                const uint4 *mc = reinterpret_cast<const uint4 *>(M) + (P1 ? t * (long long)(W16P / 4) : q0);
+                const uint4 *mc = reinterpret_cast<const uint4 *>(M) + q0;
 #pragma unroll
                 for (int q = 0; q < W16P / 4; ++q) {
-                    const uint4 v = mc[q * (P1 ? 1 : RW_QSTRIDE)];
+                    const uint4 v = mc[q * RW_QSTRIDE];
                     if (4 * q < NMW) mw[4 * q] = v.x;
                     if (4 * q + 1 < NMW) mw[4 * q + 1] = v.y;
                     if (4 * q + 2 < NMW) mw[4 * q + 2] = v.z;
                     if (4 * q + 3 < NMW) mw[4 * q + 3] = v.w;
                 }
             }
-#endif
             }
             if constexpr (!P1) {
 #pragma unroll
@@ -865,17 +826,10 @@ __global__ void __launch_bounds__(64 * RW_WAVES, PPP_RW_MINWAVES(PX))
             }
             float acc = active ? accs[cl] : 0.0f;
             lds_f32_cvp2 row = (lds_f32_cvp2)(rowbuf + RW_PAD + LCP - (az * SZP + ay * WX + ax));
-            // (experiment PPP_RW_ADDRREGS=1: the four reads of a group through address registers of
-            // their own instead of one register + immediate offsets)
-#ifndef PPP_RW_ADDRREGS
-#define PPP_RW_ADDRREGS 0
-#endif
+            // (one copy of the row pointer per read of a group: with a single pointer the compiler emits other code)
             lds_f32_cvp2 rowc[4];
 #pragma unroll
-            for (int i2 = 0; i2 < 4; ++i2) {
-                rowc[i2] = row;
-                if (PPP_RW_ADDRREGS) asm volatile("" : "+v"(rowc[i2]));
-            }
+            for (int i2 = 0; i2 < 4; ++i2) rowc[i2] = row;
             const int aw = a >> 4;
             // b in P counts only for b > a: P bits of the partners <= a go (N bits stay)
             const uint32_t above16 = ~((2u << (a & 15)) - 1u) & 0xFFFFu;
@@ -907,27 +861,18 @@ __global__ void __launch_bounds__(64 * RW_WAVES, PPP_RW_MINWAVES(PX))
                 uint2 cf[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-#ifdef PPP_RW_ABL_NOTABLE
-                    // (timing experiment: no table reads)
-                    if (w * 16 + j * 4 < C) { const uint32_t q = (m >> (8 * j)) & 0xFFu; cf[j] = make_uint2(0x28002800u ^ (q << 15), 0xA800A800u ^ (q << 7)); }
-#else
                     if (w * 16 + j * 4 < C) cf[j] = coefT[(m >> (8 * j)) & 0xFFu];
-#endif
                 float rv[2][4];
                 // (the reads of a group are issued LAST ELEMENT FIRST: the LDS returns in order, so the
                 // wait of the group's first term covers the other three -- one s_waitcnt per group
                 // instead of one per term, and an s_waitcnt costs its wave an issue slot like any
-                // instruction; PPP_RW_REVREADS=0: first element first)
+                // instruction)
                 auto load_rows = [&](int j, float (&r)[4]) {
 #pragma unroll
                     for (int i3 = 0; i3 < 4; ++i3) {
-                        const int i2 = PPP_RW_REVREADS ? 3 - i3 : i3;
+                        const int i2 = 3 - i3;
                         const int b = w * 16 + j * 4 + i2;
-#ifdef PPP_RW_ABL_NOLDS
-                        if (b < C) r[i2] = __builtin_bit_cast(float, 0x3F800000u + (uint32_t)(lane + b));   // (timing experiment)
-#else
                         if (b < C) r[i2] = rowc[i2][(b / (PY * PX)) * SZP + ((b / PX) % PY) * WX + b % PX];
-#endif
                     }
                 };
                 load_rows(0, rv[0]);
@@ -1049,7 +994,7 @@ static int rw_resident_per_cu() {
         hipError_t e;
         if constexpr (FIT) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rank_wg_kernel<P, P, P, 16, 16, 16, false, true>, 64 * RW_WAVES, 0);
         else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rank_wg_kernel<P, P, P, 8, 16, 16, false>, 64 * RW_WAVES, 0);
-        if (e != hipSuccess || nb < 1) nb = PPP_RW_MINWAVES(P);
+        if (e != hipSuccess || nb < 1) nb = RW_MINWAVES;
         memo = nb;
     }
     return memo;
@@ -1103,7 +1048,7 @@ static RwPlan rw_plan(const ppp_box &sb, const Geo &G, int resident, int residen
     bool big = big_tiles >= 4 * 256;
     static EnvSwitch tile_sw("PPP_RANK_WG_TILE");
     if (const char *e = tile_sw.get()) big = strcmp(e, "8x16x16") == 0 ? true : (strcmp(e, "8x8x16") == 0 ? false : big);
-    if (G.px == 9 && PPP_RW_ZRUNS(9) && !tile_sw.get()) big = false;
+    if (rw_zruns(G.px) && !tile_sw.get()) big = false;
     bool tall = tile_sw.get() && strcmp(tile_sw.get(), "16x8x16") == 0;
     if (G.rank_tile && !tile_sw.get()) { big = G.rank_tile == 2; tall = G.rank_tile == 3; }
     const bool by_rule = big && !tall && !tile_sw.get() && !G.rank_tile;
@@ -1210,16 +1155,13 @@ static hipError_t launch_rwg(const T *pred, const float *S, const uint8_t *ov, f
     const bool by_centres = order_sw.get() && order_sw.get()[0] == 'c';
     static EnvSwitch major_sw("PPP_RANK_TILE_MAJOR");
     const int y_major = (major_sw.get() && major_sw.get()[0] == 'z') ? 0 : 1;
-    // (occupancy experiment: PPP_RANK_WG_DYNLDS=<bytes> of unused dynamic LDS per workgroup)
-    static EnvSwitch dyn_sw("PPP_RANK_WG_DYNLDS");
-    const unsigned dyn_lds = dyn_sw.get() ? (unsigned)atoi(dyn_sw.get()) : 0u;
 #ifdef PPP_RW_STAMPS
 #define PPP_RW_STAMP_ARG , (uint32_t *)weight
 #else
 #define PPP_RW_STAMP_ARG
 #endif
 #define PPP_RW_LAUNCH1(A_, D_, E_, F_, P1_, DZ_)                                                            \
-    rank_wg_kernel<A_, A_, A_, D_, E_, F_, P1_, DZ_><<<dim3((unsigned)n_blocks), dim3(64 * RW_WAVES), dyn_lds, s>>>( \
+    rank_wg_kernel<A_, A_, A_, D_, E_, F_, P1_, DZ_><<<dim3((unsigned)n_blocks), dim3(64 * RW_WAVES), 0, s>>>(       \
         S, M, info, valid, score, sb, G, tiles_y, tiles_x, (int)n_tiles, p1 ? any_e : nullptr, order, y_major, dealT, tz_step PPP_RW_STAMP_ARG)
 #define PPP_RW_LAUNCH(A_, D_, E_, F_, DZ_)                                                                  \
     do {                                                                                                    \
@@ -1235,7 +1177,7 @@ static hipError_t launch_rwg(const T *pred, const float *S, const uint8_t *ov, f
     // pass 0: the one-bit form (when possible); then the two-bit pre-pass and kernel -- both return
     // at once unless the one-bit pre-pass found a partner that equals the threshold
     // (the dealing table of the row classes; the strides are those of the kernel's row image)
-    if (PPP_RW_BANKDEAL(7) && G.px == 7)
+    if (rw_bankdeal(G.px))
         rank_deal_table_kernel<7><<<dim3(7 * 7 * 7), dim3(32), 0, s>>>(dealT, 2 * 7 - 1, (2 * 7 - 1) * (2 * 7 - 1));
     for (int pass = p1 ? 0 : 1; pass < 2; ++pass) {
         if (pass == 1) PPP_RW_PRE(rank_masks_il_kernel, pred, ov, valid, sb, M, info, score, p1 ? any_e : nullptr, G);

@@ -7,7 +7,7 @@ whose row counts sit on both sides of what one wave and one workgroup serve: a p
 64, 65, 127, 128, 129 and 200 pair rows, through the small (one- or two-wave) kernel and the
 256-thread one -- a partly filled wave, a full one, rows that spill into a second wave or a
 further workgroup.  At 7^3 the small kernel adds the staged values of a candidate row under a
-lane mask (PPP_PA_EXEC_ADD): every row here goes through that form.  Every kernel runs twice:
+lane mask (PA_EXEC_ADD): every row here goes through that form.  Every kernel runs twice:
 with the patches' foreground bits built inside it (ppp_patch_graph_by_patch_lcg) and read from
 the table made once per patch (ppp_patch_fg_bits + ppp_patch_graph_by_patch_bits); the table
 itself is compared with the expression in NumPy for every interior centre of a volume.

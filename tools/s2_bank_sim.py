@@ -153,7 +153,7 @@ def tile_share(P, tile, enum, strides):
 
 def current_layout(P):
     """(enumeration, strides) of the kernel as committed: lines of 2 P - 1 floats; 9^3 walks z-runs on
-    a plane stride padded to 9 mod 32, 7^3 deals by banks (PPP_RW_BANKDEAL)"""
+    a plane stride padded to 9 mod 32, 7^3 deals by banks (rw_bankdeal)"""
     WX = 2 * P - 1
     SZ = WX * WX
     if P == 9:
