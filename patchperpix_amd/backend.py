@@ -588,6 +588,7 @@ class host_timer:
 
 NOTES = {}
 LAST_PLAN = None    # the memory plan of the last to_instance_seg call that made one (vote_instances.py)
+PRED_UPLOADS = 0    # to_device_pred calls whose input was NOT on the device: host -> device copies of a prediction
 
 
 def note(key, value):
@@ -670,11 +671,14 @@ def to_device_pred(pred, device="cuda", keep_f16=True):
     """Host ndarray / tensor -> contiguous device tensor (f16 and bf16 stay as they are: widening
     is exact and happens in registers; a contiguous tensor already on `device` is returned itself).
     NOTES["pred_dtype"] names the element type the kernels are given."""
+    global PRED_UPLOADS
     torch = _torch()
     if isinstance(pred, np.ndarray):
         if pred.dtype not in (np.float32, np.float16):
             pred = pred.astype(np.float32)
         pred = torch.from_numpy(np.ascontiguousarray(pred))
+    if not pred.is_cuda:
+        PRED_UPLOADS += 1
     if pred.dtype not in (torch.float32, torch.float16, torch.bfloat16):
         pred = pred.float()
     if pred.dtype == torch.float16 and not keep_f16:

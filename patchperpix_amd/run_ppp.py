@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""`label`, `decode`, `postprocess`, `postprocess_fg`, `evaluate_prediction`, `evaluate` and `visualize` tasks with the reference driver's interface
+"""`label`, `decode`, `postprocess`, `postprocess_fg`, `evaluate_prediction`, `evaluate`, `visualize` and `validate` tasks with the reference driver's interface
 (reference: experiments/run_ppp.py -- argument names :157-267, task dispatch :1974-2293,
 ``decode`` :682-746, ``vote_instances`` / ``vote_instances_sample`` :1054-1190, ``postprocess``
 :2230-2259).  The reference's ``postprocess`` has two branches: ``process_instances`` is this driver's
@@ -15,6 +15,10 @@ is not vendored).
 
 ``visualize`` (:1539-1606): patch mosaics of the prediction (``show_patches``) and instance pictures
 (``show_instances``).
+
+``validate`` (:779-1051): every parameter set of ``[validation]`` voted and scored on the predictions of
+--pred-folder, ``results.json`` and the best set (`validate.validate_checkpoints`; ``--val-id N`` runs set N only).
+A sample is loaded once for all its sets.
 
 Only the tasks on this repository's path are provided; training and prediction stay with the reference.  Usage, as in the reference README:
 
@@ -53,6 +57,27 @@ def get_list_samples(pred_folder, fmt, only=None):
     return [n for n in names if only is None or only in n]
 
 
+def stitch_kwargs(config):
+    """what `vote_instances_sample` hands ``stitch_patch_graph.main`` for a ``blockwise`` sample (run_ppp.py:1160-1170)"""
+    cfg, pred = config["vote_instances"], config["prediction"]
+    extra = {}
+    if cfg.get("vote_from_code", False):
+        # project-own option (INTEGRATION.md): a sample that holds the code is decoded into rows
+        # for its foreground voxels and voted from them; what the `decode` task is given
+        extra = dict(code_key=pred.get("code_key"), checkpoint_file=config.get("_checkpoint"))
+        if "autoencoder" not in config["model"] and config.get("autoencoder"):
+            extra["included_ae_config"] = config["autoencoder"]
+        for k in ("use_swa", "decode_batch_size"):
+            if k in pred and k not in cfg and k not in config["model"]:
+                extra[k] = pred[k]
+    # (written as one call's keyword arguments so that a name given twice is refused, as it always was)
+    return (lambda **kw: kw)(
+        **cfg, **config["model"], **config.get("visualize", {}), **extra,
+        aff_key=pred.get("aff_key"), numinst_key=pred.get("numinst_key"),
+        fg_key=pred.get("fg_key"), fg_folder=pred.get("fg_folder"),
+        fg_thresh=pred.get("fg_thresh"))
+
+
 def vote_instances_sample(config, pred_folder, output_folder, sample):
     """run_ppp.py:1119-1190."""
     from . import vote_instances as vi
@@ -70,21 +95,7 @@ def vote_instances_sample(config, pred_folder, output_folder, sample):
     if cfg.get("vote_from_code", False) and not cfg.get("blockwise", False):
         raise NotImplementedError("[vote_instances] vote_from_code = true needs blockwise = true")
     if cfg.get("blockwise", False):
-        extra = {}
-        if cfg.get("vote_from_code", False):
-            # project-own option: a sample that holds the code is decoded into rows
-            # for its foreground voxels and voted from them; what the `decode` task is given
-            extra = dict(code_key=pred.get("code_key"), checkpoint_file=config.get("_checkpoint"))
-            if "autoencoder" not in config["model"] and config.get("autoencoder"):
-                extra["included_ae_config"] = config["autoencoder"]
-            for k in ("use_swa", "decode_batch_size"):
-                if k in pred and k not in cfg and k not in config["model"]:
-                    extra[k] = pred[k]
-        vi.stitch_patch_graph.main(
-            pred_file, **cfg, **config["model"], **config.get("visualize", {}), **extra,
-            aff_key=pred.get("aff_key"), numinst_key=pred.get("numinst_key"),
-            fg_key=pred.get("fg_key"), fg_folder=pred.get("fg_folder"),
-            fg_thresh=pred.get("fg_thresh"))
+        vi.stitch_patch_graph.main(pred_file, **stitch_kwargs(config))
     else:
         cfg["affinities"] = pred_file
         vi.vote_instances.main(**cfg, **config["model"], numinst_key=pred.get("numinst_key"),
@@ -216,6 +227,15 @@ def evaluate(args, config):
     --output-folder: the header ``sample`` plus the keys, one row per sample, floats by repr -- this project's
     own format, as ``prediction_metrics.json`` is.  Returns the mean of ``[evaluation] metric`` over the
     samples."""
+    return evaluate_folder(config, config["data"]["test_data"], args.output_folder, args.output_folder, args.sample)
+
+
+def evaluate_folder(config, data, inst_folder, eval_folder, sample=None):
+    """The body of `evaluate` (run_ppp.py:1447-1536 takes the same five): the ``*.<vote_instances.output_format>``
+    files of ``inst_folder`` (those whose name contains ``sample``) against the ground truth ``data``; the
+    per-sample ``.toml`` files and ``summary.csv`` go to ``eval_folder``.  `evaluate` calls it with ``[data]
+    test_data`` and --output-folder for both folders, `validate` with ``[data] val_data`` and one folder pair
+    per parameter set."""
     import numpy as np
     from . import evaluate_instances as ei
     cfg = config["evaluation"]
@@ -226,8 +246,7 @@ def evaluate(args, config):
     if config["data"].get("add_partly_val"):
         raise NotImplementedError("[data] add_partly_val is not provided by this repository; unset it")
     fmt = config["vote_instances"].get("output_format", "hdf")
-    data = config["data"]["test_data"]
-    samples = get_list_samples(args.output_folder, fmt, args.sample)
+    samples = get_list_samples(inst_folder, fmt, sample)
     t0 = time.time()
     metrics, dicts = {}, []
     for sample in samples:
@@ -240,8 +259,8 @@ def evaluate(args, config):
             gt_key = config["data"]["one_instance_per_channel_gt"]
             logger.info("call evaluation with key %s", gt_key)
         metric_dict = ei.evaluate_file(
-            os.path.join(args.output_folder, sample + "." + fmt), gt_path, res_key=cfg["res_key"], gt_key=gt_key,
-            out_dir=args.output_folder, suffix="",
+            os.path.join(inst_folder, sample + "." + fmt), gt_path, res_key=cfg["res_key"], gt_key=gt_key,
+            out_dir=eval_folder, suffix="",
             foreground_only=cfg.get("foreground_only", False),
             debug=config.get("general", {}).get("debug", False),
             from_scratch=cfg.get("from_scratch", False),
@@ -262,7 +281,7 @@ def evaluate(args, config):
         logger.info("%s sample %-19s: %.4f", cfg["metric"], sample, value)
         metrics[sample] = value
     if "summary" in cfg:
-        with open(os.path.join(args.output_folder, "summary.csv"), "w") as f:
+        with open(os.path.join(eval_folder, "summary.csv"), "w") as f:
             f.write(",".join(["sample"] + list(cfg["summary"])) + "\n")
             for sample, metric_dict in zip(samples, dicts):
                 cells = [ei.lookup(metric_dict, k) for k in cfg["summary"]]
@@ -318,6 +337,14 @@ def visualize(args, config):
                                 max_axis=max_axis)
 
 
+def validate(args, config):
+    """run_ppp.py:919-1051 on predictions that exist: `validate.validate_checkpoints`."""
+    from . import validate as val
+    config["_checkpoint"] = args.checkpoint
+    return val.validate_checkpoints(config, args.pred_folder, args.output_folder, sample=args.sample,
+                                    val_id=args.val_id)
+
+
 def main(argv=None):
     from patchperpix_amd import backend as _backend
     _backend.tune_host_allocator(cli=True)     # (main(argv) IS the program, also behind a console script)
@@ -325,17 +352,18 @@ def main(argv=None):
     ap.add_argument("-c", "--config", action="append", required=True)
     ap.add_argument("-a", "--app", default="flylight")
     ap.add_argument("-s", "--setup", default="setup01")
-    ap.add_argument("-d", "--do", nargs="+", default=["label"], choices=["label", "decode", "postprocess", "postprocess_fg", "evaluate_prediction", "evaluate", "visualize"])
+    ap.add_argument("-d", "--do", nargs="+", default=["label"], choices=["label", "decode", "postprocess", "postprocess_fg", "evaluate_prediction", "evaluate", "visualize", "validate"])
     ap.add_argument("--pred-folder", required=True)
     ap.add_argument("--output-folder", required=True)
     ap.add_argument("--checkpoint", default=None)
     ap.add_argument("--sample", default=None)
+    ap.add_argument("--val-id", type=int, default=-1, help="validate: run only this parameter set (run_ppp.py:956)")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     config = load_config(args.config)
     for task in args.do:
         {"label": label, "decode": decode, "postprocess": postprocess, "postprocess_fg": postprocess_fg,
-         "evaluate_prediction": evaluate_prediction, "evaluate": evaluate, "visualize": visualize}[task](args, config)
+         "evaluate_prediction": evaluate_prediction, "evaluate": evaluate, "visualize": visualize, "validate": validate}[task](args, config)
 
 
 if __name__ == "__main__":

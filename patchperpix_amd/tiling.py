@@ -2489,17 +2489,24 @@ def _compact_from_code(stack, pred_file, patchshape, kw):
 
 
 def _stitch_main(stack, pred_file, result_folder=".", **kwargs):
-    import os
-    from .compact import CompactPrediction
-    from scipy import ndimage
-    from .vote_instances import utilVoteInstances as util
-    from .vote_instances.stitch_patch_graph import clean_mask
-    from .vote_instances.vote_instances import write_result
     patchshape = np.array(kwargs["patchshape"])
     kw = dict(kwargs)
     kw.pop("patchshape")
+    loaded = _stitch_load(stack, pred_file, patchshape, kw)
+    if loaded is None:
+        return
+    return _stitch_vote(loaded[0], loaded[1], loaded[2], pred_file, result_folder, patchshape, kw)
+
+
+def _stitch_load(stack, pred_file, patchshape, kw):
+    """The loading half of `_stitch_main`: (affinities, numinst, foreground) of one prediction file by its four
+    branches (rows decoded from the code, ``.npy``, a streamed zarr array behind a ZarrProvider, loadAffinities),
+    or None when loadAffinities finds the result key in the file.  ``kw`` is the caller's dict without
+    ``patchshape``; ``vote_from_code`` and ``stream_prediction`` are taken out of it and ``aff_key`` is filled in
+    for a streamed file, which is what the voting half expects."""
+    from .vote_instances import utilVoteInstances as util
     from_code = bool(kw.pop("vote_from_code", False))
-    if from_code and not kwargs.get("blockwise", False):
+    if from_code and not kw.get("blockwise", False):
         raise NotImplementedError("vote_from_code needs blockwise = true (the tiled assembly votes the rows)")
     if from_code and _holds_code(pred_file, kw):
         # ppp+dec without the decoded array: the code is decoded ONCE into rows for the foreground
@@ -2535,8 +2542,21 @@ def _stitch_main(stack, pred_file, result_folder=".", **kwargs):
     else:
         loaded = util.loadAffinities(pred_file, "", patchshape=patchshape, **kw)
         if loaded is None:
-            return
+            return None
         affinities, numinst, foreground = loaded
+    return affinities, numinst, foreground
+
+
+def _stitch_vote(affinities, numinst, foreground, pred_file, result_folder, patchshape, kw):
+    """The voting half of `_stitch_main`, on data the caller holds: bounding box of the cleaned foreground,
+    assembly of the boxed volume, post-steps, result file.  ``affinities`` is a host array, a ZarrProvider, a
+    CompactPrediction, or a (C, Z, Y, X) device tensor -- then the boxed crop is a device copy.  Nothing it is
+    given is written to: the cover mask and the numinst crop are copies, and ``kw`` is copied first."""
+    import os
+    from .compact import CompactPrediction
+    from .vote_instances.stitch_patch_graph import clean_mask
+    from .vote_instances.vote_instances import write_result
+    kw = dict(kw)
     foreground = np.squeeze(foreground)
     if foreground.ndim == 2:
         foreground = foreground[None]
@@ -2579,8 +2599,15 @@ def _stitch_main(stack, pred_file, result_folder=".", **kwargs):
     # mws = true + includeSinglePatchCCS = true every selected patch is issued an id
     # (graph_mws.py:34-41), far more than 65 535 on a large volume
     kw["_instances_dtype"] = np.uint32
+    if isinstance(affinities, np.ndarray):
+        crop = np.ascontiguousarray(affinities[sub])
+    else:
+        # a resident device tensor: the crop is a device copy of its own (.clone(): a box that is the whole
+        # volume must not hand the assembly the caller's tensor)
+        import torch
+        crop = affinities[sub].clone(memory_format=torch.contiguous_format)
     inst_bb, _ = to_instance_seg_tiled(
-        np.ascontiguousarray(affinities[sub]), fg_bb, fg_bb.copy(),
+        crop, fg_bb, fg_bb.copy(),
         np.ascontiguousarray(numinst[bb]), patchshape, n_slabs, **kw)
     instances = np.zeros(shape, dtype=np.uint32)
     instances[bb] = inst_bb
