@@ -135,7 +135,7 @@ const char *ppp_consensus_kernel_name(void);
  * form they compared.                                                                              */
 int ppp_consensus_short_form(void);
 /* the same for the last S2 call (ppp_rank_patches: "rank_v2_kernel" or "rank_kernel"; ppp_rank_patches_vm:
- * "rank_wg_kernel", "rank_wg_kernel<p1>" or "rank_vm_kernel") and the last S5 call (ppp_patch_graph:
+ * "rank_wg_kernel" or "rank_vm_kernel") and the last S5 call (ppp_patch_graph:
  * "patch_graph_kernel", "patch_graph_vm_kernel" or "patch_graph_vm2_kernel"; ppp_patch_graph_by_patch*:
  * "patch_graph_pa_kernel", or "patch_graph_pa_kernel<small>" with the small chunk); "none" before the first */
 const char *ppp_rank_kernel_name(void);

@@ -19,7 +19,6 @@
 // in LDS between the steps of a centre.  The per-centre P / N bit masks and the closed-form
 // pair count come from a coalesced pre-pass over the prediction.
 #include <stdlib.h>
-#include <string.h>
 
 #include "ppp_kernels.hpp"
 
@@ -346,25 +345,17 @@ static hipError_t launch_rv(const T *pred, const float *S, const uint8_t *ov, fl
     PPP_GRID_CHECK((sbV + 255) / 256, 256);
     rank_valid_kernel<T><<<dim3((unsigned)((G.V + 255) / 256)), dim3(256), 0, s>>>(pred, ov, valid, G);
     rank_masks_kernel<T><<<dim3((unsigned)((sbV + 255) / 256)), dim3(256), 0, s>>>(pred, ov, sb, Pb, Nb, info, score, G);
-    // tile of centres per wave: 8 x 8 x 8 by default; PPP_RANK_TILE=8x8x16 doubles it along x
-    // (fewer row stagings per centre and fuller waves, half as many tiles to spread over the CUs)
     // Tile of centres per wave.  One wave per tile, ~4 waves per SIMD resident: 4096 tiles run at
     // a time, so a volume of few tiles is cut finer (4 x 8 x 8: 140^3 -> 10.7 k tiles, 2.6 rounds
     // instead of 1.3 rounds of which the second is a third full: 95 -> 86 ms), a large one coarser
-    // (8 x 8 x 8: 5.4 instead of 7.7 row stagings per centre).  PPP_RANK_TILE overrides.  2-d
-    // patches (pz = 1): 1 x 8 x 8.
+    // (8 x 8 x 8: 5.4 instead of 7.7 row stagings per centre).  2-d patches (pz = 1): 1 x 8 x 8.
     const int shape_id = rank_vm_shape(G);
     int tile_kind = ((long long)((sZ + 7) / 8) * ((sY + 7) / 8) * ((sX + 7) / 8) < 3 * 4096) ? 2 : 0;
     // 7^3: five slices of centres instead of four -- an inner voxel then serves 5 * 49 = 245
     // (centre, a) items = 3.8 chunks of 64 lanes instead of 196 = 3.06 (the fourth chunk 6 % full)
     if (tile_kind == 2 && shape_id == 7) tile_kind = 4;
-    static EnvSwitch tile_sw("PPP_RANK_TILE");
-    if (const char *e = tile_sw.get())
-        tile_kind = strcmp(e, "8x8x16") == 0 ? 1 : (strcmp(e, "4x8x8") == 0 ? 2 : (strcmp(e, "8x8x8") == 0 ? 0 :
-                    (strcmp(e, "5x8x8") == 0 ? 4 : (strcmp(e, "7x8x8") == 0 ? 5 : tile_kind))));
     if (shape_id > 100) tile_kind = 3;
-    const int TZ = tile_kind == 3 ? 1 : (tile_kind == 2 ? 4 : (tile_kind == 4 ? 5 : (tile_kind == 5 ? 7 : 8))), TY = 8,
-              TX = tile_kind == 1 ? 16 : 8;
+    const int TZ = tile_kind == 3 ? 1 : (tile_kind == 2 ? 4 : (tile_kind == 4 ? 5 : 8)), TY = 8, TX = 8;
     const int tiles_z = (sZ + TZ - 1) / TZ, tiles_y = (sY + TY - 1) / TY, tiles_x = (sX + TX - 1) / TX;
     const long long n_tiles = (long long)tiles_z * tiles_y * tiles_x;
     const long long n_blocks = (n_tiles + 7) / 8 * 8;
@@ -374,10 +365,8 @@ static hipError_t launch_rv(const T *pred, const float *S, const uint8_t *ov, fl
         S, Pb, Nb, info, valid, score, sb, G, tiles_y, tiles_x)
 #define PPP_RV_CASE(P)                                                                                 \
     case P:                                                                                            \
-        if (tile_kind == 1) PPP_RV_LAUNCH(P, P, P, 8, 8, 16);                                          \
-        else if (tile_kind == 2) PPP_RV_LAUNCH(P, P, P, 4, 8, 8);                                      \
+        if (tile_kind == 2) PPP_RV_LAUNCH(P, P, P, 4, 8, 8);                                           \
         else if (tile_kind == 4) PPP_RV_LAUNCH(P, P, P, 5, 8, 8);                                      \
-        else if (tile_kind == 5) PPP_RV_LAUNCH(P, P, P, 7, 8, 8);                                      \
         else PPP_RV_LAUNCH(P, P, P, 8, 8, 8);                                                          \
         break;
 #define PPP_RV_CASE2D(P)                                                                               \

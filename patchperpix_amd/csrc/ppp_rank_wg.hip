@@ -188,17 +188,14 @@ __host__ __device__ __forceinline__ uint32_t interleave16(uint32_t p, uint32_t n
 // ---- pre-pass: interleaved masks, pair counts, border / background scores ------------------
 // thread per centre of the score box; masks word-major over the box (lanes = neighbouring
 // centres coalesce in the main kernel)
-// Round 12: P = 5 / 7 / 9 compiles the cubic window in (RwPreGeo, as PaGeo does for S5): the partner loop runs
+// Round 12: the cubic window P = 5 / 7 / 9 is compiled in (as PaGeo does for S5): the partner loop runs
 // over (dz, dy, dx) with constant bounds -- no division per partner -- and reads the partner's validity from
 // `valid`, which rank_valid2_kernel wrote one launch earlier, instead of evaluating pred[mid] > th && ov == 0
-// again for each of the C partners.  P = 0: the run-time loop (other shapes; PPP_RANK_PRE_CUBE=0 sends the
-// cubic windows there too: tests, A/B runs).  Same masks, info and scores either way.
+// again for each of the C partners.
 template <typename T, int P>
 __global__ void __launch_bounds__(256)
-    rank_masks_il_kernel(const T *__restrict__ pred, const uint8_t *__restrict__ ov, const uint8_t *__restrict__ valid_v,
-                         const ppp_box sb, uint32_t *__restrict__ M, uint32_t *__restrict__ info,
-                         float *__restrict__ score, const int *__restrict__ any_e, const Geo G) {
-    if (any_e && *any_e == 0) return;         // (the one-bit masks serve this launch)
+    rank_masks_il_kernel(const T *__restrict__ pred, const uint8_t *__restrict__ valid_v, const ppp_box sb,
+                         uint32_t *__restrict__ M, uint32_t *__restrict__ info, float *__restrict__ score, const Geo G) {
     const int sX = sb.x1 - sb.x0, sY = sb.y1 - sb.y0, sZ = sb.z1 - sb.z0;
     const long long sbV = (long long)sX * sY * sZ;
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -216,128 +213,32 @@ __global__ void __launch_bounds__(256)
         const long long q0 = rw_mask_quad0(t / sX, (int)(t % sX), sX, rw_mask_words(G.C) / 4);
         unsigned nP = 0, nV = 0;
         int r = 0;
-        if constexpr (P != 0) {
-            constexpr int R = P / 2, C = P * P * P;
-            uint32_t p = 0, n = 0;
-            for (int dz = 0; dz < P; ++dz)
-                for (int dy = 0; dy < P; ++dy) {
-                    const uint8_t *vrow = valid_v + vox(G, cz + dz - R, cy + dy - R, cx - R);
+        constexpr int R = P / 2, C = P * P * P;
+        uint32_t p = 0, n = 0;
+        for (int dz = 0; dz < P; ++dz)
+            for (int dy = 0; dy < P; ++dy) {
+                const uint8_t *vrow = valid_v + vox(G, cz + dz - R, cy + dy - R, cx - R);
 #pragma unroll
-                    for (int dx = 0; dx < P; ++dx, ++r) {
-                        const bool valid = vrow[dx] != 0;
-                        const float val = ldf(pred, (long long)r * G.V + lc);
-                        const int b = r & 15;
-                        if (valid) ++nV;
-                        if (valid && val > G.th_gt) p |= 1u << b;
-                        if (valid && val < G.bg_lt) n |= 1u << b;
-                        if (b == 15 || r == C - 1) {
-                            const int w = r >> 4;
-                            M[(q0 + (long long)(w >> 2) * RW_QSTRIDE) * 4 + (w & 3)] = interleave16(p, n);
-                            nP += __popc(p);
-                            p = n = 0;
-                        }
+                for (int dx = 0; dx < P; ++dx, ++r) {
+                    const bool valid = vrow[dx] != 0;
+                    const float val = ldf(pred, (long long)r * G.V + lc);
+                    const int b = r & 15;
+                    if (valid) ++nV;
+                    if (valid && val > G.th_gt) p |= 1u << b;
+                    if (valid && val < G.bg_lt) n |= 1u << b;
+                    if (b == 15 || r == C - 1) {
+                        const int w = r >> 4;
+                        M[(q0 + (long long)(w >> 2) * RW_QSTRIDE) * 4 + (w & 3)] = interleave16(p, n);
+                        nP += __popc(p);
+                        p = n = 0;
                     }
                 }
-        } else
-        for (int w = 0; w < words16; ++w) {
-            uint32_t p = 0, n = 0;
-            for (int b = 0; b < 16 && r < G.C; ++b, ++r) {
-                const int z = cz + r / (G.py * G.px) - G.rz, y = cy + (r / G.px) % G.py - G.ry,
-                          x = cx + r % G.px - G.rx;
-                const long long lz = vox(G, z, y, x);
-                const bool valid = ldf(mid, lz) > G.th_gt && (!G.use_overlap || ov[lz] == 0);
-                const float val = ldf(pred, (long long)r * G.V + lc);
-                if (valid) ++nV;
-                if (valid && val > G.th_gt) p |= 1u << b;
-                if (valid && val < G.bg_lt) n |= 1u << b;
             }
-            M[(q0 + (long long)(w >> 2) * RW_QSTRIDE) * 4 + (w & 3)] = interleave16(p, n);
-            nP += __popc(p);
-        }
         for (int w = words16; w < rw_mask_words(G.C); ++w) M[(q0 + (long long)(w >> 2) * RW_QSTRIDE) * 4 + (w & 3)] = 0u;
         // fgCnt = |P| (|V| - 1) - |P| (|P| - 1) / 2   (rankPatches.cu:139, see ppp_rank_v2.hip)
         const unsigned fg_cnt = nP ? nP * (nV - 1u) - nP * (nP - 1u) / 2u : 0u;
         inf = 0x80000000u | fg_cnt;
         if (nP == 0) score[lc] = 0.0f;   // no first pixel: acc = 0, 0 / max(1, 0)
-    }
-    info[t] = inf;
-}
-
-// ---- one bit per partner (round 5) ----------------------------------------------------------
-// The consensus entry S[u][q] is 0 whenever u or u + q is not a valid foreground voxel (the votes
-// skip such pixels: fillConsensusArray.cu:45-57, 75-83), so a term with an invalid partner adds
-// +-0 to the running sum -- which never changes it (the sum is never -0).  The masks therefore need
-// no validity, and with the background rule "v < TH" (the shipped one) a partner that is not in P
-// is in N unless its value EQUALS the threshold: ONE bit per partner (P' = v > TH), 92 bytes per
-// centre instead of 184 -- half the mask fetches, half the mask registers.  A launch in which any
-// centre has a valid partner with v == TH (or a NaN) falls back to the two-bit masks: the pre-pass
-// raises `any_e`, the one-bit main kernel returns at once and the two-bit pre-pass + kernel, launched
-// behind it, run (they return at once otherwise).
-static constexpr int rw_p1_words(int C) { return (((C + 31) / 32) + 3) & ~3; }
-template <typename T, int P>
-__global__ void __launch_bounds__(256)
-    rank_masks_p1_kernel(const T *__restrict__ pred, const uint8_t *__restrict__ ov, const uint8_t *__restrict__ valid_v,
-                         const ppp_box sb, uint32_t *__restrict__ M, uint32_t *__restrict__ info, int *__restrict__ any_e,
-                         float *__restrict__ score, const Geo G) {
-    const int sX = sb.x1 - sb.x0, sY = sb.y1 - sb.y0, sZ = sb.z1 - sb.z0;
-    const long long sbV = (long long)sX * sY * sZ;
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= sbV) return;
-    const int cx = sb.x0 + (int)(t % sX), cy = sb.y0 + (int)((t / sX) % sY), cz = sb.z0 + (int)(t / ((long long)sX * sY));
-    const long long lc = vox(G, cz, cy, cx);
-    const T *mid = pred + (long long)G.mid * G.V;
-    uint32_t inf = 0;
-    if (!interior(G, cz, cy, cx)) {
-        score[lc] = G.norm_rank ? -1.0f : -9999999.0f;
-    } else if (!(ldf(mid, lc) > G.th_gt)) {
-        score[lc] = 0.0f;   // the reference leaves the allocation's zero
-    } else {
-        const int words = (G.C + 31) / 32, wp = rw_p1_words(G.C);
-        unsigned nP = 0, nV = 0;
-        bool e = false;
-        int r = 0;
-        if constexpr (P != 0) {
-            // (the cubic window compiled in: see rank_masks_il_kernel)
-            constexpr int R = P / 2, C = P * P * P;
-            uint32_t p = 0;
-            for (int dz = 0; dz < P; ++dz)
-                for (int dy = 0; dy < P; ++dy) {
-                    const uint8_t *vrow = valid_v + vox(G, cz + dz - R, cy + dy - R, cx - R);
-#pragma unroll
-                    for (int dx = 0; dx < P; ++dx, ++r) {
-                        const bool valid = vrow[dx] != 0;
-                        const float val = ldf(pred, (long long)r * G.V + lc);
-                        const bool isp = val > G.th_gt;
-                        const int b = r & 31;
-                        if (valid) ++nV;
-                        if (valid && isp) ++nP;
-                        if (valid && !isp && !(val < G.bg_lt)) e = true;
-                        if (isp) p |= 1u << b;
-                        if (b == 31 || r == C - 1) { M[t * (long long)wp + (r >> 5)] = p; p = 0; }
-                    }
-                }
-        } else
-        for (int w = 0; w < words; ++w) {
-            uint32_t p = 0;
-            for (int b = 0; b < 32 && r < G.C; ++b, ++r) {
-                const int z = cz + r / (G.py * G.px) - G.rz, y = cy + (r / G.px) % G.py - G.ry,
-                          x = cx + r % G.px - G.rx;
-                const long long lz = vox(G, z, y, x);
-                const bool valid = ldf(mid, lz) > G.th_gt && (!G.use_overlap || ov[lz] == 0);
-                const float val = ldf(pred, (long long)r * G.V + lc);
-                const bool isp = val > G.th_gt;
-                if (valid) ++nV;
-                if (valid && isp) ++nP;
-                if (valid && !isp && !(val < G.bg_lt)) e = true;     // neither P nor N: needs the two-bit masks
-                if (isp) p |= 1u << b;
-            }
-            M[t * (long long)wp + w] = p;
-        }
-        for (int w = words; w < wp; ++w) M[t * (long long)wp + w] = 0u;
-        if (e) *any_e = 1;
-        const unsigned fg_cnt = nP ? nP * (nV - 1u) - nP * (nP - 1u) / 2u : 0u;
-        inf = 0x80000000u | fg_cnt;
-        if (nP == 0) score[lc] = 0.0f;
     }
     info[t] = inf;
 }
@@ -381,11 +282,11 @@ __device__ __forceinline__ void rw_tile_decode(int bid, int n_tiles, int tiles_y
 }
 // weight of a tile = the chunks of 64 items its workgroup walks: over the VALID voxels u of the tile
 // grown by the radius, ceil(items of u / 64) (+ 1 for the row's staging and barriers); 0 without an
-// active centre (the workgroup leaves at once).  PPP_RANK_ORDER=centres: the active centres instead.
+// active centre (the workgroup leaves at once).
 __global__ void __launch_bounds__(256)
     rank_tile_weight_kernel(const uint32_t *__restrict__ info, const uint8_t *__restrict__ valid, const ppp_box sb,
                             const int TZ, const int TY, const int TX, const int tiles_y, const int tiles_x,
-                            const int by_centres, const int y_major, int32_t *__restrict__ weight, const Geo G) {
+                            const int y_major, int32_t *__restrict__ weight, const Geo G) {
     const int bid = blockIdx.x;
     int tx_i, ty_i, tz_i;
     rw_tile_decode(bid, (int)gridDim.x, tiles_y, tiles_x, y_major, tz_i, ty_i, tx_i);
@@ -395,21 +296,19 @@ __global__ void __launch_bounds__(256)
         const int z = tz_i * TZ + cl / (TX * TY), y = ty_i * TY + (cl / TX) % TY, x = tx_i * TX + cl % TX;
         if (z < sZ && y < sY && x < sX) c += (int)(info[((long long)z * sY + y) * sX + x] >> 31);
     }
-    if (!by_centres) {
-        const int c0z = sb.z0 + tz_i * TZ, c0y = sb.y0 + ty_i * TY, c0x = sb.x0 + tx_i * TX;
-        const int tz = min(TZ, sb.z1 - c0z), ty = min(TY, sb.y1 - c0y), tx = min(TX, sb.x1 - c0x);
-        const int uz0 = max(c0z - G.rz, G.bz0), uz1 = min(c0z + tz - 1 + G.rz, G.bz0 + G.bZ - 1);
-        const int uy0 = max(c0y - G.ry, G.by0), uy1 = min(c0y + ty - 1 + G.ry, G.by0 + G.bY - 1);
-        const int ux0 = max(c0x - G.rx, G.bx0), ux1 = min(c0x + tx - 1 + G.rx, G.bx0 + G.bX - 1);
-        const int nuy = uy1 - uy0 + 1, nux = ux1 - ux0 + 1, nu = (uz1 - uz0 + 1) * nuy * nux;
-        for (int k = threadIdx.x; k < nu; k += blockDim.x) {
-            const int uz = uz0 + k / (nuy * nux), uy = uy0 + (k / nux) % nuy, ux = ux0 + k % nux;
-            if (!valid[vox(G, uz, uy, ux)]) continue;
-            const int nz = min(G.pz - 1, uz + G.rz - c0z) - max(0, uz + G.rz - (c0z + tz - 1)) + 1;
-            const int ny = min(G.py - 1, uy + G.ry - c0y) - max(0, uy + G.ry - (c0y + ty - 1)) + 1;
-            const int nx = min(G.px - 1, ux + G.rx - c0x) - max(0, ux + G.rx - (c0x + tx - 1)) + 1;
-            if (nz > 0 && ny > 0 && nx > 0) w += (nz * ny * nx + 63) / 64 + 1;
-        }
+    const int c0z = sb.z0 + tz_i * TZ, c0y = sb.y0 + ty_i * TY, c0x = sb.x0 + tx_i * TX;
+    const int tz = min(TZ, sb.z1 - c0z), ty = min(TY, sb.y1 - c0y), tx = min(TX, sb.x1 - c0x);
+    const int uz0 = max(c0z - G.rz, G.bz0), uz1 = min(c0z + tz - 1 + G.rz, G.bz0 + G.bZ - 1);
+    const int uy0 = max(c0y - G.ry, G.by0), uy1 = min(c0y + ty - 1 + G.ry, G.by0 + G.bY - 1);
+    const int ux0 = max(c0x - G.rx, G.bx0), ux1 = min(c0x + tx - 1 + G.rx, G.bx0 + G.bX - 1);
+    const int nuy = uy1 - uy0 + 1, nux = ux1 - ux0 + 1, nu = (uz1 - uz0 + 1) * nuy * nux;
+    for (int k = threadIdx.x; k < nu; k += blockDim.x) {
+        const int uz = uz0 + k / (nuy * nux), uy = uy0 + (k / nux) % nuy, ux = ux0 + k % nux;
+        if (!valid[vox(G, uz, uy, ux)]) continue;
+        const int nz = min(G.pz - 1, uz + G.rz - c0z) - max(0, uz + G.rz - (c0z + tz - 1)) + 1;
+        const int ny = min(G.py - 1, uy + G.ry - c0y) - max(0, uy + G.ry - (c0y + ty - 1)) + 1;
+        const int nx = min(G.px - 1, ux + G.rx - c0x) - max(0, ux + G.rx - (c0x + tx - 1)) + 1;
+        if (nz > 0 && ny > 0 && nx > 0) w += (nz * ny * nx + 63) / 64 + 1;
     }
     for (int o = 32; o > 0; o >>= 1) { c += __shfl_xor(c, o); w += __shfl_xor(w, o); }
     __shared__ int part[2][4];
@@ -418,7 +317,7 @@ __global__ void __launch_bounds__(256)
     if (threadIdx.x == 0) {
         const int cs = part[0][0] + part[0][1] + part[0][2] + part[0][3];
         const int ws = part[1][0] + part[1][1] + part[1][2] + part[1][3];
-        weight[bid] = by_centres ? cs : (cs ? ws : 0);
+        weight[bid] = cs ? ws : 0;
     }
 }
 // one workgroup per XCD range: its tiles in descending order of weight (position = the number of tiles
@@ -560,20 +459,17 @@ __global__ void __launch_bounds__(32) rank_deal_table_kernel(uint16_t *__restric
 // DZ (round 12): the tile's thickness in z is the run-time `tz_step` <= TZ -- TZ then only sizes accs, act_bits and
 // uvalid_bits; the tile origin is tz_i * tz_step and the kernel's ragged-tile handling does the rest.  !DZ:
 // tz_step is TZ (the launches that do not choose their thickness keep their code).
-template <int PZ, int PY, int PX, int TZ, int TY, int TX, bool P1, bool DZ = false>
+template <int PZ, int PY, int PX, int TZ, int TY, int TX, bool DZ = false>
 __global__ void __launch_bounds__(64 * RW_WAVES, RW_MINWAVES)
     rank_wg_kernel(const float *__restrict__ S, const uint32_t *__restrict__ M,
                    const uint32_t *__restrict__ info, const uint8_t *__restrict__ valid,
                    float *__restrict__ score, const ppp_box sb, const Geo G, const int tiles_y,
-                   const int tiles_x, const int n_tiles, const int *__restrict__ any_e,
-                   const int32_t *__restrict__ order, const int y_major, const uint16_t *__restrict__ dealT,
+                   const int tiles_x, const int n_tiles, const int32_t *__restrict__ order, const int y_major, const uint16_t *__restrict__ dealT,
                    const int tz_step
 #ifdef PPP_RW_STAMPS
                    , uint32_t *__restrict__ stamps
 #endif
                    ) {
-    // (one launch of each form per call when the one-bit masks are possible: the pre-pass decides)
-    if (any_e && (*any_e != 0) == P1) return;
 #ifdef PPP_RW_STAMPS
     // (diagnostic build -DPPP_RW_STAMPS, tools/s2_wg_times.py: when does every workgroup start and
     // end, and on which CU -- the tile weights' array of the workspace is free once the order is made)
@@ -581,8 +477,8 @@ __global__ void __launch_bounds__(64 * RW_WAVES, RW_MINWAVES)
     const unsigned long long t_start = wall_clock64();
 #endif
     constexpr int C = PZ * PY * PX, W16 = (C + 15) / 16, RZ = PZ / 2, RY = PY / 2, RX = PX / 2;
-    constexpr int W16P = P1 ? rw_p1_words(C) : rw_mask_words(C);   // mask words per centre in M
-    constexpr int NMW = P1 ? (C + 31) / 32 : W16;                  // ... that hold bits
+    constexpr int W16P = rw_mask_words(C);   // mask words per centre in M
+    constexpr int NMW = W16;                 // ... that hold bits
     constexpr int WZ = 2 * PZ - 1, WY = 2 * PY - 1, WX = 2 * PX - 1, W = WZ * WY * WX, LC = (W - 1) / 2;
     constexpr int NTHR = 64 * RW_WAVES;
     constexpr int NST = (W + NTHR - 1) / NTHR;
@@ -686,8 +582,7 @@ __global__ void __launch_bounds__(64 * RW_WAVES, RW_MINWAVES)
     __syncthreads();
     int turn = 0;   // rotates the wave that takes the first chunk of a row
     // geometry of a row (which pixels a of voxel u have their centre in the tile) and of the item a
-    // lane takes in chunk i0 of it -- functions of the row index, so that the masks of the NEXT
-    // chunk (of this row or of the next) can be requested ahead
+    // lane takes in chunk i0 of it
     struct RowG { int uz, uy, ux, az0, ay0, ax0, nz, ny, nx, n_box, cls; };
     struct ItemG { bool in; int cl, a, az, ay, ax; long long t, q0; };
     auto row_geom = [&](int k) -> RowG {
@@ -722,26 +617,11 @@ __global__ void __launch_bounds__(64 * RW_WAVES, RW_MINWAVES)
         const int lz = r.uz + RZ - g.az - c0z, ly = r.uy + RY - g.ay - c0y, lx = r.ux + RX - g.ax - c0x;
         g.cl = (lz * TY + ly) * TX + lx;
         g.a = (g.az * PY + g.ay) * PX + g.ax;
-        g.t = sb_index(lz, ly, lx);
-        // (two-bit masks: quad 0 of the centre, in 16-byte units)
+        g.t = sb_index(lz, ly, lx);     // (nothing reads it: without it the compiler allocates other registers)
+        // (quad 0 of the centre's masks, in 16-byte units)
         g.q0 = rw_mask_quad0((long long)(c0z + lz - sb.z0) * sY + (c0y + ly - sb.y0), c0x + lx - sb.x0, sX, W16P / 4);
         return g;
     };
-    // one-bit masks: the first PFQ 16-byte pieces of a centre's words + the word with P'[a], requested
-    // one chunk ahead (the two-bit form loads a chunk's masks when the chunk starts)
-    constexpr int PFQ = (W16P / 4) / 2;
-    uint4 pfa[PFQ > 0 ? PFQ : 1];
-    uint32_t pfw = 0u;
-    bool pf_have = false;
-    auto prefetch = [&](const RowG &r, int i0) {
-        const ItemG g = item_geom(r, i0);
-        const uint32_t *mrow = M + g.t * (long long)W16P;
-        pfw = mrow[g.a >> 5];
-        const uint4 *mc = reinterpret_cast<const uint4 *>(mrow);
-#pragma unroll
-        for (int q = 0; q < PFQ; ++q) pfa[q] = mc[q];
-    };
-    (void)prefetch; (void)pf_have; (void)pfw;
     while (uk < nu) {
         const int uk_next = __builtin_amdgcn_readfirstlane(next_valid(uk + 1));
         if (uk_next < nu) {
@@ -757,73 +637,29 @@ __global__ void __launch_bounds__(64 * RW_WAVES, RW_MINWAVES)
         const int n_box = R.n_box;
         const int first = (wave + RW_WAVES - turn) % RW_WAVES;
         turn = (turn + ((n_box + 63) >> 6)) % RW_WAVES;
-        if constexpr (P1) {
-            // (the first chunk of a row is normally prefetched at the end of the row before)
-            if (!pf_have && 64 * first < n_box) prefetch(R, 64 * first);
-            pf_have = false;
-        }
         for (int i0 = 64 * first; i0 < n_box; i0 += NTHR) {
             const ItemG it = item_geom(R, i0);
-            const bool in = it.in;
             const int ax = it.ax, ay = it.ay, az = it.az, cl = it.cl, a = it.a;
-            const long long t = it.t, q0 = it.q0;
-            (void)in; (void)q0;
+            const long long q0 = it.q0;
             bool active = it.in && ((act_bits[cl >> 5] >> (cl & 31)) & 1u) != 0;
             uint32_t mw[NMW];
-            if constexpr (P1) {
-                // ---- one-bit masks, software pipelined: the first half of this chunk's words and the
-                // word that holds P'[a] were requested a chunk ago; the second half is requested now
-                // and arrives behind the first half of the chain; then the next chunk's first half
-                // (this row's next chunk of the wave, or the first chunk of the next row)
-                const uint32_t aword = pfw;
-#pragma unroll
-                for (int q = 0; q < PFQ; ++q) {
-                    if (4 * q < NMW) mw[4 * q] = pfa[q].x;
-                    if (4 * q + 1 < NMW) mw[4 * q + 1] = pfa[q].y;
-                    if (4 * q + 2 < NMW) mw[4 * q + 2] = pfa[q].z;
-                    if (4 * q + 3 < NMW) mw[4 * q + 3] = pfa[q].w;
-                }
-                const uint4 *mc = reinterpret_cast<const uint4 *>(M + t * (long long)W16P);
-#pragma unroll
-                for (int q = PFQ; q < W16P / 4; ++q) {
-                    const uint4 v = mc[q];
-                    if (4 * q < NMW) mw[4 * q] = v.x;
-                    if (4 * q + 1 < NMW) mw[4 * q + 1] = v.y;
-                    if (4 * q + 2 < NMW) mw[4 * q + 2] = v.z;
-                    if (4 * q + 3 < NMW) mw[4 * q + 3] = v.w;
-                }
-                if (i0 + NTHR < n_box) {
-                    prefetch(R, i0 + NTHR);
-                } else if (uk_next < nu) {
-                    const RowG Rn = row_geom(uk_next);
-                    const int first_n = (wave + RW_WAVES - turn) % RW_WAVES;
-                    if (64 * first_n < Rn.n_box) { prefetch(Rn, 64 * first_n); pf_have = true; }
-                }
-                if (active) active = ((aword >> (a & 31)) & 1u) != 0;
-                if (__ballot(active) == 0) continue;
-            } else {
             // is a in P?  P bit of partner s: bit 8 (s >> 2 & 3) + (s & 3) of word s >> 4
             if (active)
                 active = ((M[(q0 + (long long)(a >> 6) * RW_QSTRIDE) * 4 + ((a >> 4) & 3)] >> (8 * ((a >> 2) & 3) + (a & 3))) & 1u) != 0;
             if (__ballot(active) == 0) continue;
             // (unconditional loads -- t is a centre of the tile for every lane -- then one select
             // per word: a predicated load is a branch per word)
-            {
-                const uint4 *mc = reinterpret_cast<const uint4 *>(M) + q0;
+            const uint4 *mc = reinterpret_cast<const uint4 *>(M) + q0;
 #pragma unroll
-                for (int q = 0; q < W16P / 4; ++q) {
-                    const uint4 v = mc[q * RW_QSTRIDE];
-                    if (4 * q < NMW) mw[4 * q] = v.x;
-                    if (4 * q + 1 < NMW) mw[4 * q + 1] = v.y;
-                    if (4 * q + 2 < NMW) mw[4 * q + 2] = v.z;
-                    if (4 * q + 3 < NMW) mw[4 * q + 3] = v.w;
-                }
+            for (int q = 0; q < W16P / 4; ++q) {
+                const uint4 v = mc[q * RW_QSTRIDE];
+                if (4 * q < NMW) mw[4 * q] = v.x;
+                if (4 * q + 1 < NMW) mw[4 * q + 1] = v.y;
+                if (4 * q + 2 < NMW) mw[4 * q + 2] = v.z;
+                if (4 * q + 3 < NMW) mw[4 * q + 3] = v.w;
             }
-            }
-            if constexpr (!P1) {
 #pragma unroll
-                for (int w = 0; w < W16; ++w) mw[w] = active ? mw[w] : 0u;
-            }
+            for (int w = 0; w < W16; ++w) mw[w] = active ? mw[w] : 0u;
             float acc = active ? accs[cl] : 0.0f;
             lds_f32_cvp2 row = (lds_f32_cvp2)(rowbuf + RW_PAD + LCP - (az * SZP + ay * WX + ax));
             // (one copy of the row pointer per read of a group: with a single pointer the compiler emits other code)
@@ -839,22 +675,7 @@ __global__ void __launch_bounds__(64 * RW_WAVES, RW_MINWAVES)
             // offset at run time)
             StaticFor<0, W16>::run([&](auto wc) {
                 constexpr int w = decltype(wc)::value;
-                uint32_t m;
-                if constexpr (P1) {
-                    // the two-bit word of these 16 partners from their P' bits: P counts for b > a,
-                    // N = not P' for every b != a (partners beyond C do not exist)
-                    constexpr uint32_t last = (w == W16 - 1 && (C & 15)) ? ((1u << (C & 15)) - 1u) : 0xFFFFu;
-                    const uint32_t pw = (mw[w >> 1] >> (16 * (w & 1))) & 0xFFFFu;
-                    const uint32_t pos = pw & (w < aw ? 0u : (w > aw ? 0xFFFFu : above16));
-                    const uint32_t neg = ~pw & (w == aw ? ~(1u << (a & 15)) : 0xFFFFFFFFu) & last;
-                    auto spread = [](uint32_t x) -> uint32_t {      // nibble j of x -> low nibble of byte j
-                        x = (x | (x << 8)) & 0x00FF00FFu;
-                        return (x | (x << 4)) & 0x0F0F0F0Fu;
-                    };
-                    m = active ? (spread(pos) | (spread(neg) << 4)) : 0u;
-                } else {
-                    m = mw[w] & (w < aw ? 0xF0F0F0F0u : (w > aw ? 0xFFFFFFFFu : keep_a));
-                }
+                const uint32_t m = mw[w] & (w < aw ? 0xF0F0F0F0u : (w > aw ? 0xFFFFFFFFu : keep_a));
                 if (__ballot(m != 0u) == 0) return;
                 // table reads of the word first; then the four groups of four partners, the row
                 // values of the next group in flight while the current chain runs
@@ -944,7 +765,6 @@ bool rank_wg_supported(const Geo &G) {
 struct RankWgWork {
     uint32_t *M, *info;       // the masks of the score box (rw_mask_bytes); [score box]
     uint8_t *valid;           // [V]
-    int *any_e;               // [1] one-bit masks: "a partner equals the threshold somewhere"
     int32_t *weight, *order;  // [RW_ORDER_MAX] each; a PPP_RW_STAMPS build reuses `weight` for its stamps
     uint16_t *dealT;          // rw_deal_bytes
 };
@@ -954,7 +774,6 @@ static RankWgWork rank_wg_layout(Carver &c, const ppp_box &sb, const Geo &G) {
     W.M = (uint32_t *)c.take_bytes(rw_mask_bytes(sZ, sY, sX, G.C));
     W.info = c.take<uint32_t>((size_t)sX * sY * sZ);
     W.valid = c.take<uint8_t>(G.V);
-    W.any_e = (int *)c.take_bytes(256);
     W.weight = c.take<int32_t>(RW_ORDER_MAX);
     W.order = c.take<int32_t>(RW_ORDER_MAX);
     W.dealT = (uint16_t *)c.take_bytes(rw_deal_bytes(G.px));
@@ -992,8 +811,8 @@ static int rw_resident_per_cu() {
     if (memo == 0) {
         int nb = 0;
         hipError_t e;
-        if constexpr (FIT) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rank_wg_kernel<P, P, P, 16, 16, 16, false, true>, 64 * RW_WAVES, 0);
-        else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rank_wg_kernel<P, P, P, 8, 16, 16, false>, 64 * RW_WAVES, 0);
+        if constexpr (FIT) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rank_wg_kernel<P, P, P, 16, 16, 16, true>, 64 * RW_WAVES, 0);
+        else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rank_wg_kernel<P, P, P, 8, 16, 16>, 64 * RW_WAVES, 0);
         if (e != hipSuccess || nb < 1) nb = RW_MINWAVES;
         memo = nb;
     }
@@ -1113,36 +932,24 @@ static hipError_t launch_rwg(const T *pred, const float *S, const uint8_t *ov, f
     const int sX = sb.x1 - sb.x0, sY = sb.y1 - sb.y0, sZ = sb.z1 - sb.z0;
     const size_t sbV = (size_t)sX * sY * sZ;
     Carver carver(work);
-    auto [M, info, valid, any_e, weight, order, dealT] = rank_wg_layout(carver, sb, G);
+    auto [M, info, valid, weight, order, dealT] = rank_wg_layout(carver, sb, G);
     if (!cons_box_covers(G, sb)) return hipErrorInvalidValue;
     PPP_GRID_CHECK((G.V + 255) / 256, 256);
     PPP_GRID_CHECK((sbV + 255) / 256, 256);
     rank_valid2_kernel<T><<<dim3((unsigned)((G.V + 255) / 256)), dim3(256), 0, s>>>(pred, ov, valid, G);
-    // one bit per partner where N is the complement of P up to values that equal the threshold
-    // (background rule "v < TH": bg_lt >= th_gt) -- only with PPP_RANK_P1=1: it halves the mask
-    // fetches and, with the prefetch, takes their latency off the chain's start, and is SLOWER
-    // (112 x 176 x 176 / 9^3: 285 ms, 272 ms without the prefetch, against 254 ms for the two-bit masks;
-    // 140^3 / 7^3: 72 vs 62 ms; profiles/r05_x_s2_one_bit_masks.txt): the 12 vector instructions that
-    // rebuild a two-bit word from 16 mask bits cost more than the fetches they save -- the kernel is
-    // not waiting for its masks.
-    static EnvSwitch p1_sw("PPP_RANK_P1");
-    const bool p1 = G.bg_lt >= G.th_gt && p1_sw.get() && p1_sw.get()[0] == '1';
-    note_rank_kernel(p1 ? "rank_wg_kernel<p1>" : "rank_wg_kernel");
-    // the pre-pass with the cubic window compiled in (PPP_RANK_PRE_CUBE=0: the run-time loop)
-    static EnvSwitch cube_sw("PPP_RANK_PRE_CUBE");
-    const int pre_p = (cube_sw.get() && cube_sw.get()[0] == '0') ? 0 : G.px;
+    note_rank_kernel("rank_wg_kernel");
+    // (rank_wg_supported admits only the cubic windows the pre-pass compiles in)
     const dim3 pre_grid((unsigned)((sbV + 255) / 256));
-#define PPP_RW_PRE(KERNEL_, ...)                                                                            \
-    do {                                                                                                    \
-        if (pre_p == 5) KERNEL_<T, 5><<<pre_grid, dim3(256), 0, s>>>(__VA_ARGS__);                          \
-        else if (pre_p == 7) KERNEL_<T, 7><<<pre_grid, dim3(256), 0, s>>>(__VA_ARGS__);                     \
-        else if (pre_p == 9) KERNEL_<T, 9><<<pre_grid, dim3(256), 0, s>>>(__VA_ARGS__);                     \
-        else KERNEL_<T, 0><<<pre_grid, dim3(256), 0, s>>>(__VA_ARGS__);                                     \
-    } while (0)
-    if (p1) {
-        hipError_t em = hipMemsetAsync(any_e, 0, 4, s);
-        if (em != hipSuccess) return em;
-        PPP_RW_PRE(rank_masks_p1_kernel, pred, ov, valid, sb, M, info, any_e, score, G);
+#define PPP_RW_PRE(P)                                                                                       \
+    case P:                                                                                                 \
+        rank_masks_il_kernel<T, P><<<pre_grid, dim3(256), 0, s>>>(pred, valid, sb, M, info, score, G);      \
+        break;
+    switch (G.px) {
+        PPP_RW_PRE(5)
+        PPP_RW_PRE(7)
+        PPP_RW_PRE(9)
+    default:
+        return hipErrorNotSupported;
     }
     const RwPlan plan = rw_plan_device(sb, G);
     const bool tall = plan.TZ == 16 && !plan.fit, big = plan.TY == 16, fit = plan.fit;
@@ -1151,60 +958,45 @@ static hipError_t launch_rwg(const T *pred, const float *S, const uint8_t *ov, f
     if (!plan.ordered) order = nullptr;
     const long long n_blocks = 8LL * plan.slots;
     PPP_GRID_CHECK(n_blocks, 64 * RW_WAVES);
-    static EnvSwitch order_sw("PPP_RANK_ORDER");
-    const bool by_centres = order_sw.get() && order_sw.get()[0] == 'c';
     static EnvSwitch major_sw("PPP_RANK_TILE_MAJOR");
     const int y_major = (major_sw.get() && major_sw.get()[0] == 'z') ? 0 : 1;
+    if (order) {
+        rank_tile_weight_kernel<<<dim3((unsigned)n_tiles), dim3(256), 0, s>>>(info, valid, sb, tz_step, plan.TY, plan.TX, tiles_y, tiles_x,
+                                                                              y_major, weight, G);
+        rank_tile_order_kernel<<<dim3(8), dim3(256), 0, s>>>(weight, (int)n_tiles, per_xcd, splits, plan.slots,
+                                                             plan.by_weight ? 1 : 0, order);
+    }
+    // (the dealing table of the row classes; the strides are those of the kernel's row image)
+    if (rw_bankdeal(G.px))
+        rank_deal_table_kernel<7><<<dim3(7 * 7 * 7), dim3(32), 0, s>>>(dealT, 2 * 7 - 1, (2 * 7 - 1) * (2 * 7 - 1));
 #ifdef PPP_RW_STAMPS
+    (void)hipMemsetAsync(weight, 0, (size_t)RW_ORDER_MAX * 4, s);      // (the weights are spent: room for the stamps)
 #define PPP_RW_STAMP_ARG , (uint32_t *)weight
 #else
 #define PPP_RW_STAMP_ARG
 #endif
-#define PPP_RW_LAUNCH1(A_, D_, E_, F_, P1_, DZ_)                                                            \
-    rank_wg_kernel<A_, A_, A_, D_, E_, F_, P1_, DZ_><<<dim3((unsigned)n_blocks), dim3(64 * RW_WAVES), 0, s>>>(       \
-        S, M, info, valid, score, sb, G, tiles_y, tiles_x, (int)n_tiles, p1 ? any_e : nullptr, order, y_major, dealT, tz_step PPP_RW_STAMP_ARG)
 #define PPP_RW_LAUNCH(A_, D_, E_, F_, DZ_)                                                                  \
-    do {                                                                                                    \
-        if (p1 && pass == 0) PPP_RW_LAUNCH1(A_, D_, E_, F_, true, DZ_);                                     \
-        else PPP_RW_LAUNCH1(A_, D_, E_, F_, false, DZ_);                                                    \
-    } while (0)
+    rank_wg_kernel<A_, A_, A_, D_, E_, F_, DZ_><<<dim3((unsigned)n_blocks), dim3(64 * RW_WAVES), 0, s>>>(   \
+        S, M, info, valid, score, sb, G, tiles_y, tiles_x, (int)n_tiles, order, y_major, dealT, tz_step PPP_RW_STAMP_ARG)
 #define PPP_RW_CASE(P)                                                                                      \
     case P:                                                                                                 \
         if (tall) PPP_RW_LAUNCH(P, 16, 8, 16, false);                                                       \
         else if (big) PPP_RW_LAUNCH(P, 8, 16, 16, false);                                                   \
         else PPP_RW_LAUNCH(P, 8, 8, 16, false);                                                             \
         break;
-    // pass 0: the one-bit form (when possible); then the two-bit pre-pass and kernel -- both return
-    // at once unless the one-bit pre-pass found a partner that equals the threshold
-    // (the dealing table of the row classes; the strides are those of the kernel's row image)
-    if (rw_bankdeal(G.px))
-        rank_deal_table_kernel<7><<<dim3(7 * 7 * 7), dim3(32), 0, s>>>(dealT, 2 * 7 - 1, (2 * 7 - 1) * (2 * 7 - 1));
-    for (int pass = p1 ? 0 : 1; pass < 2; ++pass) {
-        if (pass == 1) PPP_RW_PRE(rank_masks_il_kernel, pred, ov, valid, sb, M, info, score, p1 ? any_e : nullptr, G);
-        if (order && pass == (p1 ? 0 : 1)) {      // (`info` is the same from either pre-pass)
-            rank_tile_weight_kernel<<<dim3((unsigned)n_tiles), dim3(256), 0, s>>>(info, valid, sb, tz_step, plan.TY, plan.TX, tiles_y, tiles_x,
-                                                                                  by_centres ? 1 : 0, y_major, weight, G);
-            rank_tile_order_kernel<<<dim3(8), dim3(256), 0, s>>>(weight, (int)n_tiles, per_xcd, splits, plan.slots,
-                                                                 plan.by_weight ? 1 : 0, order);
-        }
-#ifdef PPP_RW_STAMPS
-        (void)hipMemsetAsync(weight, 0, (size_t)RW_ORDER_MAX * 4, s);      // (the weights are spent: room for the stamps)
-#endif
-        if (fit) {
-            // (the tile of run-time thickness: built for 7^3 alone, the only size the plan gives it to)
-            if (G.px != 7) return hipErrorNotSupported;
-            PPP_RW_LAUNCH(7, 16, 16, 16, true);
-        } else
-        switch (G.px) {
-            PPP_RW_CASE(5)
-            PPP_RW_CASE(7)
-            PPP_RW_CASE(9)
-        default:
-            return hipErrorNotSupported;
-        }
+    if (fit) {
+        // (the tile of run-time thickness: built for 7^3 alone, the only size the plan gives it to)
+        if (G.px != 7) return hipErrorNotSupported;
+        PPP_RW_LAUNCH(7, 16, 16, 16, true);
+    } else
+    switch (G.px) {
+        PPP_RW_CASE(5)
+        PPP_RW_CASE(7)
+        PPP_RW_CASE(9)
+    default:
+        return hipErrorNotSupported;
     }
 #undef PPP_RW_LAUNCH
-#undef PPP_RW_LAUNCH1
 #undef PPP_RW_STAMP_ARG
 #undef PPP_RW_CASE
 #undef PPP_RW_PRE

@@ -46,7 +46,6 @@ S2 = {
     "rank_v2": dict(env={}, cells={"p5": ALL, "p357": ALL}, rot="p5"),
     "rank_vm": dict(env={"PPP_RANK_WG": "0"}, cells={**{s: ALL for s in CUBIC}, "w25": ALL, "p357": ["default"]}, rot="p3"),
     "rank_wg": dict(env={}, cells={s: ALL for s in ("p5", "p7", "p9")}, rot="p5"),
-    "rank_wg_p1": dict(env={"PPP_RANK_P1": "1"}, cells={s: ALL for s in ("p5", "p7", "p9")}, rot="p7"),
 }
 S5 = {
     "pg_compact": dict(env={}, cells={"p3": ALL, "w11": ALL}, rot="p3"),
@@ -246,11 +245,7 @@ def test_s2_family_matches_oracle(fam, shape, flag, dtype, torch_cuda, monkeypat
         _same_bits(score.cpu().numpy(), want, what + " (gather form)")
         return
     score = backend.rank_patches(pred, vm, ov, Pv)
-    if fam == "rank_wg_p1":
-        # one-bit masks only where the background test is "below the threshold itself"
-        assert name() == ("rank_wg_kernel<p1>" if g["bg"] >= g["th"] else "rank_wg_kernel")
-    else:
-        assert name() == S2_KERNEL[fam]
+    assert name() == S2_KERNEL[fam]
     _same_bits(score.cpu().numpy(), want, what)
 
 

@@ -1,6 +1,6 @@
 """GPU (MI355X): the launch plan of the workgroup ranking kernel (ppp_rank_wg.hip) -- tiles of a run-time
 thickness in z, XCD ranges of equal weight, the pre-pass with the cubic window compiled in -- forced through the
-launcher's development switches (PPP_RANK_WG_TZ, PPP_RANK_WG_XCD, PPP_RANK_WG_SPLIT, PPP_RANK_PRE_CUBE), because a
+launcher's development switches (PPP_RANK_WG_TZ, PPP_RANK_WG_XCD, PPP_RANK_WG_SPLIT), because a
 volume a test can afford is far below the size at which the rule chooses them.  Scores are compared as uint32 bit
 patterns with the gather kernel on compact planes (the one pinned to the goldens and the oracle): no tolerance,
 for the whole volume and for an inner score box inside a consensus box.  The rule itself is asked through
@@ -12,8 +12,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-SWITCHES = ("PPP_RANK_WG_TILE", "PPP_RANK_WG_SPLIT", "PPP_RANK_WG_TZ", "PPP_RANK_WG_XCD", "PPP_RANK_PRE_CUBE",
-            "PPP_RANK_P1", "PPP_RANK_ORDER", "PPP_RANK_TILE_MAJOR", "PPP_RANK_WG")
+SWITCHES = ("PPP_RANK_WG_TILE", "PPP_RANK_WG_SPLIT", "PPP_RANK_WG_TZ", "PPP_RANK_WG_XCD", "PPP_RANK_ORDER",
+            "PPP_RANK_TILE_MAJOR", "PPP_RANK_WG")
 CASES = {"p7": ((7, 7, 7), (40, 37, 45), 12), "p5": ((5, 5, 5), (38, 41, 43), 9), "p9": ((9, 9, 9), (41, 36, 44), 13)}
 
 
@@ -161,27 +161,15 @@ def _run_vm(torch, case):
     return out.cpu().numpy().view(np.uint32), work.cpu().numpy()
 
 
-@pytest.mark.parametrize("p1", ["0", "1"], ids=["two-bit", "one-bit"])
-def test_prepass_cube_equals_runtime_loop(torch_cuda, case7, p1, monkeypatch):
-    """the pre-pass with the 7^3 window compiled in and partner validity read from `valid` leaves the same masks,
-    info and pre-pass scores (border, background, no first pixel) as the run-time loop: the workspace holds M and
-    info, and the final scores hold the pre-pass's"""
-    with _Env(monkeypatch, PPP_RANK_PRE_CUBE="0", PPP_RANK_P1=p1):
-        score_loop, work_loop = _run_vm(torch_cuda, case7)
-    with _Env(monkeypatch, PPP_RANK_P1=p1):
-        score_cube, work_cube = _run_vm(torch_cuda, case7)
-    assert np.count_nonzero(work_loop) > 1000
-    assert np.array_equal(work_cube, work_loop)
-    assert np.array_equal(score_cube, score_loop)
-    assert np.array_equal(score_cube, case7["want"].view(np.uint32))
-
-
-def test_prepass_cube_other_sizes(torch_cuda, case59, monkeypatch):
-    with _Env(monkeypatch, PPP_RANK_PRE_CUBE="0"):
-        score_loop, work_loop = _run_vm(torch_cuda, case59)
-    with _Env(monkeypatch):
-        score_cube, work_cube = _run_vm(torch_cuda, case59)
-    assert np.array_equal(work_cube, work_loop) and np.array_equal(score_cube, score_loop)
+def test_prepass_cube_scores_and_workspace(torch_cuda, case7, case59, monkeypatch):
+    """the raw call with no switch set, on a workspace of the test's own: the final scores -- which hold the
+    pre-pass's (border, background, no first pixel) -- are the gather kernel's, and the pre-pass with the window
+    compiled in left its masks and info in the workspace"""
+    for case in (case7, case59):
+        with _Env(monkeypatch):
+            score, work = _run_vm(torch_cuda, case)
+        assert np.count_nonzero(work) > 1000
+        assert np.array_equal(score, case["want"].view(np.uint32))
 
 
 # ---- the rule, without a launch -------------------------------------------------------------------------------
