@@ -252,6 +252,12 @@ int ppp_rank_patches_vm(const void *d_pred, int pred_dtype, const float *d_cons_
  * (no GPU is touched then), or <= 0 for the current device's.  PPP_ERR_UNSUPPORTED where another kernel ranks. */
 int ppp_rank_wg_plan(const ppp_box *score_box, const ppp_params *p, int resident_per_cu, int cus_per_xcd,
                      int32_t plan[8]);
+/* What that plan assumed of a CU, same arguments: res[0] the thickness in z that sizes the LDS arrays of the kernel
+ * it launches (7^3 tiles of a run-time thickness come in a few such sizes, >= plan[3]; otherwise plan[0]), res[1]
+ * the workgroups of that kernel a CU holds (with resident_per_cu given: that number, or fewer where 160 KB of LDS
+ * hold fewer), res[2] the kernel's LDS bytes per workgroup, res[3] the CUs of an XCD. */
+int ppp_rank_wg_plan_residency(const ppp_box *score_box, const ppp_params *p, int resident_per_cu, int cus_per_xcd,
+                               int32_t res[4]);
 
 /* --- S5: patch graph (edge emission) --------------------------------------------------
  * replaces computePatchGraph_cuda (aff_patch_graph.py:113-187) + kernel computePatchGraph

@@ -119,6 +119,8 @@ _SIGNATURES = {
     "ppp_rank_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(Box), ctypes.POINTER(Params)]),
     "ppp_rank_wg_plan": (ctypes.c_int, [ctypes.POINTER(Box), ctypes.POINTER(Params), ctypes.c_int, ctypes.c_int,
                                         ctypes.POINTER(ctypes.c_int32)]),
+    "ppp_rank_wg_plan_residency": (ctypes.c_int, [ctypes.POINTER(Box), ctypes.POINTER(Params), ctypes.c_int,
+                                                  ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]),
     "ppp_rank_patches_vm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(Box),
                                            ctypes.c_void_p, ctypes.POINTER(Params), ctypes.c_void_p]),
@@ -946,6 +948,15 @@ def rank_wg_plan(P, score_box=None, resident_per_cu=0, cus_per_xcd=0):
     check(lib().ppp_rank_wg_plan(box, ctypes.byref(P), int(resident_per_cu), int(cus_per_xcd), out))
     return dict(tile=(out[0], out[1], out[2]), tz_step=out[3], tiles=out[4], splits=out[5], slots=out[6],
                 ranges="weight" if out[7] else "count")
+
+
+def rank_wg_plan_residency(P, score_box=None, resident_per_cu=0, cus_per_xcd=0):
+    """What that plan assumed of a CU (ppp_rank_wg_plan_residency): the thickness that sizes the LDS arrays of the
+    kernel it launches, the workgroups per CU, the LDS bytes per workgroup, the CUs per XCD."""
+    box = None if score_box is None else ctypes.byref(Box(*[int(v) for v in score_box]))
+    out = (ctypes.c_int32 * 4)()
+    check(lib().ppp_rank_wg_plan_residency(box, ctypes.byref(P), int(resident_per_cu), int(cus_per_xcd), out))
+    return dict(lds_tz=out[0], resident=out[1], lds_bytes=out[2], cus_per_xcd=out[3])
 
 
 def rank_vm_available(P):

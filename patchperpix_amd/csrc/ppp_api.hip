@@ -341,6 +341,19 @@ int ppp_rank_wg_plan(const ppp_box *score_box, const ppp_params *p, int resident
     return PPP_OK;
 }
 
+int ppp_rank_wg_plan_residency(const ppp_box *score_box, const ppp_params *p, int resident_per_cu, int cus_per_xcd, int32_t *res) {
+    ppp::Geo G;
+    PPP_TRY(make_geo(p, &G));
+    if (!res) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    if (!ppp::rank_wg_supported(G))
+        return fail(PPP_ERR_UNSUPPORTED, "ppp_rank_wg_plan_residency: the workgroup-per-tile kernel does not serve these parameters");
+    ppp_box sb;
+    PPP_TRY(rank_box(score_box, p, G, &sb));
+    if (resident_per_cu <= 0 || cus_per_xcd <= 0) PPP_TRY(need_device());
+    ppp::rank_wg_plan_residency(sb, G, resident_per_cu, cus_per_xcd, res);
+    return PPP_OK;
+}
+
 #ifdef PPP_RW_STAMPS
 // diagnostic build only, not in the header: where ppp_rank_patches_vm's workspace holds the stamps (-1: nowhere)
 extern "C" int64_t ppp_rank_wg_stamps_offset(const ppp_box *score_box, const ppp_params *p) {

@@ -79,6 +79,9 @@ size_t rank_wg_workspace_bytes(const ppp_box &sb, const Geo &G);
 // the launcher's plan for this box, without a launch: out = tile z, y, x; z step; tiles; splits and order
 // slots per XCD; 1 for XCD ranges of equal weight.  resident_per_cu / cus_per_xcd <= 0: ask the device
 void rank_wg_plan(const ppp_box &sb, const Geo &G, int resident_per_cu, int cus_per_xcd, int32_t out[8]);
+// what that plan assumed of a CU: out = the thickness that sizes the kernel's LDS arrays, workgroups per CU,
+// LDS bytes per workgroup, CUs per XCD
+void rank_wg_plan_residency(const ppp_box &sb, const Geo &G, int resident_per_cu, int cus_per_xcd, int32_t out[4]);
 #ifdef PPP_RW_STAMPS
 size_t rank_wg_stamps_offset(const ppp_box &sb, const Geo &G);   // where the stamps lie in that workspace
 #endif

@@ -90,6 +90,21 @@
 //     Chosen with the tile fit only; PPP_RANK_WG_XCD=weight gives them to any launch (the parent's: 53.9 -> 50.2 ms).
 //   * PRE-PASS with the cubic window compiled in and partner validity read from `valid`: 55.5 -> 53.9 ms per call.
 //   5^3 and 9^3 launches keep their code and their plan: no workload of theirs was swept.
+//
+// Round 14, the SIXTH workgroup per CU of that launch (profiles/r14_a_*; all bit-identical):
+//   * kept: the run-time-thickness kernel in four LDS sizes -- accs, act_bits and uvalid_bits for 8 / 10 / 12 / 16 slices
+//     (RW_FIT_TZ): 20 208 / 22 448 / 24 688 / 29 152 B, which 160 KB hold 8 / 7 / 6 / 5 times (before: 29 152 B and 5 for every
+//     z step) -- at six waves per SIMD, __launch_bounds__(256, 6): 80 VGPRs, nothing spilled, because a quad of mask words is
+//     loaded one quad ahead of its terms (LAZY) instead of all six before the first term.  The occupancy is asked about the
+//     instantiation that is launched, and rw_plan takes the smallest z step in 8 .. 16 whose tiles fit the slots ITS LDS size
+//     gives: 8 at 140^3, 183 tiles per XCD for 192 slots.  S2 call at 140^3 (synthetic cells): 48.1 - 48.6 -> 47.2 - 47.4 ms;
+//     rank_patches per step of the default benchmark 50.52 - 50.60 -> 47.03 - 47.21 ms, the kernel 49.41 -> 46.61 ms per launch.
+//     SQ_WAIT_ANY / SQ_WAVE_CYCLES 0.61 -> 0.62: a wave waits as much as before, a fifth more wave-cycles run beside it.
+//   * dropped: 80 VGPRs with the six mask loads first (10 - 11 registers spilled around the term loop: 66.1 against 48.1 ms at
+//     z step 10); three waves per workgroup at 94 - 95 VGPRs (six workgroups are 18 waves per CU, the parent held 20: 49.1 ms at
+//     z step 8, 51.0 at z step 10); two quads ahead (3 registers spilled, not run).
+//   * the z-step sweep under six per CU: 8 / 9 / 10 / 11 / 12 -> 47.3 / 49.3 / 47.8 / 52.6 / 53.1 ms (parent 51.0 / 49.5 / 48.1 /
+//     53.4 / 53.8): the smallest fitting step still wins.
 #include <stdlib.h>
 #include <string.h>
 
@@ -127,6 +142,14 @@ static constexpr bool rw_zruns(int PX) { return PX == 9; }
 static constexpr bool rw_bankdeal(int PX) { return PX == 7; }
 static constexpr int RW_PAD = 8;
 static constexpr int RW_WAVES = 4;     // waves per workgroup
+// Round 14, the run-time-thickness kernel of 7^3 (DZ): its accumulators and bit arrays are sized by one of a few
+// thicknesses RW_FIT_TZ (the plan takes the smallest >= the z step), so that 160 KB of LDS hold six workgroups
+// and more where the old TZ = 16 sizing (29 KB) stopped at five.  The registers must then allow them too: six
+// workgroups of four waves are six waves per SIMD, 80 VGPRs (see LAZY in the kernel).
+static constexpr int RW_FIT_MINWAVES = 6;
+static constexpr int RW_FIT_NTZ = 4;
+static constexpr int RW_FIT_TZ[RW_FIT_NTZ] = {8, 10, 12, 16};
+static constexpr int rw_fit_index(int tz_step) { return tz_step <= 8 ? 0 : (tz_step <= 10 ? 1 : (tz_step <= 12 ? 2 : 3)); }
 // Mask words per centre, padded to whole 16-byte loads.  The masks are stored CENTRE-MAJOR,
 // M[centre][word]: a lane reads the 184 bytes of ITS centre with twelve 16-byte loads, and the
 // centres of a wave's chunk (9-runs of x neighbours) cover their cache lines densely.  The earlier
@@ -457,10 +480,29 @@ __global__ void __launch_bounds__(32) rank_deal_table_kernel(uint16_t *__restric
 
 // ---- main kernel ---------------------------------------------------------------------------
 // DZ (round 12): the tile's thickness in z is the run-time `tz_step` <= TZ -- TZ then only sizes accs, act_bits and
-// uvalid_bits; the tile origin is tz_i * tz_step and the kernel's ragged-tile handling does the rest.  !DZ:
+// uvalid_bits (round 14: the smallest of RW_FIT_TZ that holds tz_step); the tile origin is tz_i * tz_step and the kernel's ragged-tile handling does the rest.  !DZ:
 // tz_step is TZ (the launches that do not choose their thickness keep their code).
-template <int PZ, int PY, int PX, int TZ, int TY, int TX, bool DZ = false>
-__global__ void __launch_bounds__(64 * RW_WAVES, RW_MINWAVES)
+// MINW (round 14): the waves per SIMD the registers must allow -- RW_MINWAVES for every launch but the DZ one
+// (RW_FIT_MINWAVES).
+//
+// The LDS arrays of an instantiation, in elements, and their bytes as the plan counts them (every array rounded up to
+// 16 bytes: an upper bound of the kernel's group segment, which tools/kernel_regs.py prints).
+template <int P, int TZ, int TY, int TX>
+struct RwLds {
+    static constexpr int W1 = 2 * P - 1, SZ = W1 * W1;
+    static constexpr int SZP = rw_zruns(P) ? SZ + ((9 - SZ % 32) + 32) % 32 : SZ;      // plane stride of the row image (see rw_zruns)
+    static constexpr int ROW = W1 * SZP + 2 * RW_PAD;
+    static constexpr int NT = TZ * TY * TX;
+    static constexpr int ACT = (NT + 31) / 32;
+    static constexpr int UB = (TZ + 2 * (P / 2)) * (TY + 2 * (P / 2)) * (TX + 2 * (P / 2));
+    static constexpr int UV = (UB + 63) / 64 * 2;
+    static constexpr int up16(int b) { return (b + 15) & ~15; }
+    static constexpr int bytes = up16(4 * ROW) + up16(4 * NT) + up16(4 * ACT) + 256 * 8 + up16(4 * UV) + 16;
+};
+static constexpr int RW_LDS_PER_CU = 160 * 1024;
+
+template <int PZ, int PY, int PX, int TZ, int TY, int TX, bool DZ = false, int MINW = RW_MINWAVES>
+__global__ void __launch_bounds__(64 * RW_WAVES, MINW)
     rank_wg_kernel(const float *__restrict__ S, const uint32_t *__restrict__ M,
                    const uint32_t *__restrict__ info, const uint8_t *__restrict__ valid,
                    float *__restrict__ score, const ppp_box sb, const Geo G, const int tiles_y,
@@ -489,11 +531,13 @@ __global__ void __launch_bounds__(64 * RW_WAVES, RW_MINWAVES)
     constexpr int SZP = rw_zruns(PX) ? SZ + ((9 - SZ % 32) + 32) % 32 : SZ;
     constexpr int LCP = LC + (PZ - 1) * (SZP - SZ);
     auto img = [](int e) -> int { return SZP == SZ ? e : (e / SZ) * SZP + e % SZ; };
-    __shared__ float rowbuf[WZ * SZP + 2 * RW_PAD];
-    __shared__ float accs[NT];
-    __shared__ uint32_t act_bits[(NT + 31) / 32];
+    using Lds = RwLds<PX, TZ, TY, TX>;
+    static_assert(PZ == PX && PY == PX && Lds::ROW == WZ * SZP + 2 * RW_PAD && Lds::NT == NT && Lds::UB == UB, "RwLds restates these arrays");
+    __shared__ float rowbuf[Lds::ROW];
+    __shared__ float accs[Lds::NT];
+    __shared__ uint32_t act_bits[Lds::ACT];
     __shared__ uint2 coefT[256];
-    __shared__ uint32_t uvalid_bits[(UB + 63) / 64 * 2];
+    __shared__ uint32_t uvalid_bits[Lds::UV];
     __shared__ int any_act;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -650,6 +694,22 @@ __global__ void __launch_bounds__(64 * RW_WAVES, RW_MINWAVES)
             // (unconditional loads -- t is a centre of the tile for every lane -- then one select
             // per word: a predicated load is a branch per word)
             const uint4 *mc = reinterpret_cast<const uint4 *>(M) + q0;
+            // LAZY (round 14, the six-waves-per-SIMD build): a quad of mask words is loaded one quad ahead of its
+            // terms instead of all six before the first term -- 8 instead of 22 registers hold masks: 80 VGPRs and
+            // nothing spilled (with the six loads up front: 80 and 10 spilled around the term loop, 66 against 48 ms;
+            // two quads ahead: 3 spilled)
+            constexpr bool LAZY = DZ && MINW > RW_MINWAVES;
+            auto load_quad = [&](auto qc) {
+                constexpr int q = decltype(qc)::value;
+                const uint4 v = mc[q * RW_QSTRIDE];
+                if (4 * q < NMW) mw[4 * q] = active ? v.x : 0u;
+                if (4 * q + 1 < NMW) mw[4 * q + 1] = active ? v.y : 0u;
+                if (4 * q + 2 < NMW) mw[4 * q + 2] = active ? v.z : 0u;
+                if (4 * q + 3 < NMW) mw[4 * q + 3] = active ? v.w : 0u;
+            };
+            if constexpr (LAZY) {
+                load_quad(std::integral_constant<int, 0>{});
+            } else {
 #pragma unroll
             for (int q = 0; q < W16P / 4; ++q) {
                 const uint4 v = mc[q * RW_QSTRIDE];
@@ -660,6 +720,7 @@ __global__ void __launch_bounds__(64 * RW_WAVES, RW_MINWAVES)
             }
 #pragma unroll
             for (int w = 0; w < W16; ++w) mw[w] = active ? mw[w] : 0u;
+            }
             float acc = active ? accs[cl] : 0.0f;
             lds_f32_cvp2 row = (lds_f32_cvp2)(rowbuf + RW_PAD + LCP - (az * SZP + ay * WX + ax));
             // (one copy of the row pointer per read of a group: with a single pointer the compiler emits other code)
@@ -675,6 +736,7 @@ __global__ void __launch_bounds__(64 * RW_WAVES, RW_MINWAVES)
             // offset at run time)
             StaticFor<0, W16>::run([&](auto wc) {
                 constexpr int w = decltype(wc)::value;
+                if constexpr (LAZY && w % 4 == 0 && w / 4 + 1 < W16P / 4) load_quad(std::integral_constant<int, w / 4 + 1>{});
                 const uint32_t m = mw[w] & (w < aw ? 0xF0F0F0F0u : (w > aw ? 0xFFFFFFFFu : keep_a));
                 if (__ballot(m != 0u) == 0) return;
                 // table reads of the word first; then the four groups of four partners, the row
@@ -805,18 +867,27 @@ static int rw_choose_splits(int tiles_per_xcd, int slots_per_xcd) {
 }
 // workgroups of the kernel that is launched a CU holds (registers and LDS; asked once per instantiation):
 // the 8 x 16 x 16 tile, or (FIT, 7^3 only) the tile of run-time thickness up to 16
-template <int P, bool FIT>
+// Round 14: FIT asks about the instantiation of thickness TZ that the launch will use -- the answer is a function
+// of the z step (registers allow RW_FIT_MINWAVES waves per SIMD, the LDS what RwLds<7, TZ, 16, 16> leaves).
+template <int P, bool FIT, int TZ = 8>
 static int rw_resident_per_cu() {
     static thread_local int memo = 0;
     if (memo == 0) {
         int nb = 0;
         hipError_t e;
-        if constexpr (FIT) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rank_wg_kernel<P, P, P, 16, 16, 16, true>, 64 * RW_WAVES, 0);
+        if constexpr (FIT) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rank_wg_kernel<P, P, P, TZ, 16, 16, true, RW_FIT_MINWAVES>, 64 * RW_WAVES, 0);
         else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rank_wg_kernel<P, P, P, 8, 16, 16>, 64 * RW_WAVES, 0);
         if (e != hipSuccess || nb < 1) nb = RW_MINWAVES;
         memo = nb;
     }
     return memo;
+}
+// LDS bytes of the instantiation a plan launches (RwLds)
+static int rw_lds_bytes(int P, bool fit, int TZ, int TY) {
+    if (fit) return TZ <= 8 ? RwLds<7, 8, 16, 16>::bytes : (TZ <= 10 ? RwLds<7, 10, 16, 16>::bytes : (TZ <= 12 ? RwLds<7, 12, 16, 16>::bytes : RwLds<7, 16, 16, 16>::bytes));
+#define PPP_RW_LDS(P_) (TZ == 16 ? RwLds<P_, 16, 8, 16>::bytes : (TY == 16 ? RwLds<P_, 8, 16, 16>::bytes : RwLds<P_, 8, 8, 16>::bytes))
+    return P == 5 ? PPP_RW_LDS(5) : (P == 7 ? PPP_RW_LDS(7) : PPP_RW_LDS(9));
+#undef PPP_RW_LDS
 }
 static int rw_cus_per_xcd() {
     static thread_local int memo = 0;
@@ -842,14 +913,17 @@ static int rw_cus_per_xcd() {
 //   * Splits: rw_choose_splits for the 8 x 16 x 16 tile chosen by the rule; PPP_RANK_WG_SPLIT=<tiles per XCD>
 //     overrides (0: whole tiles only), also with a forced tile shape.
 //   * Tile fit (7^3 only): a launch that the 8 x 16 x 16 tiling puts between one and two rounds per XCD takes the
-//     smallest z step in 8 .. 16 whose tiles all fit the resident slots -- one round, no tail, no splits, and
-//     (t + 6) / t instead of 14 / 8 rows staged per centre in z.  PPP_RANK_WG_TZ=<t> forces the z step (tile
+//     smallest z step in 8 .. 16 whose tiles all fit the resident slots OF THAT STEP'S INSTANTIATION (round 14: the LDS
+//     arrays are sized by the thickness, so a thinner tile may have more slots) -- one round, no tail, no splits, and
+//     (t + 6) / t instead of 14 / 8 rows staged per centre in z where t > 8.  PPP_RANK_WG_TZ=<t> forces the z step (tile
 //     t x 16 x 16, 7^3 only; it wins over the tile switches).
 //   * XCD ranges: by tile count, or of equal weight (rank_tile_order_kernel) -- PPP_RANK_WG_XCD=count | weight.
 struct RwPlan {
     int TZ, TY, TX;            // the instantiation's tile
     int tz_step;               // thickness of a tile in z (= TZ unless `fit`)
     bool fit;                  // the instantiation with a run-time z step
+    int lds_tz;                // thickness that sizes its LDS arrays (one of RW_FIT_TZ when `fit`, else TZ)
+    int resident, lds_bytes;   // workgroups per CU the plan assumed for that instantiation, and its LDS bytes
     int tiles_z, tiles_y, tiles_x;
     long long n_tiles;
     int per_xcd, splits, slots;   // slots: an XCD's part of the order array = grid / 8
@@ -859,8 +933,10 @@ static int rw_env_int(EnvSwitch &sw, int none) {
     const char *e = sw.get();
     return (e && e[0] >= '0' && e[0] <= '9') ? atoi(e) : none;
 }
-// resident / resident_fit: workgroups per CU of the 8 x 16 x 16 and of the run-time-thickness instantiation
-static RwPlan rw_plan(const ppp_box &sb, const Geo &G, int resident, int resident_fit, int cus_per_xcd) {
+// workgroups per CU of the 8 x 16 x 16 instantiation and of the run-time-thickness instantiations RW_FIT_TZ
+struct RwResident { int base, fit[RW_FIT_NTZ]; };
+static RwPlan rw_plan(const ppp_box &sb, const Geo &G, const RwResident &res, int cus_per_xcd) {
+    const int resident = res.base;
     const int sX = sb.x1 - sb.x0, sY = sb.y1 - sb.y0, sZ = sb.z1 - sb.z0;
     RwPlan p{};
     const long long big_tiles = (long long)((sZ + 7) / 8) * ((sY + 15) / 16) * ((sX + 15) / 16);
@@ -879,7 +955,7 @@ static RwPlan rw_plan(const ppp_box &sb, const Geo &G, int resident, int residen
     static EnvSwitch xcd_sw("PPP_RANK_WG_XCD");
     const int split_env = rw_env_int(split_sw, -1);
     const int tz_env = G.px == 7 ? rw_env_int(tz_sw, 0) : 0;
-    const int slots_res = resident * cus_per_xcd, slots_fit = resident_fit * cus_per_xcd;
+    const int slots_res = resident * cus_per_xcd;
     auto tiles_of = [&](int t, int ty) { return (long long)((sZ + t - 1) / t) * ((sY + ty - 1) / ty) * ((sX + 15) / 16); };
     if (tz_env > 0) {
         p.fit = true; p.TZ = 16; p.TY = 16; p.TX = 16;
@@ -887,9 +963,12 @@ static RwPlan rw_plan(const ppp_box &sb, const Geo &G, int resident, int residen
     } else if (by_rule && G.px == 7 && split_env < 0) {
         const long long per0 = (tiles_of(8, 16) + 7) / 8;
         if (slots_res > 0 && per0 > slots_res && per0 < 2LL * slots_res)
-            for (int t = 9; t <= 16; ++t)
-                if ((tiles_of(t, 16) + 7) / 8 <= slots_fit) { p.fit = true; p.TZ = 16; p.tz_step = t; break; }
+            for (int t = 8; t <= 16; ++t)
+                if ((tiles_of(t, 16) + 7) / 8 <= (long long)res.fit[rw_fit_index(t)] * cus_per_xcd) { p.fit = true; p.TZ = 16; p.tz_step = t; break; }
     }
+    p.lds_tz = p.fit ? RW_FIT_TZ[rw_fit_index(p.tz_step)] : p.TZ;
+    p.resident = p.fit ? res.fit[rw_fit_index(p.tz_step)] : resident;
+    p.lds_bytes = rw_lds_bytes(G.px, p.fit, p.lds_tz, p.TY);
     p.tiles_z = (sZ + p.tz_step - 1) / p.tz_step; p.tiles_y = (sY + p.TY - 1) / p.TY; p.tiles_x = (sX + p.TX - 1) / p.TX;
     p.n_tiles = (long long)p.tiles_z * p.tiles_y * p.tiles_x;
     p.per_xcd = (int)((p.n_tiles + 7) / 8);
@@ -914,16 +993,42 @@ static RwPlan rw_plan(const ppp_box &sb, const Geo &G, int resident, int residen
     return p;
 }
 static RwPlan rw_plan_device(const ppp_box &sb, const Geo &G) {
-    const int res = G.px == 5 ? rw_resident_per_cu<5, false>() : (G.px == 7 ? rw_resident_per_cu<7, false>() : rw_resident_per_cu<9, false>());
-    return rw_plan(sb, G, res, G.px == 7 ? rw_resident_per_cu<7, true>() : res, rw_cus_per_xcd());
+    RwResident res;
+    res.base = G.px == 5 ? rw_resident_per_cu<5, false>() : (G.px == 7 ? rw_resident_per_cu<7, false>() : rw_resident_per_cu<9, false>());
+    for (int i = 0; i < RW_FIT_NTZ; ++i) res.fit[i] = res.base;
+    if (G.px == 7) {
+        res.fit[0] = rw_resident_per_cu<7, true, 8>(); res.fit[1] = rw_resident_per_cu<7, true, 10>();
+        res.fit[2] = rw_resident_per_cu<7, true, 12>(); res.fit[3] = rw_resident_per_cu<7, true, 16>();
+    }
+    return rw_plan(sb, G, res, rw_cus_per_xcd());
+}
+// a device that is not there: `resident` workgroups per CU by its registers, fewer where the LDS of the
+// instantiation holds fewer
+static RwPlan rw_plan_assumed(const ppp_box &sb, const Geo &G, int resident, int cus_per_xcd) {
+    RwResident res;
+    res.base = resident;
+    for (int i = 0; i < RW_FIT_NTZ; ++i) {
+        const int by_lds = RW_LDS_PER_CU / rw_lds_bytes(7, true, RW_FIT_TZ[i], 16);
+        res.fit[i] = resident < by_lds ? resident : by_lds;
+    }
+    return rw_plan(sb, G, res, cus_per_xcd);
 }
 // out: tile z, y, x; z step; tiles; splits per XCD; slots per XCD; 1 = ranges of equal weight.
 // resident_per_cu / cus_per_xcd <= 0: ask the device
 void rank_wg_plan(const ppp_box &sb, const Geo &G, int resident_per_cu, int cus_per_xcd, int32_t out[8]) {
-    const RwPlan p = (resident_per_cu > 0 && cus_per_xcd > 0) ? rw_plan(sb, G, resident_per_cu, resident_per_cu, cus_per_xcd)
+    const RwPlan p = (resident_per_cu > 0 && cus_per_xcd > 0) ? rw_plan_assumed(sb, G, resident_per_cu, cus_per_xcd)
                                                               : rw_plan_device(sb, G);
     out[0] = p.TZ; out[1] = p.TY; out[2] = p.TX; out[3] = p.tz_step;
     out[4] = (int32_t)p.n_tiles; out[5] = p.splits; out[6] = p.slots; out[7] = p.by_weight ? 1 : 0;
+}
+// ... and what that plan assumed of the CU: out = the thickness that sizes the kernel's LDS arrays, the
+// workgroups per CU, the LDS bytes per workgroup, the CUs per XCD
+void rank_wg_plan_residency(const ppp_box &sb, const Geo &G, int resident_per_cu, int cus_per_xcd, int32_t out[4]) {
+    const bool assumed = resident_per_cu > 0 && cus_per_xcd > 0;
+    const RwPlan p = assumed ? rw_plan_assumed(sb, G, resident_per_cu, cus_per_xcd) : rw_plan_device(sb, G);
+    const int by_lds = RW_LDS_PER_CU / p.lds_bytes;
+    out[0] = p.lds_tz; out[1] = (assumed && by_lds < p.resident) ? by_lds : p.resident; out[2] = p.lds_bytes;
+    out[3] = assumed ? cus_per_xcd : rw_cus_per_xcd();
 }
 
 template <typename T>
@@ -975,9 +1080,12 @@ static hipError_t launch_rwg(const T *pred, const float *S, const uint8_t *ov, f
 #else
 #define PPP_RW_STAMP_ARG
 #endif
+#define PPP_RW_ARGS S, M, info, valid, score, sb, G, tiles_y, tiles_x, (int)n_tiles, order, y_major, dealT, tz_step PPP_RW_STAMP_ARG
 #define PPP_RW_LAUNCH(A_, D_, E_, F_, DZ_)                                                                  \
-    rank_wg_kernel<A_, A_, A_, D_, E_, F_, DZ_><<<dim3((unsigned)n_blocks), dim3(64 * RW_WAVES), 0, s>>>(   \
-        S, M, info, valid, score, sb, G, tiles_y, tiles_x, (int)n_tiles, order, y_major, dealT, tz_step PPP_RW_STAMP_ARG)
+    rank_wg_kernel<A_, A_, A_, D_, E_, F_, DZ_><<<dim3((unsigned)n_blocks), dim3(64 * RW_WAVES), 0, s>>>(PPP_RW_ARGS)
+#define PPP_RW_LAUNCH_FIT(TZ_)                                                                              \
+    rank_wg_kernel<7, 7, 7, TZ_, 16, 16, true, RW_FIT_MINWAVES>                                             \
+        <<<dim3((unsigned)n_blocks), dim3(64 * RW_WAVES), 0, s>>>(PPP_RW_ARGS)
 #define PPP_RW_CASE(P)                                                                                      \
     case P:                                                                                                 \
         if (tall) PPP_RW_LAUNCH(P, 16, 8, 16, false);                                                       \
@@ -987,7 +1095,13 @@ static hipError_t launch_rwg(const T *pred, const float *S, const uint8_t *ov, f
     if (fit) {
         // (the tile of run-time thickness: built for 7^3 alone, the only size the plan gives it to)
         if (G.px != 7) return hipErrorNotSupported;
-        PPP_RW_LAUNCH(7, 16, 16, 16, true);
+        // (tz_step <= lds_tz: the kernel clamps, and the plan never asks for more)
+        switch (plan.lds_tz) {
+        case 8: PPP_RW_LAUNCH_FIT(8); break;
+        case 10: PPP_RW_LAUNCH_FIT(10); break;
+        case 12: PPP_RW_LAUNCH_FIT(12); break;
+        default: PPP_RW_LAUNCH_FIT(16); break;
+        }
     } else
     switch (G.px) {
         PPP_RW_CASE(5)
@@ -997,6 +1111,8 @@ static hipError_t launch_rwg(const T *pred, const float *S, const uint8_t *ov, f
         return hipErrorNotSupported;
     }
 #undef PPP_RW_LAUNCH
+#undef PPP_RW_LAUNCH_FIT
+#undef PPP_RW_ARGS
 #undef PPP_RW_STAMP_ARG
 #undef PPP_RW_CASE
 #undef PPP_RW_PRE
