@@ -1019,6 +1019,50 @@ int ppp_label_overlap(const uint32_t *d_a, int32_t La, const uint32_t *d_b, int3
 int ppp_patch_mosaic(const void *d_pred, int pred_dtype, int32_t C, const uint8_t *d_selected, int32_t S,
                      void *d_out, int32_t tz, int32_t Y, int32_t X, const int32_t *patch /* [3] */, void *stream);
 
+/* --- the ground-truth patch affinities of a label volume as an array (csrc/ppp_gt_affs.hip) -----
+ * The reference's `seg_to_affgraph_*_torch*` family (PatchPerPix/util/train_util.py:349-775): the BCE target
+ * of the patch loss, made from the labels inside every training step (torch_model.py:201-223, :366-370,
+ * :429-441) with a Python loop over the E edges.  Here it is one launch: the labels are read once, the output
+ * is written once and never read back.  Only equality and "!= 0" are used: 0 is background, every other
+ * 32-bit value is an id, negative ones included.  No workspace; neither call synchronises the stream.
+ *   d_labels int32 [B][L][Z][Y][X], vol = (Z, Y, X); 2-d data is Z = 1 with zero z-offsets.
+ *   d_nhood  int32 [E][3] on the DEVICE.
+ * ppp_gt_affs_dense: nhood[e] is an offset of any size and sign.
+ *   multi  (single = 0): out[b][e][v] = 1 iff v + nhood[e] lies inside the volume and some channel c has
+ *          labels[b][c][v] != 0 and labels[b][c][v] == labels[b][c][v + nhood[e]], else 0: the same id in
+ *          the SAME channel (train_util.py:523-610; its two foreground factors are implied).
+ *   single (single = 1, L = 1, PPP_F32): out[b][e][v] = float(c * c) with c = labels[b][v] where
+ *          c == labels[b][v + nhood[e]], else 0 -- the id SQUARED, the reference multiplies by the label
+ *          values (train_util.py:613-695); the product is the 32-bit one, exact for |id| <= 46340.
+ *   An offset with |n| >= the axis gives zeros (the reference: zeros at |n| == S, an exception beyond).
+ *   halo   HOST [6] = min z, max z, min y, max y, min x, max x over nhood: it sizes the tile of labels a
+ *          workgroup stages in LDS.  An edge outside it gets UNDEFINED values (never an access out of bounds).
+ *   box    HOST [6] = z0, z1, y0, y1, x0, x1, non-empty and inside the volume: the voxels v that are written.
+ *   d_out  [B][E][z1-z0][y1-y0][x1-x0] of out_dtype (0 and 1 are exact in all three); EVERY element is
+ *          written, the caller does not clear it.  Offsets are 64-bit: E V may pass 2^31.
+ *   ppp_gt_affs_dense_plan: what a call with these sizes does, without a launch (tests size their cases by it):
+ *          plan[5] = tile z, y, x of a workgroup; 1 when tile + halo are staged in LDS, 0 when every neighbour is
+ *          loaded from global memory (they do not fit 64 KiB); edge ranges a tile is split into.
+ * ppp_gt_affs_samples: the patch form (train_util.py:349-520).
+ *   d_samples int32 [N][4], rows (b, z, y, x): the CORNER of a patch of ps = (pz, py, px) voxels; nhood[e] is an
+ *          index INTO the patch, ctr[3] the patch's centre index.  Duplicate rows are fine.
+ *   d_out  [N][E] of out_dtype: out[n][e] = 1 iff some c has P[c][ctr] != 0 and P[c][ctr] == P[c][nhood[e]],
+ *          P the patch of row n.  A voxel outside the volume reads as 0, as does an index outside [0, ps) and a
+ *          row whose b is outside [0, B).  N = 0 returns PPP_OK and touches nothing.
+ * PPP_ERR_INVALID_ARG: B < 1, L < 1, E < 1, a bad volume, an empty box or one that leaves the volume, a halo
+ * minimum above its maximum, single with L != 1 or another type than PPP_F32, ctr outside [0, ps), N < 0, NULL
+ * or misaligned pointers.  PPP_ERR_UNSUPPORTED: V >= 2^31 per batch item, E > 65535, a grid the device would
+ * not run whole.  PPP_ERR_NO_DEVICE without a device.                                              */
+int ppp_gt_affs_dense_plan(int32_t B, int32_t L, const int32_t *vol /* [3] */, int32_t E, const int32_t *halo /* [6] */,
+                           const int32_t *box /* [6] */, int out_dtype, int32_t single, int32_t *plan /* [5] */);
+int ppp_gt_affs_dense(const int32_t *d_labels, int32_t B, int32_t L, const int32_t *vol /* [3] */,
+                      const int32_t *d_nhood, int32_t E, const int32_t *halo /* host [6] */,
+                      const int32_t *box /* host [6] */, void *d_out, int out_dtype, int32_t single, void *stream);
+int ppp_gt_affs_samples(const int32_t *d_labels, int32_t B, int32_t L, const int32_t *vol /* [3] */,
+                        const int32_t *d_samples /* [N][4] */, int64_t N, const int32_t *d_nhood, int32_t E,
+                        const int32_t *ps /* [3] */, const int32_t *ctr /* [3] */, void *d_out, int out_dtype,
+                        void *stream);
+
 /* --- synthetic input (bench / tests only; same hash as patchperpix_amd/synth.py) ------
  * fills d_pred (C,Z,Y,X) from a label volume d_labels int32 (Z,Y,X).  voxel_offset is the
  * linear index of local voxel 0 in the global volume (0 unless the buffers are a slab).    */

@@ -407,6 +407,19 @@ _SIGNATURES = {
     "ppp_patch_mosaic": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                         ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                         ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p]),
+    # the ground-truth patch affinities as an array (ppp_gt_affs.hip)
+    "ppp_gt_affs_dense_plan": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                              ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                              ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int32,
+                                              ctypes.POINTER(ctypes.c_int32)]),
+    "ppp_gt_affs_dense": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                         ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                         ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_int, ctypes.c_int32,
+                                         ctypes.c_void_p]),
+    "ppp_gt_affs_samples": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                           ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32,
+                                           ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p,
+                                           ctypes.c_int, ctypes.c_void_p]),
     # no_overlap_per_channel without the loop over components (ppp_pack_channels.hip, ppp_host_pack.cpp)
     "ppp_pack_scan_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(Params), ctypes.POINTER(Box)]),
     "ppp_pack_scan_count": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
@@ -2269,6 +2282,95 @@ def patch_mosaic(pred_tile, patchshape, selected=None, out=None):
     with _timed("patch_mosaic"):
         check(lib().ppp_patch_mosaic(_dev_ptr(pred_tile), pred_dtype_code(pred_tile), C, _dev_ptr(selected), S,
                                      _dev_ptr(out), tz, Y, X, patch, _stream()))
+    return out
+
+
+def _out_dtype_code(dtype):
+    torch = _torch()
+    codes = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
+    assert dtype in codes, "out_dtype must be float32, float16 or bfloat16, got %s" % dtype
+    return codes[dtype]
+
+
+def nhood_halo(nhood):
+    """The per-axis minimum and maximum of a device `nhood` (E, 3), the `halo` of ppp_gt_affs_dense: computed
+    ONCE per tensor (one device -> host read, kept on the tensor with the version it was made from)."""
+    have = getattr(nhood, "_ppp_halo", None)
+    if have is None or have[0] != nhood._version:
+        lo, hi = nhood.amin(dim=0).tolist(), nhood.amax(dim=0).tolist()
+        have = (nhood._version, (lo[0], hi[0], lo[1], hi[1], lo[2], hi[2]))
+        nhood._ppp_halo = have
+    return have[1]
+
+
+def gt_affs_dense_plan(B, L, vol, E, halo, box, out_dtype=None, single=False):
+    """ppp_gt_affs_dense_plan: (tile z, y, x, staged in LDS, edge ranges per tile) of a call with these sizes."""
+    torch = _torch()
+    plan = (ctypes.c_int32 * 5)()
+    check(lib().ppp_gt_affs_dense_plan(int(B), int(L), (ctypes.c_int32 * 3)(*[int(v) for v in vol]), int(E),
+                                       (ctypes.c_int32 * 6)(*[int(v) for v in halo]),
+                                       (ctypes.c_int32 * 6)(*[int(v) for v in box]),
+                                       _out_dtype_code(out_dtype or torch.float32), 1 if single else 0, plan))
+    return tuple(int(v) for v in plan)
+
+
+def gt_affs_dense(labels, nhood, box=None, out=None, out_dtype=None, single=False):
+    """ppp_gt_affs_dense: the ground-truth affinities of `labels`, a contiguous int32 device tensor (B, L, Z, Y, X)
+    -- (B, Z, Y, X) with `single`, the one-channel form whose value is the id squared (float32 only) -- for the
+    offsets `nhood`, a contiguous int32 device tensor (E, 3).  `box` = (z0, z1, y0, y1, x0, x1): the voxels
+    that are written (default: all).  Returns (B, E, z1-z0, y1-y0, x1-x0) of `out_dtype` (float32 / float16 /
+    bfloat16, default float32); `out`, when given, is that tensor and EVERY element of it is written.  Does not
+    synchronise (the halo of a `nhood` tensor is read back once, `nhood_halo`)."""
+    torch = _torch()
+    assert labels.dtype == torch.int32 and labels.dim() == (4 if single else 5), \
+        "gt_affs_dense needs int32 labels (B, L, Z, Y, X), or (B, Z, Y, X) with single"
+    assert nhood.dtype == torch.int32 and nhood.dim() == 2 and nhood.shape[1] == 3, "nhood is an int32 (E, 3) tensor"
+    B, L = int(labels.shape[0]), (1 if single else int(labels.shape[1]))
+    Z, Y, X = [int(v) for v in labels.shape[-3:]]
+    E = int(nhood.shape[0])
+    if box is None:
+        box = (0, Z, 0, Y, 0, X)
+    box = [int(v) for v in box]
+    assert len(box) == 6, "box = (z0, z1, y0, y1, x0, x1)"
+    if out_dtype is None:
+        out_dtype = torch.float32 if out is None else out.dtype
+    assert not single or out_dtype == torch.float32, "the one-channel form (id squared) is float32 only"
+    shape = (B, E, box[1] - box[0], box[3] - box[2], box[5] - box[4])
+    if out is None:
+        assert min(shape) > 0, "box %s is empty" % (box,)
+        out = torch.empty(shape, dtype=out_dtype, device=labels.device)
+    assert tuple(out.shape) == shape and out.dtype == out_dtype, "out must be %s of %s" % (shape, out_dtype)
+    halo = nhood_halo(nhood) if E > 0 else (0,) * 6
+    with _timed("gt_affs_dense"):
+        check(lib().ppp_gt_affs_dense(_dev_ptr(labels), B, L, (ctypes.c_int32 * 3)(Z, Y, X), _dev_ptr(nhood), E,
+                                      (ctypes.c_int32 * 6)(*halo), (ctypes.c_int32 * 6)(*box), _dev_ptr(out),
+                                      _out_dtype_code(out_dtype), 1 if single else 0, _stream()))
+    return out
+
+
+def gt_affs_samples(labels, samples, nhood, ps, ctr, out=None, out_dtype=None):
+    """ppp_gt_affs_samples: `labels` a contiguous int32 device tensor (B, L, Z, Y, X), `samples` int32 (N, 4) rows
+    (b, z, y, x), the corners of patches of `ps` = (pz, py, px) voxels, `nhood` int32 (E, 3) indices into the
+    patch, `ctr` the centre's index.  Returns (N, E) of `out_dtype` (default float32), or `out`.  Voxels outside
+    the volume read as 0; N = 0 gives an empty tensor.  Does not synchronise."""
+    torch = _torch()
+    assert labels.dtype == torch.int32 and labels.dim() == 5, "gt_affs_samples needs int32 labels (B, L, Z, Y, X)"
+    assert samples.dtype == torch.int32 and samples.dim() == 2 and samples.shape[1] == 4, \
+        "samples is an int32 (N, 4) tensor of rows (b, z, y, x)"
+    assert nhood.dtype == torch.int32 and nhood.dim() == 2 and nhood.shape[1] == 3, "nhood is an int32 (E, 3) tensor"
+    B, L, Z, Y, X = [int(v) for v in labels.shape]
+    N, E = int(samples.shape[0]), int(nhood.shape[0])
+    if out_dtype is None:
+        out_dtype = torch.float32 if out is None else out.dtype
+    if out is None:
+        out = torch.empty((N, E), dtype=out_dtype, device=labels.device)
+    assert tuple(out.shape) == (N, E) and out.dtype == out_dtype, "out must be %s of %s" % ((N, E), out_dtype)
+    with _timed("gt_affs_samples"):
+        check(lib().ppp_gt_affs_samples(_dev_ptr(labels), B, L, (ctypes.c_int32 * 3)(Z, Y, X),
+                                        _dev_ptr(samples) if N else None, N, _dev_ptr(nhood), E,
+                                        (ctypes.c_int32 * 3)(*[int(p) for p in ps]),
+                                        (ctypes.c_int32 * 3)(*[int(c) for c in ctr]), _dev_ptr(out) if N else None,
+                                        _out_dtype_code(out_dtype), _stream()))
     return out
 
 

@@ -1706,4 +1706,74 @@ int ppp_patch_mosaic(const void *d_pred, int pred_dtype, int32_t C, const uint8_
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_patch_mosaic");
 }
 
+/* ---- the ground-truth patch affinities as an array (ppp_gt_affs.hip) ---- */
+static int gt_affs_labels(int32_t B, int32_t L, const int32_t *vol, int32_t E) {
+    if (!vol) return fail(PPP_ERR_INVALID_ARG, "NULL vol");
+    if (B < 1 || L < 1) return fail(PPP_ERR_INVALID_ARG, "labels need at least one batch item and one channel (B = %d, L = %d)", B, L);
+    long long V;
+    PPP_TRY(post_volume(vol[0], vol[1], vol[2], &V));
+    if (E < 1) return fail(PPP_ERR_INVALID_ARG, "E = %d: at least one edge", E);
+    if (E > 65535) return fail(PPP_ERR_UNSUPPORTED, "E = %d: more than 65535 edges are not supported", E);
+    return PPP_OK;
+}
+
+static int gt_affs_dense_args(int32_t B, int32_t L, const int32_t *vol, int32_t E, const int32_t *halo, const int32_t *box,
+                              int out_dtype, int32_t single) {
+    PPP_TRY(gt_affs_labels(B, L, vol, E));
+    PPP_TRY(check_dtype(out_dtype));
+    if (single && out_dtype != PPP_F32) return fail(PPP_ERR_INVALID_ARG, "the one-channel form (id squared) is float32 only");
+    if (single && L != 1) return fail(PPP_ERR_INVALID_ARG, "the one-channel form takes L = 1, not %d", L);
+    if (!halo || !box) return fail(PPP_ERR_INVALID_ARG, "NULL halo or box");
+    for (int a = 0; a < 3; ++a) {
+        if (halo[2 * a] > halo[2 * a + 1])
+            return fail(PPP_ERR_INVALID_ARG, "halo of axis %d: minimum %d above maximum %d", a, halo[2 * a], halo[2 * a + 1]);
+        if (box[2 * a] < 0 || box[2 * a + 1] > vol[a] || box[2 * a] >= box[2 * a + 1])
+            return fail(PPP_ERR_INVALID_ARG, "box [%d, %d) of axis %d is empty or leaves the volume of %d", box[2 * a],
+                        box[2 * a + 1], a, vol[a]);
+    }
+    return PPP_OK;
+}
+
+int ppp_gt_affs_dense_plan(int32_t B, int32_t L, const int32_t *vol, int32_t E, const int32_t *halo, const int32_t *box,
+                           int out_dtype, int32_t single, int32_t *plan) {
+    PPP_TRY(gt_affs_dense_args(B, L, vol, E, halo, box, out_dtype, single));
+    if (!plan) return fail(PPP_ERR_INVALID_ARG, "NULL plan");
+    ppp::gt_affs_dense_plan(B, L, E, halo, box, plan);
+    return PPP_OK;
+}
+
+int ppp_gt_affs_dense(const int32_t *d_labels, int32_t B, int32_t L, const int32_t *vol, const int32_t *d_nhood, int32_t E,
+                      const int32_t *halo, const int32_t *box, void *d_out, int out_dtype, int32_t single, void *stream) {
+    PPP_TRY(gt_affs_dense_args(B, L, vol, E, halo, box, out_dtype, single));
+    if (!d_labels || !d_nhood || !d_out || ((uintptr_t)d_labels & 3) || ((uintptr_t)d_nhood & 3) ||
+        ((uintptr_t)d_out & (out_dtype == PPP_F32 ? 3 : 1)))
+        return fail(PPP_ERR_INVALID_ARG, "NULL or misaligned pointer argument");
+    PPP_TRY(need_device());
+    hipError_t e = ppp::run_gt_affs_dense(d_labels, B, L, vol[0], vol[1], vol[2], d_nhood, E, halo, box, d_out, out_dtype,
+                                          single ? 1 : 0, (hipStream_t)stream);
+    if (e == hipErrorInvalidConfiguration) return fail(PPP_ERR_UNSUPPORTED, "ppp_gt_affs_dense: a grid the device would not run whole");
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_gt_affs_dense");
+}
+
+int ppp_gt_affs_samples(const int32_t *d_labels, int32_t B, int32_t L, const int32_t *vol, const int32_t *d_samples, int64_t N,
+                        const int32_t *d_nhood, int32_t E, const int32_t *ps, const int32_t *ctr, void *d_out, int out_dtype,
+                        void *stream) {
+    PPP_TRY(gt_affs_labels(B, L, vol, E));
+    PPP_TRY(check_dtype(out_dtype));
+    if (!ps || !ctr) return fail(PPP_ERR_INVALID_ARG, "NULL ps or ctr");
+    for (int a = 0; a < 3; ++a)
+        if (ps[a] < 1 || ctr[a] < 0 || ctr[a] >= ps[a])
+            return fail(PPP_ERR_INVALID_ARG, "axis %d: centre %d outside the patch of %d", a, ctr[a], ps[a]);
+    if (N < 0) return fail(PPP_ERR_INVALID_ARG, "N must be >= 0");
+    if (N == 0) return PPP_OK;
+    if (!d_labels || !d_samples || !d_nhood || !d_out || ((uintptr_t)d_labels & 3) || ((uintptr_t)d_samples & 3) ||
+        ((uintptr_t)d_nhood & 3) || ((uintptr_t)d_out & (out_dtype == PPP_F32 ? 3 : 1)))
+        return fail(PPP_ERR_INVALID_ARG, "NULL or misaligned pointer argument");
+    PPP_TRY(need_device());
+    hipError_t e = ppp::run_gt_affs_samples(d_labels, B, L, vol[0], vol[1], vol[2], d_samples, (long long)N, d_nhood, E, ps, ctr,
+                                            d_out, out_dtype, (hipStream_t)stream);
+    if (e == hipErrorInvalidConfiguration) return fail(PPP_ERR_UNSUPPORTED, "ppp_gt_affs_samples: N = %lld is more than one launch runs", (long long)N);
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_gt_affs_samples");
+}
+
 }  // extern "C"

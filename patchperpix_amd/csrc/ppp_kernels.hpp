@@ -297,4 +297,13 @@ size_t label_overlap_workspace_bytes(long long V, long long streams);
 hipError_t run_label_overlap(const uint32_t *a, int La, const uint32_t *b, int Lb, long long V, uint32_t *rows,
                              long long *counts, long long cap, long long *n_rows, void *work, hipStream_t s);
 
+// the ground-truth patch affinities of a label volume as an array (ppp_gt_affs.hip): every element of `out` is
+// written; no workspace, no synchronisation.  plan out[5]: tile z, y, x; staged in LDS; edge ranges per tile
+void gt_affs_dense_plan(int B, int L, int E, const int *halo, const int *box, int32_t out[5]);
+hipError_t run_gt_affs_dense(const int32_t *labels, int B, int L, int Z, int Y, int X, const int32_t *nhood, int E,
+                             const int *halo, const int *box, void *out, int dtype, int single, hipStream_t s);
+hipError_t run_gt_affs_samples(const int32_t *labels, int B, int L, int Z, int Y, int X, const int32_t *samples,
+                               long long N, const int32_t *nhood, int E, const int *ps, const int *ctr, void *out,
+                               int dtype, hipStream_t s);
+
 }  // namespace ppp
