@@ -1063,6 +1063,66 @@ int ppp_gt_affs_samples(const int32_t *d_labels, int32_t B, int32_t L, const int
                         const int32_t *ps /* [3] */, const int32_t *ctr /* [3] */, void *d_out, int out_dtype,
                         void *stream);
 
+/* --- the fused patch loss from the labels: masked BCE with logits, forward and backward (csrc/ppp_patch_loss.hip) ---
+ * The reference's `add_affinities = "loss"` makes the target above only to feed it to MaskedBCEWithLogitsLoss
+ * (experiments/flylight/setups/setup01/torch_loss.py:47-67, called at :127-129).  Here the target is consumed
+ * where it is made and never stored: the forward reads the logits once, the backward reads them once and
+ * writes the gradient once; nothing else of that size exists.
+ *   G[b][e][v]  exactly the multi predicate of ppp_gt_affs_dense (same id in the same channel, offsets of any
+ *               size, zero outside the volume), for the voxels v of `box`; labels, vol, nhood, halo, box as there.
+ *   l(x, g)   = max(x, 0) - x g + log1p(exp(-|x|))
+ * Dense form.  d_logits [B][E][bZ][bY][bX] of `dtype` (PPP_F32 / PPP_F16 / PPP_BF16, widened exactly in registers,
+ *   float32 arithmetic per element), the box's extents; d_weight float32 [B][bZ][bY][bX] >= 0, or NULL.
+ *     with weights     cnt = num_channels * sum w;  loss = sum w[b][v] l(x[b][e][v], G[b][e][v]) / cnt, 0 when cnt == 0
+ *     without          cnt = B E bV (num_channels is not used)
+ *     backward         d_grad[b][e][v] = s w[b][v] (sigmoid(x) - g) grad_out, s = 1 / cnt, 0 when cnt == 0 (the
+ *                      reference's mean(loss) * 0.0); sigmoid(x) - g is formed as g ? -sigmoid(-x) : sigmoid(x)
+ *                      from exp(-|x|), and the product is rounded to nearest-even into `dtype` AFTER the
+ *                      multiplication by s w grad_out (a GradScaler's factor keeps float16 out of the subnormals).
+ *   A voxel with w == 0 contributes 0 and gets gradient 0 WHATEVER its logits hold; a 16-byte group of logits whose
+ *   weights are all zero is not read.  (The reference gives NaN there for a non-finite logit: 0 * inf.)
+ *   d_loss   float32 [1].   d_state double [2] = (s, sum w -- B E bV without weights): carries s from the forward
+ *            to the backward ON THE DEVICE.   d_grad_out float32 [1] on the DEVICE.
+ *   d_counts int64 [3] or NULL: over ALL elements of the box, unweighted, the number with x > 0, with G, and with
+ *            x > 0 && G (torch_loss.py:133-141 needs no more for jaccard and accuracy).  The call clears them;
+ *            with counters every element is read, w == 0 or not.
+ *   d_grad   the shape and type of d_logits; EVERY element is written, zeros included.
+ *   d_work   ppp_patch_loss_workspace_bytes(B, L, vol, E, halo, box, dtype, 0) bytes, 8-byte aligned, forward only:
+ *            one double per workgroup and sum.  Each workgroup writes its own slot and one workgroup adds the
+ *            slots in a fixed order; there is no floating-point atomic, so loss, s and gradient have the same
+ *            bits in every run.  Tiles and the staged / direct choice are ppp_gt_affs_dense_plan's.
+ *   Offsets are 64-bit: B E bV may pass 2^31.
+ * Sampled form (train_code; the reference passes no mask there).  d_logits / d_grad [N][E]; G[n][e], d_samples, ps,
+ *   ctr as ppp_gt_affs_samples defines them; loss = sum l / (N E).  Workspace: box = NULL and N.  N = 0 returns
+ *   PPP_OK and touches nothing (the caller's loss is 0, its gradient empty).
+ * The one-channel "id squared" target is not served: a BCE against c * c has no meaning.
+ * No entry point synchronises the stream or reads back to the host.  Errors as ppp_gt_affs_dense /
+ * ppp_gt_affs_samples (PPP_ERR_INVALID_ARG: sizes, box, halo, ctr, N < 0, with weights a num_channels that is not
+ * positive and finite, NULL or misaligned pointers; PPP_ERR_UNSUPPORTED: V >= 2^31, E > 65535, a grid the device
+ * would not run whole; PPP_ERR_NO_DEVICE); ppp_patch_loss_workspace_bytes returns the negative code.            */
+int64_t ppp_patch_loss_workspace_bytes(int32_t B, int32_t L, const int32_t *vol /* [3] */, int32_t E,
+                                       const int32_t *halo /* [6], dense */, const int32_t *box /* [6], or NULL: sampled */,
+                                       int dtype, int64_t N /* sampled */);
+int ppp_patch_loss_dense_fwd(const void *d_logits, int dtype, const int32_t *d_labels, int32_t B, int32_t L,
+                             const int32_t *vol /* [3] */, const int32_t *d_nhood, int32_t E, const int32_t *halo /* host [6] */,
+                             const int32_t *box /* host [6] */, const float *d_weight /* or NULL */, double num_channels,
+                             float *d_loss /* [1] */, double *d_state /* [2] */, int64_t *d_counts /* [3] or NULL */,
+                             void *d_work, void *stream);
+int ppp_patch_loss_dense_bwd(const void *d_logits, int dtype, const int32_t *d_labels, int32_t B, int32_t L,
+                             const int32_t *vol /* [3] */, const int32_t *d_nhood, int32_t E, const int32_t *halo /* host [6] */,
+                             const int32_t *box /* host [6] */, const float *d_weight /* or NULL */,
+                             const double *d_state /* [2] */, const float *d_grad_out /* device [1] */, void *d_grad,
+                             void *stream);
+int ppp_patch_loss_samples_fwd(const void *d_logits, int dtype, const int32_t *d_labels, int32_t B, int32_t L,
+                               const int32_t *vol /* [3] */, const int32_t *d_samples /* [N][4] */, int64_t N,
+                               const int32_t *d_nhood, int32_t E, const int32_t *ps /* [3] */, const int32_t *ctr /* [3] */,
+                               float *d_loss /* [1] */, double *d_state /* [2] */, void *d_work, void *stream);
+int ppp_patch_loss_samples_bwd(const void *d_logits, int dtype, const int32_t *d_labels, int32_t B, int32_t L,
+                               const int32_t *vol /* [3] */, const int32_t *d_samples /* [N][4] */, int64_t N,
+                               const int32_t *d_nhood, int32_t E, const int32_t *ps /* [3] */, const int32_t *ctr /* [3] */,
+                               const double *d_state /* [2] */, const float *d_grad_out /* device [1] */, void *d_grad,
+                               void *stream);
+
 /* --- synthetic input (bench / tests only; same hash as patchperpix_amd/synth.py) ------
  * fills d_pred (C,Z,Y,X) from a label volume d_labels int32 (Z,Y,X).  voxel_offset is the
  * linear index of local voxel 0 in the global volume (0 unless the buffers are a slab).    */

@@ -420,6 +420,30 @@ _SIGNATURES = {
                                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32,
                                            ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p,
                                            ctypes.c_int, ctypes.c_void_p]),
+    # the fused patch loss from the labels (ppp_patch_loss.hip)
+    "ppp_patch_loss_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                                        ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                                        ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int64]),
+    "ppp_patch_loss_dense_fwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                                ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_int32,
+                                                ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                                ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "ppp_patch_loss_dense_bwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                                ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_int32,
+                                                ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p]),
+    "ppp_patch_loss_samples_fwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                                  ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_int64,
+                                                  ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                                  ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p]),
+    "ppp_patch_loss_samples_bwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                                  ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_int64,
+                                                  ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                                  ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p]),
     # no_overlap_per_channel without the loop over components (ppp_pack_channels.hip, ppp_host_pack.cpp)
     "ppp_pack_scan_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(Params), ctypes.POINTER(Box)]),
     "ppp_pack_scan_count": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
@@ -2371,6 +2395,124 @@ def gt_affs_samples(labels, samples, nhood, ps, ctr, out=None, out_dtype=None):
                                         (ctypes.c_int32 * 3)(*[int(p) for p in ps]),
                                         (ctypes.c_int32 * 3)(*[int(c) for c in ctr]), _dev_ptr(out) if N else None,
                                         _out_dtype_code(out_dtype), _stream()))
+    return out
+
+
+def _patch_loss_dense_geometry(logits, labels, nhood, weight, box):
+    torch = _torch()
+    assert labels.dtype == torch.int32 and labels.dim() == 5, "patch_loss needs int32 labels (B, L, Z, Y, X)"
+    assert nhood.dtype == torch.int32 and nhood.dim() == 2 and nhood.shape[1] == 3, "nhood is an int32 (E, 3) tensor"
+    B, L, Z, Y, X = [int(v) for v in labels.shape]
+    E = int(nhood.shape[0])
+    box = [int(v) for v in (box if box is not None else (0, Z, 0, Y, 0, X))]
+    assert len(box) == 6, "box = (z0, z1, y0, y1, x0, x1)"
+    ext = (box[1] - box[0], box[3] - box[2], box[5] - box[4])
+    assert tuple(logits.shape) == (B, E) + ext, "logits must be %s, got %s" % ((B, E) + ext, tuple(logits.shape))
+    if weight is not None:
+        assert weight.dtype == torch.float32 and tuple(weight.shape) == (B,) + ext, "weight must be float32 %s" % ((B,) + ext,)
+    return B, L, (Z, Y, X), E, box
+
+
+def patch_loss_workspace_bytes(B, L, vol, E, halo=None, box=None, dtype=None, N=0):
+    """ppp_patch_loss_workspace_bytes: the dense form with `halo` and `box`, the sampled form (box None) with N."""
+    torch = _torch()
+    n = lib().ppp_patch_loss_workspace_bytes(int(B), int(L), (ctypes.c_int32 * 3)(*[int(v) for v in vol]), int(E),
+                                             (ctypes.c_int32 * 6)(*[int(v) for v in halo]) if halo is not None else None,
+                                             (ctypes.c_int32 * 6)(*[int(v) for v in box]) if box is not None else None,
+                                             _out_dtype_code(dtype or torch.float32), int(N))
+    check(min(int(n), 0))
+    return int(n)
+
+
+def patch_loss_dense_fwd(logits, labels, nhood, weight=None, box=None, num_channels=None, want_counts=False, work=None):
+    """ppp_patch_loss_dense_fwd: the masked BCE-with-logits loss of `logits`, a contiguous device tensor
+    (B, E, bZ, bY, bX) of float32 / float16 / bfloat16, against the ground-truth affinities of `labels`
+    (int32 (B, L, Z, Y, X)) for the offsets `nhood` (int32 (E, 3)) on `box` (default: the volume), which are never
+    stored.  `weight`: float32 (B, bZ, bY, bX) >= 0 or None; `num_channels`: the divisor's factor (default E).
+    Returns (loss, state, counts): a float32 tensor of 1, the float64 (s, sum w) the backward takes, and the int64
+    (x > 0, G, x > 0 and G) counts or None.  `work`: a uint8 tensor of patch_loss_workspace_bytes.  Does not
+    synchronise."""
+    torch = _torch()
+    B, L, vol, E, box = _patch_loss_dense_geometry(logits, labels, nhood, weight, box)
+    halo = nhood_halo(nhood)
+    code = _out_dtype_code(logits.dtype)
+    if work is None:
+        work = _workspace(patch_loss_workspace_bytes(B, L, vol, E, halo, box, logits.dtype), logits.device)
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    state = torch.empty(2, dtype=torch.float64, device=logits.device)
+    counts = torch.empty(3, dtype=torch.int64, device=logits.device) if want_counts else None
+    with _timed("patch_loss_dense_fwd"):
+        check(lib().ppp_patch_loss_dense_fwd(_dev_ptr(logits), code, _dev_ptr(labels), B, L, (ctypes.c_int32 * 3)(*vol),
+                                             _dev_ptr(nhood), E, (ctypes.c_int32 * 6)(*halo), (ctypes.c_int32 * 6)(*box),
+                                             _dev_ptr(weight), float(E if num_channels is None else num_channels),
+                                             _dev_ptr(loss), _dev_ptr(state), _dev_ptr(counts), _dev_ptr(work), _stream()))
+    return loss, state, counts
+
+
+def patch_loss_dense_bwd(logits, labels, nhood, state, grad_out, weight=None, box=None, out=None):
+    """ppp_patch_loss_dense_bwd: the gradient of patch_loss_dense_fwd's loss with respect to `logits`, times
+    `grad_out` (a float32 device tensor of 1), rounded once into the logits' type.  `state` is the forward's.
+    Returns a tensor like `logits`, or `out`; EVERY element is written.  Does not synchronise."""
+    torch = _torch()
+    B, L, vol, E, box = _patch_loss_dense_geometry(logits, labels, nhood, weight, box)
+    if out is None:
+        out = torch.empty(logits.shape, dtype=logits.dtype, device=logits.device)
+    assert tuple(out.shape) == tuple(logits.shape) and out.dtype == logits.dtype, "out must be like the logits"
+    assert state.dtype == torch.float64 and state.numel() == 2 and grad_out.dtype == torch.float32 and grad_out.numel() == 1, \
+        "state is the forward's float64 (2,), grad_out a float32 tensor of one element"
+    with _timed("patch_loss_dense_bwd"):
+        check(lib().ppp_patch_loss_dense_bwd(_dev_ptr(logits), _out_dtype_code(logits.dtype), _dev_ptr(labels), B, L,
+                                             (ctypes.c_int32 * 3)(*vol), _dev_ptr(nhood), E,
+                                             (ctypes.c_int32 * 6)(*nhood_halo(nhood)), (ctypes.c_int32 * 6)(*box),
+                                             _dev_ptr(weight), _dev_ptr(state), _dev_ptr(grad_out), _dev_ptr(out), _stream()))
+    return out
+
+
+def _patch_loss_samples_geometry(logits, labels, samples, nhood):
+    torch = _torch()
+    assert labels.dtype == torch.int32 and labels.dim() == 5, "patch_loss needs int32 labels (B, L, Z, Y, X)"
+    assert samples.dtype == torch.int32 and samples.dim() == 2 and samples.shape[1] == 4, \
+        "samples is an int32 (N, 4) tensor of rows (b, z, y, x)"
+    assert nhood.dtype == torch.int32 and nhood.dim() == 2 and nhood.shape[1] == 3, "nhood is an int32 (E, 3) tensor"
+    B, L, Z, Y, X = [int(v) for v in labels.shape]
+    N, E = int(samples.shape[0]), int(nhood.shape[0])
+    assert tuple(logits.shape) == (N, E), "logits must be %s, got %s" % ((N, E), tuple(logits.shape))
+    return B, L, (Z, Y, X), N, E
+
+
+def patch_loss_samples_fwd(logits, labels, samples, nhood, ps, ctr, work=None):
+    """ppp_patch_loss_samples_fwd: the mean BCE-with-logits loss of `logits` (N, E) against the sampled ground-truth
+    affinities (the arguments of gt_affs_samples).  Returns (loss, state); N = 0 gives loss 0 and launches
+    nothing.  Does not synchronise."""
+    torch = _torch()
+    B, L, vol, N, E = _patch_loss_samples_geometry(logits, labels, samples, nhood)
+    loss = torch.zeros(1, dtype=torch.float32, device=logits.device)
+    state = torch.zeros(2, dtype=torch.float64, device=logits.device)
+    if work is None and N:
+        work = _workspace(patch_loss_workspace_bytes(B, L, vol, E, dtype=logits.dtype, N=N), logits.device)
+    with _timed("patch_loss_samples_fwd"):
+        check(lib().ppp_patch_loss_samples_fwd(_dev_ptr(logits) if N else None, _out_dtype_code(logits.dtype), _dev_ptr(labels),
+                                               B, L, (ctypes.c_int32 * 3)(*vol), _dev_ptr(samples) if N else None, N,
+                                               _dev_ptr(nhood), E, (ctypes.c_int32 * 3)(*[int(p) for p in ps]),
+                                               (ctypes.c_int32 * 3)(*[int(c) for c in ctr]), _dev_ptr(loss), _dev_ptr(state),
+                                               _dev_ptr(work) if N else None, _stream()))
+    return loss, state
+
+
+def patch_loss_samples_bwd(logits, labels, samples, nhood, ps, ctr, state, grad_out, out=None):
+    """ppp_patch_loss_samples_bwd: the gradient of patch_loss_samples_fwd's loss times `grad_out` (float32, one
+    element, on the device), like `logits`, or `out`.  Does not synchronise."""
+    torch = _torch()
+    B, L, vol, N, E = _patch_loss_samples_geometry(logits, labels, samples, nhood)
+    if out is None:
+        out = torch.empty(logits.shape, dtype=logits.dtype, device=logits.device)
+    assert tuple(out.shape) == (N, E) and out.dtype == logits.dtype, "out must be like the logits"
+    with _timed("patch_loss_samples_bwd"):
+        check(lib().ppp_patch_loss_samples_bwd(_dev_ptr(logits) if N else None, _out_dtype_code(logits.dtype), _dev_ptr(labels),
+                                               B, L, (ctypes.c_int32 * 3)(*vol), _dev_ptr(samples) if N else None, N,
+                                               _dev_ptr(nhood), E, (ctypes.c_int32 * 3)(*[int(p) for p in ps]),
+                                               (ctypes.c_int32 * 3)(*[int(c) for c in ctr]), _dev_ptr(state),
+                                               _dev_ptr(grad_out), _dev_ptr(out) if N else None, _stream()))
     return out
 
 

@@ -1776,4 +1776,99 @@ int ppp_gt_affs_samples(const int32_t *d_labels, int32_t B, int32_t L, const int
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_gt_affs_samples");
 }
 
+/* ---- the fused patch loss from the labels (ppp_patch_loss.hip) ---- */
+static int patch_loss_dense_args(int32_t B, int32_t L, const int32_t *vol, int32_t E, const int32_t *halo, const int32_t *box,
+                                 int dtype) {
+    return gt_affs_dense_args(B, L, vol, E, halo, box, dtype, 0);
+}
+
+static int patch_loss_samples_args(int32_t B, int32_t L, const int32_t *vol, int32_t E, const int32_t *ps, const int32_t *ctr,
+                                   int dtype, int64_t N) {
+    PPP_TRY(gt_affs_labels(B, L, vol, E));
+    PPP_TRY(check_dtype(dtype));
+    if (!ps || !ctr) return fail(PPP_ERR_INVALID_ARG, "NULL ps or ctr");
+    for (int a = 0; a < 3; ++a)
+        if (ps[a] < 1 || ctr[a] < 0 || ctr[a] >= ps[a])
+            return fail(PPP_ERR_INVALID_ARG, "axis %d: centre %d outside the patch of %d", a, ctr[a], ps[a]);
+    if (N < 0) return fail(PPP_ERR_INVALID_ARG, "N must be >= 0");
+    return PPP_OK;
+}
+
+static bool bad_ptr(const void *p, uintptr_t mask) { return !p || ((uintptr_t)p & mask); }
+
+int64_t ppp_patch_loss_workspace_bytes(int32_t B, int32_t L, const int32_t *vol, int32_t E, const int32_t *halo,
+                                       const int32_t *box, int dtype, int64_t N) {
+    if (box) {
+        int rc = patch_loss_dense_args(B, L, vol, E, halo, box, dtype);
+        return rc != PPP_OK ? rc : (int64_t)ppp::patch_loss_workspace_bytes(B, L, E, halo, box, 0);
+    }
+    int rc = gt_affs_labels(B, L, vol, E);
+    if (rc == PPP_OK) rc = check_dtype(dtype);
+    if (rc == PPP_OK && N < 0) rc = fail(PPP_ERR_INVALID_ARG, "N must be >= 0");
+    return rc != PPP_OK ? rc : (int64_t)ppp::patch_loss_workspace_bytes(B, L, E, nullptr, nullptr, (long long)N);
+}
+
+int ppp_patch_loss_dense_fwd(const void *d_logits, int dtype, const int32_t *d_labels, int32_t B, int32_t L, const int32_t *vol,
+                             const int32_t *d_nhood, int32_t E, const int32_t *halo, const int32_t *box, const float *d_weight,
+                             double num_channels, float *d_loss, double *d_state, int64_t *d_counts, void *d_work, void *stream) {
+    PPP_TRY(patch_loss_dense_args(B, L, vol, E, halo, box, dtype));
+    if (d_weight && !(num_channels > 0.0 && num_channels <= 1.7e308))
+        return fail(PPP_ERR_INVALID_ARG, "num_channels = %g: a positive finite factor", num_channels);
+    if (bad_ptr(d_logits, dtype == PPP_F32 ? 3 : 1) || bad_ptr(d_labels, 3) || bad_ptr(d_nhood, 3) || bad_ptr(d_loss, 3) ||
+        bad_ptr(d_state, 7) || bad_ptr(d_work, 7) || ((uintptr_t)d_weight & 3) || ((uintptr_t)d_counts & 7))
+        return fail(PPP_ERR_INVALID_ARG, "NULL or misaligned pointer argument");
+    PPP_TRY(need_device());
+    hipError_t e = ppp::run_patch_loss_dense(true, d_logits, dtype, d_labels, B, L, vol[0], vol[1], vol[2], d_nhood, E, halo, box,
+                                             d_weight, num_channels, d_loss, d_state, (long long *)d_counts, nullptr, nullptr,
+                                             d_work, (hipStream_t)stream);
+    if (e == hipErrorInvalidConfiguration) return fail(PPP_ERR_UNSUPPORTED, "ppp_patch_loss_dense_fwd: a grid the device would not run whole");
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_patch_loss_dense_fwd");
+}
+
+int ppp_patch_loss_dense_bwd(const void *d_logits, int dtype, const int32_t *d_labels, int32_t B, int32_t L, const int32_t *vol,
+                             const int32_t *d_nhood, int32_t E, const int32_t *halo, const int32_t *box, const float *d_weight,
+                             const double *d_state, const float *d_grad_out, void *d_grad, void *stream) {
+    PPP_TRY(patch_loss_dense_args(B, L, vol, E, halo, box, dtype));
+    if (bad_ptr(d_logits, dtype == PPP_F32 ? 3 : 1) || bad_ptr(d_labels, 3) || bad_ptr(d_nhood, 3) || bad_ptr(d_state, 7) ||
+        bad_ptr(d_grad_out, 3) || bad_ptr(d_grad, dtype == PPP_F32 ? 3 : 1) || ((uintptr_t)d_weight & 3))
+        return fail(PPP_ERR_INVALID_ARG, "NULL or misaligned pointer argument");
+    PPP_TRY(need_device());
+    hipError_t e = ppp::run_patch_loss_dense(false, d_logits, dtype, d_labels, B, L, vol[0], vol[1], vol[2], d_nhood, E, halo, box,
+                                             d_weight, 0.0, nullptr, const_cast<double *>(d_state), nullptr, d_grad_out, d_grad,
+                                             nullptr, (hipStream_t)stream);
+    if (e == hipErrorInvalidConfiguration) return fail(PPP_ERR_UNSUPPORTED, "ppp_patch_loss_dense_bwd: a grid the device would not run whole");
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_patch_loss_dense_bwd");
+}
+
+int ppp_patch_loss_samples_fwd(const void *d_logits, int dtype, const int32_t *d_labels, int32_t B, int32_t L, const int32_t *vol,
+                               const int32_t *d_samples, int64_t N, const int32_t *d_nhood, int32_t E, const int32_t *ps,
+                               const int32_t *ctr, float *d_loss, double *d_state, void *d_work, void *stream) {
+    PPP_TRY(patch_loss_samples_args(B, L, vol, E, ps, ctr, dtype, N));
+    if (N == 0) return PPP_OK;
+    if (bad_ptr(d_logits, dtype == PPP_F32 ? 3 : 1) || bad_ptr(d_labels, 3) || bad_ptr(d_samples, 3) || bad_ptr(d_nhood, 3) ||
+        bad_ptr(d_loss, 3) || bad_ptr(d_state, 7) || bad_ptr(d_work, 7))
+        return fail(PPP_ERR_INVALID_ARG, "NULL or misaligned pointer argument");
+    PPP_TRY(need_device());
+    hipError_t e = ppp::run_patch_loss_samples(true, d_logits, dtype, d_labels, B, L, vol[0], vol[1], vol[2], d_samples, (long long)N,
+                                               d_nhood, E, ps, ctr, d_loss, d_state, nullptr, nullptr, d_work, (hipStream_t)stream);
+    if (e == hipErrorInvalidConfiguration) return fail(PPP_ERR_UNSUPPORTED, "ppp_patch_loss_samples_fwd: N = %lld is more than one launch runs", (long long)N);
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_patch_loss_samples_fwd");
+}
+
+int ppp_patch_loss_samples_bwd(const void *d_logits, int dtype, const int32_t *d_labels, int32_t B, int32_t L, const int32_t *vol,
+                               const int32_t *d_samples, int64_t N, const int32_t *d_nhood, int32_t E, const int32_t *ps,
+                               const int32_t *ctr, const double *d_state, const float *d_grad_out, void *d_grad, void *stream) {
+    PPP_TRY(patch_loss_samples_args(B, L, vol, E, ps, ctr, dtype, N));
+    if (N == 0) return PPP_OK;
+    if (bad_ptr(d_logits, dtype == PPP_F32 ? 3 : 1) || bad_ptr(d_labels, 3) || bad_ptr(d_samples, 3) || bad_ptr(d_nhood, 3) ||
+        bad_ptr(d_state, 7) || bad_ptr(d_grad_out, 3) || bad_ptr(d_grad, dtype == PPP_F32 ? 3 : 1))
+        return fail(PPP_ERR_INVALID_ARG, "NULL or misaligned pointer argument");
+    PPP_TRY(need_device());
+    hipError_t e = ppp::run_patch_loss_samples(false, d_logits, dtype, d_labels, B, L, vol[0], vol[1], vol[2], d_samples, (long long)N,
+                                               d_nhood, E, ps, ctr, nullptr, const_cast<double *>(d_state), d_grad_out, d_grad,
+                                               nullptr, (hipStream_t)stream);
+    if (e == hipErrorInvalidConfiguration) return fail(PPP_ERR_UNSUPPORTED, "ppp_patch_loss_samples_bwd: N = %lld is more than one launch runs", (long long)N);
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_patch_loss_samples_bwd");
+}
+
 }  // extern "C"

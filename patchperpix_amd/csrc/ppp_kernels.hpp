@@ -306,4 +306,18 @@ hipError_t run_gt_affs_samples(const int32_t *labels, int B, int L, int Z, int Y
                                long long N, const int32_t *nhood, int E, const int *ps, const int *ctr, void *out,
                                int dtype, hipStream_t s);
 
+// the fused patch loss from the labels (ppp_patch_loss.hip): masked BCE with logits against the predicate of
+// gt_affs_dense, forward (loss, state = (s, sum w), optional counts[3]) and backward (every element of `grad`
+// is written).  Tiles come from gt_affs_dense_plan.  Workspace: one double per workgroup and sum (box != NULL:
+// the dense form; NULL: the sampled form with N rows).  No synchronisation.
+size_t patch_loss_workspace_bytes(int B, int L, int E, const int *halo, const int *box, long long N);
+hipError_t run_patch_loss_dense(bool fwd, const void *logits, int dtype, const int32_t *labels, int B, int L, int Z, int Y,
+                                int X, const int32_t *nhood, int E, const int *halo, const int *box, const float *weight,
+                                double num_channels, float *loss, double *state, long long *counts, const float *grad_out,
+                                void *grad, void *work, hipStream_t s);
+hipError_t run_patch_loss_samples(bool fwd, const void *logits, int dtype, const int32_t *labels, int B, int L, int Z, int Y,
+                                  int X, const int32_t *samples, long long N, const int32_t *nhood, int E, const int *ps,
+                                  const int *ctr, float *loss, double *state, const float *grad_out, void *grad, void *work,
+                                  hipStream_t s);
+
 }  // namespace ppp
