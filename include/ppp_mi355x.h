@@ -306,6 +306,13 @@ int ppp_patch_graph_by_patch_chunked(const void *d_pred, int pred_dtype, const f
  * ppp_patch_graph_lcg_words is 0 for every offset when the per-patch kernel of this patch width
  * does not read masks (the 25-wide 2-d kernel: it runs the generator itself). */
 int64_t ppp_patch_graph_lcg_words(int32_t dz, int32_t dy, int32_t dx, const ppp_params *p);
+/* Host only, no device needed: the foreground bits of a px^3 patch (n_words = ceil(px^3 / 32) words, bit r
+ * of the window raster = bit r & 31 of word r >> 5, as ppp_patch_fg_bits writes them) as values per
+ * candidate plane -- the function with which the cubic small-chunk per-patch kernels form the values a lane
+ * keeps in registers.  px in {3, 5, 7}: planes[z] = bits [z px^2, (z + 1) px^2), px values.  px = 9: a
+ * plane is two chunks of candidate rows, planes[z] = rows 0-6 (bits [81 z, 81 z + 63)) and planes[9 + z] =
+ * rows 7-8 (bits [81 z + 63, 81 z + 81)), 18 values. */
+int ppp_patch_plane_bits(const uint32_t *words, int32_t n_words, int32_t px, uint64_t *planes);
 int ppp_patch_graph_lcg(const void *d_pred, int pred_dtype, const uint32_t *d_pairs,
                         const uint32_t *d_order, const int64_t *d_lcg_pos, int64_t n_lcg,
                         const int64_t *d_drop_off, uint64_t *d_drops, const ppp_params *p, void *stream);

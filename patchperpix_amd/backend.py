@@ -141,6 +141,7 @@ _SIGNATURES = {
                                                         ctypes.POINTER(Params), ctypes.c_void_p]),
     "ppp_patch_graph_lcg_words": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                    ctypes.POINTER(Params)]),
+    "ppp_patch_plane_bits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
     "ppp_patch_graph_lcg": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.POINTER(Params), ctypes.c_void_p]),

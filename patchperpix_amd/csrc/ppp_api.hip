@@ -440,6 +440,20 @@ int64_t ppp_patch_graph_lcg_words(int32_t dz, int32_t dy, int32_t dx, const ppp_
     return ppp::patch_graph_lcg_words(G, dz, dy, dx);
 }
 
+int ppp_patch_plane_bits(const uint32_t *words, int32_t n_words, int32_t px, uint64_t *planes) {
+    if (!words || !planes) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    if (px != 3 && px != 5 && px != 7 && px != 9)
+        return fail(PPP_ERR_UNSUPPORTED, "ppp_patch_plane_bits: px %d (plane values are kept for px in {3, 5, 7, 9})", px);
+    if (n_words != (px * px * px + 31) / 32)
+        return fail(PPP_ERR_INVALID_ARG, "ppp_patch_plane_bits: %d words for a %d^3 patch", n_words, px);
+    const int rpc = 64 / px < px ? 64 / px : px;          // rows of a plane's first chunk (9^3: 7 of 9)
+    for (int z = 0; z < px; ++z) {
+        planes[z] = ppp::patch_plane_bits(words, n_words, z * px * px, rpc * px);
+        if (rpc < px) planes[px + z] = ppp::patch_plane_bits(words, n_words, (z * px + rpc) * px, (px - rpc) * px);
+    }
+    return PPP_OK;
+}
+
 static int patch_graph_lcg_impl(const void *d_pred, int pred_dtype, const uint32_t *d_pairs,
                                 const uint32_t *d_order, const int64_t *d_lcg_pos, int64_t n_lcg,
                                 const int64_t *d_drop_off, uint64_t *d_drops, const ppp_params *p,

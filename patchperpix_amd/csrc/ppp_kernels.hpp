@@ -100,6 +100,8 @@ hipError_t launch_patch_graph_pa(const void *pred, int dtype, const float *S, co
 hipError_t launch_patch_fg_bits(const void *pred, int dtype, const long long *centres, long long n,
                                 uint32_t *table, const Geo &G, hipStream_t s);
 long long patch_graph_lcg_words(const Geo &G, int dz, int dy, int dx);
+// bits [first_bit, first_bit + n_bits) of a patch's bit words as one value: the per-patch kernel's own function, on the host
+unsigned long long patch_plane_bits(const uint32_t *words, int n_words, int first_bit, int n_bits);
 hipError_t launch_patch_graph_lcg(const void *pred, int dtype, const uint32_t *rows, const uint32_t *order,
                                   const long long *lcg_pos, long long n, const long long *drop_off,
                                   unsigned long long *drops, const Geo &G, hipStream_t s);

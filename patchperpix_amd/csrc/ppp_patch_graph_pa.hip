@@ -44,8 +44,39 @@
 // second set of B-patch bits takes the CU from 13 to 11 workgroups, the second pair's state does
 // not fit the 128-VGPR budget (18 spilled with its axis masks made anew per pixel, 27 with them
 // kept): 62.7 ms; with a 3-waves-per-SIMD budget (152 VGPRs, no spills) 50.9 ms.  The kernel is
-// bound by vector issue and by waves per CU, not by the staging reads (they hit in L2), and the
-// second pass walks the same union of candidate rows the second workgroup walked.
+// bound by vector issue and by waves per CU, not by the staging reads, and the second pass walks
+// the same union of candidate rows the second workgroup walked.  (The staging reads do NOT hit in
+// L2, as this header once said: FETCH_SIZE per launch is about the bytes staged -- 23 946 patches
+// x 1.38 workgroups x ~300 rows x 8.8 KB ~ 87 GB per step -- so practically every row comes over
+// the fabric; profiles/r10_*, and r15_a_pmc_fetch.txt for the figures of this round.  They are
+// hidden behind the other waves of the CU, which is why waves per CU is what pays.)
+//
+// The bits of patch B in registers (round 15; the cubic small-chunk kernels: pa_b_in_regs).
+// The bits of a lane's patch B do not change while the wave walks the ~300 foreground pixels of A,
+// yet every pixel step and candidate plane extracted the plane's bits again from the [words][64]
+// LDS array: up to three LDS reads, 64-bit shifts and ORs, ~7 x 300 times per lane for 7 values.
+// Now each lane forms the PX plane values once (pa_plane_bits; 14 VGPRs at 7^3), the chunk body
+// takes Bp[z2o] (z2o is wave-uniform: the array stays in registers, read through s_set_gpr_idx,
+// two v_mov per plane), and the LDS array is gone: 11.6 -> 8.9 KB per workgroup at 7^3, LDS would
+// allow 18 workgroups per CU instead of 13, and the 110 VGPRs (96 before) allow 16.  140^3 / 7^3
+// benchmark, S5 kernel per step, parent and new alternating in one call, three runs each
+// (profiles/r15_a_bench_ab.txt): 35.05-35.10 ms -> 28.32-28.37 ms (-19 %).  Same sums in the same
+// order: aff is bit-identical (tests/test_s5_plane_bits.py; the run-time instantiation and the
+// 256-thread kernel keep the LDS form and are the cross-check).  9^3 / 128 threads takes it too:
+// two chunks per plane, the second one (rows 7-8) 18 bits, so 9 64-bit + 9 32-bit values; 114 ->
+// 138 VGPRs, nothing spilled, 31.6 -> 19.8 KB of LDS per two-wave workgroup: 5 -> 6 workgroups per
+// CU (three waves per SIMD by registers; LDS alone would hold 8).  synth256_p9, S5 per step, LDS
+// form and this alternating, three runs each: 628.8-629.5 -> 495.1-495.8 ms (-21 %), same CRC.
+// Measured and dropped in the same call:
+//   - an XCD-aware block order (bid = (bid % 8) * per + bid / 8 as in consensus_v3_kernel, so that
+//     the two chunks of a patch and raster neighbours run on one XCD): 30.30-30.38 ms against
+//     28.32-28.37 ms -- 2 ms SLOWER.  FETCH_SIZE of the launch (profiles/r15_a_pmc_fetch.txt): parent
+//     44.29, new 44.52, with this order 43.87 x 10^6 KiB raw: -1.5 %, not the 27 % of the staged
+//     bytes that the second chunks re-read -- they do not walk the same rows at the same time.
+//   - MIN_WAVES_SMALL = 5 at 7^3: see PaCfg (96 VGPRs only with 10 spilled; 0.3 ms; not taken).
+//   - the register prefetch of the next row at 7^3 (mask loads issued first): not built -- its 35
+//     staging registers on top of 110 leave the 128 of four waves per SIMD, and three waves per
+//     SIMD is the occupancy this round bought its gain by leaving.
 //
 // The foreground bits of the patches (round 10).  A and every B need their C bits
 // mid[u_r] > th && pred[r][c] > th; built here they are 2 C scattered loads per pair row, and a
@@ -96,8 +127,48 @@ template <int PX> struct PaCfg {
     // 35.15-35.25 ms per step at 140^3, 9^3 with 4 waves 5.188 s against 5.187 s at 512^3; the registers do
     // not change with the bound and LDS, not registers, caps the workgroups per CU: the bounds stay,
     // profiles/r11_a_bench_ab.txt.)
+    // (Round 15, after the bits of patch B left LDS -- pa_b_in_regs below: 8.9 KB per workgroup at 7^3, LDS allows
+    // 18 per CU, the registers decide.  4 waves per SIMD: 110 VGPRs, nothing spilled, 16 workgroups per CU,
+    // 28.32-28.37 ms per step at 140^3.  5 waves per SIMD: the compiler meets 96 VGPRs only by spilling 10 of them
+    // (44 bytes of scratch), 28.04-28.07 ms -- 0.3 ms for a kernel with scratch traffic in its pixel loop: not
+    // taken, the bound stays 4.  profiles/r15_a_bench_ab.txt, r15_a_kernel_regs.txt.)
     static constexpr int MIN_WAVES_SMALL = PX >= 25 ? 1 : (PX >= 9 ? 2 : 4);
 };
+
+// Bits [o, o + nb) of a bit string held in 32-bit words (bit r = bit r & 31 of word r >> 5) as one
+// 64-bit value, nb <= 64; words from n_words on read as zero.  With o = z * py * PX and nb = py * PX:
+// the foreground bits of candidate plane z of a patch.  The bits span up to three words (7^3: planes
+// start at bit 49 z -- plane 1 lies in words 1-3, plane 6 ends 9 bits before word 10 does).
+__host__ __device__ __forceinline__ unsigned long long pa_plane_bits(const uint32_t *w, const int n_words, const int o,
+                                                                     const int nb) {
+    typedef unsigned long long u64;
+    const int w0 = o >> 5, sh = o & 31;
+    const uint32_t lo = w[w0];
+    const uint32_t mi = w0 + 1 < n_words ? w[w0 + 1] : 0u;
+    const uint32_t hi = w0 + 2 < n_words ? w[w0 + 2] : 0u;
+    const u64 v = ((((u64)mi << 32) | lo) >> sh) | (sh ? ((u64)hi << (64 - sh)) : 0ull);
+    return nb >= 64 ? v : (v & ((1ull << nb) - 1ull));
+}
+// Where the lanes keep the foreground bits of their patch B.  The cubic small-chunk kernels hold them
+// as values per candidate plane in registers, made once per pair row: 3^3, 5^3, 7^3 / 64 threads one
+// 64-bit value per plane (a plane is one chunk of at most 49 bits), 9^3 / 128 threads a 64-bit and a
+// 32-bit value per plane (rows 0-6: 63 bits, rows 7-8: 18 bits).  Every other instantiation holds the
+// words in LDS ([words][threads]) and extracts a chunk's bits on every pixel step.  The kernel and the
+// launcher's LDS size ask this.
+static constexpr bool pa_b_in_regs(const int px, const int threads, const bool cube) {
+    return cube && ((px <= 7 && threads == 64) || (px == 9 && threads == 128));
+}
+static_assert(PaCfg<3>::THREADS_SMALL == 64 && PaCfg<5>::THREADS_SMALL == 64 && PaCfg<7>::THREADS_SMALL == 64 &&
+                  PaCfg<9>::THREADS_SMALL == 128 && PaCfg<7>::THREADS != 64 && PaCfg<9>::THREADS != 128,
+              "pa_b_in_regs names the small chunk of 3^3, 5^3, 7^3 and 9^3 by its size");
+static size_t pa_lds_bytes(const int px, const int words, const int WB, const int threads, const bool cube) {
+    const int row_bufs = px >= 7 ? 1 : 2;
+    const int fbw = pa_b_in_regs(px, threads, cube) ? 0 : ((words * threads + 1) & ~1);
+    return (size_t)(row_bufs * WB + ((words + 3) & ~3) + fbw) * 4;
+}
+unsigned long long patch_plane_bits(const uint32_t *words, int n_words, int first_bit, int n_bits) {
+    return pa_plane_bits(words, n_words, first_bit, n_bits);
+}
 // Patch widths whose per-patch kernel reads thinning masks made beforehand (patch_graph_lcg_kernel)
 // instead of running the generator: all 3-d widths.  How the masks reach the lanes decides whether
 // that pays (256^3 / 9^3, S5 per volume; profiles/r04_z[h-p]_*): the generator 1219 ms; one 8-byte
@@ -244,10 +315,21 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
     constexpr int ROW_BUFS = PaCfg<PX>::ROW_BUFS;
     float *rowbuf = reinterpret_cast<float *>(lds_raw);           // [ROW_BUFS][WB]
     uint32_t *faw = lds_raw + ROW_BUFS * WB;                      // [words]
-    uint32_t *fbw = faw + ((words + 3) & ~3);                     // [words][PA_THREADS]
+    uint32_t *fbw = faw + ((words + 3) & ~3);                     // [words][PA_THREADS] (absent when REGB)
     typedef unsigned long long u64;
+    // the bits of this lane's patch B as one value per candidate plane, in registers (pa_b_in_regs)
+    constexpr bool REGB = pa_b_in_regs(PX, PA_THREADS, CUBE);
+    constexpr int NBP = REGB ? PX : 1;
+    u64 Bp[NBP];
+#pragma unroll
+    for (int z = 0; z < NBP; ++z) Bp[z] = 0ull;                   // (idle lanes keep zeros)
     constexpr int RPC = 64 / PX;                         // candidate rows per 64-bit chunk
     constexpr int NCH = (PX + RPC - 1) / RPC;            // chunks (the launcher checks py <= NCH * RPC)
+    // (9^3: the plane's second chunk, rows 7-8, 18 bits)
+    constexpr int NBQ = REGB && NCH == 2 ? PX : 1;
+    uint32_t Bq[NBQ];
+#pragma unroll
+    for (int z = 0; z < NBQ; ++z) Bq[z] = 0u;
 
     // ---- The range / intersection / stored conditions of a whole (y2o, x2o) candidate plane
     // are evaluated at once as bit masks, bit (y2o - y_first) * PX + x2o, for chunks of RPC rows
@@ -339,7 +421,42 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
         rnd = pair_seed(G, az, ay, ax, bz, by, bx);
         const long long lb = vox(G, bz, by, bx);
         int r = 0;
-        if (bits != nullptr) {
+        if constexpr (REGB) {
+            // the words of B in registers (every index below is a constant once unrolled), then one
+            // value per candidate plane; the words are dead after that
+            constexpr int NW = PaGeo<PX, true>::words();
+            uint32_t bw[NW];
+            if (bits != nullptr) {
+                const uint32_t *src = bits + bits_slot(lb) * NW;
+#pragma unroll
+                for (int w = 0; w < NW; ++w) bw[w] = src[w];
+            } else {
+#pragma unroll
+                for (int w = 0; w < NW; ++w) bw[w] = 0u;
+                // one rolled loop over the words: a finished word enters at the top of the register
+                // row and the row moves down by one, so word w ends in bw[w] after NW trips
+#pragma unroll 1
+                for (int w = 0; w < NW; ++w) {
+                    uint32_t m = 0;
+                    for (int b = 0; b < 32 && r < geo.C(); ++b, ++r) {
+                        const int z = bz + r / (PX * PX) - PX / 2, y = by + (r / PX) % PX - PX / 2, x = bx + r % PX - PX / 2;
+                        const bool on = ldf(mid, vox(G, z, y, x)) > G.th_gt &&
+                                        ldf(pred, (long long)r * G.V + lb) > G.th_gt;
+                        m |= (on ? 1u : 0u) << b;
+                    }
+#pragma unroll
+                    for (int v = 0; v + 1 < NW; ++v) bw[v] = bw[v + 1];
+                    bw[NW - 1] = m;
+                }
+            }
+#pragma unroll
+            for (int z = 0; z < PX; ++z) Bp[z] = pa_plane_bits(bw, NW, z * PX * PX, (RPC < PX ? RPC : PX) * PX);
+            if constexpr (NCH == 2) {
+#pragma unroll
+                for (int z = 0; z < PX; ++z)
+                    Bq[z] = (uint32_t)pa_plane_bits(bw, NW, (z * PX + RPC) * PX, (PX - RPC) * PX);
+            }
+        } else if (bits != nullptr) {
             const uint32_t *src = bits + bits_slot(lb) * words;
             for (int w = 0; w < words; ++w) fbw[w * PA_THREADS + tid] = src[w];
         } else
@@ -354,7 +471,7 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
             }
             fbw[w * PA_THREADS + tid] = bits;
         }
-    } else {
+    } else if constexpr (!REGB) {
         for (int w = 0; w < words; ++w) fbw[w * PA_THREADS + tid] = 0u;
     }
     __syncthreads();
@@ -578,7 +695,11 @@ __global__ void __launch_bounds__(PA_THREADS, PA_THREADS == PaCfg<PX>::THREADS ?
                     PA_STAT(1, lane == 0 ? 1 : 0);
                     // foreground bits of patch B on these candidate rows
                     M valid;
-                    {
+                    if constexpr (REGB) {
+                        // (one chunk per plane: the plane's value, made once per pair row; z2o is
+                        // wave-uniform, the array stays in registers)
+                        valid = c == 0 ? (M)Bp[REGB ? z2o : 0] : (M)Bq[NBQ > 1 ? z2o : 0];
+                    } else {
                         const int nb = c_rows * PX;
                         const int o = (z2o * geo.py() + c_first) * PX, w0 = o >> 5, sh = o & 31;
                         const uint32_t lo = fbw[w0 * PA_THREADS + tid];
@@ -1138,12 +1259,11 @@ hipError_t launch_patch_graph_pa(const void *pred, int dtype, const float *S, co
     if (W > (cube + threads - 1) / threads * threads) return hipErrorNotSupported;
     // candidate planes are handled as ceil(px / (64 / px)) 64-bit chunks of 64 / px rows
     if (G.py > (G.px + 64 / G.px - 1) / (64 / G.px) * (64 / G.px) || G.pz > 32) return hipErrorNotSupported;
-    const int row_bufs = G.px >= 7 ? 1 : 2;
-    const size_t lds = (size_t)(row_bufs * WB + ((words + 3) & ~3) + ((words * threads + 1) & ~1)) * 4;
-    if (lds > 80 * 1024 || n_blocks >= (1ll << 31) || grid_too_big((unsigned long long)n_blocks, threads))
-        return hipErrorNotSupported;
     // the cubic instantiation: the window's sizes compiled in (PaGeo above)
     const bool cubic = pa_cube(G);
+    const size_t lds = pa_lds_bytes(G.px, words, WB, threads, cubic);
+    if (lds > 80 * 1024 || n_blocks >= (1ll << 31) || grid_too_big((unsigned long long)n_blocks, threads))
+        return hipErrorNotSupported;
     note_patch_graph_kernel(small ? "patch_graph_pa_kernel<small>" : "patch_graph_pa_kernel", cubic ? "cube" : "generic");
 #define PPP_PA_ARGS (const T *)pred, S, rows, order, group_start, chunk_offsets, n_groups, n_blocks, aff, drop_off, drops, bits_centres, n_bits, bits, G, lds, s
 #define PPP_PA_CASE(P)                                                                                  \
