@@ -792,6 +792,22 @@ int64_t ppp_host_mws(const uint32_t *pairs, const float *aff, int64_t n_rows, co
 int64_t ppp_host_mws_sorted(const int32_t *eu, const int32_t *ev, int64_t n_edges, int64_t n_nodes,
                             int32_t *labels);
 
+/* ppp_host_mws_sorted_stats: ppp_host_mws_sorted, which walks a long list in blocks and drops,
+ *   between blocks and on several threads, the unvisited edges that can do nothing any more
+ *   (csrc/ppp_host_mws.cpp; PPP_MWS_PRUNE=0: the plain loop, PPP_MWS_PRUNE_BLOCK / _MIN: block
+ *   size and shortest list in edges).  Same labels and return value; stats int64
+ *   [PPP_MWS_N_STATS] (may be null): [0] blocks run (0 = the plain loop), [1]-[4] edges dropped
+ *   by rules 1-4, [5] edges visited, [6] threads, [7] prune passes; [1]+..+[5] = n_edges.    */
+#define PPP_MWS_N_STATS 8
+int64_t ppp_host_mws_sorted_stats(const int32_t *eu, const int32_t *ev, int64_t n_edges, int64_t n_nodes,
+                                  int32_t *labels, int64_t *stats);
+
+/* ppp_host_mws_sorted_classes: the plain loop, noting what each edge did in cls uint8 [n_edges]:
+ *   attractive 0 new component, 1 joined one, 2 merged two, 3 same cluster, 4 refused by a mutex
+ *   key; repulsive 5 same cluster, 6 key already there, 7 key inserted (tools/time_mws.py).  */
+int64_t ppp_host_mws_sorted_classes(const int32_t *eu, const int32_t *ev, int64_t n_edges, int64_t n_nodes,
+                                    int32_t *labels, uint8_t *cls);
+
 /* ppp_host_pack_channels: the channel assignment of `no_overlap_per_channel`
  *   (graph_to_labeling.py:86-106: one painted volume, one .sum() and one masked test per component
  *   and channel) as a greedy walk over sizes and overlap pairs (closed form: ppp_pack_channels.hip).

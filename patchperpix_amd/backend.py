@@ -235,6 +235,10 @@ _SIGNATURES = {
                                        ctypes.c_void_p, ctypes.POINTER(Params), ctypes.c_void_p]),
     "ppp_host_mws_sorted": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                              ctypes.c_int64, ctypes.c_void_p]),
+    "ppp_host_mws_sorted_stats": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                   ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "ppp_host_mws_sorted_classes": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                     ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     "ppp_rank_order_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(Params)]),
     "ppp_rank_order": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),

@@ -15,8 +15,15 @@
 //     position and a component emptied by a merge stays in the list (:79-82) -- so the instance
 //     label of a node is 1 + position of its component's id in that order.
 #include <stdint.h>
+#include <stdlib.h>
 
 #include <algorithm>
+#include <condition_variable>
+#include <functional>
+#include <memory>
+#include <mutex>
+#include <system_error>
+#include <thread>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
@@ -92,6 +99,87 @@ struct KeySet {
     }
 };
 
+// Runs f(0) .. f(n - 1) at once, f(0) on the calling thread; the other threads are started once
+// per watershed and sleep between the prune passes.  (Letting the first of them start the rest
+// while the caller walks its first block measured no different: r16_a_time_mws.txt.)
+class Pool {
+    int n_ = 1;
+    std::vector<std::thread> th_;
+    std::mutex m_;
+    std::condition_variable go_, done_;
+    uint64_t gen_ = 0;
+    int pending_ = 0;
+    bool stop_ = false;
+    const std::function<void(int)> *job_ = nullptr;
+    void worker(int t) {
+        uint64_t seen = 0;
+        std::unique_lock<std::mutex> l(m_);
+        for (;;) {
+            go_.wait(l, [&] { return gen_ != seen; });
+            seen = gen_;
+            if (stop_) return;
+            const std::function<void(int)> *f = job_;
+            l.unlock();
+            (*f)(t);
+            l.lock();
+            if (--pending_ == 0) done_.notify_one();
+        }
+    }
+
+public:
+    explicit Pool(int n) {
+        th_.reserve((size_t)std::max(n, 1));
+        try {
+            for (int t = 1; t < n; ++t) {
+                th_.emplace_back([this, t] { worker(t); });
+                ++n_;
+            }
+        } catch (const std::system_error &) {}     // no more threads to be had: go on with these
+    }
+    ~Pool() {
+        {
+            std::lock_guard<std::mutex> l(m_);
+            stop_ = true;
+            ++gen_;
+        }
+        go_.notify_all();
+        for (std::thread &t : th_) t.join();
+    }
+    int size() const { return n_; }
+    void run(const std::function<void(int)> &f) {
+        {
+            std::lock_guard<std::mutex> l(m_);
+            job_ = &f;
+            pending_ = n_ - 1;
+            ++gen_;
+        }
+        go_.notify_all();
+        f(0);
+        std::unique_lock<std::mutex> l(m_);
+        done_.wait(l, [&] { return pending_ == 0; });
+    }
+};
+
+// at most 16 threads, fewer where OMP_NUM_THREADS or the machine says fewer
+int prune_threads() {
+    int n = 16;
+    const unsigned hw = std::thread::hardware_concurrency();
+    if (hw > 0 && (int)hw < n) n = (int)hw;
+    if (const char *s = getenv("OMP_NUM_THREADS")) {
+        const long v = strtol(s, nullptr, 10);
+        if (v >= 1 && v < n) n = (int)v;
+    }
+    return n;
+}
+
+int64_t env_i64(const char *name, int64_t fallback) {
+    const char *s = getenv(name);
+    if (!s || !*s) return fallback;
+    char *end = nullptr;
+    const long long v = strtoll(s, &end, 10);
+    return end == s || v < 0 ? fallback : (int64_t)v;
+}
+
 // The loop of graph_mws.mws (:31-77) over edges that are already in visiting order.
 //   eu / ev [n_edges]: node numbers, bit 31 of ev = attractive; label [n_nodes] out: 1 + position
 //   of the node's component id in creation order, 0 = the node ended in no component.
@@ -106,30 +194,73 @@ struct KeySet {
 // of its edges repulsive -- BASELINE config [4] with a random decoder -- 705 ns per edge; this
 // form: see tools/time_mws.py.)  A mutex edge inside one cluster can never matter again (clusters
 // only grow) and is dropped.
-void watershed(const int32_t *eu, const int32_t *ev, int64_t n_edges, int32_t N, int32_t *label,
-               int64_t *issued) {
+//
+// Most edges of a patch graph do nothing: with some 54 edges per node the clusters and the keys
+// between them are settled long before the list ends, and the loop still pays two finds and a
+// branch for each of them, one after the other.  So long lists are walked in blocks
+// (filter-Kruskal): after a block, the edges not yet visited that can never do anything again are
+// dropped by several threads at once and the rest is compacted stably -- the survivors keep their
+// order, so the loop makes exactly the decisions it would have made on the whole list.  Three
+// facts carry every rule: (i) clusters only grow; (ii) a cluster with an id keeps an id for ever
+// -- every merge gives the united root one -- so an unassigned cluster is a singleton, and only
+// the first branch, which asks for two unassigned nodes, ever merges across a key; (iii) hence two
+// clusters with a key between them, one of which has an id, never merge, and the key follows them
+// through their own merges.  An unvisited edge (a, b) with roots r0, r1 is dropped iff
+//   1. repulsive, r0 == r1: it is skipped now, and by (i) a and b stay together;
+//   2. attractive, r0 == r1, the root has an id: no branch fires for c0 == c1 != 0, and by (i),
+//      (ii) that is what a and b's cluster will always show;
+//   3. repulsive, r0 != r1, key (r0, r1) present: the insert finds its key.  Later the two
+//      clusters are either still apart, with the key rewritten to their roots, or -- both were
+//      unassigned -- merged by the first branch, and then rule 1 describes the edge;
+//   4. attractive, r0 != r1, key (r0, r1) present, r0 or r1 has an id: the second or third branch
+//      refuses it.  By (iii) the two never merge; an unassigned side can only pick up an id (then
+//      the third branch refuses), and the key stays between whatever the two grow into.
+// Kept on purpose: an attractive edge whose cluster has no id -- r0 == r1 is then the self-loop
+// a == b on an unseen node, which issues an id -- and an attractive edge between two unassigned
+// nodes whatever keys there are, because the first branch (:36-42) does not look at the mutex.
+// A prune writes nothing the threads read: one sequential pass points every node at its root,
+// after which a find is parent[x], and KeySet::contains does not modify the set.
+enum { ST_BLOCKS = 0, ST_RULE1, ST_RULE2, ST_RULE3, ST_RULE4, ST_VISITED, ST_THREADS, ST_PRUNES, ST_N };
+static_assert(ST_N == PPP_MWS_N_STATS, "stats layout");
+// classes of ppp_host_mws_sorted_classes (what the visit of an edge did)
+enum { CL_A_NEW = 0, CL_A_JOIN, CL_A_MERGE, CL_A_SAME, CL_A_REFUSED, CL_R_SAME, CL_R_KNOWN, CL_R_INSERT };
+
+// Measured on the flagship's list (1 292 850 edges, 23 946 nodes; profiles/r16_a_time_mws.txt):
+// first block = 1 / PRUNE_FIRST_SHARE of the list, every later block PRUNE_GROWTH times the one
+// before.  A prune costs about as much per edge as a visit (two parents and a key lookup) and gains
+// by its threads alone, so it must come late enough to drop most of what it looks at: after 1/32 of
+// the list it dropped 1 % of the rest, after 1/8 90 %.
+constexpr int64_t PRUNE_FIRST_SHARE = 8, PRUNE_GROWTH = 4;
+constexpr int64_t PRUNE_MIN_EDGES = 200000;     // shorter lists: the plain loop, no thread started
+
+struct Mws {
+    int32_t N;
     Dsu dsu;
-    dsu.parent.resize((size_t)N);
-    for (int32_t i = 0; i < N; ++i) dsu.parent[i] = i;
-    std::vector<int32_t> cc_of_root((size_t)N, 0);      // component id carried by a root (0: none)
-    std::vector<std::vector<int32_t>> nbrs((size_t)N);  // clusters this root has a mutex key with
-    KeySet mutex(1 << 16);
+    std::vector<int32_t> cc_of_root;               // component id carried by a root (0: none)
+    std::vector<std::vector<int32_t>> nbrs;        // clusters this root has a mutex key with
+    std::vector<int32_t> n_nbrs;                   // list lengths, next to each other (the vector
+                                                   // headers are 24 bytes apiece)
+    KeySet mutex;
     // ids currently held by some node: only "the largest one" is ever asked (:37-38), so a flag
     // per id and a maximum that is walked down lazily when its id dies (amortised O(1), no tree)
-    std::vector<uint8_t> alive((size_t)N + 2, 0);
+    std::vector<uint8_t> alive;
     int32_t max_alive = 0;
-    std::vector<int32_t> created;                       // ids in creation order (first issue)
-    std::vector<uint8_t> ever;                          // id was issued before (ids are <= N)
-    ever.assign((size_t)N + 2, 0);
-    auto key = [](int32_t a, int32_t b) -> uint64_t {
+    std::vector<int32_t> created;                  // ids in creation order (first issue)
+    std::vector<uint8_t> ever;                     // id was issued before (ids are <= N)
+
+    explicit Mws(int32_t n)
+        : N(n), cc_of_root((size_t)n, 0), nbrs((size_t)n), n_nbrs((size_t)n, 0), mutex(1 << 16),
+          alive((size_t)n + 2, 0), ever((size_t)n + 2, 0) {
+        dsu.parent.resize((size_t)n);
+        for (int32_t i = 0; i < n; ++i) dsu.parent[i] = i;
+    }
+    static uint64_t key(int32_t a, int32_t b) {
         const uint32_t lo = (uint32_t)std::min(a, b), hi = (uint32_t)std::max(a, b);
         return ((uint64_t)lo << 32) | hi;
-    };
-    auto has_mutex = [&](int32_t r0, int32_t r1) { return mutex.contains(key(r0, r1)); };
+    }
+    bool has_mutex(int32_t r0, int32_t r1) const { return mutex.contains(key(r0, r1)); }
     // the two clusters become one; returns its root (the one with the longer list)
-    std::vector<int32_t> n_nbrs((size_t)N, 0);          // list lengths, next to each other (the
-                                                        // vector headers are 24 bytes apiece)
-    auto unite = [&](int32_t ra, int32_t rb) -> int32_t {
+    int32_t unite(int32_t ra, int32_t rb) {
         int32_t keep = ra, drop = rb;
         if (n_nbrs[keep] < n_nbrs[drop]) std::swap(keep, drop);
         if (n_nbrs[drop]) {
@@ -148,54 +279,157 @@ void watershed(const int32_t *eu, const int32_t *ev, int64_t n_edges, int32_t N,
         }
         dsu.parent[drop] = keep;
         return keep;
-    };
-    constexpr int64_t AHEAD = 24;          // the edge list is known: fetch the nodes' entries early
-    for (int64_t i = 0; i < n_edges; ++i) {
-        if (i + AHEAD < n_edges) {
-            const int32_t pa = eu[i + AHEAD], pb = ev[i + AHEAD] & 0x7FFFFFFF;
-            __builtin_prefetch(&dsu.parent[pa]);
-            __builtin_prefetch(&dsu.parent[pb]);
-        }
-        const int32_t a = eu[i], b = ev[i] & 0x7FFFFFFF;
-        const int32_t r0 = dsu.find(a), r1 = dsu.find(b);
-        if (ev[i] < 0) {                                  // attractive
-            const int32_t c0 = cc_of_root[r0], c1 = cc_of_root[r1];
-            if (c0 == 0 && c1 == 0) {
-                // both unassigned (:36-42): a new component, id = max id in use + 1
-                while (max_alive > 0 && !alive[(size_t)max_alive]) --max_alive;
-                const int32_t id = max_alive + 1;
-                const int32_t r = r0 != r1 ? unite(r0, r1) : r0;
-                cc_of_root[r] = id;
-                alive[(size_t)id] = 1;
-                max_alive = id;
-                if (!ever[(size_t)id]) { ever[(size_t)id] = 1; created.push_back(id); }
-            } else if (c0 == 0 || c1 == 0) {
-                // the unassigned node joins unless a mutex edge links it to the component (:44-56)
-                if (!has_mutex(r0, r1)) {
-                    const int32_t id = c0 == 0 ? c1 : c0;
-                    cc_of_root[unite(r0, r1)] = id;
-                }
-            } else if (c0 != c1) {
-                // two components merge into the smaller id unless a mutex edge links them (:57-71)
-                if (!has_mutex(r0, r1)) {
-                    const int32_t keep = std::min(c0, c1), drop = std::max(c0, c1);
-                    cc_of_root[unite(r0, r1)] = keep;
-                    alive[(size_t)drop] = 0;
-                }
+    }
+
+    // TRACE: also note what each edge did (cls [n_edges], CL_*)
+    template <bool TRACE>
+    void visit(const int32_t *eu, const int32_t *ev, int64_t n_edges, uint8_t *cls) {
+        constexpr int64_t AHEAD = 24;      // the edge list is known: fetch the nodes' entries early
+        for (int64_t i = 0; i < n_edges; ++i) {
+            if (i + AHEAD < n_edges) {
+                const int32_t pa = eu[i + AHEAD], pb = ev[i + AHEAD] & 0x7FFFFFFF;
+                __builtin_prefetch(&dsu.parent[pa]);
+                __builtin_prefetch(&dsu.parent[pb]);
             }
-        } else if (r0 != r1) {                            // repulsive (:76-77)
-            if (mutex.insert(key(r0, r1))) {
-                nbrs[r0].push_back(r1);
-                nbrs[r1].push_back(r0);
-                ++n_nbrs[r0];
-                ++n_nbrs[r1];
+            const int32_t a = eu[i], b = ev[i] & 0x7FFFFFFF;
+            const int32_t r0 = dsu.find(a), r1 = dsu.find(b);
+            if (ev[i] < 0) {                                  // attractive
+                const int32_t c0 = cc_of_root[r0], c1 = cc_of_root[r1];
+                if (TRACE) cls[i] = CL_A_SAME;
+                if (c0 == 0 && c1 == 0) {
+                    // both unassigned (:36-42): a new component, id = max id in use + 1
+                    while (max_alive > 0 && !alive[(size_t)max_alive]) --max_alive;
+                    const int32_t id = max_alive + 1;
+                    const int32_t r = r0 != r1 ? unite(r0, r1) : r0;
+                    cc_of_root[r] = id;
+                    alive[(size_t)id] = 1;
+                    max_alive = id;
+                    if (!ever[(size_t)id]) { ever[(size_t)id] = 1; created.push_back(id); }
+                    if (TRACE) cls[i] = CL_A_NEW;
+                } else if (c0 == 0 || c1 == 0) {
+                    // the unassigned node joins unless a mutex edge links it to the component (:44-56)
+                    if (TRACE) cls[i] = CL_A_REFUSED;
+                    if (!has_mutex(r0, r1)) {
+                        const int32_t id = c0 == 0 ? c1 : c0;
+                        cc_of_root[unite(r0, r1)] = id;
+                        if (TRACE) cls[i] = CL_A_JOIN;
+                    }
+                } else if (c0 != c1) {
+                    // two components merge into the smaller id unless a mutex edge links them (:57-71)
+                    if (TRACE) cls[i] = CL_A_REFUSED;
+                    if (!has_mutex(r0, r1)) {
+                        const int32_t keep = std::min(c0, c1), drop = std::max(c0, c1);
+                        cc_of_root[unite(r0, r1)] = keep;
+                        alive[(size_t)drop] = 0;
+                        if (TRACE) cls[i] = CL_A_MERGE;
+                    }
+                }
+            } else if (r0 != r1) {                            // repulsive (:76-77)
+                if (TRACE) cls[i] = CL_R_KNOWN;
+                if (mutex.insert(key(r0, r1))) {
+                    nbrs[r0].push_back(r1);
+                    nbrs[r1].push_back(r0);
+                    ++n_nbrs[r0];
+                    ++n_nbrs[r1];
+                    if (TRACE) cls[i] = CL_R_INSERT;
+                }
+            } else if (TRACE) {
+                cls[i] = CL_R_SAME;
             }
         }
     }
-    std::vector<int32_t> label_of_id((size_t)N + 2, 0);
-    for (size_t i = 0; i < created.size(); ++i) label_of_id[(size_t)created[i]] = (int32_t)i + 1;
-    for (int32_t n = 0; n < N; ++n) label[n] = label_of_id[(size_t)cc_of_root[dsu.find(n)]];
-    *issued = (int64_t)created.size();
+
+    // the rule (1-4) by which an unvisited edge is dropped, 0 = it stays.  Read-only; every
+    // node points at its root (compress()).
+    int settled(int32_t a, int32_t evb) const {
+        const int32_t r0 = dsu.parent[a], r1 = dsu.parent[evb & 0x7FFFFFFF];
+        if (evb < 0) {
+            if (r0 == r1) return cc_of_root[r0] != 0 ? 2 : 0;
+            return (cc_of_root[r0] != 0 || cc_of_root[r1] != 0) && has_mutex(r0, r1) ? 4 : 0;
+        }
+        if (r0 == r1) return 1;
+        return has_mutex(r0, r1) ? 3 : 0;
+    }
+    void compress() {
+        for (int32_t x = 0; x < N; ++x) dsu.parent[x] = dsu.find(x);
+    }
+
+    void labels(int32_t *label, int64_t *issued) {
+        std::vector<int32_t> label_of_id((size_t)N + 2, 0);
+        for (size_t i = 0; i < created.size(); ++i) label_of_id[(size_t)created[i]] = (int32_t)i + 1;
+        for (int32_t n = 0; n < N; ++n) label[n] = label_of_id[(size_t)cc_of_root[dsu.find(n)]];
+        *issued = (int64_t)created.size();
+    }
+};
+
+// what one thread keeps of its slice of a prune pass
+struct alignas(64) Slice {
+    int64_t dropped[5] = {0, 0, 0, 0, 0};        // by rule; [0]: kept
+    int64_t kept = 0, at = 0;                    // this pass: survivors, and where they go
+};
+
+// stats [PPP_MWS_N_STATS] or null
+void watershed(const int32_t *eu, const int32_t *ev, int64_t n_edges, int32_t N, int32_t *label,
+               int64_t *issued, int64_t *stats) {
+    int64_t st[ST_N] = {0};
+    Mws w(N);
+    const int64_t min_len = env_i64("PPP_MWS_PRUNE_MIN", PRUNE_MIN_EDGES);
+    const int64_t fixed_block = env_i64("PPP_MWS_PRUNE_BLOCK", 0);
+    if (env_i64("PPP_MWS_PRUNE", 1) == 0 || n_edges < min_len || n_edges == 0) {
+        w.visit<false>(eu, ev, n_edges, nullptr);
+        st[ST_VISITED] = n_edges;
+    } else {
+        Pool pool(prune_threads());
+        const int T = pool.size();
+        st[ST_THREADS] = T;
+        std::vector<Slice> part((size_t)T);
+        std::unique_ptr<int32_t[]> su, sv;             // the survivors of the latest prune
+        std::unique_ptr<uint8_t[]> rule;               // per unvisited edge: the rule that drops it, 0 = none
+        const int32_t *cu = eu, *cv = ev;              // the edges not yet visited
+        int64_t left = n_edges;
+        int64_t block = fixed_block > 0 ? fixed_block : std::max<int64_t>(n_edges / PRUNE_FIRST_SHARE, 1);
+        for (;;) {
+            const int64_t b = std::min(block, left);
+            w.visit<false>(cu, cv, b, nullptr);
+            ++st[ST_BLOCKS];
+            st[ST_VISITED] += b;
+            cu += b; cv += b; left -= b;
+            if (left == 0) break;
+            w.compress();
+            if (!rule) rule.reset(new uint8_t[(size_t)left]);
+            const int64_t per = (left + T - 1) / T;
+            pool.run([&](int t) {
+                Slice &s = part[(size_t)t];
+                s.kept = 0;
+                const int64_t lo = std::min(left, per * t), hi = std::min(left, lo + per);
+                for (int64_t i = lo; i < hi; ++i) {
+                    const int r = w.settled(cu[i], cv[i]);
+                    rule[(size_t)i] = (uint8_t)r;
+                    ++s.dropped[r];
+                    s.kept += r == 0;
+                }
+            });
+            int64_t kept = 0;
+            for (Slice &s : part) { s.at = kept; kept += s.kept; }
+            // (not std::vector: it would write zeros over what is overwritten at once)
+            std::unique_ptr<int32_t[]> nu(new int32_t[(size_t)kept]), nv(new int32_t[(size_t)kept]);
+            pool.run([&](int t) {
+                int64_t at = part[(size_t)t].at;
+                const int64_t lo = std::min(left, per * t), hi = std::min(left, lo + per);
+                for (int64_t i = lo; i < hi; ++i)
+                    if (rule[(size_t)i] == 0) { nu[(size_t)at] = cu[i]; nv[(size_t)at] = cv[i]; ++at; }
+            });
+            su.swap(nu); sv.swap(nv);
+            cu = su.get(); cv = sv.get(); left = kept;
+            ++st[ST_PRUNES];
+            if (left == 0) break;
+            if (fixed_block <= 0) block *= PRUNE_GROWTH;
+        }
+        for (const Slice &s : part)
+            for (int r = 1; r <= 4; ++r) st[ST_RULE1 + r - 1] += s.dropped[r];
+    }
+    w.labels(label, issued);
+    if (stats) std::copy(st, st + ST_N, stats);
 }
 
 }  // namespace
@@ -206,9 +440,30 @@ extern "C" {
 // on the device by ppp_mws_edges).  labels int32 [n_nodes] out; returns the number of ids issued.
 int64_t ppp_host_mws_sorted(const int32_t *eu, const int32_t *ev, int64_t n_edges, int64_t n_nodes,
                             int32_t *labels) {
+    return ppp_host_mws_sorted_stats(eu, ev, n_edges, n_nodes, labels, nullptr);
+}
+
+// The same, and stats int64 [PPP_MWS_N_STATS] (may be null): blocks run (0: the plain loop), edges
+// dropped by rules 1-4, edges visited, threads, prune passes.  dropped + visited = n_edges.
+int64_t ppp_host_mws_sorted_stats(const int32_t *eu, const int32_t *ev, int64_t n_edges, int64_t n_nodes,
+                                  int32_t *labels, int64_t *stats) {
+    int64_t issued = 0;
+    if (stats) std::fill(stats, stats + PPP_MWS_N_STATS, 0);
+    if (n_nodes <= 0) return 0;
+    watershed(eu, ev, n_edges, (int32_t)n_nodes, labels, &issued, stats);
+    return issued;
+}
+
+// The plain loop, noting what every edge did: cls uint8 [n_edges], 0-4 attractive (new component,
+// joined, merged, same cluster, refused by a mutex key), 5-7 repulsive (same cluster, key already
+// there, key inserted).  For tools/time_mws.py --classes.
+int64_t ppp_host_mws_sorted_classes(const int32_t *eu, const int32_t *ev, int64_t n_edges, int64_t n_nodes,
+                                    int32_t *labels, uint8_t *cls) {
     int64_t issued = 0;
     if (n_nodes <= 0) return 0;
-    watershed(eu, ev, n_edges, (int32_t)n_nodes, labels, &issued);
+    Mws w((int32_t)n_nodes);
+    w.visit<true>(eu, ev, n_edges, cls);
+    w.labels(labels, &issued);
     return issued;
 }
 
@@ -321,7 +576,7 @@ int64_t ppp_host_mws(const uint32_t *pairs, const float *aff, int64_t n_rows, co
     std::vector<Edge>().swap(edges);
     std::vector<int32_t> label((size_t)N);
     int64_t issued = 0;
-    watershed(eu.data(), ev.data(), (int64_t)eu.size(), N, label.data(), &issued);
+    watershed(eu.data(), ev.data(), (int64_t)eu.size(), N, label.data(), &issued, nullptr);
 
     // ---- labels ------------------------------------------------------------------------------
     for (int32_t n = 0; n < N; ++n) {

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Development aid: run one flylight140_p7 step with the shipped flags on the GPU and save what the
 two host stages (set-cover thinning, mutex watershed) receive and return, so that they can be
-profiled / re-implemented off the GPU box.  Writes gpurun_out/host_stage_inputs.npz."""
+profiled / re-implemented off the GPU box.  Writes host_stage_inputs.npz into the output folder
+(PPP_OUT_DIR, default out/) and, for the watershed's host loop alone (ppp_host_mws_sorted),
+mws_edges_<workload>.npz: the sorted edge list eu / ev (bit 31 of ev = attractive), n_nodes, the
+labels and the ids issued -- tools/time_mws.py --edges takes that file."""
 import os
 import sys
 import time
@@ -15,7 +18,8 @@ import bench  # noqa: E402
 from patchperpix_amd import backend, flags  # noqa: E402
 from patchperpix_amd.vote_instances import vote_instances as vi  # noqa: E402
 
-shape, ps, cell = bench.WORKLOADS[sys.argv[1] if len(sys.argv) > 1 else "flylight140_p7"]
+name = sys.argv[1] if len(sys.argv) > 1 else "flylight140_p7"
+shape, ps, cell = bench.WORKLOADS[name]
 kw = dict(flags.FLYLIGHT)
 P = backend.make_params(shape, ps, **kw)
 labels = bench.device_labels(torch, shape, cell, seed=0)
@@ -23,6 +27,7 @@ pred = backend.synth_pred(labels, P, seed=0, f16=True)
 fg = (labels != 0).cpu().numpy()
 saved = {}
 orig_thin, orig_mws = backend.host_thin_cover, backend.host_mws
+orig_edges = backend.mws_edges_device
 
 
 def thin(mask, patchshape, sel_lin, bits):
@@ -41,9 +46,30 @@ def mws(pairs, aff, shp):
     return out
 
 
-backend.host_thin_cover, backend.host_mws = thin, mws
+def edges(rows, aff, nodes, P_):
+    eu, ev = orig_edges(rows, aff, nodes, P_)
+    k = int(nodes.shape[0])
+    lab = np.zeros((k,), dtype=np.int32)
+    times = []
+    for _ in range(5):                      # the loop on this host, the list warm after the first
+        t0 = time.perf_counter()
+        issued = int(backend.lib().ppp_host_mws_sorted(backend._np_ptr(eu), backend._np_ptr(ev), len(eu), k,
+                                                       backend._np_ptr(lab)))
+        times.append(1e3 * (time.perf_counter() - t0))
+    saved_edges.update(eu=eu.copy(), ev=ev.copy(), n_nodes=np.int64(k), labels=lab, issued=np.int64(issued),
+                       loop_ms=np.array(times))
+    return eu, ev
+
+
+saved_edges = {}
+backend.host_thin_cover, backend.host_mws, backend.mws_edges_device = thin, mws, edges
 inst, _ = vi.to_instance_seg(pred, fg.copy(), fg.copy(), fg.astype(np.uint8), ps, **kw)
 print("instances", len(np.unique(inst)) - 1, "thin s", saved.get("thin_seconds"), "mws s", saved.get("mws_seconds"))
-os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-np.savez_compressed(os.path.join(ROOT, "gpurun_out", "host_stage_inputs.npz"), shape=np.array(shape),
+OUT = os.path.join(ROOT, os.environ.get("PPP_OUT_DIR", "out"))
+os.makedirs(OUT, exist_ok=True)
+np.savez_compressed(os.path.join(OUT, "host_stage_inputs.npz"), shape=np.array(shape),
                     patchshape=np.array(ps), instances=inst, **saved)
+if saved_edges:
+    print("mws edges", len(saved_edges["eu"]), "nodes", int(saved_edges["n_nodes"]), "ids issued",
+          int(saved_edges["issued"]), "loop ms", " ".join("%.2f" % t for t in saved_edges["loop_ms"]))
+    np.savez(os.path.join(OUT, "mws_edges_%s.npz" % name), **saved_edges)
