@@ -1170,6 +1170,34 @@ int ppp_counter_calibration(const void *d_src, int src_dtype, int64_t n_read, fl
 int ppp_pred_check(const void *d_pred, int pred_dtype, int64_t n_values, int32_t *d_unclean, const ppp_params *p,
                    void *stream);
 
+/* --- one read of the prediction for every compare against a threshold (csrc/ppp_prepass.hip) ---------
+ * ppp_pred_check, the pre-pass of ppp_rank_patches_vm and ppp_patch_bits_volume each stream the whole
+ * prediction and evaluate compares of the same values.  ppp_pred_prepass reads it once and leaves, in d_work:
+ *   unclean   i32           the bits of ppp_pred_check over all C * Z * Y * X values
+ *   M, info   the interleaved P / N masks and pair counts of the centres of score_box, byte for byte what the
+ *             ranking call's own pre-pass writes; valid u8 [Z*Y*X] likewise (d_overlap as in ppp_rank_patches_vm)
+ *   bits_vol  u32 [Z*Y*X][ceil(C/32)]   ppp_patch_bits_volume for fc_threshold (independent of p's thresholds)
+ * and writes into d_score (float [Z][Y][X]) the scores that need no consensus: border centres, background
+ * centres, centres without a first pixel.  Served: cubic patches of 5 / 7 / 9 without count_pos_neg and
+ * ring_z -- ppp_pred_prepass_workspace_bytes returns 0 otherwise (-1: invalid parameters) and the caller keeps
+ * the separate calls.  ppp_pred_prepass_layout: the byte offsets of {M, info, valid, bits_vol, unclean} in
+ * d_work (the size query, the launch and this answer share one description).  p->cons_box is not looked at.
+ * d_work: 16-byte aligned.  Does not synchronise.
+ * ppp_rank_patches_vm_prepared: ppp_rank_patches_vm for a caller that holds such a d_work for the same score_box
+ * and the same p (thresholds, overlap): no pre-pass runs, the prediction is not read; d_score must still hold
+ * what ppp_pred_prepass wrote.  d_work: ppp_rank_prepared_workspace_bytes(p) (0: not served).
+ * ppp_patch_bits_from_table: d_bits[k] = row of centre k (d_centres u32[n][3], inside the volume) of such a
+ * bits_vol: ppp_patch_bits for a list of centres without touching the prediction again.                    */
+int64_t ppp_pred_prepass_workspace_bytes(const ppp_box *score_box, const ppp_params *p);
+int ppp_pred_prepass_layout(const ppp_box *score_box, const ppp_params *p, int64_t *offsets /* [5] */);
+int ppp_pred_prepass(const void *d_pred, int pred_dtype, const uint8_t *d_overlap, double fc_threshold, float *d_score,
+                     const ppp_box *score_box, void *d_work, const ppp_params *p, void *stream);
+int64_t ppp_rank_prepared_workspace_bytes(const ppp_params *p);
+int ppp_rank_patches_vm_prepared(const float *d_cons_vm, float *d_score, const ppp_box *score_box, void *d_prepass_work,
+                                 void *d_work, const ppp_params *p, void *stream);
+int ppp_patch_bits_from_table(const uint32_t *d_bits_vol, const uint32_t *d_centres, uint64_t n, uint32_t *d_bits,
+                              const ppp_params *p, void *stream);
+
 /* The same generator for a BOX of a larger volume (tile-wise generation, BASELINE config [3]:
  * a rank of the 1024^3 workload holds one tile + halo of the prediction at a time).
  * p: Z / Y / X = extent of the prediction box, origin_* = its position in the volume;

@@ -69,6 +69,19 @@ _SIGNATURES = {
     "ppp_abi_version": (ctypes.c_int, []),
     "ppp_pred_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p,
                                       ctypes.POINTER(Params), ctypes.c_void_p]),
+    # one read of the prediction for the clean flag, S2's masks and the cover's patch bits (ppp_prepass.hip)
+    "ppp_pred_prepass_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(Box), ctypes.POINTER(Params)]),
+    "ppp_pred_prepass_layout": (ctypes.c_int, [ctypes.POINTER(Box), ctypes.POINTER(Params),
+                                               ctypes.POINTER(ctypes.c_int64)]),
+    "ppp_pred_prepass": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_double,
+                                        ctypes.c_void_p, ctypes.POINTER(Box), ctypes.c_void_p,
+                                        ctypes.POINTER(Params), ctypes.c_void_p]),
+    "ppp_rank_prepared_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(Params)]),
+    "ppp_rank_patches_vm_prepared": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(Box),
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(Params),
+                                                    ctypes.c_void_p]),
+    "ppp_patch_bits_from_table": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                 ctypes.c_void_p, ctypes.POINTER(Params), ctypes.c_void_p]),
     "ppp_last_error": (ctypes.c_char_p, []),
     "ppp_consensus_kernel_name": (ctypes.c_char_p, []),
     "ppp_consensus_short_form": (ctypes.c_int, []),
@@ -760,6 +773,58 @@ def pred_check(pred, P):
     return 1 if bad == 0 else 2
 
 
+class PredPrepass:
+    """What ppp_pred_prepass made of ONE prediction tensor in its single read (valid while the tensor, the
+    thresholds and the overlap mask stay what they were): `work` is the library's workspace (S2's masks, pair
+    counts and `valid` for `score_box`, handed to rank_patches as `prepared`), `bits_vol` the int32 (V, words)
+    view of the per-voxel patch bits for `fc_threshold` inside it, `clean` the value of ppp_params.pred_clean."""
+    __slots__ = ("work", "score_box", "bits_vol", "offsets", "clean", "unclean_bits", "fc_threshold")
+
+
+def pred_prepass(pred, overlap, fc_threshold, P, score, score_box=None):
+    """ppp_pred_prepass: the clean flag, S2's pre-pass for `score_box` (its border / background scores go into
+    `score`, float32 (Z, Y, X)) and the cover's per-voxel patch bits from one read of `pred`.  Returns a
+    PredPrepass, or None where the library does not serve the geometry or PPP_PRED_PREPASS=0 asks for the
+    separate launches -- the caller then keeps pred_check / rank_patches / patch_bits as they are."""
+    torch = _torch()
+    if os.environ.get("PPP_PRED_PREPASS", "1") == "0" or not torch.is_tensor(pred) or not pred.is_cuda \
+            or not pred.is_contiguous():
+        return None
+    sb = (0, 0, 0) + tuple(int(v) for v in P.shape) if score_box is None else tuple(int(v) for v in score_box)
+    box = ctypes.byref(Box(*sb))
+    nbytes = int(lib().ppp_pred_prepass_workspace_bytes(box, ctypes.byref(P)))
+    if nbytes == 0:
+        return None
+    pre = PredPrepass()
+    pre.work = _workspace(nbytes, pred.device)
+    off = (ctypes.c_int64 * 5)()
+    check(lib().ppp_pred_prepass_layout(box, ctypes.byref(P), off))
+    with _timed("pred_prepass"):
+        check(lib().ppp_pred_prepass(_dev_ptr(pred), pred_dtype_code(pred), _dev_ptr(overlap), float(fc_threshold),
+                                     _dev_ptr(score), box, _dev_ptr(pre.work), ctypes.byref(P), _stream()))
+    V = int(P.Z) * int(P.Y) * int(P.X)
+    words = (P.pz * P.py * P.px + 31) // 32
+    pre.score_box, pre.offsets, pre.fc_threshold = sb, tuple(int(o) for o in off), float(fc_threshold)
+    pre.bits_vol = pre.work[off[3]:off[3] + V * words * 4].view(torch.int32).view(V, words)
+    pre.unclean_bits = int(pre.work[off[4]:off[4] + 4].view(torch.int32).item())
+    note("pred_unclean_bits", pre.unclean_bits)
+    # (PPP_S1_CLEAN=0: S1 is never told, as pred_check never asks)
+    pre.clean = 2 if os.environ.get("PPP_S1_CLEAN", "1") == "0" or pre.unclean_bits else 1
+    return pre
+
+
+def patch_bits_from_table(bits_vol, centres, P):
+    """ppp_patch_bits_from_table: the rows of `centres` (int32 [n, 3] on the device) out of a per-voxel
+    table (PredPrepass.bits_vol): patch_bits without another look at the prediction."""
+    torch = _torch()
+    n = int(centres.shape[0])
+    bits = torch.empty((n, int(bits_vol.shape[1])), dtype=torch.int32, device=bits_vol.device)
+    with _timed("patch_bits"):
+        check(lib().ppp_patch_bits_from_table(_dev_ptr(bits_vol), _dev_ptr(centres.contiguous()), n, _dev_ptr(bits),
+                                              ctypes.byref(P), _stream()))
+    return bits
+
+
 def with_pred_clean(pred, P):
     """P with pred_clean decided (a copy when it was not): callers that pass the same tensor to many
     S1 launches (tiling.assemble: once per frame) decide once; a direct call decides per call."""
@@ -950,10 +1015,27 @@ def _big_empty(shape, device):
         return torch.empty(shape, dtype=torch.float32, device=device)
 
 
-def rank_patches(pred, cons, overlap, P, score_box=None, out=None):
+def rank_patches(pred, cons, overlap, P, score_box=None, out=None, prepared=None):
     """S2.  Returns the (Z, Y, X) float32 score volume on the device.  With a VOXEL_MAJOR
-    consensus (P.cons_layout) the row-stationary kernel runs (ppp_rank_patches_vm)."""
+    consensus (P.cons_layout) the row-stationary kernel runs (ppp_rank_patches_vm).  prepared: the
+    PredPrepass of this tensor and score box, whose pass wrote the border and background scores into
+    `out` -- the kernel then starts from its masks (ppp_rank_patches_vm_prepared)."""
     torch = _torch()
+    if prepared is not None:
+        sb = (0, 0, 0) + tuple(int(v) for v in P.shape) if score_box is None else tuple(int(v) for v in score_box)
+        assert out is not None and P.cons_layout == CONS_VOXEL_MAJOR and prepared.score_box == sb, \
+            "a prepared ranking call takes the score volume and the box of its pre-pass"
+        work = _workspace(lib().ppp_rank_prepared_workspace_bytes(ctypes.byref(P)), pred.device)
+        cb = P.cons_box
+        rad = (P.pz // 2, P.py // 2, P.px // 2)
+        lo3 = [max(sb[a] - rad[a], (cb.z0, cb.y0, cb.x0)[a]) for a in range(3)]
+        hi3 = [min(sb[3 + a] + rad[a], (cb.z1, cb.y1, cb.x1)[a]) for a in range(3)]
+        note_add("s2_base_voxels", int(np.prod([max(0, h - l) for l, h in zip(lo3, hi3)])))
+        with _timed("rank_patches"):
+            check(lib().ppp_rank_patches_vm_prepared(_dev_ptr(cons), _dev_ptr(out), ctypes.byref(Box(*sb)),
+                                                     _dev_ptr(prepared.work), _dev_ptr(work), ctypes.byref(P),
+                                                     _stream()))
+        return out
     if out is None:
         out = torch.zeros(P.shape, dtype=torch.float32, device=pred.device)
     box = None if score_box is None else ctypes.byref(Box(*[int(v) for v in score_box]))

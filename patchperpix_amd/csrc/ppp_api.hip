@@ -1040,6 +1040,94 @@ int ppp_pred_check(const void *d_pred, int pred_dtype, int64_t n_values, int32_t
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_pred_check");
 }
 
+/* ---- the fused pre-pass over the prediction (ppp_prepass.hip) ---- */
+// (before S1 there is no consensus box yet: the pre-pass asks for none, the prepared ranking call checks its own)
+static int prepass_box(const ppp_box *score_box, const ppp_params *p, ppp_box *sb) {
+    *sb = ppp_box{0, 0, 0, p->Z, p->Y, p->X};
+    if (score_box) *sb = *score_box;
+    if (sb->z0 < 0 || sb->y0 < 0 || sb->x0 < 0 || sb->z1 > p->Z || sb->y1 > p->Y || sb->x1 > p->X ||
+        sb->z1 <= sb->z0 || sb->y1 <= sb->y0 || sb->x1 <= sb->x0)
+        return fail(PPP_ERR_INVALID_ARG, "score_box outside the volume");
+    return PPP_OK;
+}
+
+int64_t ppp_pred_prepass_workspace_bytes(const ppp_box *score_box, const ppp_params *p) {
+    ppp::Geo G;
+    ppp_box sb;
+    if (!p || make_geo(p, &G) != PPP_OK) return -1;
+    if (!ppp::pred_prepass_supported(G)) return 0;
+    if (prepass_box(score_box, p, &sb) != PPP_OK) return -1;
+    return (int64_t)ppp::pred_prepass_workspace_bytes(sb, G);
+}
+
+int ppp_pred_prepass_layout(const ppp_box *score_box, const ppp_params *p, int64_t *offsets) {
+    ppp::Geo G;
+    ppp_box sb;
+    PPP_TRY(make_geo(p, &G));
+    if (!offsets) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    if (!ppp::pred_prepass_supported(G)) return fail(PPP_ERR_UNSUPPORTED, "ppp_pred_prepass: cubic patches of 5 / 7 / 9 only");
+    PPP_TRY(prepass_box(score_box, p, &sb));
+    char base;                                            // (any base: only the differences count)
+    ppp::Carver c(&base);
+    const ppp::PrepassWork W = ppp::pred_prepass_layout(c, sb, G);
+    offsets[0] = (char *)W.M - &base; offsets[1] = (char *)W.info - &base; offsets[2] = (char *)W.valid - &base;
+    offsets[3] = (char *)W.bits_vol - &base; offsets[4] = (char *)W.unclean - &base;
+    return PPP_OK;
+}
+
+int ppp_pred_prepass(const void *d_pred, int pred_dtype, const uint8_t *d_overlap, double fc_threshold, float *d_score,
+                     const ppp_box *score_box, void *d_work, const ppp_params *p, void *stream) {
+    ppp::Geo G;
+    ppp_box sb;
+    PPP_TRY(make_geo(p, &G));
+    PPP_TRY(check_dtype(pred_dtype));
+    if (!d_pred || !d_score || !d_work) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    if (G.use_overlap && !d_overlap) return fail(PPP_ERR_INVALID_ARG, "use_overlap set but d_overlap is NULL");
+    if (((uintptr_t)d_work & 15) != 0) return fail(PPP_ERR_INVALID_ARG, "ppp_pred_prepass: d_work must be 16-byte aligned");
+    if (!ppp::pred_prepass_supported(G))
+        return fail(PPP_ERR_UNSUPPORTED, "ppp_pred_prepass: cubic patches of 5 / 7 / 9, no count_pos_neg, no ring "
+                                         "(use ppp_pred_check, ppp_rank_patches_vm and ppp_patch_bits_volume otherwise)");
+    PPP_TRY(prepass_box(score_box, p, &sb));
+    PPP_TRY(need_device());
+    hipError_t e = ppp::launch_pred_prepass(d_pred, pred_dtype, d_overlap, (float)fc_threshold, d_score, sb, d_work, G,
+                                            (hipStream_t)stream);
+    if (e == hipErrorInvalidConfiguration) return fail(PPP_ERR_UNSUPPORTED, "ppp_pred_prepass: a grid the device would not run whole");
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_pred_prepass");
+}
+
+int64_t ppp_rank_prepared_workspace_bytes(const ppp_params *p) {
+    ppp::Geo G;
+    if (!p || make_geo(p, &G) != PPP_OK) return -1;
+    if (!ppp::rank_wg_supported(G) || G.ring) return 0;
+    return (int64_t)ppp::rank_wg_prepared_workspace_bytes(G);
+}
+
+int ppp_rank_patches_vm_prepared(const float *d_cons_vm, float *d_score, const ppp_box *score_box, void *d_prepass_work,
+                                 void *d_work, const ppp_params *p, void *stream) {
+    ppp::Geo G;
+    PPP_TRY(make_geo(p, &G));
+    if (!d_cons_vm || !d_score || !d_prepass_work || !d_work) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    if (!ppp::rank_wg_supported(G) || G.ring)
+        return fail(PPP_ERR_UNSUPPORTED, "ppp_rank_patches_vm_prepared: VOXEL_MAJOR rows of a plain box, cubic patches of 5 / 7 / 9");
+    ppp_box sb;
+    PPP_TRY(rank_box(score_box, p, G, &sb));
+    PPP_TRY(need_device());
+    hipError_t e = ppp::launch_rank_wg_prepared(d_cons_vm, d_score, sb, d_prepass_work, d_work, G, (hipStream_t)stream);
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_rank_patches_vm_prepared");
+}
+
+int ppp_patch_bits_from_table(const uint32_t *d_bits_vol, const uint32_t *d_centres, uint64_t n, uint32_t *d_bits,
+                              const ppp_params *p, void *stream) {
+    ppp::Geo G;
+    PPP_TRY(make_geo(p, &G));
+    if (n == 0) return PPP_OK;
+    if (!d_bits_vol || !d_centres || !d_bits) return fail(PPP_ERR_INVALID_ARG, "NULL pointer argument");
+    PPP_TRY(need_device());
+    hipError_t e = ppp::launch_patch_bits_from_table(d_bits_vol, d_centres, n, d_bits, G, (hipStream_t)stream);
+    if (e == hipErrorInvalidConfiguration) return fail(PPP_ERR_UNSUPPORTED, "ppp_patch_bits_from_table: more rows than one launch copies");
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_patch_bits_from_table");
+}
+
 int ppp_decode_tail(const float *d_x, int64_t n, int32_t fmaps, int32_t side, const float *d_w1, float b1,
                     const float *d_w2, float b2, const float *d_w3, float b3, const int64_t *d_dst,
                     void *d_pred, int pred_dtype, const ppp_params *p, void *stream) {

@@ -1,5 +1,9 @@
-// ppp_aux.hip -- small helpers around the hot path: patch bit masks for the host-side
-// greedy cover, and the procedural synthetic prediction generator used by bench / tests.
+// ppp_aux.hip -- small helpers around the hot path: the patch bits of the greedy cover and the
+// thinning (per centre, and for every voxel of a volume), the "clean" check S1 picks its
+// classification by, the procedural synthetic prediction generator used by bench / tests, and the
+// counter calibration kernels.  The bit kernels and the check each read the prediction on their
+// own; on the resident single box of cubic 5 / 7 / 9 patches one pass serves all of them and S2's
+// masks (ppp_prepass.hip), and these kernels serve every other path and geometry.
 #include "ppp_kernels.hpp"
 
 namespace ppp {

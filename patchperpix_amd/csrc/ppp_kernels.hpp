@@ -87,6 +87,26 @@ size_t rank_wg_stamps_offset(const ppp_box &sb, const Geo &G);   // where the st
 #endif
 hipError_t launch_rank_wg(const void *pred, int dtype, const float *S, const uint8_t *ov, float *score,
                           const ppp_box &sb, void *work, const Geo &G, hipStream_t s);
+// ... with M / info / valid of the score box made by launch_pred_prepass (pre_work: its workspace); `work` holds
+// rank_wg_prepared_workspace_bytes
+size_t rank_wg_prepared_workspace_bytes(const Geo &G);
+hipError_t launch_rank_wg_prepared(const float *S, float *score, const ppp_box &sb, void *pre_work, void *work,
+                                   const Geo &G, hipStream_t s);
+hipError_t launch_rank_valid(const void *pred, int dtype, const uint8_t *ov, uint8_t *valid, const Geo &G, hipStream_t s);
+// one read of the prediction for the clean flag, S2's masks and the cover's per-voxel patch bits (ppp_prepass.hip)
+struct PrepassWork {
+    uint32_t *M, *info;       // as rank_wg_kernel reads them (ppp_rank_masks.hpp)
+    uint8_t *valid;           // [V]
+    uint32_t *bits_vol;       // [V][ceil(C / 32)]
+    int32_t *unclean;         // the bits of ppp_pred_check
+};
+bool pred_prepass_supported(const Geo &G);
+PrepassWork pred_prepass_layout(Carver &c, const ppp_box &sb, const Geo &G);
+size_t pred_prepass_workspace_bytes(const ppp_box &sb, const Geo &G);
+hipError_t launch_pred_prepass(const void *pred, int dtype, const uint8_t *ov, float fc_thresh, float *score,
+                               const ppp_box &sb, void *work, const Geo &G, hipStream_t s);
+hipError_t launch_patch_bits_from_table(const uint32_t *bits_vol, const uint32_t *centres, uint64_t n, uint32_t *bits,
+                                        const Geo &G, hipStream_t s);
 hipError_t launch_patch_graph(const void *pred, int dtype, const float *cons,
                               const uint32_t *pairs, const uint32_t *order, uint64_t n,
                               float *aff, const Geo &G, hipStream_t s);

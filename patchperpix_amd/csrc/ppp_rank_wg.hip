@@ -111,6 +111,7 @@
 #include <type_traits>
 
 #include "ppp_kernels.hpp"
+#include "ppp_rank_masks.hpp"
 
 namespace ppp {
 
@@ -150,28 +151,8 @@ static constexpr int RW_FIT_MINWAVES = 6;
 static constexpr int RW_FIT_NTZ = 4;
 static constexpr int RW_FIT_TZ[RW_FIT_NTZ] = {8, 10, 12, 16};
 static constexpr int rw_fit_index(int tz_step) { return tz_step <= 8 ? 0 : (tz_step <= 10 ? 1 : (tz_step <= 12 ? 2 : 3)); }
-// Mask words per centre, padded to whole 16-byte loads.  The masks are stored CENTRE-MAJOR,
-// M[centre][word]: a lane reads the 184 bytes of ITS centre with twelve 16-byte loads, and the
-// centres of a wave's chunk (9-runs of x neighbours) cover their cache lines densely.  The earlier
-// word-major layout M[word][centre] made each of the 46 loads of a chunk touch eight 128-byte lines
-// for 36 bytes apiece: 47 KB of line traffic per chunk for 11.8 KB of masks -- and because a
-// workgroup's masks (377 KB) are re-read on every one of the 729 steps while 128 workgroups per
-// XCD share a 4 MB L2, most of those lines came over the fabric (the kernel ran at the fabric's
-// bandwidth: profiles/r04_b_s2_ablations.txt -- 205 ms, 126 ms without the mask loads).
-static constexpr int rw_mask_words(int C) { return (((C + 15) / 16) + 3) & ~3; }
-// Round 5: the two-bit masks in ROWS OF 16 X-NEIGHBOURS, M[row][quad of words][centre in row][4 words]:
-// the 16-byte load of quad q by the nine x-neighbours of a run touches 144 contiguous bytes (two or
-// three lines) instead of nine lines 184 bytes apart -- the bytes fetched stay the same, the
-// addresses the vector cache has to look up per load fall to a quarter.
-// index (in 16-byte units) of quad 0 of the centre at x of line zy (score-box coordinates)
-__host__ __device__ __forceinline__ long long rw_mask_quad0(long long zy, int x, int sX, int quads) {
-    return ((zy * ((sX + 15) >> 4) + (x >> 4)) * quads) * 16 + (x & 15);
-}
-static constexpr int RW_QSTRIDE = 16;      // 16-byte units between a centre's quads
-static size_t rw_mask_bytes(int sZ, int sY, int sX, int C) {
-    const size_t cols = (size_t)((sX + 15) >> 4) * 16;
-    return (size_t)sZ * sY * cols * rw_mask_words(C) * 4;
-}
+// (the masks' layout -- rw_mask_words, rw_mask_quad0, RW_QSTRIDE, rw_mask_bytes, interleave16 -- is in
+// ppp_rank_masks.hpp: the fused pre-pass of ppp_prepass.hip writes it too)
 typedef const volatile __attribute__((address_space(3))) float *lds_f32_cvp2;
 
 // acc + r * c with c a float16 in the low / high half of a register: the compiler selects
@@ -199,18 +180,11 @@ struct StaticFor<END, END> {
     static __device__ __forceinline__ void run(F &&) {}
 };
 
-// 16 P bits and 16 N bits -> one word: byte j = P nibble j | N nibble j << 4
-__host__ __device__ __forceinline__ uint32_t interleave16(uint32_t p, uint32_t n) {
-    uint32_t out = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        out |= (((p >> (4 * j)) & 0xFu) | (((n >> (4 * j)) & 0xFu) << 4)) << (8 * j);
-    return out;
-}
-
 // ---- pre-pass: interleaved masks, pair counts, border / background scores ------------------
-// thread per centre of the score box; masks word-major over the box (lanes = neighbouring
-// centres coalesce in the main kernel)
+// thread per centre of the score box; each centre's masks go to its slot of the row-of-16 layout
+// (rw_mask_quad0), one 4-byte word at a time.  This is the pre-pass of a caller that brings no masks; a
+// caller on the fused path (ppp_pred_prepass, ppp_prepass.hip) hands M / info / valid in and neither this
+// kernel nor rank_valid2_kernel is launched (launch_rank_wg_prepared).
 // Round 12: the cubic window P = 5 / 7 / 9 is compiled in (as PaGeo does for S5): the partner loop runs
 // over (dz, dy, dx) with constant bounds -- no division per partner -- and reads the partner's validity from
 // `valid`, which rank_valid2_kernel wrote one launch earlier, instead of evaluating pred[mid] > th && ov == 0
@@ -830,18 +804,21 @@ struct RankWgWork {
     int32_t *weight, *order;  // [RW_ORDER_MAX] each; a PPP_RW_STAMPS build reuses `weight` for its stamps
     uint16_t *dealT;          // rw_deal_bytes
 };
-static RankWgWork rank_wg_layout(Carver &c, const ppp_box &sb, const Geo &G) {
-    const int sX = sb.x1 - sb.x0, sY = sb.y1 - sb.y0, sZ = sb.z1 - sb.z0;
-    RankWgWork W;
-    W.M = (uint32_t *)c.take_bytes(rw_mask_bytes(sZ, sY, sX, G.C));
-    W.info = c.take<uint32_t>((size_t)sX * sY * sZ);
-    W.valid = c.take<uint8_t>(G.V);
+// the launch's own part (a caller that hands the masks in brings only this: rank_wg_prepared_workspace_bytes)
+static void rank_wg_sched_layout(Carver &c, const Geo &G, RankWgWork &W) {
     W.weight = c.take<int32_t>(RW_ORDER_MAX);
     W.order = c.take<int32_t>(RW_ORDER_MAX);
     W.dealT = (uint16_t *)c.take_bytes(rw_deal_bytes(G.px));
+}
+static RankWgWork rank_wg_layout(Carver &c, const ppp_box &sb, const Geo &G) {
+    const RankMasks m = rank_masks_layout(c, sb, G);
+    RankWgWork W;
+    W.M = m.M; W.info = m.info; W.valid = m.valid;
+    rank_wg_sched_layout(c, G, W);
     return W;
 }
 size_t rank_wg_workspace_bytes(const ppp_box &sb, const Geo &G) { Carver c(nullptr); rank_wg_layout(c, sb, G); return c.used; }
+size_t rank_wg_prepared_workspace_bytes(const Geo &G) { Carver c(nullptr); RankWgWork W; rank_wg_sched_layout(c, G, W); return c.used; }
 #ifdef PPP_RW_STAMPS
 size_t rank_wg_stamps_offset(const ppp_box &sb, const Geo &G) {      // (tools/s2_wg_times.py reads them back)
     char base;                                                       // (any base: only the difference counts)
@@ -1031,6 +1008,9 @@ void rank_wg_plan_residency(const ppp_box &sb, const Geo &G, int resident_per_cu
     out[3] = assumed ? cus_per_xcd : rw_cus_per_xcd();
 }
 
+static hipError_t launch_rwg_main(const float *S, const RankWgWork &W, float *score, const ppp_box &sb, const Geo &G,
+                                  hipStream_t s);
+
 template <typename T>
 static hipError_t launch_rwg(const T *pred, const float *S, const uint8_t *ov, float *score,
                              const ppp_box &sb, void *work, const Geo &G, hipStream_t s) {
@@ -1056,6 +1036,17 @@ static hipError_t launch_rwg(const T *pred, const float *S, const uint8_t *ov, f
     default:
         return hipErrorNotSupported;
     }
+#undef PPP_RW_PRE
+    return launch_rwg_main(S, RankWgWork{M, info, valid, weight, order, dealT}, score, sb, G, s);
+}
+
+// everything after the pre-pass: tile weights and order, the dealing table, the kernel
+static hipError_t launch_rwg_main(const float *S, const RankWgWork &W, float *score, const ppp_box &sb, const Geo &G,
+                                  hipStream_t s) {
+    uint32_t *const M = W.M, *const info = W.info;
+    uint8_t *const valid = W.valid;
+    int32_t *const weight = W.weight, *order = W.order;
+    uint16_t *const dealT = W.dealT;
     const RwPlan plan = rw_plan_device(sb, G);
     const bool tall = plan.TZ == 16 && !plan.fit, big = plan.TY == 16, fit = plan.fit;
     const int tiles_y = plan.tiles_y, tiles_x = plan.tiles_x, per_xcd = plan.per_xcd, splits = plan.splits, tz_step = plan.tz_step;
@@ -1115,7 +1106,6 @@ static hipError_t launch_rwg(const T *pred, const float *S, const uint8_t *ov, f
 #undef PPP_RW_ARGS
 #undef PPP_RW_STAMP_ARG
 #undef PPP_RW_CASE
-#undef PPP_RW_PRE
     return hipGetLastError();
 }
 
@@ -1126,6 +1116,33 @@ hipError_t launch_rank_wg(const void *pred, int dtype, const float *S, const uin
         using T = PPP_PRED_T(tag);
         return launch_rwg<T>((const T *)pred, S, ov, score, sb, work, G, s);
     });
+}
+
+// rank_valid2_kernel on its own (the fused pre-pass of ppp_prepass.hip reads `valid` as the kernel above does)
+hipError_t launch_rank_valid(const void *pred, int dtype, const uint8_t *ov, uint8_t *valid, const Geo &G, hipStream_t s) {
+    PPP_GRID_CHECK((G.V + 255) / 256, 256);
+    return with_pred_type(dtype, [&](auto tag) {
+        using T = PPP_PRED_T(tag);
+        rank_valid2_kernel<T><<<dim3((unsigned)((G.V + 255) / 256)), dim3(256), 0, s>>>((const T *)pred, ov, valid, G);
+        return hipGetLastError();
+    });
+}
+
+// The same launch for a caller that has M / info / valid of this score box already (and the border,
+// background and nP == 0 scores in `score`): ppp_pred_prepass made them in its one read of the prediction.
+// `pre_work` is that pre-pass's workspace, which begins with rank_masks_layout; `work` holds
+// rank_wg_prepared_workspace_bytes.
+hipError_t launch_rank_wg_prepared(const float *S, float *score, const ppp_box &sb, void *pre_work, void *work,
+                                   const Geo &G, hipStream_t s) {
+    if (!rank_wg_supported(G) || G.ring) return hipErrorNotSupported;
+    if (!cons_box_covers(G, sb)) return hipErrorInvalidValue;
+    Carver pre(pre_work), own(work);
+    const RankMasks m = rank_masks_layout(pre, sb, G);
+    RankWgWork W;
+    W.M = m.M; W.info = m.info; W.valid = m.valid;
+    rank_wg_sched_layout(own, G, W);
+    note_rank_kernel("rank_wg_kernel");
+    return launch_rwg_main(S, W, score, sb, G, s);
 }
 
 }  // namespace ppp

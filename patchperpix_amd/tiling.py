@@ -564,9 +564,17 @@ class DeviceOps:
     def pred_check(self, pred, P):
         return backend.pred_check(pred, P)
 
-    def rank_patches(self, pred, cons, ov, P, score_box, out=None):
+    def pred_prepass(self, pred, ov, fc_threshold, P, score, score_box):
+        """one read of the prediction for the clean flag, S2's pre-pass and the cover's patch bits
+        (backend.pred_prepass); None: not served, or PPP_PRED_PREPASS=0"""
+        return backend.pred_prepass(pred, ov if P.use_overlap else None, fc_threshold, P, score, score_box)
+
+    def patch_bits_from_table(self, bits_vol, centres, P):
+        return backend.patch_bits_from_table(bits_vol, centres, P)
+
+    def rank_patches(self, pred, cons, ov, P, score_box, out=None, prepared=None):
         return backend.rank_patches(pred, cons, ov if P.use_overlap else None, P,
-                                    score_box=score_box, out=out)
+                                    score_box=score_box, out=out, prepared=prepared)
 
     def rank_on_voxel_major(self, P):
         return backend.rank_vm_available(P)
@@ -1482,6 +1490,23 @@ class _Assembly:
         trials = [1, 3] if (tile_env == "auto" and n_launches >= 6 and getattr(self.ops, "times_rank_tiles", False)) else []
         timed = []            # (shape, start event, stop event, centres)
 
+        # The resident single box (one rank, one tile that is the whole frame, its rows kept for the pair stage):
+        # the clean flag S1 asks for, S2's masks and the patch bits of the cover and the thinning are all compares
+        # of the same values -- ONE read of the prediction before S1 makes them (ppp_pred_prepass) instead of four.
+        # PPP_PRED_PREPASS=0, or a geometry the library does not serve: the separate launches, as on every other path.
+        self.pre = None
+        fr = self.whole
+        if self.keep_cons and fr is not None and fr.clean == 0 and self.comm.world == 1 and not self.ring_z and \
+                self.cache is None and hasattr(self.ops, "pred_prepass") and hasattr(self.ops, "voxel_major_pool") and \
+                fr.origin == (0, 0, 0) and fr.shape == (self.Zf, self.Y, self.X) == tuple(self.shape) and self.flo == 0 and \
+                tiles == [(0, self.Z, 0, self.Y, 0, self.X)]:
+            P = backend.make_params(fr.shape, self.ps, origin=fr.origin, **self.flags)
+            if self.can_vm and self.ops.rank_on_voxel_major(P):
+                self.pre = self.ops.pred_prepass(fr.pred, fr.ov, self.kw["fc_threshold"], P, self.score_f, (0, 0, 0) + fr.shape)
+            if self.pre is not None:
+                fr.clean = self.pre.clean
+        del fr
+
         for ti, t in enumerate(tiles):
             z0, z1, y0, y1, x0, x1 = t
             cbox = self.bases_for_pairs(t) if self.keep_cons else self.bases_for_scores(t)
@@ -1517,7 +1542,8 @@ class _Assembly:
                     ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                     ev[0].record(torch.cuda.current_stream())
                 sc = self.ops.rank_patches(fr.pred, cons, fr.ov, P, (z0 - o[0], y0 - o[1], x0 - o[2], z1 - o[0], y1 - o[1], x1 - o[2]),
-                                      **({"out": self.score_f} if same and hasattr(self.ops, "voxel_major_pool") else {}))
+                                      **({"out": self.score_f} if same and hasattr(self.ops, "voxel_major_pool") else {}),
+                                      **({"prepared": self.pre} if self.pre is not None else {}))
                 if trial:
                     ev[1].record(torch.cuda.current_stream())
                     timed.append((trial, ev[0], ev[1], (z1 - z0) * (y1 - y0) * (x1 - x0)))
@@ -1671,6 +1697,10 @@ class _Assembly:
                     if self.provider and self.comm.world == 1 and hasattr(self.ops, "voxel_major_pool"):
                         order = self.ops.cover_options(self.mask_d, ov, self.bits_own, lin_t, rscores_t, pix_ths, radslice,
                                                        self.Pg, self.kw, bits_first_voxel=self.oz0 * self.plane)
+                    elif getattr(self, "pre", None) is not None:
+                        # (the pre-pass's table has a row per voxel of the whole volume: read in place)
+                        order = self.ops.cover_options(self.mask_d, ov, self.pre.bits_vol, lin_t, rscores_t, pix_ths, radslice,
+                                                       self.Pg, self.kw, bits_first_voxel=0)
                     else:
                         bits = self.gathered_bits(self.coords_t, self.kw["fc_threshold"], True)
                         order = self.ops.cover_options(self.mask_d, ov, bits, lin_t, rscores_t, pix_ths, radslice,
@@ -1720,6 +1750,10 @@ class _Assembly:
                         # order would double its 92 bytes per voxel)
                         selected = self.ops.greedy_cover(self.mask_d, self.bits_own, lin_t, rscores_t, never, pix_ths, radslice,
                                                     self.Pg, self.kw, bits_first_voxel=self.oz0 * self.plane)
+                    elif getattr(self, "pre", None) is not None:
+                        # (likewise the table of the pre-pass over the resident prediction: no gather of 2.5 M rows)
+                        selected = self.ops.greedy_cover(self.mask_d, self.pre.bits_vol, lin_t, rscores_t, never, pix_ths, radslice,
+                                                    self.Pg, self.kw, bits_first_voxel=0)
                     else:
                         bits = self.gathered_bits(self.coords_t, self.kw["fc_threshold"], True)
                         selected = self.ops.greedy_cover(self.mask_d, bits, lin_t, rscores_t, never, pix_ths, radslice, self.Pg, self.kw)
@@ -1773,7 +1807,10 @@ class _Assembly:
                     else:
                         mask_g = self.mask_d
                     sel_t = torch.from_numpy(np.ascontiguousarray(self.sel_coords)).to(self.dev)
-                    bits = self.gathered_bits(sel_t, self.kw["fc_threshold"])
+                    if getattr(self, "pre", None) is not None:
+                        bits = self.ops.patch_bits_from_table(self.pre.bits_vol, sel_t, self.Pg)
+                    else:
+                        bits = self.gathered_bits(sel_t, self.kw["fc_threshold"])
                     sel_lin = (self.sel_coords[:, 0].astype(np.int64) * self.Y + self.sel_coords[:, 1]) * self.X + self.sel_coords[:, 2]
                     if hasattr(self.ops, "thin_cover") and os.environ.get("PPP_THIN", "device") != "host" \
                             and self.ps[2] <= 32:
