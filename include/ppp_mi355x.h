@@ -1256,6 +1256,37 @@ int ppp_rows_compact(const void *d_pred_box, int dtype, int32_t C, const ppp_box
                      const void *d_index, int32_t Z, int32_t Y, int32_t X,
                      void *d_rows, void *stream);
 
+/* --- a stored zarr chunk to its place in a device tensor (csrc/ppp_chunk.hip) -------------------------
+ * The reference loads a prediction with zarr / numcodecs on the host (utilVoteInstances.py:136-251); here the
+ * host runs the codec only (zstd, lz4, zlib) and the device does the rest in one pass over the chunk:
+ * un-shuffle, optional value flags, scatter.  There is no un-shuffled copy of the chunk on the device.
+ *
+ * d_src (4-byte aligned): the `nbytes` decompressed, still shuffled bytes of ONE chunk, the blocks of a
+ *   Blosc-1 frame back to back: block b covers bytes [b * blocksize, min(nbytes, (b + 1) * blocksize)).
+ *   PPP_SHUFFLE_BIT: of the nel = bsize / typesize elements of a block the first n = nel / 8 * 8 are held as
+ *   8 * typesize planes of n / 8 bytes, plane 8 j + k = bit k of byte j, element e at bit e % 8 of byte e / 8
+ *   (little bit order); the remaining elements follow as they are.  PPP_SHUFFLE_BYTE: typesize runs of nel
+ *   bytes, run j = byte j of every element.  PPP_SHUFFLE_NONE: the chunk as it is (uncompressed, zlib and
+ *   gzip arrays); blocksize is ignored.  nbytes must be the chunk's element count times typesize and
+ *   blocksize a multiple of typesize, at most 2^30.
+ * geometry: ndim <= 4 axes, C order; chunk_shape; chunk_origin = the array coordinate of the chunk's first
+ *   element; the selection [sel_lo, sel_hi) in array coordinates.  d_dst is a C-contiguous tensor of shape
+ *   sel_hi - sel_lo with elements of typesize bytes (aligned to typesize).  The intersection of chunk and
+ *   selection is written to its place and NOTHING else; an empty intersection is a successful call without a
+ *   launch.  Runs of the fastest axis go out as 16-, 8- or 4-byte stores where they land so aligned, else by
+ *   element.
+ * flags: d_flags = NULL, or three device int32 {any x < 0, any x > 1, any NaN} over the ELEMENTS WRITTEN, read
+ *   as flags_dtype = PPP_F16 (typesize 2, compared after exact widening) or PPP_F32 (typesize 4).  A flag is
+ *   only ever set to 1: the caller zeroes the three once and reads them once after all the calls of a load.
+ *   -0.0 sets none.
+ * typesize other than 1, 2, 4 (and more than 4 axes): PPP_ERR_UNSUPPORTED -- the caller un-shuffles on the
+ * host.  Asynchronous on `stream`; no workspace. */
+enum ppp_shuffle { PPP_SHUFFLE_NONE = 0, PPP_SHUFFLE_BYTE = 1, PPP_SHUFFLE_BIT = 2 };
+int ppp_chunk_scatter(const void *d_src, int64_t nbytes, int32_t typesize, int64_t blocksize, int32_t shuffle,
+                      int32_t ndim, const int64_t *chunk_shape, const int64_t *chunk_origin,
+                      const int64_t *sel_lo, const int64_t *sel_hi, void *d_dst,
+                      int32_t flags_dtype, int32_t *d_flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -475,7 +475,14 @@ _SIGNATURES = {
                                                     ctypes.c_void_p, ctypes.POINTER(Params), ctypes.c_void_p]),
     "ppp_host_pack_channels": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                                 ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]),
+    # a stored zarr chunk, still Blosc-shuffled, to its place in a device tensor (ppp_chunk.hip)
+    "ppp_chunk_scatter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+                                         ctypes.c_int32, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                         ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p,
+                                         ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
 }
+ERR_UNSUPPORTED = -4      # PPP_ERR_UNSUPPORTED
+SHUFFLE_NONE, SHUFFLE_BYTE, SHUFFLE_BIT = 0, 1, 2
 
 
 def library_path():
@@ -743,6 +750,42 @@ def to_device_pred(pred, device="cuda", keep_f16=True):
     pred = pred.to(device).contiguous()
     note("pred_dtype", str(pred.dtype).replace("torch.", ""))
     return pred
+
+
+def chunk_scatter_rc(src, typesize, blocksize, shuffle, chunk_shape, origin, ranges, out, flags=None):
+    """ppp_chunk_scatter, its return code as it is.  src: uint8 device tensor, the decompressed, still
+    shuffled bytes of one chunk; shuffle: None / "byte" / "bit"; chunk_shape, origin, ranges ((start, stop)
+    per axis): the chunk, the array coordinate of its first element and the selection; out: the contiguous
+    device tensor of the selection's un-squeezed shape; flags: int32[3] device tensor {any < 0, any > 1,
+    any NaN} the call only ever sets (float16 / float32 `out`), or None."""
+    torch = _torch()
+    n = len(chunk_shape)
+    if not (len(origin) == len(ranges) == n == out.dim()) or tuple(out.shape) != tuple(b - a for a, b in ranges):
+        raise ValueError("chunk_scatter: `out` must have the selection's un-squeezed shape")
+    if out.element_size() != int(typesize) and int(typesize) in (1, 2, 4):
+        raise ValueError("chunk_scatter: elements of %d bytes into a %s tensor" % (typesize, out.dtype))
+    if src.dtype != torch.uint8:
+        raise TypeError("chunk_scatter: `src` holds bytes (uint8)")
+    fdt = -1
+    if flags is not None:
+        if out.dtype not in (torch.float16, torch.float32) or flags.dtype != torch.int32 or flags.numel() != 3:
+            raise TypeError("chunk_scatter: flags are int32[3], for a float16 / float32 destination")
+        fdt = pred_dtype_code(out)
+    i64 = lambda seq: (ctypes.c_int64 * n)(*[int(v) for v in seq])
+    return lib().ppp_chunk_scatter(_dev_ptr(src), int(src.numel()), int(typesize), int(blocksize),
+                                   {None: SHUFFLE_NONE, "byte": SHUFFLE_BYTE, "bit": SHUFFLE_BIT}[shuffle], n,
+                                   i64(chunk_shape), i64(origin), i64([a for a, _ in ranges]), i64([b for _, b in ranges]),
+                                   _dev_ptr(out), fdt, _dev_ptr(flags), _stream())
+
+
+def chunk_scatter(src, typesize, blocksize, shuffle, chunk_shape, origin, ranges, out, flags=None):
+    """`chunk_scatter_rc`; False when the library does not serve the chunk's form (PPP_ERR_UNSUPPORTED: the
+    caller un-shuffles on the host), True when the kernel was launched; every other code raises."""
+    rc = chunk_scatter_rc(src, typesize, blocksize, shuffle, chunk_shape, origin, ranges, out, flags)
+    if rc == ERR_UNSUPPORTED:
+        return False
+    check(rc)
+    return True
 
 
 # ----------------------------------------------------------------------------------------

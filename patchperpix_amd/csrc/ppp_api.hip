@@ -1973,4 +1973,70 @@ int ppp_patch_loss_samples_bwd(const void *d_logits, int dtype, const int32_t *d
     return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_patch_loss_samples_bwd");
 }
 
+/* ---- a stored chunk to its place in a device tensor (ppp_chunk.hip) ---- */
+int ppp_chunk_scatter(const void *d_src, int64_t nbytes, int32_t typesize, int64_t blocksize, int32_t shuffle,
+                      int32_t ndim, const int64_t *chunk_shape, const int64_t *chunk_origin,
+                      const int64_t *sel_lo, const int64_t *sel_hi, void *d_dst,
+                      int32_t flags_dtype, int32_t *d_flags, void *stream) {
+    if (typesize != 1 && typesize != 2 && typesize != 4)
+        return fail(PPP_ERR_UNSUPPORTED, "ppp_chunk_scatter: elements of %d bytes (1, 2 and 4 are served)", typesize);
+    if (ndim > 4) return fail(PPP_ERR_UNSUPPORTED, "ppp_chunk_scatter: %d axes (up to 4 are served)", ndim);
+    if (ndim < 1 || !chunk_shape || !chunk_origin || !sel_lo || !sel_hi || nbytes < 0)
+        return fail(PPP_ERR_INVALID_ARG, "ppp_chunk_scatter: bad argument");
+    if (shuffle != PPP_SHUFFLE_NONE && shuffle != PPP_SHUFFLE_BYTE && shuffle != PPP_SHUFFLE_BIT)
+        return fail(PPP_ERR_INVALID_ARG, "ppp_chunk_scatter: bad shuffle kind %d", shuffle);
+    if (shuffle == PPP_SHUFFLE_NONE) blocksize = 1 << 22;       // no block structure: any split serves
+    if (blocksize <= 0 || blocksize > (1ll << 30) || blocksize % typesize)
+        return fail(PPP_ERR_INVALID_ARG, "ppp_chunk_scatter: blocksize %lld must be a multiple of the element size, at most 2^30",
+                    (long long)blocksize);
+    if (d_flags && !((flags_dtype == PPP_F16 && typesize == 2) || (flags_dtype == PPP_F32 && typesize == 4)))
+        return fail(PPP_ERR_INVALID_ARG, "ppp_chunk_scatter: flags are for float16 (2 bytes) and float32 (4 bytes) elements");
+    ppp::ChunkGeo g;
+    memset(&g, 0, sizeof(g));
+    const int pad = 4 - ndim;
+    long long count = 1, extent[4] = {1, 1, 1, 1}, first = 0;
+    bool empty = false;
+    for (int a = 0; a < 4; ++a) g.cs[a] = 1, g.clo[a] = 0, g.chi[a] = 1;
+    for (int i = 0; i < ndim; ++i) {
+        const int a = pad + i;
+        if (chunk_shape[i] <= 0 || chunk_shape[i] > 0x7fffffffll || sel_hi[i] < sel_lo[i] || chunk_origin[i] < 0 || sel_lo[i] < 0)
+            return fail(PPP_ERR_INVALID_ARG, "ppp_chunk_scatter: bad extent on axis %d", i);
+        count *= chunk_shape[i];
+        if (count > (1ll << 40)) return fail(PPP_ERR_INVALID_ARG, "ppp_chunk_scatter: chunk too large");
+        g.cs[a] = (int)chunk_shape[i];
+        const long long lo = sel_lo[i] > chunk_origin[i] ? sel_lo[i] - chunk_origin[i] : 0;
+        const long long hi = sel_hi[i] - chunk_origin[i] < chunk_shape[i] ? sel_hi[i] - chunk_origin[i] : chunk_shape[i];
+        if (hi <= lo) empty = true;
+        g.clo[a] = (int)lo;
+        g.chi[a] = (int)(hi > lo ? hi : lo);
+        extent[a] = sel_hi[i] - sel_lo[i];
+    }
+    if (count * typesize != nbytes)
+        return fail(PPP_ERR_INVALID_ARG, "ppp_chunk_scatter: %lld bytes are not a chunk of %lld elements of %d bytes",
+                    (long long)nbytes, count, typesize);
+    if (empty || nbytes == 0) return PPP_OK;
+    if (!d_src || !d_dst || ((uintptr_t)d_src & 3) || ((uintptr_t)d_dst & (uintptr_t)(typesize - 1)))
+        return fail(PPP_ERR_INVALID_ARG, "ppp_chunk_scatter: NULL or misaligned pointer argument");
+    // destination strides (elements) and the element the chunk coordinate clo lands on
+    long long stride[4];
+    stride[3] = 1;
+    for (int a = 2; a >= 0; --a) stride[a] = stride[a + 1] * extent[a + 1];
+    for (int a = 0; a < 4; ++a) {
+        const long long org = a >= pad ? chunk_origin[a - pad] - sel_lo[a - pad] : 0;
+        first += (org + g.clo[a]) * stride[a];
+        if (a < 3) g.dstride[a] = stride[a];
+    }
+    g.src = (const uint8_t *)d_src;
+    g.nbytes = nbytes;
+    g.blocksize = blocksize;
+    g.shuffle = shuffle;
+    g.dst = (char *)d_dst + first * typesize;
+    g.fkind = d_flags ? flags_dtype : -1;
+    g.flags = d_flags;
+    PPP_TRY(need_device());
+    hipError_t e = ppp::launch_chunk_scatter(g, typesize, (hipStream_t)stream);
+    if (e == hipErrorInvalidConfiguration) return fail(PPP_ERR_UNSUPPORTED, "ppp_chunk_scatter: the chunk is more than one launch runs");
+    return e == hipSuccess ? PPP_OK : hip_fail(e, "ppp_chunk_scatter");
+}
+
 }  // extern "C"

@@ -342,4 +342,23 @@ hipError_t run_patch_loss_samples(bool fwd, const void *logits, int dtype, const
                                   const int *ctr, float *loss, double *state, const float *grad_out, void *grad, void *work,
                                   hipStream_t s);
 
+// one stored chunk, still Blosc-shuffled, to its place in a device tensor (ppp_chunk.hip).  The caller has
+// clipped the selection to the chunk: [clo, chi) in chunk coordinates, not empty, and `dst` points at the
+// destination element of chunk coordinate clo.  nblocks / waves_per_block are the launcher's.
+struct ChunkGeo {
+    const uint8_t *src;
+    long long nbytes, blocksize;
+    int shuffle;                // enum ppp_shuffle
+    int cs[4];                  // chunk shape, leading axes of size 1 for fewer than 4
+    int clo[4], chi[4];
+    long long dstride[3];       // destination element strides of axes 0 .. 2 (axis 3: 1)
+    void *dst;
+    int fkind;                  // PPP_F16 / PPP_F32: the flags' element type; -1: no flags
+    int *flags;
+    long long nblocks;
+    int waves_per_block;
+    int small;                  // the chunk-linear index of every piece fits 31 bits
+};
+hipError_t launch_chunk_scatter(ChunkGeo g, int typesize, hipStream_t s);
+
 }  // namespace ppp

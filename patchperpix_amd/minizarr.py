@@ -118,10 +118,11 @@ def bit_shuffle(block, typesize):
 # ---------------------------------------------------------------------------------------------
 # Blosc-1 frames
 # ---------------------------------------------------------------------------------------------
-def blosc_decode(frame, unshuffle=True):
+def blosc_decode(frame, unshuffle=True, out=None):
     """Blosc-1 frame (bytes) -> uint8 array of the decompressed chunk.  With unshuffle=False the
     blocks are returned still shuffled, together with (typesize, blocksize, shuffle kind) -- the
-    device path un-shuffles on the GPU."""
+    device path un-shuffles on the GPU.  out: a uint8 array of at least the frame's size to decode into
+    (a pinned staging buffer); the result is then its leading part."""
     buf = np.frombuffer(frame, dtype=np.uint8)
     if len(buf) < 16:
         raise ValueError("not a Blosc frame")
@@ -132,7 +133,12 @@ def blosc_decode(frame, unshuffle=True):
     if cbytes > len(buf):
         raise ValueError("truncated Blosc frame")
     shuffle = "bit" if flags & BLOSC_DOBITSHUFFLE else ("byte" if flags & BLOSC_DOSHUFFLE else None)
-    out = np.empty(nbytes, dtype=np.uint8)
+    if out is None:
+        out = np.empty(nbytes, dtype=np.uint8)
+    elif out.dtype != np.uint8 or out.ndim != 1 or len(out) < nbytes or not out.flags.c_contiguous:
+        raise ValueError("blosc_decode: `out` must be a contiguous uint8 array of at least %d bytes" % nbytes)
+    else:
+        out = out[:nbytes]
     if nbytes == 0:
         return out if unshuffle else (out, typesize, blocksize, None)
     if flags & BLOSC_MEMCPYED:
@@ -238,6 +244,73 @@ def blosc_encode(data, typesize, cname="zstd", clevel=3, shuffle="bit", blocksiz
     for c in streams:
         out += struct.pack("<i", len(c)) + c
     return bytes(out)
+
+
+# ---------------------------------------------------------------------------------------------
+# one chunk, decompressed but still shuffled, to its place in a selection: the definition the device
+# kernel (csrc/ppp_chunk.hip, ppp_chunk_scatter) is held to, and what a CPU device runs
+# ---------------------------------------------------------------------------------------------
+SHUFFLE_CODES = {None: 0, "byte": 1, "bit": 2}      # enum ppp_shuffle
+DEVICE_TYPESIZES = (1, 2, 4)
+RING_SLOTS = 4                                      # staging buffers of Array.read_device, each one chunk large
+
+
+def unshuffle_blocks(src, typesize, blocksize, shuffle):
+    """The still shuffled bytes of a chunk (what ``blosc_decode(frame, unshuffle=False)[0]`` holds) ->
+    its bytes: block b covers [b * blocksize, min(nbytes, (b + 1) * blocksize)), each un-shuffled on
+    its own by bit_unshuffle / byte_unshuffle.  shuffle None: the bytes as they are."""
+    src = np.ascontiguousarray(src, dtype=np.uint8).reshape(-1)
+    if shuffle is None or len(src) == 0:
+        return src
+    out = np.empty_like(src)
+    fn = bit_unshuffle if shuffle == "bit" else byte_unshuffle
+    for b0 in range(0, len(src), int(blocksize)):
+        blk = src[b0:b0 + int(blocksize)]
+        out[b0:b0 + len(blk)] = fn(blk, typesize)
+    return out
+
+
+def _clip(chunk_shape, origin, ranges):
+    """(source slices in the chunk, destination slices in the selection) of their intersection, or None"""
+    src, dst = [], []
+    for c, o, (a, b) in zip(chunk_shape, origin, ranges):
+        s0, s1 = max(a, o), min(b, o + c)
+        if s1 <= s0:
+            return None
+        src.append(slice(s0 - o, s1 - o))
+        dst.append(slice(s0 - a, s1 - a))
+    return tuple(src), tuple(dst)
+
+
+def value_flags(values):
+    """(any x < 0, any x > 1, any NaN) of a float16 / float32 array -- False thrice for every other
+    dtype and for no values.  -0.0 sets none; float16 compares after exact widening."""
+    values = np.asarray(values)
+    if values.dtype not in (np.float16, np.float32) or values.size == 0:
+        return False, False, False
+    w = values.astype(np.float32)
+    with np.errstate(invalid="ignore"):
+        return bool((w < 0).any()), bool((w > 1).any()), bool(np.isnan(w).any())
+
+
+def chunk_scatter_host(src, typesize, blocksize, shuffle, chunk_shape, origin, ranges, out, flags=False):
+    """ppp_chunk_scatter in NumPy.  src: the decompressed, still shuffled bytes of one chunk; typesize,
+    blocksize, shuffle (None / "byte" / "bit"): its Blosc header; chunk_shape, origin: the chunk and the
+    array coordinate of its first element; ranges: the selection, (start, stop) per axis; out: the array of
+    the selection's un-squeezed shape (itemsize == typesize).  The intersection of chunk and selection is
+    written to its place in `out` and nothing else.  Returns the value flags of the ELEMENTS WRITTEN
+    (`value_flags`) when flags is set, else None."""
+    if out.dtype.itemsize != typesize:
+        raise ValueError("chunk_scatter_host: elements of %d bytes into an array of %s" % (typesize, out.dtype))
+    data = unshuffle_blocks(src, typesize, blocksize, shuffle)
+    if len(data) != int(np.prod(chunk_shape)) * typesize:
+        raise ValueError("chunk_scatter_host: %d bytes are not a chunk of shape %s" % (len(data), tuple(chunk_shape)))
+    clip = _clip(chunk_shape, origin, ranges)
+    written = np.empty(0, dtype=out.dtype)
+    if clip is not None:
+        written = data.view(out.dtype).reshape(chunk_shape)[clip[0]]
+        out[clip[1]] = written
+    return value_flags(written) if flags else None
 
 
 # ---------------------------------------------------------------------------------------------
@@ -400,6 +473,191 @@ class Array:
         else:
             for p in pos:
                 work(p)
+
+    # ---- the device path: the codec on host threads, un-shuffle and scatter where the tensor lives
+    def decode_chunk_shuffled(self, raw, out=None):
+        """bytes of a chunk file -> (uint8 array, typesize, blocksize, shuffle kind): the codec only, the
+        Blosc blocks still shuffled.  out: a uint8 buffer to decode into (the result is its leading part)."""
+        c = self.compressor
+        if c is not None and c["id"] == "blosc":
+            return blosc_decode(raw, unshuffle=False, out=out)
+        if c is None:
+            data = np.frombuffer(raw, dtype=np.uint8)
+        elif c["id"] == "zlib":
+            data = np.frombuffer(zlib.decompress(raw), dtype=np.uint8)
+        elif c["id"] == "gzip":
+            data = np.frombuffer(zlib.decompress(raw, 16 + zlib.MAX_WBITS), dtype=np.uint8)
+        else:
+            raise NotImplementedError("zarr compressor %r" % c["id"])
+        if out is not None:
+            out[:len(data)] = data
+            data = out[:len(data)]
+        return data, self.dtype.itemsize, max(len(data), 1), None
+
+    def _device_served(self):
+        """does ppp_chunk_scatter serve this array?  (Fortran order and filters never get this far)"""
+        return self.dtype.itemsize in DEVICE_TYPESIZES and self.dtype.isnative and 1 <= self.ndim <= 4 and \
+            self.dtype.kind in "fiub"
+
+    def _ring(self, device, nbytes):
+        """the staging ring of `device`, cached on the array: RING_SLOTS host buffers (pinned for a GPU) and,
+        for a GPU, as many device buffers, each one chunk large, a copy stream and an event per slot"""
+        import torch
+        rings = self.__dict__.setdefault("_rings", {})
+        ring = rings.get(str(device))
+        if ring is None or ring["nbytes"] < nbytes:
+            gpu = device.type == "cuda"
+            ring = rings[str(device)] = {
+                "nbytes": nbytes,
+                "host": [torch.empty(nbytes, dtype=torch.uint8, pin_memory=gpu) for _ in range(RING_SLOTS)],
+                "dev": [torch.empty(nbytes, dtype=torch.uint8, device=device) for _ in range(RING_SLOTS)] if gpu else None,
+                "events": [None] * RING_SLOTS,
+                "stream": torch.cuda.Stream(device=device) if gpu else None,
+                "flags": torch.zeros(3, dtype=torch.int32, device=device) if gpu else None,
+            }
+        return ring
+
+    def read_device(self, sel, device="cuda", flags=False):
+        """The selection as a tensor on `device`, of the selection's UN-SQUEEZED shape and the array's dtype
+        -- equal, bit for bit, to ``self[sel]`` -- without un-shuffling on the host.  flags=True: also
+        (any x < 0, any x > 1, any NaN) over the selection as Python bools (`value_flags`).
+
+        Host worker threads (``min(16, os.cpu_count() or 1)``, as `_read`) read the chunk files and run the
+        codec only, into a ring of RING_SLOTS = 4 staging buffers of one chunk each (pinned for a GPU), cached on
+        this object with as many device buffers: at most 4 chunks of host and 4 chunks of device memory,
+        whatever the selection.  The CALLING thread copies a decoded chunk host -> device on a copy stream and
+        launches ppp_chunk_scatter behind it; an event per slot keeps a slot from being decoded into again
+        before its copy and kernel are done.  Worker threads make no GPU call.  The caller's current stream
+        waits for the copy stream before this returns: the tensor is safe on it.  The flags are cleared once
+        and read once, the only synchronisation of a load.  A missing chunk file leaves `fill_value`, which
+        takes part in the flags.  With a CPU `device` the same pipeline runs `chunk_scatter_host`.
+
+        What the kernel does not serve -- element sizes other than 1, 2, 4, foreign byte order, more than 4
+        axes, a selection `_normalise` refuses -- takes ``self[sel]`` and a plain upload, with equal result.
+        ``backend.PRED_UPLOADS`` advances by one per call that ends on a GPU."""
+        import threading
+        import torch
+        device = torch.device(device)
+        gpu = device.type == "cuda"
+        if gpu:
+            from . import backend
+            if device.index is None:
+                device = torch.device("cuda", torch.cuda.current_device())
+        ranges = squeeze = None
+        if self._device_served():
+            try:
+                ranges, squeeze = self._normalise(sel)
+            except NotImplementedError:
+                pass
+        if ranges is None:
+            return self._read_device_host(sel, device, flags)
+        shape = [b - a for a, b in ranges]
+        pos, grids = self._chunks_of(ranges)
+        chunk_bytes = int(np.prod(self.chunks)) * self.dtype.itemsize
+        with self.__dict__.setdefault("_ring_lock", threading.Lock()):
+            if gpu:
+                backend.PRED_UPLOADS += 1
+                got = self._read_device_ring(ranges, shape, pos, grids, chunk_bytes, device, flags, backend)
+                if got is None:         # (the library refused the chunk's form: nothing was relied on)
+                    backend.PRED_UPLOADS -= 1
+                    return self._read_device_host(sel, device, flags)
+                return got
+            return self._read_device_ring(ranges, shape, pos, grids, chunk_bytes, device, flags, None)
+
+    def _read_device_host(self, sel, device, flags):
+        import torch
+        try:
+            ranges, _ = self._normalise(sel)
+            host = np.full([b - a for a, b in ranges], self.fill_value, dtype=self.dtype)
+            self._read(ranges, host)
+        except NotImplementedError:
+            host = np.asarray(self[sel])
+        t = torch.from_numpy(np.ascontiguousarray(host.astype(host.dtype.newbyteorder("="), copy=False)))
+        if device.type == "cuda":
+            from . import backend
+            backend.PRED_UPLOADS += 1
+            t = t.to(device)
+        return (t, value_flags(host)) if flags else t
+
+    def _read_device_ring(self, ranges, shape, pos, grids, chunk_bytes, device, flags, backend):
+        import torch
+        gpu = backend is not None
+        tdt = torch.from_numpy(np.empty(0, dtype=self.dtype)).dtype
+        ts = self.dtype.itemsize
+        want_flags = bool(flags) and self.dtype in (np.float16, np.float32)
+        seen = [False, False, False]
+        n_out = int(np.prod(shape))
+        ring = self._ring(device, chunk_bytes) if pos else None
+        idx_of = [tuple(g[i] for g, i in zip(grids, p)) for p in pos]
+
+        def work(k):
+            """worker thread: file read and codec, into the slot's host buffer; no GPU call"""
+            raw = self.read_chunk_bytes(idx_of[k])
+            if raw is None:
+                return None
+            return self.decode_chunk_shuffled(raw, out=ring["host"][k % RING_SLOTS].numpy())
+
+        if gpu:
+            cur = torch.cuda.current_stream(device)
+            out = torch.empty(shape, dtype=tdt, device=device)
+            if pos:
+                ring["stream"].wait_stream(cur)
+        else:
+            out = torch.empty(shape, dtype=tdt)
+            out_np = out.numpy() if n_out else np.empty(shape, dtype=self.dtype)
+        refused = False
+        if pos:
+            import contextlib
+            scope = torch.cuda.stream(ring["stream"]) if gpu else contextlib.nullcontext()
+            with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool, scope:
+                if gpu and want_flags:
+                    ring["flags"].zero_()
+                futures = {}
+                for k in range(min(RING_SLOTS, len(pos))):
+                    if gpu and ring["events"][k] is not None:
+                        ring["events"][k].synchronize()             # (the last user of the slot: an earlier call)
+                    futures[k] = pool.submit(work, k)
+                for k in range(len(pos)):
+                    got = futures.pop(k).result()
+                    slot = k % RING_SLOTS
+                    origin = [i * c for i, c in zip(idx_of[k], self.chunks)]
+                    if refused:
+                        pass
+                    elif got is None:
+                        # no chunk file: that part keeps the fill value, which takes part in the flags
+                        clip = _clip(self.chunks, origin, ranges)
+                        if clip is not None:
+                            out[clip[1]] = self.fill_value
+                            if want_flags:
+                                seen = [a or b for a, b in zip(seen, value_flags(np.asarray(self.fill_value, dtype=self.dtype)))]
+                    else:
+                        data, typesize, blocksize, shuffle = got
+                        if typesize != ts or len(data) != chunk_bytes:
+                            raise ValueError("chunk %s of %s holds %d bytes of %d-byte elements, not a %s chunk of %s"
+                                             % (idx_of[k], self.path, len(data), typesize, self.dtype, self.chunks))
+                        if gpu:
+                            dev = ring["dev"][slot][:chunk_bytes]
+                            dev.copy_(ring["host"][slot][:chunk_bytes], non_blocking=True)
+                            refused = not backend.chunk_scatter(dev, typesize, blocksize, shuffle, self.chunks, origin,
+                                                                ranges, out, ring["flags"] if want_flags else None)
+                            ring["events"][slot] = ring["stream"].record_event()
+                        else:
+                            f = chunk_scatter_host(data, typesize, blocksize, shuffle, self.chunks, origin, ranges,
+                                                   out_np, flags=want_flags)
+                            if want_flags:
+                                seen = [a or b for a, b in zip(seen, f)]
+                    nxt = k + RING_SLOTS
+                    if nxt < len(pos):
+                        if gpu and ring["events"][slot] is not None:
+                            ring["events"][slot].synchronize()      # the slot's copy and kernel are done
+                        futures[nxt] = pool.submit(work, nxt)
+            if gpu:
+                cur.wait_stream(ring["stream"])
+                if refused:
+                    return None
+                if want_flags:
+                    seen = [a or bool(b) for a, b in zip(seen, ring["flags"].cpu().tolist())]
+        return (out, tuple(seen)) if flags else out
 
     def __array__(self, dtype=None, copy=None):
         a = self[...]

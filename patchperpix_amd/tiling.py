@@ -419,10 +419,15 @@ class ZarrProvider:
     for next -- decodes that box into a second pinned buffer on a worker thread while the device
     works on the current tile (chunk decompression runs in C, outside the interpreter lock).
     expit: apply the logistic function to logits (loadAffinities decides that from the value
-    range of the whole array, utilVoteInstances.py:249-250; a provider is told)."""
+    range of the whole array, utilVoteInstances.py:249-250; a provider is told).
+    device_decode (off by default; a minizarr array on a GPU): the box is filled by ``arr.read_device`` -- the codec
+    on host threads, un-shuffle and scatter on the device -- in place of ``read_into`` and the upload; the thread
+    that reads (the prefetch worker, or the caller) issues that GPU work and hands over tensor and event as the
+    upload does."""
 
-    def __init__(self, arr, device="cuda", expit=False):
+    def __init__(self, arr, device="cuda", expit=False, device_decode=False):
         self.arr, self.device, self.expit = arr, device, bool(expit)
+        self.device_decode = bool(device_decode) and hasattr(arr, "read_device") and str(device).startswith("cuda")
         self._pinned = [None, None]
         self._cur = 0
         self._ahead = None            # (box, thread, buffer index, error holder, host buffer, upload slot)
@@ -451,6 +456,9 @@ class ZarrProvider:
     def _read(self, box, host, err, upload=None, which=None):
         z0, z1, y0, y1, x0, x1 = box
         try:
+            if self.device_decode:
+                self._decode_on_device(box, upload)
+                return
             if which is not None and self._upload_events[which] is not None:
                 self._upload_events[which].synchronize()     # the copy that last read this pinned buffer
                 self._upload_events[which] = None
@@ -461,6 +469,16 @@ class ZarrProvider:
                     self._upload_events[which] = upload.get("event")
         except BaseException as e:          # reported by the pred_box that consumes the buffer
             err.append(e)
+
+    def _decode_on_device(self, box, slot):
+        """device_decode: the box straight into a device tensor (minizarr.Array.read_device, whose GPU work this
+        thread issues); slot receives the tensor and an event behind it on this thread's stream"""
+        import torch
+        z0, z1, y0, y1, x0, x1 = box
+        dev = torch.device(self.device)
+        with torch.cuda.device(dev):
+            slot["dev"] = self.arr.read_device((slice(None), slice(z0, z1), slice(y0, y1), slice(x0, x1)), device=dev)
+            slot["event"] = torch.cuda.current_stream().record_event()
 
     def _upload(self, host, slot):
         """Worker thread (round 6): the box it has just decoded goes host -> HBM at once, on a copy
@@ -493,7 +511,7 @@ class ZarrProvider:
                 return
             self._ahead[1].join()
         which = 1 - self._cur
-        host, err, slot = self._buffer(which, self._shape(box)), [], {}
+        host, err, slot = (None if self.device_decode else self._buffer(which, self._shape(box))), [], {}
         th = threading.Thread(target=self._read, args=(box, host, err, slot, which), daemon=True)
         th.start()
         self._ahead = (box, th, which, err, host, slot)
@@ -523,13 +541,21 @@ class ZarrProvider:
                     torch.cuda.current_stream().wait_event(ahead[5]["event"])
                     uploaded.record_stream(torch.cuda.current_stream())
                     self.boxes_uploaded_ahead += 1
+            elif self.device_decode:
+                host, err, slot = None, [], {}
+                self._read(box, host, err, slot)
+                if err:
+                    raise err[0]
+                uploaded = slot["dev"]
+                torch.cuda.current_stream().wait_event(slot["event"])
             else:
                 host = self._buffer(self._cur, shape)
                 err = []
                 self._read(box, host, err, which=self._cur)
                 if err:
                     raise err[0]
-        self.bytes_read += host.numel() * host.element_size()
+        self.bytes_read += int(np.prod(shape)) * np.dtype(self.arr.dtype).itemsize if host is None else \
+            host.numel() * host.element_size()
         if uploaded is not None:
             pred = uploaded
         else:
@@ -2543,6 +2569,7 @@ def _stitch_load(stack, pred_file, patchshape, kw):
     for a streamed file, which is what the voting half expects."""
     from .vote_instances import utilVoteInstances as util
     from_code = bool(kw.pop("vote_from_code", False))
+    on_device = _want_load_on_device(kw)
     if from_code and not kw.get("blockwise", False):
         raise NotImplementedError("vote_from_code needs blockwise = true (the tiled assembly votes the rows)")
     if from_code and _holds_code(pred_file, kw):
@@ -2575,13 +2602,87 @@ def _stitch_load(stack, pred_file, patchshape, kw):
         # logits: loadAffinities' test over the whole array (utilVoteInstances.py:249-250), one
         # z-chunk at a time; `logits=True / False` in the configuration skips the scan
         logits = kw.get("logits")
-        affinities = ZarrProvider(arr, expit=_logits_in(arr, patchshape) if logits is None else bool(logits))
+        affinities = ZarrProvider(arr, expit=_logits_in(arr, patchshape) if logits is None else bool(logits),
+                                  device_decode=on_device and hasattr(arr, "read_device"))
     else:
-        loaded = util.loadAffinities(pred_file, "", patchshape=patchshape, **kw)
+        loaded = _HOST_LOAD
+        if on_device and pred_file.rstrip("/").endswith(".zarr"):
+            loaded = _load_on_device(pred_file, patchshape, kw)
+        if loaded is _HOST_LOAD:
+            loaded = util.loadAffinities(pred_file, "", patchshape=patchshape, **kw)
         if loaded is None:
             return None
         affinities, numinst, foreground = loaded
     return affinities, numinst, foreground
+
+
+_HOST_LOAD = object()       # _load_on_device: not served, load on the host
+
+
+def _want_load_on_device(kw):
+    """``load_on_device`` (this project's own option, default off; PPP_LOAD_DEVICE=1 / 0 overrides it), taken out
+    of `kw`: load a resident zarr prediction with the un-shuffle, the logits test and the scatter on the GPU
+    (minizarr.Array.read_device).  Only with a GPU."""
+    import torch
+    want = kw.pop("load_on_device", False)
+    env = os.environ.get("PPP_LOAD_DEVICE")
+    if env in ("0", "1"):
+        want = env == "1"
+    return bool(want) and torch.cuda.is_available()
+
+
+def _load_on_device(pred_file, patchshape, kw):
+    """loadAffinities for a resident zarr prediction, loaded on the device: (float tensor (C, Z, Y, X) on the GPU,
+    numinst, foreground), None when the result key already exists in the file, `_HOST_LOAD` for what the device
+    path does not serve (PredictionFile.affinities_device) or the free memory cannot hold."""
+    import torch
+    from .vote_instances import io_hdflike, utilVoteInstances as util
+    with io_hdflike.open_container(pred_file, "r") as f:
+        if "vote_instances" in f.keys():
+            logger.info("%s vote_instances already computed", pred_file)
+            return None
+        pf = util.PredictionFile(f, patchshape=patchshape, **kw)
+        try:
+            ds = pf.dataset
+        except KeyError:
+            return _HOST_LOAD
+        # the stored array, its float32 image when it holds logits (a few channels at a time), and the ring of
+        # staging buffers of the load (minizarr.RING_SLOTS chunks on the device)
+        n = float(np.prod(ds.shape))
+        item = np.dtype(ds.dtype).itemsize
+        staging = 4.0 * item * float(np.prod(getattr(ds, "chunks", None) or ds.shape))
+        need = n * item + (0.0 if kw.get("logits") is False else 4.0 * n) + staging + float(1 << 28)
+        free = torch.cuda.mem_get_info()[0]
+        if need > free:
+            logger.info("load_on_device: %.2f GB needed, %.2f GB free -- loading %s on the host", need / 1e9, free / 1e9, pred_file)
+            return _HOST_LOAD
+        got = pf.affinities_device("cuda")
+        if got is None:
+            return _HOST_LOAD
+        aff, (neg, gt1, nan) = got
+        numinst = pf.numinst()
+        cropped = any(kw.get("crop_%s_s" % a, 0) or kw.get("crop_%s_e" % a) is not None for a in "zyx")
+        if kw.get("fg_key") is not None or kw.get("numinst_key") is not None or cropped:
+            foreground = pf.foreground()[0]
+        else:
+            # PredictionFile.foreground's third source, the centre channel as stored (before any expit), from the
+            # tensor instead of a second decode of every chunk
+            mid = int(np.prod(patchshape)) // 2
+            centre = aff[mid, 0] if len(ds.shape) == 3 else aff[mid]
+            foreground = np.expand_dims(centre.cpu().numpy(), axis=0) > util.getFgThreshold(**kw)
+    logits = kw.get("logits")
+    if logits is None:
+        # np.min(a) < 0 and np.max(a) > 1: a NaN anywhere makes both compares false
+        logits = (not nan) and neg and gt1
+    if logits:
+        # scipy.special.expit of the stored array, as ZarrProvider.pred_box maps a device tensor: evaluated in
+        # float64, narrowed to float32, a few channels at a time
+        out = torch.empty(aff.shape, dtype=torch.float32, device=aff.device)
+        step = max(1, (1 << 26) // max(1, int(np.prod(aff.shape[1:]))))
+        for c0 in range(0, int(aff.shape[0]), step):
+            out[c0:c0 + step] = torch.sigmoid(aff[c0:c0 + step].double()).float()
+        aff = out
+    return aff.contiguous(), numinst, foreground
 
 
 def _stitch_vote(affinities, numinst, foreground, pred_file, result_folder, patchshape, kw):

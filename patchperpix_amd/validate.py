@@ -259,6 +259,7 @@ class SampleSession:
         from .vote_instances import utilVoteInstances as util
         f = self.reader
         from_code = bool(kw.pop("vote_from_code", False))
+        kw.pop("load_on_device", None)      # (the session keeps its host load: its sample stays resident anyway)
         if from_code and (kw.get("code_key") or "volumes/pred_code") in f:
             key = repr([kw.get(k) for k in ("code_key", "numinst_key", "fg_key", "fg_thresh", "decode_batch_size",
                                             "checkpoint_file", "logits", "use_swa")] + [patchshape.tolist()])

@@ -139,6 +139,24 @@ class PredictionFile:
             aff = aff[:, :, ::2, ::2]
         return aff
 
+    def affinities_device(self, device="cuda"):
+        """``affinities()`` as a tensor on `device`, loaded without un-shuffling on the host
+        (minizarr.Array.read_device), with the value flags (any x < 0, any x > 1, any NaN) of what was loaded:
+        (tensor, flags).  Served for the arrays the prediction step writes -- ``volumes/...``, channels first,
+        2-d or 3-d, in a store read through minizarr, without isbiHack; None for everything else (the caller
+        loads on the host)."""
+        if not self.modern or self.kw.get("isbiHack") or self.patchshape is None:
+            return None
+        ds = self.dataset
+        nd = len(ds.shape) - 1
+        if not hasattr(ds, "read_device") or nd not in (2, 3) or self.channels_last:
+            return None
+        aff, flags = ds.read_device((slice(None),) + self._crop("zyx"[-nd:]), device=device, flags=True)
+        aff = aff.squeeze()                  # np.squeeze: every axis of size 1
+        if nd == 2:
+            aff = aff.unsqueeze(1)
+        return aff, flags
+
     # ---- instance count and foreground -----------------------------------------------------
     def numinst(self):
         """uint8 per voxel, or None without a numinst_key (utilVoteInstances.py:260-272)."""
